@@ -17,9 +17,15 @@ only meet at the timing barriers.  --mode train times the train step instead (fo
 + ONE RCCL all-reduce of the flat gradient bucket + clip + Adam; reference trainer.py:429-442), the
 only place a collective sits on the path.
 
-Prints ONE JSON line on rank 0.  `roofline` is the dominant kernel of the step; `kernels` adds the
-HBM roofline of the Relate/Filter logic kernels on >= 65536 resident predicates (SURVEY.md §8(d));
-`cpu_baseline` is the CPU oracle (a port of the reference's algorithm) timed on this host.
+Prints ONE JSON line on rank 0: `value` (questions/s over the --steps timed steps) and `ms_per_step`.
+A plain run does nothing else.  --full adds the other legs: `roofline` is the dominant kernel of the
+step; `kernels` adds the HBM roofline of the Relate/Filter logic kernels on >= 65536 resident
+predicates; `cpu_baseline` is the CPU oracle (a port of the reference's algorithm)
+timed on this host; `parity` checks the timed batch against it; `value_*` are the other loop rates.
+
+--dump-outputs DIR writes what the last timed step returned (log-probabilities and answers; train:
+loss, log-probabilities and the updated parameters) as DIR/<name>.npy.  Inputs and weights are seeded,
+so two builds run with the same arguments can be compared output for output.
 """
 
 import argparse
@@ -106,6 +112,12 @@ def parse(argv=None):
     ap.add_argument("--parity-fp64", type=int, default=1, help="1: the parity leg also runs the oracle in float64 (the tolerance policy's yardstick)")
     ap.add_argument("--cpu-budget", type=float, default=60.0, help="seconds of host time the cpu_baseline + parity legs may take in total: the number of "
                                                                     "questions checked beyond the timed sample shrinks to fit (the default run must finish within minutes)")
+    ap.add_argument("--full", action="store_true", help="also run every leg beyond the headline: one-replay-at-a-time, sustained, streamed, "
+                    "fresh-programs, end-to-end and calibrated rates, per-kernel times and rooflines, the logic kernels' stress, the CPU baseline and "
+                    "the parity check (inference); the standalone all-reduce, the replica check and per-kernel rooflines (train); per-kernel times "
+                    "and parity (--data).  Without it a run sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step returned to its "
+                    "caller as DIR/<name>.npy (float32 / float64, at most 64 MB in all: an array over its share keeps a fixed, seeded sample)")
     args = ap.parse_args(argv)
     if args.objects is None:
         args.objects = {"north_star": 100, "c1": 36, "c3": 100, "c4": 256}[args.workload]
@@ -236,6 +248,54 @@ def emit(line):
     out.flush()
 
 
+DUMP_LIMIT = 60 * 10 ** 6                                        # bytes of array data --dump-outputs writes in all (64 MB less room for .npy headers)
+
+
+def _host_float(x):
+    """A tensor / array as a host numpy array of float32 or float64 (integers and 16-bit floats widen)."""
+    if torch.is_tensor(x):
+        x = x.detach()
+        x = (x.float() if x.dtype in (torch.float16, torch.bfloat16) else x).cpu().numpy()
+    x = np.asarray(x)
+    return x if x.dtype in (np.float32, np.float64) else x.astype(np.float64)
+
+
+def forward_outputs(res):
+    """What a caller of the forward receives, as float arrays: every question's log-probability and its answers, flattened - an answer as
+    its index among the question's options (-1: not one of them), with the log-probability the forward gave it - plus the number of
+    answers per question."""
+    from dfol_vqa_amd.fol_types import QuestionType
+    out = {"log_probability": _host_float(res["log_probability"])}
+    answers = [a if isinstance(a, (list, tuple)) else [a] for a in (res.get("answer") or [])]
+    if answers:
+        opts = res.get("options") or []
+        per_q = opts if res.get("type") == QuestionType.QUERY else [opts] * len(answers)
+        out["answer_count"] = np.array([len(a) for a in answers], np.float64)
+        out["answer_index"] = np.array([list(o).index(x) if x in o else -1 for a, o in zip(answers, per_q) for x in a], np.float64)
+        alp = [a if isinstance(a, (list, tuple)) else [a] for a in (res.get("answer_log_probability") or [])]
+        out["answer_log_probability"] = np.array([float(x) for a in alp for x in a], np.float64)
+    return out
+
+
+def dump_outputs(path, arrays, rank=0, world=1, limit=DUMP_LIMIT):
+    """--dump-outputs: every array as <path>/<name>.npy (<name>.rank<r>.npy on ranks > 0), at most `limit` / world bytes per rank.  The arrays
+    are written smallest first, each within an equal share of what is left; one over its share is flattened and keeps a fixed, seeded
+    sample of its entries (the same entries for the same shape in every run)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: _host_float(v) for k, v in arrays.items()}
+    left = limit // max(1, world)
+    order = sorted(arrays, key=lambda k: arrays[k].nbytes)
+    for i, name in enumerate(order):
+        a = arrays[name]
+        share = left // (len(order) - i)
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            idx = np.unique(np.random.RandomState(0).randint(0, a.size, size=keep))
+            a = a.reshape(-1)[idx]
+        left -= a.nbytes
+        np.save(os.path.join(path, name + ("" if rank == 0 else ".rank%d" % rank) + ".npy"), a)
+
+
 def setup(args):
     """Rank / device / process group; fails loudly when the launch does not match --gpus."""
     rank = int(os.environ.get("RANK", "0"))
@@ -335,6 +395,7 @@ def build_model(args, device, train=False):
     if train and getattr(args, "mlp_math", "fp32") == "bf16":
         cfg["mlp_math"] = "bf16"
     ontology = experiment.build_ontology(cfg)
+    torch.manual_seed(0)                                         # the layers' default init draws from torch's generator: same weights in every run
     model = experiment.build_model(cfg, ontology)
     init_weights(model)
     model = model.to(device)
@@ -422,8 +483,10 @@ def main(argv=None):
         res = run_steps(args.steps)
         barrier()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, forward_outputs(res), rank, world)
         serial_elapsed = None
-        if pipelined:                                            # the same steps one at a time (what `value` was before round 6's pipelining), for the record
+        if pipelined and args.full:                              # the same steps one at a time (what `value` was before round 6's pipelining), for the record
             barrier()
             t0 = time.perf_counter()
             run_steps(args.steps, serial=True)
@@ -441,7 +504,8 @@ def main(argv=None):
             args.ragged, args.objects, args.questions_per_image, "" if args.share_scenes else ", scenes NOT shared")
     out = {"argv": list(argv), "metric": metric, "value": total_q / elapsed, "unit": "questions/s",
            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "data": "synthetic",
+           "dtype": "f32 logic arithmetic on bf16 relation tiles" if args.workload == "c4" else "f32",
            "config": {"workload": (WORKLOADS[args.workload] % (args.batch, args.objects)).replace("QPI", str(args.questions_per_image)).replace(
                " (the size BASELINE.json's metric is quoted on)", " (the size BASELINE.json's metric is quoted on)" if args.objects == 100 else ""),
                       "workload_id": args.workload, "batch_per_gpu": args.batch, "questions_per_image": args.questions_per_image,
@@ -468,7 +532,7 @@ def main(argv=None):
         out["value_one_replay_at_a_time"] = total_q / serial_elapsed
     if getattr(args, "_shard", None):
         out["shard"] = args._shard
-    if args.sustain > 0:
+    if args.full and args.sustain > 0:
         # the headline rate again over >= --sustain seconds of back-to-back steps (the --steps region at N = 100 lasts 47 ms when the
         # driver passes --steps 20: too short for an outside sampler to see)
         # (the step count comes from the max-over-ranks time of the --steps region, so every rank runs the same number of steps)
@@ -485,12 +549,12 @@ def main(argv=None):
             sus = float(t.item())
         out["value_sustained"] = args.batch * world * n_sus / sus
         out["sustained"] = {"steps": n_sus, "seconds": sus, "ms_per_step": sus / n_sus * 1e3}
-    if args.streamed:
+    if args.full and args.streamed:
         # every rank streams its own batches (the ranks share the host's PCIe root complexes, so this is measured with all of them live)
         sv = streamed_rate(args, step if graphed else eager, pbs, td, share, device)
         out["value_streamed"] = sv["questions_per_s"] * world
         out["streamed"] = sv
-    if args.fresh_batches > 0 and args.workload in ("north_star", "c1"):
+    if args.full and args.fresh_batches > 0 and args.workload in ("north_star", "c1"):
         # every rank runs its own stream of unseen batches (max over ranks of the elapsed time: the whole-job rate)
         fp = fresh_programs_rate(args, model, ontology, names, paths, device, rank, n_batches=args.fresh_batches)
         fp["per_rank"] = per_rank_rates(td, world, rank, fp)
@@ -513,9 +577,9 @@ def main(argv=None):
         out["value_end_to_end"] = ee["questions_per_s"] * world
         ee["vs_value"] = "%.2f x the replayed-batch rate `value`" % (out["value_end_to_end"] / out["value"])
         out["end_to_end"] = ee
-    if args.calibrated_leg and world == 1 and args.workload == "north_star" and args.fresh_batches > 0:
+    if args.full and args.calibrated_leg and world == 1 and args.workload == "north_star" and args.fresh_batches > 0:
         out["calibrated"] = calibrated_leg(args, device)          # (before the roofline leg: that one's launches must be the process's last)
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel, measured live with HIP events on the launch stream ------
         # --roofline-reps EAGER steps, one event pair per launch.  They come after every other leg that launches these kernels, so
         # they are the last launches of the dominant kernel in the process: tools/summarize_profile.py averages exactly those launches
@@ -566,7 +630,7 @@ def main(argv=None):
                 par["note"] = "bf16 relation tiles (configs[4]); against the REFERENCE itself: golden g20 under -m gpu"
                 par["policy"] = {"applies": True, "rule": "|lp - lp64| <= 4 hops x 2^-9 x L (= 12) + 2 x the oracle's own fp32 noise + 1e-4 where lp64 >= -5; answers equal",
                                  "bound": bound, "max_abs_dlp_vs_fp64_where_lp_ge_-5": got, "pass": bool(got is None or got <= bound) and agree[0] == agree[1]}
-                out["dtype"] = "f32 logic arithmetic on bf16 relation tiles"
+    if rank == 0:
         out["config"]["legs"] = legs_summary(out)
         emit(json.dumps(out))
         sys.stdout.flush()
@@ -830,8 +894,10 @@ def data_main(args, rank, world, device, td, share):
             nq += sum(pb.batch_size() for pb in pbs)
         barrier()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, forward_outputs(res), rank, world)
         # per-kernel device time of one pass over this rank's batches (HIP events on the launch stream)
-        if rank == 0:
+        if rank == 0 and args.full:
             L.enable_kernel_timing(list(L.SIGNATURES))
             for _, items in mine:
                 model(prepare(items), False)
@@ -846,7 +912,7 @@ def data_main(args, rank, world, device, td, share):
     if rank == 0:
         # parity: the oracle on the first batch of every program file of this rank (fp32 and float64), under the tolerance policy
         parity = None
-        if args.cpu_sample != 0:
+        if args.full and args.cpu_sample != 0:
             from oracle import dfol_oracle as orc
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import golden_util as gu
@@ -881,7 +947,6 @@ def data_main(args, rank, world, device, td, share):
                       "policy": {"K": 2.0, "p_tol": 1e-6, "lp_tol": 1e-4, "pass": True}}
             cpu = {"value": checked / t_cpu if t_cpu else None, "unit": "questions/s", "cores": 1, "kind": "port",
                    "sample": "%d questions (the first <= 16 of every program file), numpy fp32 oracle incl. the full tables, %.1f s" % (checked, t_cpu)}
-        dom = max(timing, key=lambda k: timing[k][1])
         out = {"argv": sys.argv[1:], "metric": "questions/sec (GQA programs from .h5 files: %s)" % d, "value": nq / elapsed, "unit": "questions/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
                "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "files: %s" % d,
@@ -894,12 +959,15 @@ def data_main(args, rank, world, device, td, share):
                           "model": "%d -> %d, %d / %d -> %s -> %d -> %d concepts" % (
                               cfg["box_features_dim"], cfg["oracle_input_dim"], cfg["oracle_input_dim"] + 4, 2 * (cfg["oracle_input_dim"] + 4) + 4,
                               cfg["attribute_network_layers_config"], cfg["word_embedding_dim"], len(ontology._vocabulary["idx_to_arg"]))},
-               "error_rate": training.metric_dict(err / np.maximum(cnt, 1)), "ranks": ranks,
+               "error_rate": training.metric_dict(err / np.maximum(cnt, 1)), "ranks": ranks}
+        if args.full:
+            dom = max(timing, key=lambda k: timing[k][1])
+            out.update({
                "kernel_ms_per_pass": {k: round(v[1] * 1e3, 4) for k, v in sorted(timing.items(), key=lambda kv: -kv[1][1])},
                "roofline": {"kernel": dom, "bound": "mfma" if ("pair_ll" in dom or "linear_act" in dom) else "hbm", "achieved": None, "peak": None, "unit": None,
                             "frac": None, "traffic": None, "us_per_launch": timing[dom][1] / timing[dom][0] * 1e6,
                             "note": "the dominant entry point of a pass over the files; its roofline at the benchmark shape is in the north-star line"},
-               "cpu_baseline": cpu if args.cpu_sample != 0 else None, "parity": parity}
+               "cpu_baseline": cpu if args.cpu_sample != 0 else None, "parity": parity})
         emit(json.dumps(out))
         sys.stdout.flush()
     if td is not None:
@@ -1403,14 +1471,20 @@ def train_main(args, rank, world, device, td, share):
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, _ = step()
+        loss, res = step()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        # what the step hands its caller: this rank's loss, the forward's results and the parameters the optimizer step left behind
+        arrays = {"loss": np.array([float(loss)], np.float64)}
+        arrays.update(forward_outputs(res))
+        arrays.update({"param." + k: p for k, p in model.named_parameters() if p.requires_grad})
+        dump_outputs(args.dump_outputs, arrays, rank, world)
     loss = float(loss)
     equal = True
     ranks = rank_report(td, share, device, rank, world, elapsed, args.steps)
     allreduce_ms = None
-    if td is not None:
+    if td is not None and args.full:
         # the collective alone: 10 all-reduces of a bucket-sized buffer, barrier + synchronize on both sides, MAX over ranks
         scratch = torch.zeros_like(bucket.flat)
         for _ in range(3):
@@ -1428,22 +1502,27 @@ def train_main(args, rank, world, device, td, share):
         t = torch.tensor([elapsed], device="cpu" if share else device, dtype=torch.float64)
         td.all_reduce(t, op=td.ReduceOp.MAX)
         elapsed = float(t.item())
-        dg = parallel.parameters_digest(model).to("cpu" if share else device)
-        both = [torch.zeros_like(dg) for _ in range(world)]
-        td.all_gather(both, dg)
-        equal = all(torch.equal(both[0], b) for b in both)
+        equal = None                                         # (checked by --full)
+        if args.full:
+            dg = parallel.parameters_digest(model).to("cpu" if share else device)
+            both = [torch.zeros_like(dg) for _ in range(world)]
+            td.all_gather(both, dg)
+            equal = all(torch.equal(both[0], b) for b in both)
         lt = torch.tensor([loss], device="cpu" if share else device, dtype=torch.float64)
         td.all_reduce(lt)
         loss = float(lt.item())
     # per-kernel times of two more steps (every rank runs them: the step contains the collective; rank 0 keeps the numbers)
+    per_step = {}
+    if args.full:
+        if rank == 0:
+            L.enable_kernel_timing(list(L.SIGNATURES))
+        for _ in range(2):
+            eager_step()
+        torch.cuda.synchronize()
+        if rank == 0:
+            timing = L.disable_kernel_timing()
+            per_step = {k: (n / 2.0, t / 2.0) for k, (n, t) in timing.items() if n}
     if rank == 0:
-        L.enable_kernel_timing(list(L.SIGNATURES))
-    for _ in range(2):
-        eager_step()
-    torch.cuda.synchronize()
-    if rank == 0:
-        timing = L.disable_kernel_timing()
-        per_step = {k: (n / 2.0, t / 2.0) for k, (n, t) in timing.items() if n}
         out = {"metric": "training questions/sec (GQA programs, N=%s objects; forward + backward + all-reduce + clip + Adam)"
                          % (args.objects if not args.ragged else "U{%d..%d}" % (args.ragged, args.objects)),
                "value": gb * args.steps / elapsed, "unit": "questions/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1464,7 +1543,7 @@ def train_main(args, rank, world, device, td, share):
                           "collective": "%s of the flat fp32 bucket per step (%s)" % (
                               "three all-reduces(sum) of contiguous ranges, issued during the backward," if (td is not None and args.overlap_allreduce)
                               else "one all-reduce(sum)", "gloo, shared GPU" if share else "RCCL")},
-               "loss": loss, "replicas_equal": bool(equal), "ranks": ranks, "allreduce_ms": allreduce_ms,
+               "loss": loss, "replicas_equal": None if equal is None else bool(equal), "ranks": ranks, "allreduce_ms": allreduce_ms,
                "allreduce_note": None if allreduce_ms is None else "standalone all-reduce(sum) of a %d-byte fp32 buffer (the gradient bucket's size), mean of 10, max over ranks; "
                                  "inside the step it is %s" % (bucket.nbytes(), "issued per range during the backward" if args.overlap_allreduce else "one call after the backward"),
                "peak_mem_GB": torch.cuda.max_memory_allocated() / 1e9,
@@ -1472,6 +1551,9 @@ def train_main(args, rank, world, device, td, share):
                "kernels": train_kernel_rooflines(args, per_step), "roofline": None, "cpu_baseline": None}
         # the roofline object: the entry point the step spends most time in (the split-kernel GEMMs)
         out["roofline"] = max(out["kernels"], key=lambda k: k["ms_per_step"]) if out["kernels"] else None
+        if not args.full:
+            for k in ("allreduce_ms", "allreduce_note", "kernel_ms_per_step", "kernels", "roofline"):
+                del out[k]
         emit(json.dumps(out))
         sys.stdout.flush()
     if td is not None:

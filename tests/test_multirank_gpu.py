@@ -73,7 +73,7 @@ def test_bench_launches_its_own_ranks(mode):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "16", "--objects", "20",
-           "--cpu-sample", "0", "--stress-preds", "0", "--sustain", "0.2", "--fresh-batches", "3", "--mode", mode]
+           "--cpu-sample", "0", "--stress-preds", "0", "--sustain", "0.2", "--fresh-batches", "3", "--mode", mode, "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -115,7 +115,7 @@ def test_bench_over_rccl_world_size_one(mode, overlap):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "16", "--objects", "20",
-           "--cpu-sample", "0", "--stress-preds", "0", "--sustain", "0.2", "--fresh-batches", "3", "--mode", mode, "--overlap-allreduce", str(overlap)]
+           "--cpu-sample", "0", "--stress-preds", "0", "--sustain", "0.2", "--fresh-batches", "3", "--mode", mode, "--overlap-allreduce", str(overlap), "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = r.stdout.strip().splitlines()
@@ -159,7 +159,7 @@ def test_bench_shards_ragged_scenes_by_cost():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "c3", "--steps", "2", "--warmup", "1", "--batch", "32", "--objects", "40",
-           "--questions-per-image", "4", "--cpu-sample", "0", "--stress-preds", "0", "--sustain", "0.2", "--streamed", "0"]
+           "--questions-per-image", "4", "--cpu-sample", "0", "--stress-preds", "0", "--sustain", "0.2", "--streamed", "0", "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -184,7 +184,7 @@ def test_bench_over_rccl_two_gpus(mode):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "DFOL_BENCH_SHARE_GPU", "DFOL_BENCH_FORCE_PG"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "16", "--objects", "20",
-           "--cpu-sample", "0", "--stress-preds", "0", "--sustain", "0.2", "--fresh-batches", "2", "--mode", mode]
+           "--cpu-sample", "0", "--stress-preds", "0", "--sustain", "0.2", "--fresh-batches", "2", "--mode", mode, "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -211,7 +211,7 @@ def test_bench_on_files_in_the_reference_formats(tmp_path):
             shutil.copy(os.path.join(golden, "h5", f), str(d / "objects" / f))
         elif f.startswith("g18_"):
             shutil.copy(os.path.join(golden, "h5", f), str(d / "programs" / f))
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c3", "--data", str(d), "--batch", "4", "--steps", "16", "--warmup", "2"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c3", "--data", str(d), "--batch", "4", "--steps", "16", "--warmup", "2", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -230,7 +230,7 @@ def test_bench_eight_ranks_share_one_gpu(mode):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "OMP_NUM_THREADS"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--stress-preds", "0",
-           "--sustain", "0.2"]
+           "--sustain", "0.2", "--full"]
     if mode == "c3":
         cmd += ["--workload", "c3", "--batch", "64", "--objects", "40", "--questions-per-image", "1", "--streamed", "0"]
     else:
@@ -257,3 +257,42 @@ def test_bench_eight_ranks_share_one_gpu(mode):
         sh = out["shard"]
         assert len(sh["questions_per_rank"]) == 8 and sum(sh["questions_per_rank"]) == 512
         assert 1.0 <= sh["imbalance_max_over_mean"] <= 1.05, sh
+
+
+@pytest.mark.parametrize("mode", ["infer", "train"])
+def test_bench_plain_run_is_the_headline_and_dumps_its_last_step(tmp_path, mode):
+    """`bench.py` without --full: one JSON line with the headline and none of the other legs, --steps timed steps; --dump-outputs writes what
+    the last timed step returned as float32 / float64 .npy files, and two runs with the same arguments write the same arrays."""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "DFOL_BENCH_SHARE_GPU", "DFOL_BENCH_FORCE_PG"):
+        env.pop(k, None)
+    outs = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "16", "--objects", "20",
+               "--mode", mode, "--dump-outputs", str(tmp_path / run)]
+        r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-1000:]
+        outs.append(json.loads(lines[0]))
+    for out in outs:
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["n_gpus"] == 1
+        assert abs(out["value"] - 16 * 1e3 / out["ms_per_step"]) <= 1e-9 * out["value"]
+        assert out["unit"] == "questions/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+        assert not [k for k in out if k.startswith("value_")], sorted(out)
+        assert all(out.get(k) is None for k in ("roofline", "kernels", "kernel_ms_per_step", "cpu_baseline", "parity", "calibrated", "allreduce_ms"))
+    names = sorted(os.listdir(str(tmp_path / "a")))
+    assert names == sorted(os.listdir(str(tmp_path / "b")))
+    if mode == "infer":
+        assert names == ["answer_count.npy", "answer_index.npy", "answer_log_probability.npy", "log_probability.npy"]
+    else:
+        assert "loss.npy" in names and "log_probability.npy" in names and any(n.startswith("param.") for n in names)
+    total = 0
+    for n in names:
+        a, b = np.load(str(tmp_path / "a" / n)), np.load(str(tmp_path / "b" / n))
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and a.shape == b.shape, n
+        assert np.allclose(a, b, rtol=1e-5, atol=1e-6), (n, float(np.abs(a - b).max()))
+        total += os.path.getsize(str(tmp_path / "a" / n))
+    assert total <= 64e6
+    assert np.load(str(tmp_path / "a" / "log_probability.npy")).shape == (16,)

@@ -228,3 +228,48 @@ def test_bench_launcher_needs_the_gpus_it_is_asked_for():
         return
     r = _bench(["--gpus", "2", "--steps", "1"], {})
     assert r.returncode != 0 and "GPU(s) visible" in r.stderr
+
+
+def test_bench_plain_and_full_options():
+    """A plain run is the headline only; --full turns the other legs on; --dump-outputs names the directory of the last step's outputs."""
+    import bench
+    a = bench.parse(["--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    b = bench.parse(["--full", "--dump-outputs", "out"])
+    assert b.full is True and b.dump_outputs == "out"
+
+
+def test_bench_forward_outputs_as_float_arrays():
+    """What a caller of the forward receives, as float arrays: binary answers as their index in ['no', 'yes'], open answers as their index
+    among the question's own options, flattened with a count per question."""
+    import bench
+    res = {"log_probability": torch.tensor([-0.1, -2.0, -0.5]), "answer": [["yes"], ["no"], ["yes"]], "options": ["no", "yes"],
+           "answer_log_probability": [[-0.1], [-0.14], [-0.5]], "type": QuestionType.BINARY}
+    out = bench.forward_outputs(res)
+    assert out["log_probability"].dtype == np.float32 and out["log_probability"].tolist() == res["log_probability"].tolist()
+    assert out["answer_index"].tolist() == [1, 0, 1] and out["answer_count"].tolist() == [1, 1, 1]
+    assert out["answer_log_probability"].dtype == np.float64 and np.allclose(out["answer_log_probability"], [-0.1, -0.14, -0.5])
+    q = {"log_probability": torch.tensor([-1.0, -3.0], dtype=torch.float64), "answer": [["red", "blue"], ["big"]],
+         "options": [["blue", "red"], ["small", "large"]], "answer_log_probability": [[-1.0, -1.2], [-3.0]], "type": QuestionType.QUERY}
+    out = bench.forward_outputs(q)
+    assert out["log_probability"].dtype == np.float64
+    assert out["answer_index"].tolist() == [1, 0, -1] and out["answer_count"].tolist() == [2, 1]
+    train = bench.forward_outputs({"log_probability": torch.zeros(4, requires_grad=True), "answer": [], "type": QuestionType.BINARY})
+    assert list(train) == ["log_probability"]
+
+
+def test_bench_dump_outputs_stays_within_its_budget(tmp_path):
+    """--dump-outputs writes float32 / float64 .npy files (integers and 16-bit floats widen); an array over its share of the budget keeps a
+    seeded sample of its entries, the same in every run; ranks > 0 write <name>.rank<r>.npy."""
+    import bench
+    big = torch.arange(100000, dtype=torch.float32)
+    arrays = {"small": torch.tensor([1, 2, 3]), "half": torch.ones(5, dtype=torch.bfloat16), "big": big}
+    bench.dump_outputs(str(tmp_path / "a"), arrays, limit=40000)
+    bench.dump_outputs(str(tmp_path / "b"), arrays, limit=40000)
+    bench.dump_outputs(str(tmp_path / "r"), arrays, rank=1, world=2, limit=40000)
+    small, half, b = (np.load(str(tmp_path / "a" / (n + ".npy"))) for n in ("small", "half", "big"))
+    assert small.dtype == np.float64 and small.tolist() == [1, 2, 3] and half.dtype == np.float32 and half.tolist() == [1.0] * 5
+    assert b.dtype == np.float32 and 0 < b.nbytes <= 40000 - small.nbytes - half.nbytes and b.size < big.numel()
+    assert np.array_equal(b, np.load(str(tmp_path / "b" / "big.npy"))) and np.all(np.diff(b) > 0)
+    assert sorted(os.listdir(str(tmp_path / "r"))) == ["big.rank1.npy", "half.rank1.npy", "small.rank1.npy"]
+    assert np.load(str(tmp_path / "r" / "big.rank1.npy")).nbytes <= 20000

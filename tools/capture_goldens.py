@@ -1243,6 +1243,41 @@ def g24():
     save("g24_calibrator_train_step", arrays, meta)
 
 
+# ---------------------------------------------------------------------------------------- g25
+def g25():
+    """The GQA metadata the reference ships (data/metadata: attribute, class, relation and vocabulary JSON), the input of
+    tests/test_host_logic.py::test_real_metadata_parses_like_the_reference (2335 argument columns, 333 relations).  The vocabulary keeps the
+    op and argument tables; its image-id tables (85218 entries, 2.4 MB, read by nothing the ontology builds) are stored empty."""
+    src = os.path.join(ref_harness.REF_SRC, "nsvqa", "data", "metadata")
+    dst = os.path.join(OUT, "g25_gqa_metadata")
+    os.makedirs(dst, exist_ok=True)
+    for name in ("gqa_all_attribute.json", "gqa_all_class.json", "gqa_relation.json", "gqa_vocab.json"):
+        with open(os.path.join(src, name)) as f:
+            v = json.load(f)
+        if name == "gqa_vocab.json":
+            v = {k: v[k] for k in ("op_to_idx", "idx_to_op", "arg_to_idx", "idx_to_arg")}
+            v.update({"img_to_idx": {}, "idx_to_img": []})
+        with open(os.path.join(dst, name), "w") as f:
+            json.dump(v, f)
+    print("wrote g25_gqa_metadata")
+
+
+# ---------------------------------------------------------------------------------------- g26
+def g26():
+    """The reference's config YAMLs (config/sample_config.yaml and config/curriculum_training/cur0..cur7), parsed, keyed by their path under
+    config/: the inputs of tests/test_host_logic.py::test_reference_config_yamls_build (parameter counts of every curriculum phase)."""
+    import glob
+    import yaml
+    base = os.path.join(os.path.dirname(ref_harness.REF_SRC), "config")
+    cfgs = {}
+    for f in sorted(glob.glob(os.path.join(base, "**", "*.yaml"), recursive=True)):
+        with open(f) as fh:
+            cfgs[os.path.relpath(f, base)] = yaml.load(fh, Loader=yaml.FullLoader)
+    with open(os.path.join(OUT, "g26_reference_configs.json"), "w") as f:
+        json.dump({"source": "config/**/*.yaml", "configs": cfgs}, f, indent=1, sort_keys=True)
+    print("wrote g26_reference_configs", len(cfgs))
+
+
 # ---------------------------------------------------------------------------------------- g22
 def g22():
     """The argument vocabulary the reference ships (data/metadata/gqa_vocab.json: idx_to_arg, 2335 names - the table columns of SURVEY 8(a) a3):

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/order_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace -d $OUT/trace -o run -- python3 $R/bench.py --mode train --steps 6 --warmup 2 --cpu-sample 0 --stress-preds 0 --sustain 0 "$@" > $OUT/bench.log 2>&1
+rocprofv3 --kernel-trace -d $OUT/trace -o run -- python3 $R/bench.py --full --mode train --steps 6 --warmup 2 --cpu-sample 0 --stress-preds 0 --sustain 0 "$@" > $OUT/bench.log 2>&1
 cd $R
 tail -1 $OUT/bench.log | cut -c1-300
 python3 - "$OUT" > $R/gpurun_out/order_$TAG.txt <<'PY'

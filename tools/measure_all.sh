@@ -11,26 +11,26 @@ mkdir -p $O
 bash tools/profile_bench.sh $TAG > $O/prof.log 2>&1
 cp gpurun_out/prof_$TAG/summary.md $O/rocprof_summary.md 2>/dev/null
 cp gpurun_out/prof_$TAG/traffic.json $O/traffic.json 2>/dev/null && cp $O/traffic.json profiles/traffic.json
-timeout 600 python bench.py > $O/bench_n100.json 2> $O/bench_n100.err
-timeout 300 python bench.py --workload c1 > $O/bench_c1_n36.json 2> $O/bench_c1.err
-timeout 600 python bench.py --workload c4 --steps 10 > $O/bench_c4_n256.json 2> $O/bench_c4.err
-timeout 300 python bench.py --workload c3 > $O/bench_c3_shared.json 2> $O/bench_c3.err
-timeout 300 python bench.py --workload c3 --share-scenes 0 --cpu-sample 0 --stress-preds 0 > $O/bench_c3_unshared.json 2>> $O/bench_c3.err
+timeout 600 python bench.py --full > $O/bench_n100.json 2> $O/bench_n100.err
+timeout 300 python bench.py --full --workload c1 > $O/bench_c1_n36.json 2> $O/bench_c1.err
+timeout 600 python bench.py --full --workload c4 --steps 10 > $O/bench_c4_n256.json 2> $O/bench_c4.err
+timeout 300 python bench.py --full --workload c3 > $O/bench_c3_shared.json 2> $O/bench_c3.err
+timeout 300 python bench.py --full --workload c3 --share-scenes 0 --cpu-sample 0 --stress-preds 0 > $O/bench_c3_unshared.json 2>> $O/bench_c3.err
 cp gpurun_out/prof_$TAG/roofline_rocprof_merged.json $O/roofline_rocprof.json 2>/dev/null
 timeout 300 python tools/bench_kernels.py > $O/kernel_microbench.jsonl 2> $O/kb.err
 # the north-star line with round 3's arithmetic (three bf16 pieces, six products) and on the fp32 pipe, for the A/B table of DESIGN 3.4
-DFOL_PAIR_MATH=bf16x3 DFOL_DENSE_MATH=bf16x3 timeout 300 python bench.py --steps 50 --cpu-sample 0 --stress-preds 0 --fresh-batches 0 --streamed 0 --sustain 0 > $O/bench_n100_bf16x3.json 2>> $O/bench_n100.err
-DFOL_PAIR_MATH=f32 DFOL_DENSE_MATH=f32 timeout 300 python bench.py --steps 50 --cpu-sample 0 --stress-preds 0 --fresh-batches 0 --streamed 0 --sustain 0 > $O/bench_n100_f32pipe.json 2>> $O/bench_n100.err
+DFOL_PAIR_MATH=bf16x3 DFOL_DENSE_MATH=bf16x3 timeout 300 python bench.py --full --steps 50 --cpu-sample 0 --stress-preds 0 --fresh-batches 0 --streamed 0 --sustain 0 > $O/bench_n100_bf16x3.json 2>> $O/bench_n100.err
+DFOL_PAIR_MATH=f32 DFOL_DENSE_MATH=f32 timeout 300 python bench.py --full --steps 50 --cpu-sample 0 --stress-preds 0 --fresh-batches 0 --streamed 0 --sustain 0 > $O/bench_n100_f32pipe.json 2>> $O/bench_n100.err
 timeout 300 python tools/bench_ops.py > $O/ops_throughput.jsonl 2> $O/ops.err
 for a in "--objects 36" "--objects 100" "--objects 100 --ragged 10" "--objects 100 --calibrator 1" "--objects 100 --mlp-math bf16" "--objects 100 --graph 0" "--objects 100 --calibrator 1 --graph 0" "--objects 100 --hops ragged" "--objects 100 --hops ragged --mlp-math bf16"; do
-  timeout 300 python bench.py --mode train --steps 10 $a >> $O/train_step.jsonl 2>> $O/train.err
+  timeout 300 python bench.py --full --mode train --steps 10 $a >> $O/train_step.jsonl 2>> $O/train.err
 done
-DFOL_BF16_STORE=0 timeout 300 python bench.py --mode train --steps 10 --objects 100 --mlp-math bf16 >> $O/train_step_bf16_fp32_storage.jsonl 2>> $O/train.err
+DFOL_BF16_STORE=0 timeout 300 python bench.py --full --mode train --steps 10 --objects 100 --mlp-math bf16 >> $O/train_step_bf16_fp32_storage.jsonl 2>> $O/train.err
 timeout 200 python tools/lab/bf16_store_lab.py > $O/bf16_storage_kernels.txt 2>&1
-DFOL_BENCH_FORCE_PG=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29611 timeout 300 python bench.py --gpus 1 --steps 10 --mode train --objects 36 --overlap-allreduce 1 > $O/train_rccl_world1.json 2> $O/train_rccl1.err
-DFOL_BENCH_FORCE_PG=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29612 timeout 300 python bench.py --gpus 1 --steps 10 --mode train --objects 100 --calibrator 1 > $O/train_rccl_world1_cal.json 2>> $O/train_rccl1.err
-DFOL_BENCH_SHARE_GPU=1 timeout 300 python bench.py --gpus 2 --steps 10 > $O/bench_2ranks_one_gpu.json 2> $O/bench_2r.err
-DFOL_BENCH_SHARE_GPU=1 timeout 300 python bench.py --gpus 2 --steps 10 --mode train --objects 36 > $O/train_2ranks_one_gpu.json 2> $O/train_2r.err
+DFOL_BENCH_FORCE_PG=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29611 timeout 300 python bench.py --full --gpus 1 --steps 10 --mode train --objects 36 --overlap-allreduce 1 > $O/train_rccl_world1.json 2> $O/train_rccl1.err
+DFOL_BENCH_FORCE_PG=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29612 timeout 300 python bench.py --full --gpus 1 --steps 10 --mode train --objects 100 --calibrator 1 > $O/train_rccl_world1_cal.json 2>> $O/train_rccl1.err
+DFOL_BENCH_SHARE_GPU=1 timeout 300 python bench.py --full --gpus 2 --steps 10 > $O/bench_2ranks_one_gpu.json 2> $O/bench_2r.err
+DFOL_BENCH_SHARE_GPU=1 timeout 300 python bench.py --full --gpus 2 --steps 10 --mode train --objects 36 > $O/train_2ranks_one_gpu.json 2> $O/train_2r.err
 timeout 300 python tools/bench_calibrated.py > $O/calibrated_forward.txt 2>&1
 bash tools/step_breakdown.sh ${TAG}_n100 > $O/step_breakdown_n100.md 2>&1
 bash tools/step_breakdown.sh ${TAG}_n36 --objects 36 > $O/step_breakdown_n36.md 2>&1

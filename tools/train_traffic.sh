@@ -8,8 +8,8 @@ cd $R
 O=gpurun_out/$TAG
 mkdir -p $O
 for m in fp32 bf16; do
-  bash tools/pmc_run.sh ${TAG}_train_fetch_$m "FETCH_SIZE" bench.py --mode train --objects 100 --steps 3 --warmup 1 --graph 0 --cpu-sample 0 --mlp-math $m > $O/pmc_train_fetch_$m.txt 2>&1
-  bash tools/pmc_run.sh ${TAG}_train_write_$m "WRITE_SIZE" bench.py --mode train --objects 100 --steps 3 --warmup 1 --graph 0 --cpu-sample 0 --mlp-math $m > $O/pmc_train_write_$m.txt 2>&1
+  bash tools/pmc_run.sh ${TAG}_train_fetch_$m "FETCH_SIZE" bench.py --full --mode train --objects 100 --steps 3 --warmup 1 --graph 0 --cpu-sample 0 --mlp-math $m > $O/pmc_train_fetch_$m.txt 2>&1
+  bash tools/pmc_run.sh ${TAG}_train_write_$m "WRITE_SIZE" bench.py --full --mode train --objects 100 --steps 3 --warmup 1 --graph 0 --cpu-sample 0 --mlp-math $m > $O/pmc_train_write_$m.txt 2>&1
 done
 python3 - $O $TAG <<'PY' > $O/train_traffic.md
 import re, sys, os
