@@ -58,6 +58,49 @@ __device__ __forceinline__ float dfol_lnot(float x) { return dfol_slog(1.0f - df
 // util.py:46-47 with beta = 1:  log(max(alpha + (1 - 2 alpha) e^x, eps)); c = 1 - 2 alpha
 __device__ __forceinline__ float dfol_pnot(float x, float alpha, float c) { return dfol_slog(alpha + c * dfol_exp(x)); }
 
+// ---- activations ------------------------------------------------------------------------------------------------------------------
+// Sigmoid on the hardware exp2 / rcp (1 ulp each, absolute error < 2e-7), the form of the streaming kernels and the producers of the
+// matrix-pipe kernels: it ignores -DDFOL_PRECISE_MATH.
+__device__ __forceinline__ float dfol_sigmoid_hw(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896340736f * x)); }
+// its derivative h (1 - h), h = dfol_sigmoid_hw(x)
+__device__ __forceinline__ float dfol_dsigmoid_hw(float x) {
+    const float h = dfol_sigmoid_hw(x);
+    return h * (1.0f - h);
+}
+
+// The epilogue activations of the matrix-pipe linear kernels: branch-free forms on dfol_exp / dfol_log and the hardware rcp (1 ulp each;
+// absolute error < 2e-7 on these ranges).  They follow -DDFOL_PRECISE_MATH through dfol_exp / dfol_log.
+template <int ACT>
+__device__ __forceinline__ float dfol_act(float x) {
+    if (ACT == DFOL_ACT_SIGMOID) return __builtin_amdgcn_rcpf(1.0f + dfol_exp(-x));
+    if (ACT == DFOL_ACT_ELU) return fmaxf(x, dfol_exp(fminf(x, 0.f)) - 1.0f);
+    if (ACT == DFOL_ACT_LOGSIGMOID) return fminf(x, 0.f) - dfol_log(1.0f + dfol_exp(-fabsf(x)));
+    return x;
+}
+
+// ---- object pairs -----------------------------------------------------------------------------------------------------------------
+// batch_gqa_boxfeatures_pipeline.py:263-279: {distance, angle, sign dx, sign dy} of subject box ps and object box po ({x, y, w, h})
+__device__ __forceinline__ float4 dfol_pair_geometry(const float* ps, const float* po) {
+    const float x1 = ps[0], y1 = ps[1], w1 = ps[2], h1 = ps[3], x2 = po[0], y2 = po[1], w2 = po[2], h2 = po[3];
+    const float dx = x1 + w1 / 2.0f - x2 - w2 / 2.0f, dy = y1 + h1 / 2.0f - y2 - h2 / 2.0f;
+    const float dist = sqrtf(dx * dx + dy * dy);
+    return make_float4(dist, asinf(dy / fmaxf(dist, 1e-10f)), (x2 - x1 > 0.f) ? 1.f : ((x2 - x1 < 0.f) ? -1.f : 0.f),
+                       (y2 - y1 > 0.f) ? 1.f : ((y2 - y1 < 0.f) ? -1.f : 0.f));
+}
+
+// Ordered pair e of an image of n >= 2 objects, the diagonal left out (util.py:87-103): subject s = e / (n - 1), object o != s
+__device__ __forceinline__ void dfol_offdiag_slot(int e, int n, int& s, int& o) {
+    s = e / (n - 1);
+    const int oo = e - s * (n - 1);
+    o = oo + (oo >= s);
+}
+// The same without the integer-division sequence: (e + 0.5) / (n - 1) is at least 0.5 / (n - 1) away from an integer
+__device__ __forceinline__ void dfol_offdiag_slot_rcp(int e, int n, int& s, int& o) {
+    s = (int)(((float)e + 0.5f) * __builtin_amdgcn_rcpf((float)(n - 1)));
+    const int oo = e - s * (n - 1);
+    o = oo + (oo >= s);
+}
+
 // ---- EXISTS aggregation without cancellation ----------------------------------------------------------
 // The reference aggregates an EXISTS variable as  log_not(sum_i log_not(u_i)) = log(1 - prod_i (1 - y_i)),  y_i = e^{u_i}
 // (util.py:35-36, batch_base_ops.py:102-133, batch_base_types.py:115-123).  Evaluated as written in fp32, every factor 1 - y_i is

@@ -244,6 +244,7 @@ __global__ void pair_features_kernel(const float* __restrict__ obj, int64_t ld_o
         if (f < D) v = fs[f];
         else if (f < 2 * D) v = fo[f - D];
         else {
+            // (dfol_pair_geometry, written out: this thread needs one of the four, and the call changes the kernel's code)
             const float x1 = fs[D - 4], y1 = fs[D - 3], w1 = fs[D - 2], h1 = fs[D - 1];
             const float x2 = fo[D - 4], y2 = fo[D - 3], w2 = fo[D - 2], h2 = fo[D - 1];
             const float dx = x1 + w1 / 2.0f - x2 - w2 / 2.0f, dy = y1 + h1 / 2.0f - y2 - h2 / 2.0f;   // :271-272
@@ -361,19 +362,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const bool valid = e_slot < n * n;
     const int s = valid ? e_slot / n : 0, o = valid ? e_slot - s * n : 0;
 
-    // geometry of this lane's pair: batch_gqa_boxfeatures_pipeline.py:260-279
-    float geo[4];
-    {
-        const float* ps = pos + (int64_t)(first + s) * ld_pos;
-        const float* po = pos + (int64_t)(first + o) * ld_pos;
-        const float x1 = ps[0], y1 = ps[1], w1 = ps[2], h1 = ps[3], x2 = po[0], y2 = po[1], w2 = po[2], h2 = po[3];
-        const float dx = x1 + w1 / 2.0f - x2 - w2 / 2.0f, dy = y1 + h1 / 2.0f - y2 - h2 / 2.0f;
-        const float dist = sqrtf(dx * dx + dy * dy);
-        geo[0] = dist;
-        geo[1] = asinf(dy / fmaxf(dist, 1e-10f));
-        geo[2] = (x2 - x1 > 0.f) ? 1.f : ((x2 - x1 < 0.f) ? -1.f : 0.f);
-        geo[3] = (y2 - y1 > 0.f) ? 1.f : ((y2 - y1 < 0.f) ? -1.f : 0.f);
-    }
+    const float4 geo = dfol_pair_geometry(pos + (int64_t)(first + s) * ld_pos, pos + (int64_t)(first + o) * ld_pos);     // this lane's pair
     for (int i = tid; i < HID1; i += 256) *reinterpret_cast<float4*>(&Wgs[i * 4]) = *reinterpret_cast<const float4*>(Wg + i * 4);
 
     const float* Urow = UV + (int64_t)(first + s) * ld_uv;
@@ -418,7 +407,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             for (int c = 0; c < 4; ++c) {
                 const int kk = k0 + 16 * half + 4 * j + c, k = KEXACT ? kk : min(kk, HID1 - 1);
                 const float4 g = *reinterpret_cast<const float4*>(&Wgs[k * 4]);
-                float z = uu[c] + vv[c] + (g.x * geo[0] + g.y * geo[1] + g.z * geo[2] + g.w * geo[3]);
+                float z = uu[c] + vv[c] + (g.x * geo.x + g.y * geo.y + g.z * geo.z + g.w * geo.w);
                 z = z > 0.f ? z : dfol_exp(z) - 1.0f;       // nn.ELU (hardware exp: abs error < 1e-7 on a hidden activation)
                 a[4 * j + c] = (KEXACT || kk < HID1) ? z : 0.f;
             }
@@ -591,18 +580,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int e_slot = tb * 128 + wave * 16 + r16;
     const bool valid = e_slot < n * n;
     const int s = valid ? e_slot / n : 0, o = valid ? e_slot - s * n : 0;
-    float geo[4];
-    {
-        const float* ps = pos + (int64_t)(first + s) * ld_pos;
-        const float* po = pos + (int64_t)(first + o) * ld_pos;
-        const float x1 = ps[0], y1 = ps[1], w1 = ps[2], h1 = ps[3], x2 = po[0], y2 = po[1], w2 = po[2], h2 = po[3];
-        const float dx = x1 + w1 / 2.0f - x2 - w2 / 2.0f, dy = y1 + h1 / 2.0f - y2 - h2 / 2.0f;
-        const float dist = sqrtf(dx * dx + dy * dy);
-        geo[0] = dist;
-        geo[1] = asinf(dy / fmaxf(dist, 1e-10f));
-        geo[2] = (x2 - x1 > 0.f) ? 1.f : ((x2 - x1 < 0.f) ? -1.f : 0.f);
-        geo[3] = (y2 - y1 > 0.f) ? 1.f : ((y2 - y1 < 0.f) ? -1.f : 0.f);
-    }
+    const float4 geo = dfol_pair_geometry(pos + (int64_t)(first + s) * ld_pos, pos + (int64_t)(first + o) * ld_pos);
     for (int i = tid; i < HID1; i += 512) *reinterpret_cast<float4*>(&Wgs[i * 4]) = *reinterpret_cast<const float4*>(Wg + i * 4);
     const float* Urow = UV + (int64_t)(first + s) * ld_uv;
     const float* Vrow = UV + (int64_t)(first + o) * ld_uv + HID1;
@@ -639,7 +617,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const float4 g = *reinterpret_cast<const float4*>(&Wgs[(k0 + 8 * kh + 4 * j + c) * 4]);
-                float z = uu[c] + vv[c] + (g.x * geo[0] + g.y * geo[1] + g.z * geo[2] + g.w * geo[3]);
+                float z = uu[c] + vv[c] + (g.x * geo.x + g.y * geo.y + g.z * geo.z + g.w * geo.w);
                 a[4 * j + c] = z > 0.f ? z : dfol_exp(z) - 1.0f;      // nn.ELU
             }
         }

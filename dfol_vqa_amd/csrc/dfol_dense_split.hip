@@ -16,6 +16,7 @@
 // column blocks of a row block run on the same XCD and hit its L2).
 // -DDFOL_DENSE_TRACE: clock64 stamps of one workgroup (tools/scratch/trace_dense.py).
 #include "dfol_common.h"
+#include "dfol_split.h"
 
 #include <stdlib.h>
 
@@ -29,10 +30,6 @@ __device__ long long dfol_dense_trace_buf[4 * 64];
 #endif
 
 namespace {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int LS_BM = 128, LS_BN = 128, LS_BK = 32;
 // Two measured variants of the step loop for the two-piece kernels, both OFF: -DLS_DOUBLE_BUFFER=1 (two LDS buffers, one barrier per step)
@@ -56,56 +53,11 @@ constexpr int LS_BM = 128, LS_BN = 128, LS_BK = 32;
 #define LS_XRING 2                // steps of X rows in flight in the double-buffered form (register sets of 16 per 128-row block)
 #endif
 
-__device__ __forceinline__ int ls_swz(int row) { return (4 - ((row >> 2) & 3)) & 3; }
-__device__ __forceinline__ void ls_split(float x, uint32_t& h, uint32_t& m, uint32_t& l) {
-    h = __float_as_uint(x);
-    const float r = x - __uint_as_float(h & 0xffff0000u);
-    m = __float_as_uint(r);
-    l = __float_as_uint(r - __uint_as_float(m & 0xffff0000u));
-}
-__device__ __forceinline__ uint32_t ls_pack(uint32_t x0, uint32_t x1) { return __builtin_amdgcn_perm(x1, x0, 0x07060302u); }
-
-// 8 consecutive fp32 -> the three 8 x bf16 pieces
-__device__ __forceinline__ void ls_split8(const float4& a, const float4& b, u32x4& h, u32x4& m, u32x4& l) {
-    const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    uint32_t ph[8], pm[8], pl[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ls_split(v[j], ph[j], pm[j], pl[j]);
-    h = u32x4{ls_pack(ph[0], ph[1]), ls_pack(ph[2], ph[3]), ls_pack(ph[4], ph[5]), ls_pack(ph[6], ph[7])};
-    m = u32x4{ls_pack(pm[0], pm[1]), ls_pack(pm[2], pm[3]), ls_pack(pm[4], pm[5]), ls_pack(pm[6], pm[7])};
-    l = u32x4{ls_pack(pl[0], pl[1]), ls_pack(pl[2], pl[3]), ls_pack(pl[4], pl[5]), ls_pack(pl[6], pl[7])};
-}
-
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-// NP = 2, round 4: TWO fp16 pieces per operand x = h + l (h = fp16(x), l = fp16(x - h), round to nearest even; x - h is exact) and
-// THREE products xl wh + xh wl + xh wh on v_mfma_f32_16x16x32_f16 (csrc/dfol_pair_h2.hip has the accuracy story: 22 - 23 significand bits
-// per operand, the dropped product below 2^-22; every row of W is scaled by its own power of two at pack time so that its low pieces
-// are normal fp16 numbers, and the epilogue multiplies the accumulator by 2^-e_n).  X is split UNSCALED: an element's error is
-// max(2^-22 |x|, 2^-25) - fp32-class for activations of order 1 (features, Sigmoid / ELU outputs: the forward products), and NOT for
-// operands of arbitrary magnitude (gradients): the backward products stay on the three bf16 pieces, whose exponent range is fp32's.
-// |x| > 65504 overflows fp16 (the result is NaN, loudly).
-__device__ __forceinline__ void ls_split2h(float x0, float x1, uint32_t& h, uint32_t& l) {
-    const f32x2 x = {x0, x1};
-    const f16x2 hh = __builtin_convertvector(x, f16x2);
-    const f32x2 r = x - __builtin_convertvector(hh, f32x2);
-    h = __builtin_bit_cast(uint32_t, hh);
-    l = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, f16x2));
-}
-__device__ __forceinline__ void ls_split8h(const float4& a, const float4& b, u32x4& h, u32x4& l) {
-    uint32_t hh[4], ll[4];
-    ls_split2h(a.x, a.y, hh[0], ll[0]);
-    ls_split2h(a.z, a.w, hh[1], ll[1]);
-    ls_split2h(b.x, b.y, hh[2], ll[2]);
-    ls_split2h(b.z, b.w, hh[3], ll[3]);
-    h = u32x4{hh[0], hh[1], hh[2], hh[3]};
-    l = u32x4{ll[0], ll[1], ll[2], ll[3]};
-}
-// two fp32 -> two bf16, round to nearest even (v_cvt_pk_bf16_f32): the operand form of the bf16 mode (NP = 1)
-__device__ __forceinline__ uint32_t ls_rne2(float x0, float x1) { return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{x0, x1}, bf16x2)); }
+// NP = 2, round 4: TWO fp16 pieces per operand (dfol_split2h) and THREE products xl wh + xh wl + xh wh on v_mfma_f32_16x16x32_f16; every
+// row of W is scaled by its own power of two at pack time (dfol_scale_exp) and the epilogue multiplies the accumulator by 2^-e_n.  X is
+// split UNSCALED: an element's error is max(2^-22 |x|, 2^-25) - fp32-class for activations of order 1 (features, Sigmoid / ELU outputs:
+// the forward products), and NOT for operands of arbitrary magnitude (gradients): the backward products stay on the three bf16 pieces
+// (dfol_split3), whose exponent range is fp32's.  NP = 1, the bf16 mode: one piece, rounded to nearest even (dfol_rne2).
 
 // np = 2: one wavefront per (padded) row of W: e_n puts the row's largest magnitude into [2^13, 2^14); tail[n] = 2^-e_n, tail[rows + n] = e_n.
 __global__ void linear_row_scale_kernel(const float* __restrict__ W, int64_t ldw, int N, int K, int rows, float* __restrict__ tail) {
@@ -116,13 +68,7 @@ __global__ void linear_row_scale_kernel(const float* __restrict__ W, int64_t ldw
         for (int k = lane; k < K; k += 64) m = fmaxf(m, fabsf(W[(int64_t)n * ldw + k]));
 #pragma unroll
     for (int s = 32; s >= 1; s >>= 1) m = fmaxf(m, __shfl_xor(m, s, 64));
-    int e = 0;
-    if (m > 0.f && m < 3.0e38f) {
-        int x;
-        (void)frexpf(m, &x);
-        e = 14 - x;
-        e = e < -100 ? -100 : (e > 100 ? 100 : e);
-    }
+    const int e = dfol_scale_exp(m);
     if (lane == 0) {
         tail[n] = ldexpf(1.0f, -e);
         reinterpret_cast<int32_t*>(tail)[rows + n] = e;
@@ -140,14 +86,14 @@ __global__ void linear_pack_w_split_kernel(const float* __restrict__ W, int64_t 
     const int64_t tile = idx / tile_pieces;
     const int ks = (int)(tile % ksteps), nb = (int)(tile / ksteps);
     const int p = rem / (LS_BN * 4), rr = rem - p * LS_BN * 4, r = rr >> 2, slot = rr & 3;
-    const int kq = slot ^ ls_swz(r), n = nb * LS_BN + r, k0 = ks * LS_BK + kq * 8;
+    const int kq = slot ^ dfol_swz(r), n = nb * LS_BN + r, k0 = ks * LS_BK + kq * 8;
     uint32_t piece[8];
     float w[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         w[j] = (n < N && k0 + j < K) ? W[(int64_t)n * ldw + k0 + j] : 0.f;
         uint32_t h, m, l;
-        ls_split(w[j], h, m, l);
+        dfol_split3(w[j], h, m, l);
         piece[j] = p == 0 ? h : (p == 1 ? m : l);
     }
     if (np == 2) {
@@ -156,12 +102,12 @@ __global__ void linear_pack_w_split_kernel(const float* __restrict__ W, int64_t 
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             uint32_t h, l;
-            ls_split2h(ldexpf(w[2 * j], e), ldexpf(w[2 * j + 1], e), h, l);
+            dfol_split2h(ldexpf(w[2 * j], e), ldexpf(w[2 * j + 1], e), h, l);
             q[j] = p == 0 ? h : l;
         }
         out[idx] = u32x4{q[0], q[1], q[2], q[3]};
-    } else if (np == 1) out[idx] = u32x4{ls_rne2(w[0], w[1]), ls_rne2(w[2], w[3]), ls_rne2(w[4], w[5]), ls_rne2(w[6], w[7])};
-    else out[idx] = u32x4{ls_pack(piece[0], piece[1]), ls_pack(piece[2], piece[3]), ls_pack(piece[4], piece[5]), ls_pack(piece[6], piece[7])};
+    } else if (np == 1) out[idx] = u32x4{dfol_rne2(w[0], w[1]), dfol_rne2(w[2], w[3]), dfol_rne2(w[4], w[5]), dfol_rne2(w[6], w[7])};
+    else out[idx] = u32x4{dfol_pack(piece[0], piece[1]), dfol_pack(piece[2], piece[3]), dfol_pack(piece[4], piece[5]), dfol_pack(piece[6], piece[7])};
 }
 
 // PROD (round 4): the A operand is PRODUCED, not loaded - the backward of the pair MLP's logit layer folded into the input-gradient
@@ -185,20 +131,6 @@ struct LsProducer {
     // when an X element is beyond fp16's largest finite value (its high piece is inf and the products NaN)
     uint32_t* status;
 };
-__device__ __forceinline__ float ls_dsigmoid(float x) {
-    const float h = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896340736f * x));
-    return h * (1.0f - h);
-}
-
-template <int ACT>
-__device__ __forceinline__ float ls_act(float x) {
-    // branch-free forms on the hardware exp / log / rcp (1 ulp each; absolute error < 2e-7 on these ranges)
-    if (ACT == DFOL_ACT_SIGMOID) return __builtin_amdgcn_rcpf(1.0f + dfol_exp(-x));
-    if (ACT == DFOL_ACT_ELU) return fmaxf(x, dfol_exp(fminf(x, 0.f)) - 1.0f);
-    if (ACT == DFOL_ACT_LOGSIGMOID) return fminf(x, 0.f) - dfol_log(1.0f + dfol_exp(-fabsf(x)));
-    return x;
-}
-
 // XV: floats per X load (4: rows 16-byte aligned; 2: rows 8-byte aligned, e.g. the 2054-column raw feature matrix)
 // NT: column tiles of 16 per wavefront - 4, or 2 for a last column block of at most 64 valid columns (N = 300 = 128 + 128 + 44: the third
 // block would otherwise spend a full block's MFMAs on 44 columns, 28 % of the pair layer's forward product)
@@ -252,13 +184,7 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
             const int pc = max(p, 0);
             const float gg = live ? prod.g[rc] : 0.f;
             const float bound = fabsf(gg) * prod.emax[pc] * 0.25f;
-            int e = 0;
-            if (bound > 0.f && bound < 3.0e38f) {
-                int x;
-                (void)frexpf(bound, &x);
-                e = 14 - x;
-                e = e < -100 ? -100 : (e > 100 ? 100 : e);
-            }
+            const int e = dfol_scale_exp(bound);
             gs[h] = ldexpf(gg, e);
             ep[h] = prod.E + (int64_t)pc * prod.ld_e + aq * 8;
             if (aq == 0) Rs[arow + 64 * h] = ldexpf(1.0f, -e);        // read by the epilogue, many barriers later
@@ -266,7 +192,6 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
     }
     // X registers: two steps in flight (HBM latency is longer than one step of 96 MFMAs).  The loads are unconditional - addresses
     // clamped, out-of-range k zeroed afterwards - so that every wavefront issues exactly 4 per step and the vmcnt arithmetic below holds.
-    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
     typedef typename std::conditional<BIO, u32x2, float4>::type XR;  // four consecutive k of a row as loaded
     constexpr int XD = DB ? LS_XRING : 2;                           // X register sets = steps of X in flight
     XR xa[XD][RH][2];                                               // [set][row half][k half]
@@ -309,7 +234,7 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
 #pragma unroll
         for (int h = 0; h < RH; ++h) {
             const int row = arow + 64 * h;
-            const int at = off + row * 4 + (aq ^ ls_swz(row));
+            const int at = off + row * 4 + (aq ^ dfol_swz(row));
             if constexpr (BIO) {
                 const u32x2 zz = u32x2{0u, 0u};
                 const u32x2 v0 = k < K ? xa[S][h][0] : zz, v1 = k + 4 < K ? xa[S][h][1] : zz;
@@ -319,14 +244,14 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
                 float4 v0 = k < K ? xa[S][h][0] : z, v1 = k + 4 < K ? xa[S][h][1] : z;
                 if constexpr (PROD) {
                     auto dp = [&](const float4& x, const float4& e) __attribute__((always_inline)) {
-                        return make_float4((gs[h] * e.x) * ls_dsigmoid(x.x), (gs[h] * e.y) * ls_dsigmoid(x.y), (gs[h] * e.z) * ls_dsigmoid(x.z),
-                                           (gs[h] * e.w) * ls_dsigmoid(x.w));
+                        return make_float4((gs[h] * e.x) * dfol_dsigmoid_hw(x.x), (gs[h] * e.y) * dfol_dsigmoid_hw(x.y), (gs[h] * e.z) * dfol_dsigmoid_hw(x.z),
+                                           (gs[h] * e.w) * dfol_dsigmoid_hw(x.w));
                     };
                     v0 = k < K ? dp(xa[S][h][0], ea[h][0]) : z;
                     v1 = k + 4 < K ? dp(xa[S][h][1], ea[h][1]) : z;
                 }
                 if (NP == 1) {
-                    As[at] = u32x4{ls_rne2(v0.x, v0.y), ls_rne2(v0.z, v0.w), ls_rne2(v1.x, v1.y), ls_rne2(v1.z, v1.w)};
+                    As[at] = u32x4{dfol_rne2(v0.x, v0.y), dfol_rne2(v0.z, v0.w), dfol_rne2(v1.x, v1.y), dfol_rne2(v1.z, v1.w)};
                 } else if (NP == 2) {
                     u32x4 ph, pl;
                     if constexpr (!PROD) {                      // (the produced operand is scaled into range by construction)
@@ -335,12 +260,12 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
                         xmax = fmaxf(fmaxf(xmax, fabsf(v1.x)), fabsf(v1.y));
                         xmax = fmaxf(fmaxf(xmax, fabsf(v1.z)), fabsf(v1.w));
                     }
-                    ls_split8h(v0, v1, ph, pl);
+                    dfol_split2hx8(v0, v1, ph, pl);
                     As[at] = ph;
                     As[BM * 4 + at] = pl;
                 } else {
                     u32x4 ph, pm, pl;
-                    ls_split8(v0, v1, ph, pm, pl);
+                    dfol_split3x8(v0, v1, ph, pm, pl);
                     As[at] = ph;
                     As[BM * 4 + at] = pm;
                     As[2 * BM * 4 + at] = pl;
@@ -365,8 +290,8 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
         for (int i = 0; i < TILE_PIECES / 256; ++i) Bs[off + 256 * i + tid] = wb[i];
     };
 
-    const int aoff = (wm * (16 * RT) + r16) * 4 + (kh ^ ls_swz(r16));
-    const int boff = (wn * WN + r16) * 4 + (kh ^ ls_swz(r16));
+    const int aoff = (wm * (16 * RT) + r16) * 4 + (kh ^ dfol_swz(r16));
+    const int boff = (wn * WN + r16) * 4 + (kh ^ dfol_swz(r16));
 
     u32x4 bq[1][BG ? NT : 1][BG ? NP : 1];                           // BG: the B fragments of the step (requested at its top, under the split of the X rows)
     auto load_bq = [&](int ks, auto set_tag) __attribute__((always_inline)) {
@@ -574,15 +499,14 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
             for (int e = 0; e < 4; ++e)
 #pragma unroll
                 for (int j = 0; j < NT; ++j)
-                    stage[(wm * (16 * RT) + i * 16 + 4 * kh + e) * PITCH + wn * WN + j * 16 + r16] = (uint16_t)ls_rne2(ls_act<ACT>(acc[i][j][e] + bv[j]), 0.f);
+                    stage[(wm * (16 * RT) + i * 16 + 4 * kh + e) * PITCH + wn * WN + j * 16 + r16] = (uint16_t)dfol_rne2(dfol_act<ACT>(acc[i][j][e] + bv[j]), 0.f);
         __syncthreads();
-        typedef uint32_t u32x2s __attribute__((ext_vector_type(2)));
         const int cols = min(N - n0, NT == 4 ? LS_BN : 2 * WN);           // valid columns of this block
 #pragma unroll
         for (int it = 0; it < BM * (LS_BN / 4) / 256; ++it) {
             const int c = tid + 256 * it, row = c / (LS_BN / 4), cc = c % (LS_BN / 4);
             if (m0 + row < M && 4 * cc < cols)
-                *reinterpret_cast<u32x2s*>(Y + (int64_t)(m0 + row) * ldy + n0 + 4 * cc) = *reinterpret_cast<const u32x2s*>(stage + row * PITCH + 4 * cc);
+                *reinterpret_cast<u32x2*>(Y + (int64_t)(m0 + row) * ldy + n0 + 4 * cc) = *reinterpret_cast<const u32x2*>(stage + row * PITCH + 4 * cc);
         }
         return;
     }
@@ -604,7 +528,7 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
                     for (int e = 0; e < 4; ++e)
 #pragma unroll
                         for (int j = 0; j < NT; ++j)
-                            stage[(wm * (16 * IPP) + ii * 16 + 4 * kh + e) * PITCH + wn * WN + j * 16 + r16] = ls_act<ACT>(acc[p * IPP + ii][j][e] + bv[j]);
+                            stage[(wm * (16 * IPP) + ii * 16 + 4 * kh + e) * PITCH + wn * WN + j * 16 + r16] = dfol_act<ACT>(acc[p * IPP + ii][j][e] + bv[j]);
                 __syncthreads();
 #pragma unroll
                 for (int it = 0; it < 16 * RT * (LS_BN / 4) / 256; ++it) {
@@ -628,8 +552,8 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
                             live = pr >= 0;
                             e = *reinterpret_cast<const float4*>(prod.E + (int64_t)max(pr, 0) * prod.ld_e + n0 + 4 * c4);
                         }
-                        float sum = ls_act<DFOL_ACT_SIGMOID>(v.x) * e.x + ls_act<DFOL_ACT_SIGMOID>(v.y) * e.y + ls_act<DFOL_ACT_SIGMOID>(v.z) * e.z +
-                                    ls_act<DFOL_ACT_SIGMOID>(v.w) * e.w;
+                        float sum = dfol_act<DFOL_ACT_SIGMOID>(v.x) * e.x + dfol_act<DFOL_ACT_SIGMOID>(v.y) * e.y + dfol_act<DFOL_ACT_SIGMOID>(v.z) * e.z +
+                                    dfol_act<DFOL_ACT_SIGMOID>(v.w) * e.w;
                         sum = live ? sum : 0.f;
 #pragma unroll
                         for (int sh = 1; sh < 16; sh <<= 1) sum += __shfl_xor(sum, sh, 64);
@@ -661,7 +585,7 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
 #pragma unroll
             for (int e = 0; e < 4; ++e)
 #pragma unroll
-                for (int j = 0; j < NT; ++j) yp[(int64_t)(i * 16 + e) * ldy + j * 16] = out(ls_act<ACT>(acc[i][j][e] + bv[j]));
+                for (int j = 0; j < NT; ++j) yp[(int64_t)(i * 16 + e) * ldy + j * 16] = out(dfol_act<ACT>(acc[i][j][e] + bv[j]));
     } else {
 #pragma unroll
         for (int i = 0; i < RT; ++i)
@@ -670,7 +594,7 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
                 const bool row_ok = m0 + wm * (16 * RT) + i * 16 + 4 * kh + e < M;
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
-                    const float v = ls_act<ACT>(acc[i][j][e] + bv[j]);
+                    const float v = dfol_act<ACT>(acc[i][j][e] + bv[j]);
                     if (row_ok && n0 + wn * WN + j * 16 + r16 < N) yp[(int64_t)(i * 16 + e) * ldy + j * 16] = out(v);
                 }
             }
@@ -687,7 +611,7 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
                 for (int j = 0; j < NT; ++j) {
                     const int col = n0 + wn * WN + j * 16 + r16;
                     if (pr >= 0 && col < N)
-                        sum += ls_act<DFOL_ACT_SIGMOID>(acc[i][j][e] + bv[j]) * (lg_uni ? lg_ej[j] : prod.E[(int64_t)pr * prod.ld_e + col]);
+                        sum += dfol_act<DFOL_ACT_SIGMOID>(acc[i][j][e] + bv[j]) * (lg_uni ? lg_ej[j] : prod.E[(int64_t)pr * prod.ld_e + col]);
                 }
 #pragma unroll
                 for (int sh = 1; sh < 16; sh <<= 1) sum += __shfl_xor(sum, sh, 64);

@@ -18,6 +18,7 @@
 //           comes precomputed (tall_row_scale_kernel: gs[r] = 2^e_r dx[r], rsinv[r] = 2^-e_r)
 //   MODE 2: MODE 0 plus the logit layer's partial sums from the epilogue (see dfol_linear_logit_h2_f32), one slot per column group (4)
 #include "dfol_common.h"
+#include "dfol_split.h"
 
 #include <stdlib.h>
 
@@ -25,47 +26,8 @@
 
 namespace {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int TL_XS = 1408;                                           // floats of per-column / per-row epilogue inputs in LDS (see `xs`)
 constexpr int TL_BM = 128, TL_BK = 32, TL_XD = 4;                     // rows of a block, k of a step, steps of X rows in flight
-
-__device__ __forceinline__ int tl_swz(int row) { return (4 - ((row >> 2) & 3)) & 3; }
-__device__ __forceinline__ void tl_split2h(float x0, float x1, uint32_t& h, uint32_t& l) {
-    const f32x2 x = {x0, x1};
-    const f16x2 hh = __builtin_convertvector(x, f16x2);
-    const f32x2 r = x - __builtin_convertvector(hh, f32x2);
-    h = __builtin_bit_cast(uint32_t, hh);
-    l = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, f16x2));
-}
-__device__ __forceinline__ void tl_split8h(const float4& a, const float4& b, u32x4& h, u32x4& l) {
-    uint32_t hh[4], ll[4];
-    tl_split2h(a.x, a.y, hh[0], ll[0]);
-    tl_split2h(a.z, a.w, hh[1], ll[1]);
-    tl_split2h(b.x, b.y, hh[2], ll[2]);
-    tl_split2h(b.z, b.w, hh[3], ll[3]);
-    h = u32x4{hh[0], hh[1], hh[2], hh[3]};
-    l = u32x4{ll[0], ll[1], ll[2], ll[3]};
-}
-__device__ __forceinline__ float tl_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896340736f * x)); }
-__device__ __forceinline__ float tl_dsigmoid(float x) {
-    const float h = tl_sigmoid(x);
-    return h * (1.0f - h);
-}
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 tl_bf16x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t tl_rne2(float x0, float x1) {     // two fp32 -> two bf16, round to nearest even (v_cvt_pk_bf16_f32)
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{x0, x1}, tl_bf16x2));
-}
-__device__ __forceinline__ float4 tl_widen(const u32x2& v) {
-    return make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u));
-}
 
 struct TlExtra {
     const float* gs;                // MODE 1: 2^e_r dx[r] [M]
@@ -95,7 +57,7 @@ __global__ __launch_bounds__(256) void tall_row_scale_kernel(const float* __rest
         const int p = row_pred[r];
         const float gg = p >= 0 ? dx[r] : 0.f;
         const float bound = fabsf(gg) * emax[max(p, 0)] * 0.25f;
-        int e = 0;
+        int e = 0;                                                    // (dfol_scale_exp, written out: the call changes this kernel's schedule)
         if (bound > 0.f && bound < 3.0e38f) {
             int x;
             (void)frexpf(bound, &x);
@@ -242,16 +204,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     auto store_a = [&](auto set_tag, int off) __attribute__((always_inline)) {
         constexpr int S = decltype(set_tag)::value;
         const int k = sks * TL_BK + aq * 8;
-        const int at = off + arow * 4 + (aq ^ tl_swz(arow));
+        const int at = off + arow * 4 + (aq ^ dfol_swz(arow));
         if constexpr (BIO) {
             const u32x2 zz = u32x2{0u, 0u};
             u32x2 v0 = k < K ? xa[S][0] : zz, v1 = k + 4 < K ? xa[S][1] : zz;
             if constexpr (PROD) {                                     // ((dx E) h) (1 - h), rounded to nearest even: the values dfol_pair_logit_bwd_bf16 stores
                 auto dp = [&](const u32x2& xb, const float4& e) __attribute__((always_inline)) {
-                    const float4 x = tl_widen(xb);
-                    const float h0 = tl_sigmoid(x.x), h1 = tl_sigmoid(x.y), h2 = tl_sigmoid(x.z), h3 = tl_sigmoid(x.w);
-                    return u32x2{tl_rne2(gs_cur * e.x * h0 * (1.0f - h0), gs_cur * e.y * h1 * (1.0f - h1)),
-                                 tl_rne2(gs_cur * e.z * h2 * (1.0f - h2), gs_cur * e.w * h3 * (1.0f - h3))};
+                    const float4 x = dfol_widen(xb);
+                    const float h0 = dfol_sigmoid_hw(x.x), h1 = dfol_sigmoid_hw(x.y), h2 = dfol_sigmoid_hw(x.z), h3 = dfol_sigmoid_hw(x.w);
+                    return u32x2{dfol_rne2(gs_cur * e.x * h0 * (1.0f - h0), gs_cur * e.y * h1 * (1.0f - h1)),
+                                 dfol_rne2(gs_cur * e.z * h2 * (1.0f - h2), gs_cur * e.w * h3 * (1.0f - h3))};
                 };
                 v0 = k < K ? dp(xa[S][0], ea[0]) : zz;
                 v1 = k + 4 < K ? dp(xa[S][1], ea[1]) : zz;
@@ -263,16 +225,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             if constexpr (PROD) {
                 auto dp = [&](const float4& x, const float4& e) __attribute__((always_inline)) {
                     if constexpr (MULTI)                              // (the readers' dx are inside e already: load_e)
-                        return make_float4(e.x * tl_dsigmoid(x.x), e.y * tl_dsigmoid(x.y), e.z * tl_dsigmoid(x.z), e.w * tl_dsigmoid(x.w));
+                        return make_float4(e.x * dfol_dsigmoid_hw(x.x), e.y * dfol_dsigmoid_hw(x.y), e.z * dfol_dsigmoid_hw(x.z), e.w * dfol_dsigmoid_hw(x.w));
                     else
-                        return make_float4((gs_cur * e.x) * tl_dsigmoid(x.x), (gs_cur * e.y) * tl_dsigmoid(x.y), (gs_cur * e.z) * tl_dsigmoid(x.z),
-                                           (gs_cur * e.w) * tl_dsigmoid(x.w));
+                        return make_float4((gs_cur * e.x) * dfol_dsigmoid_hw(x.x), (gs_cur * e.y) * dfol_dsigmoid_hw(x.y), (gs_cur * e.z) * dfol_dsigmoid_hw(x.z),
+                                           (gs_cur * e.w) * dfol_dsigmoid_hw(x.w));
                 };
                 v0 = k < K ? dp(xa[S][0], ea[0]) : z;
                 v1 = k + 4 < K ? dp(xa[S][1], ea[1]) : z;
             }
             u32x4 ph, pl;
-            tl_split8h(v0, v1, ph, pl);
+            dfol_split2hx8(v0, v1, ph, pl);
             tl_sm[at] = ph;
             tl_sm[at + TL_BM * 4] = pl;
         }
@@ -283,12 +245,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     };
 
     // ---- the step's MFMAs
-    const int aoff = (wm * 64 + r16) * 4 + (kh ^ tl_swz(r16));
+    const int aoff = (wm * 64 + r16) * 4 + (kh ^ dfol_swz(r16));
     int boff[NTW];                                                    // fragment of column tile j: block (col >> 7), row col & 127 of its tile
 #pragma unroll
     for (int j = 0; j < NTW; ++j) {
         const int col0 = wn * (16 * NTW) + j * 16;
-        boff[j] = TILE + (col0 >> 7) * TILE + ((col0 & 127) + r16) * 4 + (kh ^ tl_swz(r16));
+        boff[j] = TILE + (col0 >> 7) * TILE + ((col0 & 127) + r16) * 4 + (kh ^ dfol_swz(r16));
     }
     constexpr int PA3[3] = {1, 0, 0}, PB3[3] = {0, 1, 0};             // xl wh, xh wl, xh wh (smallest first)
     auto multiply = [&](int off) __attribute__((always_inline)) {
@@ -406,17 +368,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                             v += bv[j];
                         }
                         if constexpr (BIO) {                          // rounded to nearest even, staged for the 8-byte stores below; what follows sees the stored value
-                            const uint32_t hv = tl_rne2(v, 0.f) & 0xffffu;
+                            const uint32_t hv = dfol_rne2(v, 0.f) & 0xffffu;
                             stage[lrow * PITCH + col] = (uint16_t)hv;
                             v = __uint_as_float(hv << 16);
                         } else {
                             if (row_ok && col < N) Y[(int64_t)row * ldy + col] = v;
                         }
                         if constexpr (LOGIT) {
-                            if constexpr (UNI) sum += tl_sigmoid(v) * le[j];          // (le = 0 in the columns past N)
+                            if constexpr (UNI) sum += dfol_sigmoid_hw(v) * le[j];          // (le = 0 in the columns past N)
                             else if (far) {
-                                if (col < N) sum += tl_sigmoid(v) * ex.E[(int64_t)pr * ex.ld_e + col];
-                            } else if (pr >= 0) sum += tl_sigmoid(v) * (at0 ? le[j] : le1[j]);
+                                if (col < N) sum += dfol_sigmoid_hw(v) * ex.E[(int64_t)pr * ex.ld_e + col];
+                            } else if (pr >= 0) sum += dfol_sigmoid_hw(v) * (at0 ? le[j] : le1[j]);
                         }
                         acc[i][j][e] = 0.f;
                     }
@@ -558,13 +520,7 @@ extern "C" int dfol_linear_tall_h2_f32(const float* X, int64_t ldx, const void* 
 // the bound is zero)
 __global__ void tall_wgrad_scale_kernel(const float* __restrict__ bound_max, float* __restrict__ scale) {
     const float b = bound_max[0];
-    int e = 0;
-    if (b > 0.f && b < 3.0e38f) {
-        int x;
-        (void)frexpf(b, &x);
-        e = 14 - x;
-        e = e < -100 ? -100 : (e > 100 ? 100 : e);
-    }
+    const int e = dfol_scale_exp(b);
     scale[0] = ldexpf(1.0f, e);
     scale[1] = ldexpf(1.0f, -e);
 }
@@ -606,13 +562,7 @@ __global__ __launch_bounds__(256) void tall_row_scale_multi_kernel(const float* 
             g[q] = (p >= 0 && q < nr) ? dx[(int64_t)q * dx_stride + r] : 0.f;
             bound += fabsf(g[q]) * (q < nr ? emax[(int64_t)q * P + max(p, 0)] : 0.f) * 0.25f;
         }
-        int e = 0;
-        if (bound > 0.f && bound < 3.0e38f) {
-            int x;
-            (void)frexpf(bound, &x);
-            e = 14 - x;
-            e = e < -100 ? -100 : (e > 100 ? 100 : e);
-        }
+        const int e = dfol_scale_exp(bound);
 #pragma unroll
         for (int q = 0; q < TL_MAXR; ++q)
             if (q < nr) gs[(int64_t)q * M + r] = ldexpf(g[q], e);

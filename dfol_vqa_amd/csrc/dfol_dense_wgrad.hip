@@ -14,6 +14,7 @@
 // per slab and block group; every slab writes its partial [N, K] block and a second kernel adds the slabs in a FIXED order:
 // no atomics, bit-identical from run to run.
 #include "dfol_common.h"
+#include "dfol_split.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -229,23 +230,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // eight registers, split and packed, is the operand of tile t (same free row / column map as wgrad_tn4_kernel).  Per step of 16 rows
 // and wavefront: 16 loads, 96 MFMAs (3072 cycles) and ~350 VALU instructions of splitting at the top of the step; the next step's rows are
 // in flight under the MFMAs.
-typedef __bf16 w3_bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t w3_u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void w3_split(float x, uint32_t& h, uint32_t& m, uint32_t& l) {
-    h = __float_as_uint(x);
-    const float r = x - __uint_as_float(h & 0xffff0000u);
-    m = __float_as_uint(r);
-    l = __float_as_uint(r - __uint_as_float(m & 0xffff0000u));
-}
-__device__ __forceinline__ uint32_t w3_pack(uint32_t x0, uint32_t x1) { return __builtin_amdgcn_perm(x1, x0, 0x07060302u); }
-__device__ __forceinline__ void w3_split8(const float (&v)[8], w3_u32x4& h, w3_u32x4& m, w3_u32x4& l) {
+__device__ __forceinline__ void w3_split8(const float (&v)[8], u32x4& h, u32x4& m, u32x4& l) {
     uint32_t ph[8], pm[8], pl[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) w3_split(v[j], ph[j], pm[j], pl[j]);
-    h = w3_u32x4{w3_pack(ph[0], ph[1]), w3_pack(ph[2], ph[3]), w3_pack(ph[4], ph[5]), w3_pack(ph[6], ph[7])};
-    m = w3_u32x4{w3_pack(pm[0], pm[1]), w3_pack(pm[2], pm[3]), w3_pack(pm[4], pm[5]), w3_pack(pm[6], pm[7])};
-    l = w3_u32x4{w3_pack(pl[0], pl[1]), w3_pack(pl[2], pl[3]), w3_pack(pl[4], pl[5]), w3_pack(pl[6], pl[7])};
+    for (int j = 0; j < 8; ++j) dfol_split3(v[j], ph[j], pm[j], pl[j]);
+    h = u32x4{dfol_pack(ph[0], ph[1]), dfol_pack(ph[2], ph[3]), dfol_pack(ph[4], ph[5]), dfol_pack(ph[6], ph[7])};
+    m = u32x4{dfol_pack(pm[0], pm[1]), dfol_pack(pm[2], pm[3]), dfol_pack(pm[4], pm[5]), dfol_pack(pm[6], pm[7])};
+    l = u32x4{dfol_pack(pl[0], pl[1]), dfol_pack(pl[2], pl[3]), dfol_pack(pl[4], pl[5]), dfol_pack(pl[6], pl[7])};
 }
 
 // Addressing: the rows of a step come through buffer descriptors rebuilt per step from wave-uniform values (base = the step's first
@@ -258,8 +249,6 @@ __device__ __forceinline__ void w3_split8(const float (&v)[8], w3_u32x4& h, w3_u
 // X three times for the pair layer: 13.9 GB per launch, HBM-bound at 2.96 ms.)  A last group of one or two blocks splits its rows in two
 // halves over the four wavefronts; the second half's accumulators go through LDS and are added by the first half's wavefront - a
 // fixed order.
-typedef uint32_t w3_u32x2 __attribute__((ext_vector_type(2)));
-
 // (every input through readfirstlane: hipcc wraps each buffer load in a waterfall loop unless the descriptor is provably wave-uniform)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t w3_descriptor(const void* base, int64_t bytes) {
     const uint64_t p = reinterpret_cast<uint64_t>(base);
@@ -268,13 +257,11 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t w3_descriptor(const void* base
     return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), 0, n, 0x00020000);
 }
 
-typedef __bf16 w3_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float w3_f32x2 __attribute__((ext_vector_type(2)));
-// eight fp32 -> eight bf16, round to nearest even (v_cvt_pk_bf16_f32): the operand of the bf16 mode (NP = 1)
-__device__ __forceinline__ w3_u32x4 w3_rne8(const float (&v)[8]) {
-    w3_u32x4 r;
+// eight fp32 -> eight bf16, round to nearest even: the operand of the bf16 mode (NP = 1)
+__device__ __forceinline__ u32x4 w3_rne8(const float (&v)[8]) {
+    u32x4 r;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) r[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(w3_f32x2{v[2 * j], v[2 * j + 1]}, w3_bf16x2));
+    for (int j = 0; j < 4; ++j) r[j] = dfol_rne2(v[2 * j], v[2 * j + 1]);
     return r;
 }
 
@@ -305,7 +292,7 @@ __device__ __forceinline__ void wgrad_tn3_accumulate(const float* __restrict__ d
     for (int t = 0; t < AV; ++t) bs[t] = 0.f;
 
     float ra[8][AV];                                                               // the step's dY and X rows: dead once the pieces are built,
-    w3_u32x4 rb[8];                                                                // then refilled with the next step's (in flight under the MFMAs)
+    u32x4 rb[8];                                                                   // then refilled with the next step's (in flight under the MFMAs)
     auto load = [&](int s) __attribute__((always_inline)) {
         const int left = rows - 16 * s;                                            // rows of the range from this step on
         const int64_t bytes_a = left > 0 ? ((int64_t)(left - 1) * ld_dy + N) * 4 : 0, bytes_b = left > 0 ? ((int64_t)(left - 1) * ld_x + K) * 4 : 0;
@@ -313,10 +300,10 @@ __device__ __forceinline__ void wgrad_tn3_accumulate(const float* __restrict__ d
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             if (AV == 4) {
-                const w3_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(da, va[r], 0, 0);
+                const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(da, va[r], 0, 0);
                 ra[r][0] = __uint_as_float(v.x), ra[r][1] = __uint_as_float(v.y), ra[r][2] = __uint_as_float(v.z), ra[r][3] = __uint_as_float(v.w);
             } else {
-                const w3_u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(da, va[r], 0, 0);
+                const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(da, va[r], 0, 0);
                 ra[r][0] = __uint_as_float(v.x), ra[r][1] = __uint_as_float(v.y);
             }
             rb[r] = __builtin_amdgcn_raw_buffer_load_b128(db, vb[r], 0, 0);
@@ -329,7 +316,7 @@ __device__ __forceinline__ void wgrad_tn3_accumulate(const float* __restrict__ d
     load(0);
     __builtin_amdgcn_sched_barrier(0);
     for (int s = 0; s < steps; ++s) {
-        w3_u32x4 ap[AV][NP], bp[4][NP];
+        u32x4 ap[AV][NP], bp[4][NP];
         if (want_bias) {
 #pragma unroll
             for (int t = 0; t < AV; ++t)
@@ -361,8 +348,8 @@ __device__ __forceinline__ void wgrad_tn3_accumulate(const float* __restrict__ d
             for (int t = 0; t < AV; ++t)
 #pragma unroll
                 for (int x = NP == 1 ? 5 : 0; x < 6; ++x)                       // (the bf16 mode keeps the last product: piece 0 x piece 0)
-                    acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(w3_bf16x8, ap[t][PA6[x]]),
-                                                                        __builtin_bit_cast(w3_bf16x8, bp[u][PB6[x]]), acc[t][u], 0, 0, 0);
+                    acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ap[t][PA6[x]]),
+                                                                        __builtin_bit_cast(bf16x8, bp[u][PB6[x]]), acc[t][u], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -397,7 +384,7 @@ __device__ __forceinline__ void wgrad_tn3_accumulate(const uint16_t* __restrict_
     // HBM latency any more, so the rows of W3B_D steps ahead are (a ring of register sets, 32 registers each).
     constexpr int D = W3B_D;
     uint32_t ra[D][8][WA];
-    w3_u32x2 rb[D][8];
+    u32x2 rb[D][8];
     auto load = [&](int s, auto set_tag) __attribute__((always_inline)) {
         constexpr int S = decltype(set_tag)::value;
         const int left = rows - 16 * s;
@@ -406,7 +393,7 @@ __device__ __forceinline__ void wgrad_tn3_accumulate(const uint16_t* __restrict_
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             if (AV == 4) {
-                const w3_u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(da, va[r], 0, 0);
+                const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(da, va[r], 0, 0);
                 ra[S][r][0] = v.x, ra[S][r][WA - 1] = v.y;
             } else {
                 ra[S][r][0] = __builtin_amdgcn_raw_buffer_load_b32(da, va[r], 0, 0);
@@ -417,14 +404,14 @@ __device__ __forceinline__ void wgrad_tn3_accumulate(const uint16_t* __restrict_
     // eight rows' element `odd` of one word each -> the operand's four registers (row 2j in the low half)
     auto gather = [](uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t w4, uint32_t w5, uint32_t w6, uint32_t w7, bool odd)
         __attribute__((always_inline)) {
-        return odd ? w3_u32x4{__builtin_amdgcn_perm(w1, w0, 0x07060302u), __builtin_amdgcn_perm(w3, w2, 0x07060302u),
-                              __builtin_amdgcn_perm(w5, w4, 0x07060302u), __builtin_amdgcn_perm(w7, w6, 0x07060302u)}
-                   : w3_u32x4{__builtin_amdgcn_perm(w1, w0, 0x05040100u), __builtin_amdgcn_perm(w3, w2, 0x05040100u),
-                              __builtin_amdgcn_perm(w5, w4, 0x05040100u), __builtin_amdgcn_perm(w7, w6, 0x05040100u)};
+        return odd ? u32x4{__builtin_amdgcn_perm(w1, w0, 0x07060302u), __builtin_amdgcn_perm(w3, w2, 0x07060302u),
+                           __builtin_amdgcn_perm(w5, w4, 0x07060302u), __builtin_amdgcn_perm(w7, w6, 0x07060302u)}
+                   : u32x4{__builtin_amdgcn_perm(w1, w0, 0x05040100u), __builtin_amdgcn_perm(w3, w2, 0x05040100u),
+                           __builtin_amdgcn_perm(w5, w4, 0x05040100u), __builtin_amdgcn_perm(w7, w6, 0x05040100u)};
     };
     auto one_step = [&](int s, auto set_tag) __attribute__((always_inline)) {
         constexpr int S = decltype(set_tag)::value;
-        w3_u32x4 ap[AV], bp[4];
+        u32x4 ap[AV], bp[4];
         if (want_bias) {
 #pragma unroll
             for (int t = 0; t < AV; ++t) {
@@ -449,7 +436,7 @@ __device__ __forceinline__ void wgrad_tn3_accumulate(const uint16_t* __restrict_
         for (int u = 0; u < 4; ++u)
 #pragma unroll
             for (int t = 0; t < AV; ++t)
-                acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(w3_bf16x8, ap[t]), __builtin_bit_cast(w3_bf16x8, bp[u]), acc[t][u], 0, 0, 0);
+                acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ap[t]), __builtin_bit_cast(bf16x8, bp[u]), acc[t][u], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
     };
     load(0, std::integral_constant<int, 0>());
@@ -762,34 +749,17 @@ extern "C" int dfol_linear_wgrad_bias_bf16_bf16(const void* dY_bf16, int64_t ld_
 // A row's gradient has no natural scale and the contraction runs over the rows, so ONE power of two S for the whole launch (from the
 // caller: S max_r |dx[r]| max|E[p(r)]| / 4 in [2^13, 2^14)) scales dpre2 into fp16's range: an element's error is
 // max(2^-23 |a|, 2^-39 max_r(|dx[r]| max|E[p(r)]|)) - rows that far below the largest do not move the sum.  Z is split unscaled (ELU outputs).
-// one fp32 -> its bfloat16 (round to nearest even) as the bits of the fp32 it widens back to
-__device__ __forceinline__ uint32_t w3_pack1(float x) {
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(w3_f32x2{x, 0.f}, w3_bf16x2)) << 16;
-}
-typedef _Float16 pw_f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 pw_f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int PW_TA = 10, PW_TB = 8;                                   // 32-wide tiles of H2 (<= 320) and of H1 (<= 256)
 constexpr int PW_A_ENT = 2 * 2 * PW_TA * 64, PW_B_ENT = 2 * 2 * PW_TB * 64;   // 16-byte entries per buffer: [k-step][piece][tile][lane]
 constexpr int PW_BUF = PW_A_ENT + PW_B_ENT;
 
-__device__ __forceinline__ void pw_split2(float x0, float x1, uint32_t& h, uint32_t& l) {
-    const w3_f32x2 x = {x0, x1};
-    const pw_f16x2 hh = __builtin_convertvector(x, pw_f16x2);
-    const w3_f32x2 r = x - __builtin_convertvector(hh, w3_f32x2);
-    h = __builtin_bit_cast(uint32_t, hh);
-    l = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, pw_f16x2));
-}
-__device__ __forceinline__ void pw_split8(const float (&v)[8], w3_u32x4& h, w3_u32x4& l) {
+__device__ __forceinline__ void pw_split8(const float (&v)[8], u32x4& h, u32x4& l) {
     uint32_t hh[4], ll[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) pw_split2(v[2 * j], v[2 * j + 1], hh[j], ll[j]);
-    h = w3_u32x4{hh[0], hh[1], hh[2], hh[3]};
-    l = w3_u32x4{ll[0], ll[1], ll[2], ll[3]};
-}
-__device__ __forceinline__ float pw_dsigmoid(float x) {
-    const float h = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896340736f * x));
-    return h * (1.0f - h);
+    for (int j = 0; j < 4; ++j) dfol_split2h(v[2 * j], v[2 * j + 1], hh[j], ll[j]);
+    h = u32x4{hh[0], hh[1], hh[2], hh[3]};
+    l = u32x4{ll[0], ll[1], ll[2], ll[3]};
 }
 
 // CPT: columns of dpre2 per thread - 3 when H2 is a multiple of 3 (HID2 = 300: 100 x 4 = 400 building threads with 24 prefetched registers
@@ -802,7 +772,7 @@ __device__ __forceinline__ float pw_dsigmoid(float x) {
 // SIMD's two wavefronts find each other's gaps.  A pair of rows leaves for LDS as soon as it is built (4-byte pieces of the 16-byte
 // operand entries) and its registers are refilled at once with the same rows of step s + 2: one register set is both the prefetch ring
 // and the work space.
-typedef uint32_t w3_u32x3 __attribute__((ext_vector_type(3)));
+typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
 // SUMS: the sums of the logit layer's backward from the same pass (every h and dx is in registers here): per thread the running sums of
 // dx h (dE of the current predicate) and of dpre2 (db2) over its rows; the dE sums are flushed where the thread's rows cross into the
 // next predicate - its own first row past the boundary, or, for threads whose rows of the boundary step all lie before it, the step
@@ -822,7 +792,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const TIN* __restrict__ Z = reinterpret_cast<const TIN*>(Zv);
     constexpr int EB = sizeof(TIN), NPC = BIO ? 1 : 2;                // bytes per stored element; pieces per operand
     constexpr int A_ENT = 2 * NPC * PW_TA * 64, B_ENT = 2 * NPC * PW_TB * 64, BUFK = A_ENT + B_ENT;      // 16-byte entries: [k-step][piece][tile][lane]
-    extern __shared__ __attribute__((aligned(16))) w3_u32x4 pw_lds[];
+    extern __shared__ __attribute__((aligned(16))) u32x4 pw_lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m_begin = blockIdx.x * rows_per_slab, m_end = min(M, m_begin + rows_per_slab);
     const int steps = (m_end - m_begin + 31) >> 5;
@@ -836,7 +806,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const bool is_z = tid < 4 * QB;
     const int cz = is_z ? tid % QB : 0, oz = is_z ? tid / QB : 0;
 
-    for (int i = tid; i < 2 * BUFK; i += 512) pw_lds[i] = w3_u32x4{0u, 0u, 0u, 0u};      // (columns past the matrices stay zero for good)
+    for (int i = tid; i < 2 * BUFK; i += 512) pw_lds[i] = u32x4{0u, 0u, 0u, 0u};      // (columns past the matrices stay zero for good)
 
     f32x16 acc[5][2];
 #pragma unroll
@@ -849,8 +819,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // The rows of a macro step come through buffer descriptors rebuilt per step from wave-uniform values (base = the step's first row,
     // size = what is left of the slab), with per-lane byte offsets that never change and the row within the octet as the scalar offset:
     // no 64-bit address arithmetic on the vector ALU, and rows past the slab read as zero (dx = 0 switches such a row off).
-    typename std::conditional<BIO, w3_u32x2, typename std::conditional<CPT == 3, w3_u32x3, w3_u32x4>::type>::type xa[8];
-    typename std::conditional<BIO, uint32_t, w3_u32x2>::type xz[8];
+    typename std::conditional<BIO, u32x2, typename std::conditional<CPT == 3, u32x3, u32x4>::type>::type xa[8];
+    typename std::conditional<BIO, uint32_t, u32x2>::type xz[8];
     // The predicate of the step's first row and the row its range ends at, wave-uniform (the rows of a predicate are contiguous and
     // row_pred is non-decreasing): an octet that ends before that row reads the predicate's embedding columns through a uniform base; the
     // few octets at a boundary look their rows up one by one.
@@ -917,7 +887,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     };
     bool same = false;
     float ev[CPT];
-    w3_u32x2 gq;                                                       // dx of the row pair that comes next
+    u32x2 gq;                                                       // dx of the row pair that comes next
     auto begin_a = [&](int s, const Desc& d) __attribute__((always_inline)) {          // before the first pair of rows
         if (is_a) {
             const int goff = k_goff(), col0 = k_col0();
@@ -967,8 +937,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     float xv;
                     if constexpr (BIO) xv = __uint_as_float((t & 1) ? (xa[i][t >> 1] & 0xffff0000u) : (xa[i][t >> 1] << 16));
                     else xv = __uint_as_float(xa[i][t]);
-                    const float hh = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896340736f * xv));
-                    if constexpr (BIO) v[r][t] = __uint_as_float(w3_pack1(gs * e[t] * hh * (1.0f - hh)));      // (the value dfol_pair_logit_bwd_bf16 stores)
+                    const float hh = dfol_sigmoid_hw(xv);
+                    if constexpr (BIO) v[r][t] = __uint_as_float(dfol_rne2(gs * e[t] * hh * (1.0f - hh), 0.f) << 16);      // (the value dfol_pair_logit_bwd_bf16 stores)
                     else v[r][t] = (gs * e[t]) * (hh * (1.0f - hh));
                     if constexpr (SUMS) {
                         sde[t] = fmaf(gs, hh, sde[t]);
@@ -990,20 +960,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     buf32[at] = (__float_as_uint(v[0][t]) >> 16) | (__float_as_uint(v[1][t]) & 0xffff0000u);      // (rounded above: the high halves are the bf16 bits)
                 } else {
                     uint32_t h, l;
-                    pw_split2(v[0][t], v[1][t], h, l);
+                    dfol_split2h(v[0][t], v[1][t], h, l);
                     buf32[at] = h;
                     buf32[at + PW_TA * 64 * 4] = l;
                 }
             }
         }
     };
-    auto columns_z = [&](const Desc& next, w3_u32x4* __restrict__ buf) __attribute__((always_inline)) {
+    auto columns_z = [&](const Desc& next, u32x4* __restrict__ buf) __attribute__((always_inline)) {
         if (is_z) {
             const int at = k_at_z();
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
                 if constexpr (BIO) {                                   // eight rows' halfword c of one word each -> the entry's four words (row 2 j in the low half)
-                    w3_u32x4 en;
+                    u32x4 en;
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
                         en[j] = c ? ((xz[2 * j] >> 16) | (xz[2 * j + 1] & 0xffff0000u)) : ((xz[2 * j] & 0xffffu) | (xz[2 * j + 1] << 16));
@@ -1012,7 +982,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     float v[8];
 #pragma unroll
                     for (int i = 0; i < 8; ++i) v[i] = __uint_as_float(xz[i][c]);
-                    w3_u32x4 h, l;
+                    u32x4 h, l;
                     pw_split8(v, h, l);
                     buf[at + c] = h;
                     buf[at + c + PW_TB * 64] = l;
@@ -1023,20 +993,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     };
     const int ta0 = 5 * (wave >> 2), tb0 = 2 * (wave & 3);
     // one tile row of the step's MFMAs: k-step ks, A tile t against both B tiles (fragments read just before)
-    auto tile_row = [&](const w3_u32x4* __restrict__ buf, int ks, int t) __attribute__((always_inline)) {
-        const w3_u32x4* Ab = buf + ks * NPC * PW_TA * 64 + lane;
-        const w3_u32x4* Bb = buf + A_ENT + ks * NPC * PW_TB * 64 + lane;
+    auto tile_row = [&](const u32x4* __restrict__ buf, int ks, int t) __attribute__((always_inline)) {
+        const u32x4* Ab = buf + ks * NPC * PW_TA * 64 + lane;
+        const u32x4* Bb = buf + A_ENT + ks * NPC * PW_TB * 64 + lane;
         if constexpr (BIO) {
-            const w3_bf16x8 a = __builtin_bit_cast(w3_bf16x8, Ab[(ta0 + t) * 64]);
+            const bf16x8 a = __builtin_bit_cast(bf16x8, Ab[(ta0 + t) * 64]);
 #pragma unroll
             for (int u = 0; u < 2; ++u)
-                acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(w3_bf16x8, Bb[(tb0 + u) * 64]), acc[t][u], 0, 0, 0);
+                acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, Bb[(tb0 + u) * 64]), acc[t][u], 0, 0, 0);
             return;
         }
-        const pw_f16x8 ah = __builtin_bit_cast(pw_f16x8, Ab[(ta0 + t) * 64]), al = __builtin_bit_cast(pw_f16x8, Ab[((NPC - 1) * PW_TA + ta0 + t) * 64]);
+        const f16x8 ah = __builtin_bit_cast(f16x8, Ab[(ta0 + t) * 64]), al = __builtin_bit_cast(f16x8, Ab[((NPC - 1) * PW_TA + ta0 + t) * 64]);
 #pragma unroll
         for (int u = 0; u < 2; ++u) {                                  // smallest terms first
-            const pw_f16x8 bh = __builtin_bit_cast(pw_f16x8, Bb[(tb0 + u) * 64]), bl = __builtin_bit_cast(pw_f16x8, Bb[((NPC - 1) * PW_TB + tb0 + u) * 64]);
+            const f16x8 bh = __builtin_bit_cast(f16x8, Bb[(tb0 + u) * 64]), bl = __builtin_bit_cast(f16x8, Bb[((NPC - 1) * PW_TB + tb0 + u) * 64]);
             acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[t][u], 0, 0, 0);
             acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[t][u], 0, 0, 0);
             acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[t][u], 0, 0, 0);
@@ -1059,8 +1029,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     __syncthreads();
     for (int s = 0; s < steps; ++s) {
-        const w3_u32x4* cur = pw_lds + (s & 1) * BUFK;
-        w3_u32x4* nxt = pw_lds + ((s + 1) & 1) * BUFK;
+        const u32x4* cur = pw_lds + (s & 1) * BUFK;
+        u32x4* nxt = pw_lds + ((s + 1) & 1) * BUFK;
         uint32_t* nxt32 = reinterpret_cast<uint32_t*>(nxt);
         const bool more = s + 1 < steps;                               // (uniform) is there a step s + 1 to build
         const int p_old = p_cur, end_old = end_cur;

@@ -19,6 +19,7 @@
 // same order of the products, the same epilogue): results are bit for bit those of csrc/dfol_dense_split.hip
 // (tests/test_kernels_gpu.py::test_linear_wide_equals_the_tiled_kernel_bit_for_bit).
 #include "dfol_common.h"
+#include "dfol_split.h"
 
 #include <stdlib.h>
 
@@ -27,42 +28,10 @@
 
 namespace {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int WD_BM = 128, WD_BK = 32, WD_XD = 3;                      // rows of a block, k of a step, steps of X rows in flight (a step is ~1.3 us)
 constexpr int WD_TILE = 2 * 128 * 4;                                   // 16-byte pieces of one [2 pieces][128 rows][4 k-groups] tile (16 KB)
 constexpr int WD_NMAX = 512;
 constexpr size_t WD_LDS = (size_t)6 * WD_TILE * 16 + 2 * WD_NMAX * 4 + 8 * 4096;  // A0, A1, B0 (two column blocks), B1; row scales and bias; the epilogue's 4 KB per wavefront
-
-__device__ __forceinline__ int wd_swz(int row) { return (4 - ((row >> 2) & 3)) & 3; }
-__device__ __forceinline__ void wd_split2h(float x0, float x1, uint32_t& h, uint32_t& l) {
-    const f32x2 x = {x0, x1};
-    const f16x2 hh = __builtin_convertvector(x, f16x2);
-    const f32x2 r = x - __builtin_convertvector(hh, f32x2);
-    h = __builtin_bit_cast(uint32_t, hh);
-    l = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, f16x2));
-}
-__device__ __forceinline__ void wd_split8h(const float4& a, const float4& b, u32x4& h, u32x4& l) {
-    uint32_t hh[4], ll[4];
-    wd_split2h(a.x, a.y, hh[0], ll[0]);
-    wd_split2h(a.z, a.w, hh[1], ll[1]);
-    wd_split2h(b.x, b.y, hh[2], ll[2]);
-    wd_split2h(b.z, b.w, hh[3], ll[3]);
-    h = u32x4{hh[0], hh[1], hh[2], hh[3]};
-    l = u32x4{ll[0], ll[1], ll[2], ll[3]};
-}
-
-template <int ACT>
-__device__ __forceinline__ float wd_act(float x) {                     // (the forms of csrc/dfol_dense_split.hip: ls_act)
-    if (ACT == DFOL_ACT_SIGMOID) return __builtin_amdgcn_rcpf(1.0f + dfol_exp(-x));
-    if (ACT == DFOL_ACT_ELU) return fmaxf(x, dfol_exp(fminf(x, 0.f)) - 1.0f);
-    if (ACT == DFOL_ACT_LOGSIGMOID) return fminf(x, 0.f) - dfol_log(1.0f + dfol_exp(-fabsf(x)));
-    return x;
-}
 
 // XV: floats per X load (4: rows 16-byte aligned; 2: rows 8-byte aligned - the 2054-column raw feature matrix)
 template <int ACT, int XV>
@@ -130,7 +99,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     auto store_a = [&](auto set_tag, int buf) __attribute__((always_inline)) {
         constexpr int S = decltype(set_tag)::value;
         const int k = sks * WD_BK + aq * 8;
-        const int at = A0 + buf * WD_TILE + arow * 4 + (aq ^ wd_swz(arow));
+        const int at = A0 + buf * WD_TILE + arow * 4 + (aq ^ dfol_swz(arow));
         const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
         const float4 v0 = k < K ? xa[S][0] : z, v1 = k + 4 < K ? xa[S][1] : z;
         xmax = fmaxf(fmaxf(xmax, fabsf(v0.x)), fabsf(v0.y));
@@ -138,15 +107,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         xmax = fmaxf(fmaxf(xmax, fabsf(v1.x)), fabsf(v1.y));
         xmax = fmaxf(fmaxf(xmax, fabsf(v1.z)), fabsf(v1.w));
         u32x4 ph, pl;
-        wd_split8h(v0, v1, ph, pl);
+        dfol_split2hx8(v0, v1, ph, pl);
         wd_sm[at] = ph;
         wd_sm[at + WD_BM * 4] = pl;
         if (++sks == ksteps) sks = 0;
     };
 
     // ---- a half-step's MFMAs: rows 64 wm .., columns 256 h + 64 wn .. (column block wn >> 1 of the half's two, rows 64 (wn & 1) .. of its tile)
-    const int aoff = (wm * 64 + r16) * 4 + (kh ^ wd_swz(r16));
-    const int boff = (wn >> 1) * WD_TILE + ((wn & 1) * 64 + r16) * 4 + (kh ^ wd_swz(r16));
+    const int aoff = (wm * 64 + r16) * 4 + (kh ^ dfol_swz(r16));
+    const int boff = (wn >> 1) * WD_TILE + ((wn & 1) * 64 + r16) * 4 + (kh ^ dfol_swz(r16));
     constexpr int PA3[3] = {1, 0, 0}, PB3[3] = {0, 1, 0};              // xl wh, xh wl, xh wh (smallest first)
     u32x4 afr[4][2];                                                   // the step's A fragments: read once, used by both halves
     auto load_a = [&](int abuf) __attribute__((always_inline)) {
@@ -203,7 +172,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll 4
                 for (int r = 0; r < 16; ++r) {
                     const int row = m0 + i * 16 + r;
-                    const float v = wd_act<ACT>(stage[r * 64 + lane] * cs + bv);          // (cs is a power of two: the product is exact, as in the tiled kernel)
+                    const float v = dfol_act<ACT>(stage[r * 64 + lane] * cs + bv);          // (cs is a power of two: the product is exact, as in the tiled kernel)
                     if (row < M && col < N) yp[(int64_t)row * ldy] = v;
                 }
             }

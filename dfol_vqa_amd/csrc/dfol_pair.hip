@@ -8,31 +8,26 @@
 // covered by the other's MFMAs, with no hand-made phase offsets.
 //
 // W2 comes PACKED (dfol_pair_pack_w2_f32): chunk-major [HID1/16][320][16] with rows >= HID2 zero and the four 4-float
-// k-groups of row r stored at group kq ^ swz[(r >> 2) & 3], swz = {0,3,2,1}.  A chunk is then 20 KB of contiguous
-// memory that is copied to LDS verbatim (coalesced, spread over all L2 channels), needs no padding, and every
-// ds_read_b128 of the B operand is bank-conflict-free: a b128 read is served in four groups of 16 lanes
-// ({0-3,12-15,20-27}, ...), i.e. rows {0-3,12-15} of k-group kh with rows {4-11} of k-group kh+1 (or kh-1); with the
-// swizzle those 16 (row, group) pairs cover all 64 banks exactly once.
+// k-groups of row r stored at group kq ^ dfol_swz(r).  A chunk is then 20 KB of contiguous memory that is copied to LDS
+// verbatim (coalesced, spread over all L2 channels), needs no padding, and every ds_read_b128 of the B operand is
+// bank-conflict-free.
 #include "dfol_common.h"
+#include "dfol_split.h"
 
 #include <stdlib.h>
 
 namespace {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
 constexpr int PB_ROWS = 320;                                // W2 rows per packed chunk
 constexpr int PB_CH = 16;                                   // K per chunk
 constexpr int PB_CHUNK = PB_ROWS * PB_CH;                   // floats per chunk
-
-__device__ __forceinline__ int pb_swz(int row) { return (4 - ((row >> 2) & 3)) & 3; }      // {0,3,2,1}[(row>>2)&3]
 
 __global__ void pair_pack_w2_kernel(const float* __restrict__ W2, int64_t ld_w2, int HID2, int HID1, float* __restrict__ out) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;      // one float4 of the packed image
     const int total = (HID1 / PB_CH) * PB_ROWS * 4;
     if (idx >= total) return;
     const int c = idx / (PB_ROWS * 4), rem = idx - c * (PB_ROWS * 4), r = rem >> 2, slot = rem & 3;
-    const int kq = slot ^ pb_swz(r);                        // the k-group stored in this slot
+    const int kq = slot ^ dfol_swz(r);                        // the k-group stored in this slot
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (r < HID2) {
         const float* src = W2 + (int64_t)r * ld_w2 + c * PB_CH + kq * 4;
@@ -65,18 +60,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int e_slot = tb * 64 + wave * 16 + r16;
     const bool valid = e_slot < n * n;
     const int s = valid ? e_slot / n : 0, o = valid ? e_slot - s * n : 0;
-    float geo[4];
-    {                                                       // batch_gqa_boxfeatures_pipeline.py:263-279
-        const float* ps = pos + (int64_t)(first + s) * ld_pos;
-        const float* po = pos + (int64_t)(first + o) * ld_pos;
-        const float x1 = ps[0], y1 = ps[1], w1 = ps[2], h1 = ps[3], x2 = po[0], y2 = po[1], w2 = po[2], h2 = po[3];
-        const float dx = x1 + w1 / 2.0f - x2 - w2 / 2.0f, dy = y1 + h1 / 2.0f - y2 - h2 / 2.0f;
-        const float dist = sqrtf(dx * dx + dy * dy);
-        geo[0] = dist;
-        geo[1] = asinf(dy / fmaxf(dist, 1e-10f));
-        geo[2] = (x2 - x1 > 0.f) ? 1.f : ((x2 - x1 < 0.f) ? -1.f : 0.f);
-        geo[3] = (y2 - y1 > 0.f) ? 1.f : ((y2 - y1 < 0.f) ? -1.f : 0.f);
-    }
+    const float4 geo = dfol_pair_geometry(pos + (int64_t)(first + s) * ld_pos, pos + (int64_t)(first + o) * ld_pos);
     for (int i = tid; i < HID1; i += 256) *reinterpret_cast<float4*>(&Wgs[i * 4]) = *reinterpret_cast<const float4*>(Wg + i * 4);
     const float* Urow = UV + (int64_t)(first + s) * ld_uv + 4 * kh;
     const float* Vrow = UV + (int64_t)(first + o) * ld_uv + HID1 + 4 * kh;
@@ -105,11 +89,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const float4 g = *reinterpret_cast<const float4*>(&Wgs[(k0 + 4 * kh + c) * 4]);
-            const float z = uu[c] + vv[c] + (g.x * geo[0] + g.y * geo[1] + g.z * geo[2] + g.w * geo[3]);
+            const float z = uu[c] + vv[c] + (g.x * geo.x + g.y * geo.y + g.z * geo.z + g.w * geo.w);
             a[c] = z > 0.f ? z : dfol_exp(z) - 1.0f;        // nn.ELU
         }
     };
-    const int boff = r16 * PB_CH + 4 * (kh ^ pb_swz(r16));  // this lane's float4 of column-tile row r16 (+ 256 floats per tile)
+    const int boff = r16 * PB_CH + 4 * (kh ^ dfol_swz(r16));  // this lane's float4 of column-tile row r16 (+ 256 floats per tile)
 
     float a_cur[4], a_next[4];
     const int nchunk = HID1 / PB_CH, lastc = nchunk - 1;
@@ -220,7 +204,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kh = lane >> 4, r16 = lane & 15;
     const int first = obj_off[q];
-    float geo[2][4];
+    float4 geo[2];
     const float* Urow[2];
     const float* Vrow[2];
 #pragma unroll
@@ -228,15 +212,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int e_slot = tb * 128 + wave * 32 + m * 16 + r16;
         const bool valid = e_slot < n * n;
         const int s = valid ? e_slot / n : 0, o = valid ? e_slot - s * n : 0;
-        const float* ps = pos + (int64_t)(first + s) * ld_pos;
-        const float* po = pos + (int64_t)(first + o) * ld_pos;
-        const float x1 = ps[0], y1 = ps[1], w1 = ps[2], h1 = ps[3], x2 = po[0], y2 = po[1], w2 = po[2], h2 = po[3];
-        const float dx = x1 + w1 / 2.0f - x2 - w2 / 2.0f, dy = y1 + h1 / 2.0f - y2 - h2 / 2.0f;
-        const float dist = sqrtf(dx * dx + dy * dy);
-        geo[m][0] = dist;
-        geo[m][1] = asinf(dy / fmaxf(dist, 1e-10f));
-        geo[m][2] = (x2 - x1 > 0.f) ? 1.f : ((x2 - x1 < 0.f) ? -1.f : 0.f);
-        geo[m][3] = (y2 - y1 > 0.f) ? 1.f : ((y2 - y1 < 0.f) ? -1.f : 0.f);
+        geo[m] = dfol_pair_geometry(pos + (int64_t)(first + s) * ld_pos, pos + (int64_t)(first + o) * ld_pos);
         Urow[m] = UV + (int64_t)(first + s) * ld_uv + 4 * kh;
         Vrow[m] = UV + (int64_t)(first + o) * ld_uv + HID1 + 4 * kh;
     }
@@ -269,7 +245,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // The two slots of a lane share every geometry weight: their first-layer sums go through packed fp32 math (v_pk_add_f32 /
     // v_pk_fma_f32, two lanes of work per instruction; -2 % kernel time)
     typedef float f2 __attribute__((ext_vector_type(2)));
-    const f2 G0 = {geo[0][0], geo[1][0]}, G1 = {geo[0][1], geo[1][1]}, G2 = {geo[0][2], geo[1][2]}, G3 = {geo[0][3], geo[1][3]};
+    const f2 G0 = {geo[0].x, geo[1].x}, G1 = {geo[0].y, geo[1].y}, G2 = {geo[0].z, geo[1].z}, G3 = {geo[0].w, geo[1].w};
     auto make_a = [&](int k0, float (&a)[2][4]) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -287,7 +263,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             a[1][c] = z.y > 0.f ? z.y : dfol_exp(z.y) - 1.0f;
         }
     };
-    const int boff = r16 * PB_CH + 4 * (kh ^ pb_swz(r16));
+    const int boff = r16 * PB_CH + 4 * (kh ^ dfol_swz(r16));
 
     float a_cur[2][4], a_next[2][4];
     const int nchunk = HID1 / PB_CH, lastc = nchunk - 1;

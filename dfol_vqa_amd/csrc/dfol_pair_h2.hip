@@ -21,13 +21,14 @@
 //     magnitude 58.  The clamp costs nothing (it is the third operand of the v_med3 that implements the ELU's select).
 //
 // W2 image (dfol_pair_pack_w2_f16x2): per 32 k (one MFMA's depth) a 40 KB chunk [2 pieces][320 rows][4 k-groups] x 16 bytes, rows >=
-// HID2 zero, the four 8-element k-groups of row r stored at group kq ^ swz[(r >> 2) & 3] (64-byte rows: every ds_read_b128 of a B
+// HID2 zero, the four 8-element k-groups of row r stored at group kq ^ dfol_swz(r) (64-byte rows: every ds_read_b128 of a B
 // fragment is bank-conflict-free), copied to LDS verbatim by LDS-DMA; after the chunks 320 floats -log2(e) 2^-e_r (the Sigmoid's
 // per-column multiplier) and the 320 exponents.
 //
 // Schedule: the ping-pong of the bf16x3 kernel (one 8-wavefront workgroup per CU; in every tick one half runs a chunk's MFMAs - 114 now,
 // not 228 - while the other half loads U / V rows, requests the next W2 chunk and builds its A pieces).
 #include "dfol_common.h"
+#include "dfol_split.h"
 
 #include <stdlib.h>
 
@@ -69,12 +70,6 @@ __device__ long long dfol_h2_trace_buf[8 * 8 * 64];
 
 namespace {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr float H2_NL2E = -1.44269504088896340736f;         // -log2(e)
 constexpr int H2_CH = 32;                                   // K per chunk = one v_mfma_f32_16x16x32_f16
 constexpr int H2_ROWS = 320, H2_TILES = 20;                 // rows (hidden columns) of the packed image
@@ -82,18 +77,6 @@ constexpr int H2_PIECES = 2 * H2_ROWS * 4;                  // 16-byte pieces pe
 constexpr float H2_AMAX = 60000.0f;                         // activations saturate here (fp16 max 65504); in units of 1 / ln 2 (see make_a): ELU outputs of 41 589
 constexpr float H2_L2E = 1.44269504088896340736f;           // log2(e) = 1 / ln 2
 constexpr float H2_LN2 = 0.69314718055994530942f;
-
-__device__ __forceinline__ int h2_swz(int row) { return (4 - ((row >> 2) & 3)) & 3; }      // {0,3,2,1}[(row>>2)&3]
-
-// (x0, x1) = (h0 + l0, h1 + l1) up to 2^-22 |x| (2^-25 absolute below 2^-3): v_cvt_pk_f16_f32, two v_cvt_f32_f16, v_pk_add_f32, v_cvt_pk_f16_f32
-__device__ __forceinline__ void h2_split2(float x0, float x1, uint32_t& h, uint32_t& l) {
-    const f32x2 x = {x0, x1};
-    const f16x2 hh = __builtin_convertvector(x, f16x2);
-    const f32x2 r = x - __builtin_convertvector(hh, f32x2);
-    const f16x2 ll = __builtin_convertvector(r, f16x2);
-    h = __builtin_bit_cast(uint32_t, hh);
-    l = __builtin_bit_cast(uint32_t, ll);
-}
 
 // The ELU's negative branch in the kernel's units: z' = z / ln 2 comes in (UV and the geometry weights are pre-multiplied by log2(e)), and
 // (e^min(z, 0) - 1) / ln 2 = (2^min(z', 0) - 1) / ln 2 goes out - the hardware exponential with the CLAMP output modifier (2^z' clamped to
@@ -129,13 +112,7 @@ __global__ void h2_row_scale_kernel(const float* __restrict__ W2, int64_t ld_w2,
         for (int k = lane; k < HID1; k += 64) m = fmaxf(m, fabsf(W2[(int64_t)r * ld_w2 + k] * H2_LN2));
 #pragma unroll
     for (int s = 32; s >= 1; s >>= 1) m = fmaxf(m, __shfl_xor(m, s, 64));
-    int e = 0;
-    if (m > 0.f && m < 3.0e38f) {
-        int x;
-        (void)frexpf(m, &x);                                // m = f 2^x, f in [0.5, 1)
-        e = 14 - x;
-        e = e < -100 ? -100 : (e > 100 ? 100 : e);
-    }
+    const int e = dfol_scale_exp(m);
     if (lane == 0) {
         tail[r] = ldexpf(H2_NL2E, -e);
         reinterpret_cast<int32_t*>(tail)[H2_ROWS + r] = e;
@@ -149,7 +126,7 @@ __global__ void h2_pack_w2_kernel(const float* __restrict__ W2, int64_t ld_w2, i
     if (idx >= (HID1 / H2_CH) * H2_PIECES) return;
     const int c = idx / H2_PIECES, rem = idx - c * H2_PIECES;
     const int p = rem / (H2_ROWS * 4), rr = rem - p * H2_ROWS * 4, r = rr >> 2, slot = rr & 3;
-    const int kq = slot ^ h2_swz(r);
+    const int kq = slot ^ dfol_swz(r);
     const int e = reinterpret_cast<const int32_t*>(tail)[H2_ROWS + r];
     uint32_t piece[4];
 #pragma unroll
@@ -161,7 +138,7 @@ __global__ void h2_pack_w2_kernel(const float* __restrict__ W2, int64_t ld_w2, i
             w1 = ldexpf(W2[(int64_t)r * ld_w2 + c * H2_CH + h2_kperm(kq, 2 * j + 1)] * H2_LN2, e);
         }
         uint32_t h, l;
-        h2_split2(w0, w1, h, l);
+        dfol_split2h(w0, w1, h, l);
         piece[j] = p == 0 ? h : l;
     }
     out[idx] = u32x4{piece[0], piece[1], piece[2], piece[3]};
@@ -262,18 +239,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 const int e_slot = tb * SLOTS + wave * (MT * 16) + m * 16 + r16;
                 const bool valid = e_slot < npairs;
                 zoff[m] = (TRAIN && valid) ? (uint32_t)(e_slot * HID1 + 4 * kh) * 4u : 0xffffffffu;
-                const int s = valid ? e_slot / (n - 1) : 0, oo_ = valid ? e_slot - s * (n - 1) : 0, o = oo_ + (oo_ >= s);      // (n >= 2 here)
-                const float* ps = pos + (int64_t)(first + s) * ld_pos;
-                const float* po = pos + (int64_t)(first + o) * ld_pos;
-                const float x1 = ps[0], y1 = ps[1], w1 = ps[2], h1 = ps[3], x2 = po[0], y2 = po[1], w2 = po[2], h2 = po[3];
-                const float dx = x1 + w1 / 2.0f - x2 - w2 / 2.0f, dy = y1 + h1 / 2.0f - y2 - h2 / 2.0f;
-                const float dist = sqrtf(dx * dx + dy * dy);
+                // (n >= 2 here; dfol_offdiag_slot written out: selecting e_slot before the division changes the kernel's code)
+                const int s = valid ? e_slot / (n - 1) : 0, oo_ = valid ? e_slot - s * (n - 1) : 0, o = oo_ + (oo_ >= s);
+                const float4 g = dfol_pair_geometry(pos + (int64_t)(first + s) * ld_pos, pos + (int64_t)(first + o) * ld_pos);
                 uint32_t gh01, gl01, gh23, gl23;
-                const float ang = asinf(dy / fmaxf(dist, 1e-10f));
-                const float sgx = (x2 - x1 > 0.f) ? 1.f : ((x2 - x1 < 0.f) ? -1.f : 0.f), sgy = (y2 - y1 > 0.f) ? 1.f : ((y2 - y1 < 0.f) ? -1.f : 0.f);
-                h2_split2(dist, ang, gh01, gl01);
-                h2_split2(sgx, sgy, gh23, gl23);
-                if (TRAIN && valid && kh == 0) *reinterpret_cast<floatx4*>(tr.geo + (prow0 + e_slot) * 4) = floatx4{dist, ang, sgx, sgy};      // (dfol_pair_train.hip: pair_geometry)
+                dfol_split2h(g.x, g.y, gh01, gl01);
+                dfol_split2h(g.z, g.w, gh23, gl23);
+                if (TRAIN && valid && kh == 0) *reinterpret_cast<floatx4*>(tr.geo + (prow0 + e_slot) * 4) = floatx4{g.x, g.y, g.z, g.w};
                 geoB[m] = kh == 0 ? u32x4{gh01, gh23, gl01, gl23} : (kh == 1 ? u32x4{gh01, gh23, 0u, 0u} : u32x4{0u, 0u, 0u, 0u});
                 uoff[m] = (uint32_t)(s * (int)ld_uv + 4 * kh) * 4u;          // the lane's k of a chunk: 16 t + 4 kh + 0..3, t = 0, 1 (h2_kperm)
                 voff[m] = (uint32_t)(o * (int)ld_uv + HID1 + 4 * kh) * 4u;
@@ -393,7 +365,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     }
             }
         };
-        const int boff = r16 * 4 + (kh ^ h2_swz(r16));                  // the lane's 16-byte piece inside a 16-row block
+        const int boff = r16 * 4 + (kh ^ dfol_swz(r16));                  // the lane's 16-byte piece inside a 16-row block
         int bbase = boff;                                               // + the chunk buffer's offset
         auto load_b = [&](int i, f16x8 (&b)[2]) __attribute__((always_inline)) {
 #pragma unroll
@@ -436,8 +408,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 if (khh < 2) {
                     const float4 g = *reinterpret_cast<const float4*>(Wg + (kt * 16 + (ln & 15)) * 4);
                     uint32_t h01, l01, h23, l23;                    // (times log2(e): the first layer's sums come out in units of ln 2, as UV holds them)
-                    h2_split2(g.x * H2_L2E, g.y * H2_L2E, h01, l01);
-                    h2_split2(g.z * H2_L2E, g.w * H2_L2E, h23, l23);
+                    dfol_split2h(g.x * H2_L2E, g.y * H2_L2E, h01, l01);
+                    dfol_split2h(g.z * H2_L2E, g.w * H2_L2E, h23, l23);
                     frag = khh == 0 ? u32x4{h01, h23, h01, h23} : u32x4{l01, l23, 0u, 0u};      // [0..3] wg_h, [4..7] wg_h, [8..11] wg_l
                 }
                 WgA[i] = frag;
@@ -600,12 +572,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 const float v = hi ? shifted : vm[0];
                 const int ee = tb * SLOTS + wave * (MT * 16) + hi * 16 + 4 * kh + (r16 & 3);
                 if (ee < npairs) {
-                    // ee / (n - 1) without the integer-division sequence: (ee + 0.5) / (n - 1) is at least 0.5 / (n - 1) away from an integer
                     if (TRAIN) {                                          // the reader's raw logit of this pair row (its bias and LogSigmoid stay with the caller)
                         tr.x[(int64_t)k * tr.ld_x + prow0 + ee] = v;
                         continue;
                     }
-                    const int ss = (int)(((float)ee + 0.5f) * __builtin_amdgcn_rcpf((float)(n - 1))), op = ee - ss * (n - 1), oo = op + (op >= ss);
+                    int ss, oo;
+                    dfol_offdiag_slot_rcp(ee, n, ss, oo);
                     const float x = v + (be ? be[col] : 0.f);
                     const float val = fminf(x, 0.f) - dfol_log(1.0f + dfol_exp(-fabsf(x)));        // nn.LogSigmoid (the diagonal keeps the caller's fill)
                     const int64_t at = (int64_t)req_tile[(int64_t)k * Q + q] * tile_sz +

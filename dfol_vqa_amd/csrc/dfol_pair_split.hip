@@ -11,12 +11,13 @@
 // Six bf16 MFMAs replace sixteen fp32 ones' worth of matrix-pipe time: 6/16 of the cost.
 //
 // W2 comes pre-split and packed (dfol_pair_pack_w2_bf16x3): per 32 k (one MFMA's depth) a 60 KB chunk of 20 column tiles x 3 pieces,
-// rows >= HID2 zero, the four 8-element k-groups of row r stored at group kq ^ swz[(r >> 2) & 3] (64-byte rows: the same bank
-// geometry as the fp32 image, so every ds_read_b128 of a B fragment is conflict-free; SQ_LDS_BANK_CONFLICT = 0).  A chunk is
-// copied to LDS verbatim by LDS-DMA.  Every wavefront owns 32 pair slots and all 19 column tiles (152 accumulator registers).
+// rows >= HID2 zero, the four 8-element k-groups of row r stored at group kq ^ dfol_swz(r) (64-byte rows: every ds_read_b128 of a B
+// fragment is conflict-free; SQ_LDS_BANK_CONFLICT = 0).  A chunk is copied to LDS verbatim by LDS-DMA.  Every wavefront owns 32 pair
+// slots and all 19 column tiles (152 accumulator registers).
 // The schedule (ping-pong between the two wavefronts of a SIMD, see pair_ll32s_kernel) came out of clock64 traces
 // (tools/scratch/trace_pair.py, -DDFOL_PAIR_TRACE).
 #include "dfol_common.h"
+#include "dfol_split.h"
 
 #include <stdlib.h>
 
@@ -45,24 +46,8 @@ __device__ long long dfol_trace_buf[8 * 8 * 64];
 
 namespace {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr float SP_NL2E = -1.44269504088896340736f;          // -log2(e)
 constexpr int SP_CH = 32;                                   // K per chunk = one v_mfma_f32_16x16x32_bf16
-
-__device__ __forceinline__ int sp_swz(int row) { return (4 - ((row >> 2) & 3)) & 3; }      // {0,3,2,1}[(row>>2)&3]
-
-// x = h + m + l exactly, each the fp32 whose low 16 bits are (or can be taken as) zero: the bf16 piece is the top half.
-__device__ __forceinline__ void sp_split(float x, uint32_t& h, uint32_t& m, uint32_t& l) {
-    h = __float_as_uint(x);
-    const float r = x - __uint_as_float(h & 0xffff0000u);
-    m = __float_as_uint(r);
-    l = __float_as_uint(r - __uint_as_float(m & 0xffff0000u));
-}
-// {top half of x0, top half of x1} as one register (element 0 in the low half)
-__device__ __forceinline__ uint32_t sp_pack(uint32_t x0, uint32_t x1) { return __builtin_amdgcn_perm(x1, x0, 0x07060302u); }
 
 // Packed image geometry: a chunk always holds 20 column tiles (rows >= HID2 zero) in two REGIONS - tiles 0..7 and 8..19 - each
 // stored [piece][row][4 k-groups] x 16 bytes, so that a region is one contiguous run of 1536 / 2304 DMA pieces (6 / 9 passes of a
@@ -80,16 +65,16 @@ __global__ void pair_pack_w2_split_kernel(const float* __restrict__ W2, int64_t 
     rem -= region ? SP_R0_PIECES : 0;
     const int rows_r = (region ? SP_TILES - SP_T0 : SP_T0) * 16;
     const int p = rem / (rows_r * 4), rr = rem - p * rows_r * 4, r = (region ? SP_T0 * 16 : 0) + (rr >> 2), slot = rr & 3;
-    const int kq = slot ^ sp_swz(r);
+    const int kq = slot ^ dfol_swz(r);
     uint32_t piece[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const float w = r < HID2 ? W2[(int64_t)r * ld_w2 + c * SP_CH + kq * 8 + j] : 0.f;
         uint32_t h, m, l;
-        sp_split(w, h, m, l);
+        dfol_split3(w, h, m, l);
         piece[j] = p == 0 ? h : (p == 1 ? m : l);
     }
-    out[idx] = u32x4{sp_pack(piece[0], piece[1]), sp_pack(piece[2], piece[3]), sp_pack(piece[4], piece[5]), sp_pack(piece[6], piece[7])};
+    out[idx] = u32x4{dfol_pack(piece[0], piece[1]), dfol_pack(piece[2], piece[3]), dfol_pack(piece[4], piece[5]), dfol_pack(piece[6], piece[7])};
 }
 
 // Every wavefront owns 32 pair slots (two 16-slot tiles) and all column tiles.  Two schedules:
@@ -154,16 +139,10 @@ __global__ __launch_bounds__(PP ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
     for (int m = 0; m < MT; ++m) {
         const int e_slot = tb * SLOTS + wave * (MT * 16) + m * 16 + r16;
         const bool valid = e_slot < npairs;
-        const int s = valid ? e_slot / (n - 1) : 0, oo_ = valid ? e_slot - s * (n - 1) : 0, o = oo_ + (oo_ >= s);      // (n >= 2 here)
-        const float* ps = pos + (int64_t)(first + s) * ld_pos;
-        const float* po = pos + (int64_t)(first + o) * ld_pos;
-        const float x1 = ps[0], y1 = ps[1], w1 = ps[2], h1 = ps[3], x2 = po[0], y2 = po[1], w2 = po[2], h2 = po[3];
-        const float dx = x1 + w1 / 2.0f - x2 - w2 / 2.0f, dy = y1 + h1 / 2.0f - y2 - h2 / 2.0f;
-        const float dist = sqrtf(dx * dx + dy * dy);
-        geo[m][0] = dist;
-        geo[m][1] = asinf(dy / fmaxf(dist, 1e-10f));
-        geo[m][2] = (x2 - x1 > 0.f) ? 1.f : ((x2 - x1 < 0.f) ? -1.f : 0.f);
-        geo[m][3] = (y2 - y1 > 0.f) ? 1.f : ((y2 - y1 < 0.f) ? -1.f : 0.f);
+        // (n >= 2 here; dfol_offdiag_slot written out: selecting e_slot before the division changes the kernel's code)
+        const int s = valid ? e_slot / (n - 1) : 0, oo_ = valid ? e_slot - s * (n - 1) : 0, o = oo_ + (oo_ >= s);
+        const float4 g = dfol_pair_geometry(pos + (int64_t)(first + s) * ld_pos, pos + (int64_t)(first + o) * ld_pos);
+        geo[m][0] = g.x, geo[m][1] = g.y, geo[m][2] = g.z, geo[m][3] = g.w;
         Urow[m] = UV + (int64_t)(first + s) * ld_uv + 8 * kh;
         Vrow[m] = UV + (int64_t)(first + o) * ld_uv + HID1 + 8 * kh;
     }
@@ -244,15 +223,15 @@ __global__ __launch_bounds__(PP ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
                     const float a0 = z.x > 0.f ? z.x : dfol_exp(z.x) - 1.0f;   // nn.ELU
                     const float a1 = z.y > 0.f ? z.y : dfol_exp(z.y) - 1.0f;
                     uint32_t h0, m0, l0, h1, m1, l1;
-                    sp_split(a0, h0, m0, l0);
-                    sp_split(a1, h1, m1, l1);
-                    ap[m][0][2 * half + jp] = sp_pack(h0, h1);
-                    ap[m][1][2 * half + jp] = sp_pack(m0, m1);
-                    ap[m][2][2 * half + jp] = sp_pack(l0, l1);
+                    dfol_split3(a0, h0, m0, l0);
+                    dfol_split3(a1, h1, m1, l1);
+                    ap[m][0][2 * half + jp] = dfol_pack(h0, h1);
+                    ap[m][1][2 * half + jp] = dfol_pack(m0, m1);
+                    ap[m][2][2 * half + jp] = dfol_pack(l0, l1);
                 }
             }
     };
-    const int boff = r16 * 4 + (kh ^ sp_swz(r16));                  // the lane's 16-byte piece inside a 16-row block
+    const int boff = r16 * 4 + (kh ^ dfol_swz(r16));                  // the lane's 16-byte piece inside a 16-row block
     // The MFMAs of column tiles i .. i+NT-1: six piece products for each slot tile, smallest terms first.  Consecutive MFMAs go to
     // different accumulators (NT * MT of them in rotation): an MFMA that accumulates onto the result of the one just issued waits for
     // its full latency, about twice its issue time.
@@ -424,8 +403,8 @@ __global__ __launch_bounds__(PP ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
                 const float v = r16 == 0 ? part[0] : (r16 == 1 ? part[1] : (r16 == 2 ? part[2] : part[3]));
                 const int ee = tb * SLOTS + wave * (MT * 16) + m * 16 + 4 * kh + r16;
                 if (ee < npairs) {
-                    // ee / (n - 1) without the integer-division sequence: (ee + 0.5) / (n - 1) is at least 0.5 / (n - 1) away from an integer
-                    const int ss = (int)(((float)ee + 0.5f) * __builtin_amdgcn_rcpf((float)(n - 1))), op = ee - ss * (n - 1), oo = op + (op >= ss);
+                    int ss, oo;
+                    dfol_offdiag_slot_rcp(ee, n, ss, oo);
                     const float x = v + (be ? be[col] : 0.f);
                     const float val = fminf(x, 0.f) - dfol_log(1.0f + dfol_exp(-fabsf(x)));        // nn.LogSigmoid (the diagonal keeps the caller's fill)
                     const int64_t at = (int64_t)req_tile[(int64_t)k * Q + q] * tile_sz +

@@ -13,6 +13,7 @@
 //                 one workgroup per predicate, no atomics
 // Rows are the reference's ordered pairs: image-major, subject-major, the diagonal left out (util.py:87-103).
 #include "dfol_common.h"
+#include "dfol_split.h"
 
 #include <stdlib.h>
 #include <type_traits>
@@ -20,55 +21,35 @@
 namespace {
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-// Sigmoid / ELU on the hardware exp2 / rcp (1 ulp each, absolute error < 2e-7 on these ranges - the forms the inference kernels use).
-// With libm's expf / expm1f and an IEEE division these streams were VALU-bound at 2.0 - 3.6 TB/s (25 - 30 instructions per element).
-__device__ __forceinline__ float pt_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896340736f * x)); }
+// Sigmoid (dfol_sigmoid_hw) / ELU on the hardware exp2 / rcp (1 ulp each, absolute error < 2e-7 on these ranges - the forms the inference
+// kernels use).  With libm's expf / expm1f and an IEEE division these streams were VALU-bound at 2.0 - 3.6 TB/s (25 - 30 instructions per element).
 __device__ __forceinline__ float pt_elu(float x) { return x > 0.f ? x : __builtin_amdgcn_exp2f(1.44269504088896340736f * x) - 1.0f; }
 __device__ __forceinline__ void st4(float* p, const float4& v) { *reinterpret_cast<float4*>(p) = v; }
 // streams that are written / read once per step and are far larger than the caches (2.6 - 3 GB): non-temporal accesses
-typedef float pt_f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void st4_stream(float* p, const float4& v) {
-    __builtin_nontemporal_store(pt_f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<pt_f32x4*>(p));
+    __builtin_nontemporal_store(floatx4{v.x, v.y, v.z, v.w}, reinterpret_cast<floatx4*>(p));
 }
 __device__ __forceinline__ float4 ld4_stream(const float* p) {
-    const pt_f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const pt_f32x4*>(p));
+    const floatx4 v = __builtin_nontemporal_load(reinterpret_cast<const floatx4*>(p));
     return make_float4(v.x, v.y, v.z, v.w);
 }
 
 // bf16 storage of the per-pair activations (the bf16 mode, BASELINE configs[3]: Z, pre2 and their gradients are the 14 GB a train step
 // moves): the same streams over 2-byte elements, arithmetic in fp32 registers as before.  `pt_bf16` = the bits of a bfloat16.
 typedef uint16_t pt_bf16;
-typedef uint32_t pt_u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 pt_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float pt_f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pt_rne2(float x0, float x1) {                 // v_cvt_pk_bf16_f32: round to nearest even
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(pt_f32x2{x0, x1}, pt_bf16x2));
-}
-__device__ __forceinline__ float4 pt_widen(const pt_u32x2& v) {
-    return make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u));
-}
-__device__ __forceinline__ float4 ld4(const pt_bf16* p) { return pt_widen(*reinterpret_cast<const pt_u32x2*>(p)); }
-__device__ __forceinline__ float4 ld4_stream(const pt_bf16* p) { return pt_widen(__builtin_nontemporal_load(reinterpret_cast<const pt_u32x2*>(p))); }
+__device__ __forceinline__ float4 ld4(const pt_bf16* p) { return dfol_widen(*reinterpret_cast<const u32x2*>(p)); }
+__device__ __forceinline__ float4 ld4_stream(const pt_bf16* p) { return dfol_widen(__builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p))); }
 __device__ __forceinline__ void st4_stream(pt_bf16* p, const float4& v) {
-    __builtin_nontemporal_store(pt_u32x2{pt_rne2(v.x, v.y), pt_rne2(v.z, v.w)}, reinterpret_cast<pt_u32x2*>(p));
+    __builtin_nontemporal_store(u32x2{dfol_rne2(v.x, v.y), dfol_rne2(v.z, v.w)}, reinterpret_cast<u32x2*>(p));
 }
 // the same loads as raw registers (a consumer that keeps loads in flight across a scheduling barrier widens them when it uses them)
 template <typename T> struct pt_raw;
-template <> struct pt_raw<float> { using type = pt_f32x4; };
-template <> struct pt_raw<pt_bf16> { using type = pt_u32x2; };
-__device__ __forceinline__ pt_f32x4 ld4_stream_raw(const float* p) { return __builtin_nontemporal_load(reinterpret_cast<const pt_f32x4*>(p)); }
-__device__ __forceinline__ pt_u32x2 ld4_stream_raw(const pt_bf16* p) { return __builtin_nontemporal_load(reinterpret_cast<const pt_u32x2*>(p)); }
-__device__ __forceinline__ float4 pt_widen(const pt_f32x4& v) { return make_float4(v.x, v.y, v.z, v.w); }
+template <> struct pt_raw<float> { using type = floatx4; };
+template <> struct pt_raw<pt_bf16> { using type = u32x2; };
+__device__ __forceinline__ floatx4 ld4_stream_raw(const float* p) { return __builtin_nontemporal_load(reinterpret_cast<const floatx4*>(p)); }
+__device__ __forceinline__ u32x2 ld4_stream_raw(const pt_bf16* p) { return __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p)); }
 __device__ __forceinline__ float ld1(const float* p) { return *p; }
 __device__ __forceinline__ float ld1(const pt_bf16* p) { return __uint_as_float((uint32_t)*p << 16); }
-
-__device__ __forceinline__ float4 pair_geometry(const float* ps, const float* po) {      // batch_gqa_boxfeatures_pipeline.py:263-279
-    const float x1 = ps[0], y1 = ps[1], w1 = ps[2], h1 = ps[3], x2 = po[0], y2 = po[1], w2 = po[2], h2 = po[3];
-    const float dx = x1 + w1 / 2.0f - x2 - w2 / 2.0f, dy = y1 + h1 / 2.0f - y2 - h2 / 2.0f;
-    const float dist = sqrtf(dx * dx + dy * dy);
-    return make_float4(dist, asinf(dy / fmaxf(dist, 1e-10f)), (x2 - x1 > 0.f) ? 1.f : ((x2 - x1 < 0.f) ? -1.f : 0.f),
-                       (y2 - y1 > 0.f) ? 1.f : ((y2 - y1 < 0.f) ? -1.f : 0.f));
-}
 
 // geometry of every ordered pair, one thread per pair (the per-pair arithmetic - a square root, an arc sine, two divisions - would
 // otherwise be repeated by every wavefront that touches the pair's row of Z)
@@ -78,8 +59,10 @@ __global__ __launch_bounds__(256) void pair_geometry_kernel(const float* __restr
     const int q = blockIdx.y, n = n_obj[q];
     const int e = blockIdx.x * 256 + (int)threadIdx.x;
     if (n < 2 || e >= n * (n - 1)) return;
-    const int s = e / (n - 1), oo = e - s * (n - 1), o = oo + (oo >= s), first = obj_off[q];
-    st4(geo_out + (pair_off[q] + e) * 4, pair_geometry(pos + (int64_t)(first + s) * ld_pos, pos + (int64_t)(first + o) * ld_pos));
+    int s, o;
+    dfol_offdiag_slot(e, n, s, o);
+    const int first = obj_off[q];
+    st4(geo_out + (pair_off[q] + e) * 4, dfol_pair_geometry(pos + (int64_t)(first + s) * ld_pos, pos + (int64_t)(first + o) * ld_pos));
 }
 
 // grid (tiles_per_image, Q); 256 threads = 256 / (H1 / 4) row slots of H1 / 4 lanes; a slot walks HF_ROWS consecutive pairs of one image
@@ -115,7 +98,8 @@ __global__ __launch_bounds__(256) void pair_hidden1_fwd_kernel(const float* __re
 #pragma unroll
         for (int i = 0; i < 4; ++i) {                            // all loads of four rows first (rows beyond the image are clamped)
             const int e = min(e0 + r0 + i, rows - 1);
-            const int s = e / (n - 1), oo = e - s * (n - 1), o = oo + (oo >= s);
+            int s, o;
+            dfol_offdiag_slot(e, n, s, o);
             g[i] = ld4(geo + (base + e) * 4);
             if (two) u[i] = s == sA ? uA : uB;
             else u[i] = ld4(U + (int64_t)(first + s) * ld_u + k);
@@ -256,7 +240,7 @@ __global__ __launch_bounds__(THREADS) void pair_hidden1_bwd_kernel(const TZ* __r
                 if (slot * G < n) {
                     const int o = g + slot * G;
                     const float m = (o < n && o != s) ? 1.f : 0.f;                  // (a lane without a pair adds exact zeros)
-                    const float4 d = pt_widen(dzr[decltype(SET)::value][j]), ge = ger[decltype(SET)::value][j];
+                    const float4 d = dfol_widen(dzr[decltype(SET)::value][j]), ge = ger[decltype(SET)::value][j];
                     float4 z;
                     if constexpr (RECOMP) {                      // (pair_hidden1_fwd_kernel's expression, term for term)
                         const float4 u = ur[decltype(SET)::value], v = ld4(&vs[min(o, n - 1) * H1 + k]);
@@ -267,7 +251,7 @@ __global__ __launch_bounds__(THREADS) void pair_hidden1_bwd_kernel(const TZ* __r
                             out[t] = pt_elu(uv[t] + (wg4[t].x * ge.x + wg4[t].y * ge.y + wg4[t].z * ge.z + wg4[t].w * ge.w));
                         z = make_float4(out[0], out[1], out[2], out[3]);
                     } else {
-                        z = pt_widen(zr[decltype(SET)::value][j]);
+                        z = dfol_widen(zr[decltype(SET)::value][j]);
                     }
                     add(slot, make_float4(m * d.x, m * d.y, m * d.z, m * d.w), z, ge, du);
                 }
@@ -355,7 +339,7 @@ __global__ __launch_bounds__(256) void pair_logit_fwd_kernel(const TP* __restric
 #pragma unroll
             for (int i = 0; i < 4; ++i) v[i] = ld1(P2 + min(row0 + i, r1 - 1) * ld_p2 + j);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) acc[i] = fmaf(pt_sigmoid(v[i]), ev, acc[i]);
+            for (int i = 0; i < 4; ++i) acc[i] = fmaf(dfol_sigmoid_hw(v[i]), ev, acc[i]);
         }
     }
     const float b = be ? be[p] : 0.f;
@@ -385,7 +369,7 @@ __global__ __launch_bounds__(256) void pair_logit_fwd4_kernel(const TP* __restri
             for (int i = 0; i < 4; ++i) v[i] = ld4_stream(P2 + min(row0 + i, r1 - 1) * ld_p2 + 4 * j4);
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                acc[i] = fmaf(pt_sigmoid(v[i].x), ev.x, fmaf(pt_sigmoid(v[i].y), ev.y, fmaf(pt_sigmoid(v[i].z), ev.z, fmaf(pt_sigmoid(v[i].w), ev.w, acc[i]))));
+                acc[i] = fmaf(dfol_sigmoid_hw(v[i].x), ev.x, fmaf(dfol_sigmoid_hw(v[i].y), ev.y, fmaf(dfol_sigmoid_hw(v[i].z), ev.z, fmaf(dfol_sigmoid_hw(v[i].w), ev.w, acc[i]))));
         }
     }
     const float b = be ? be[p] : 0.f;
@@ -415,7 +399,7 @@ __global__ __launch_bounds__(1024) void pair_logit_bwd4_kernel(const float* __re
     float4 de = make_float4(0.f, 0.f, 0.f, 0.f), d2 = make_float4(0.f, 0.f, 0.f, 0.f);
     float db = 0.f;
     auto one = [&](int64_t row, const float4& v, float g) __attribute__((always_inline)) {
-        const float h[4] = {pt_sigmoid(v.x), pt_sigmoid(v.y), pt_sigmoid(v.z), pt_sigmoid(v.w)};
+        const float h[4] = {dfol_sigmoid_hw(v.x), dfol_sigmoid_hw(v.y), dfol_sigmoid_hw(v.z), dfol_sigmoid_hw(v.w)};
         const float4 dp = make_float4(g * ev.x * h[0] * (1.0f - h[0]), g * ev.y * h[1] * (1.0f - h[1]), g * ev.z * h[2] * (1.0f - h[2]),
                                       g * ev.w * h[3] * (1.0f - h[3]));
         if (dP2) st4_stream(dP2 + row * ld_dp2 + 4 * j4, dp);          // (null: dpre2 is produced inside the two products that read it)
@@ -496,7 +480,7 @@ __global__ __launch_bounds__(1024) void pair_logit_bwd_kernel(const float* __res
         for (int t = 0; t < LG_T; ++t) {
             const int j = lane + 64 * t;
             if (j < H2) {
-                const float ha = pt_sigmoid(va[t]), hb = pt_sigmoid(vb[t]);
+                const float ha = dfol_sigmoid_hw(va[t]), hb = dfol_sigmoid_hw(vb[t]);
                 if (dP2) dP2[row * ld_dp2 + j] = ga * ev[t] * ha * (1.0f - ha);
                 if (dP2 && has_b) dP2[row_b * ld_dp2 + j] = gb * ev[t] * hb * (1.0f - hb);
                 de[t] = fmaf(ga, ha, fmaf(gb, hb, de[t]));
