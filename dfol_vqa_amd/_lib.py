@@ -133,6 +133,7 @@ SIGNATURES = {
     "dfol_lstm_cell_bwd_f32": [_p, _p, _p, _p, _p, _i32, _i32, _p, _p, _p],
     "dfol_modulate_bwd_f32": [_p, _p, _p, _p, _p, _i32, _i32, _p, _p, _p],
     "dfol_attr_ll_f32": [_p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _i32, _i32, _f, _p, _p],
+    "dfol_attr_head_h2_f32": [_p, _i64, _i32, _p, _p, _i32, _p, _i64, _p, _p, _i32, _i32, _p, _p, _i32, _i32, _f, _p, _p],
     "dfol_pair_ll_f32": [_p, _i64, _i32, _p, _i64, _p, _p, _i64, _i32, _p, _i32, _p, _i64, _p, _p, _p, _i32, _i32, _p, _p, _p, _i32,
                          _i32, _f, _p, _p],
     "dfol_pair_pack_w2_f32": [_p, _i64, _i32, _i32, _p, _p],
@@ -828,6 +829,22 @@ def attr_ll(hidden, emb_w, emb_b, obj_off, pred_q, pred_col, NS, default_ll=-30.
     ll = torch.empty(P, NS, dtype=F32, device=hidden.device)
     call("dfol_attr_ll_f32", _dp(hidden), hidden.stride(0), hidden.shape[1], _dp(emb_w), emb_w.stride(0),
          _ptr(emb_b, F32, True), _ptr(obj_off, I32), _ptr(pred_q, I32), _ptr(pred_col, I32), P, NS, default_ll, _ptr(ll), _stream())
+    return ll
+
+
+def attr_head_supported(hid1, hid2):
+    """Shapes dfol_attr_head_h2_f32 takes (the full-size attribute network: 516 -> 256 -> 300): the pair kernel's second-layer shapes."""
+    return pair_split_supported(hid1, hid2)
+
+
+def attr_head_h2(pre1, w2_h2, b2, hid2, emb_w, emb_b, obj_off, pred_q, pred_col, NS, default_ll=-30.0):
+    """attr_ll without the hidden table (csrc/dfol_pair_h2.hip: attr_head_h2_kernel): pre1 [O, hid1] = the attribute network's first-layer
+    pre-activations, w2_h2 = pair_pack_w2_h2 of its second layer.  Same result layout as attr_ll; pred_q in any order."""
+    P = pred_q.numel()
+    ll = torch.empty(P, NS, dtype=F32, device=pre1.device)
+    call("dfol_attr_head_h2_f32", _dp(pre1), pre1.stride(0), pre1.shape[1], _ptr(w2_h2, torch.float16), _ptr(b2, F32), hid2, _dp(emb_w), emb_w.stride(0),
+         _ptr(emb_b, F32, True), _ptr(obj_off, I32), obj_off.numel() - 1, pre1.shape[0], _ptr(pred_q, I32), _ptr(pred_col, I32), P, NS, default_ll,
+         _ptr(ll), _stream())
     return ll
 
 

@@ -665,6 +665,226 @@ __global__ __launch_bounds__(512) void h2_uv_range_kernel(const float* __restric
     }
 }
 
+
+// ---- the attribute head: the fused body with an OBJECT per slot --------------------------------------------------------------------
+// The attribute MLP is the relation MLP after its first layer (516 -> 256 -> 300 -> concepts, ELU then Sigmoid), so its head runs the same
+// second layer: per 128-object tile the eight chunks of the packed W2 image through LDS, A pieces built from the object's own row of
+// first-layer PRE-activations (no geometry product, no U[s] + V[o]), the three piece products, Sigmoid in registers, dot products with the
+// requested embedding rows, LogSigmoid into ll[p][o].  The hidden table [O, HID2] never exists.
+//   * four wavefronts, two 16-slot tiles each (the pair kernel's chunk_mfma shape: 2 x NB16 accumulator tiles): 128 slots per workgroup,
+//     200 workgroups at 256 x 100 objects.  No ping-pong: the build is one row load, an ELU and a split per element; the next chunk's
+//     DMA and rows are requested behind the barrier that publishes the current chunk and land under its MFMAs (one barrier per chunk).
+//   * the rows come in plain units (the first layer is the ordinary dense kernel without activation): one multiply by log2(e) per
+//     element puts them into the units of h2_elu_neg and of the packed image (which carries the factor ln 2).
+//   * a tile straddles images (three at N = 100, up to 128 at N = 1), and the request table is per predicate, in any order: per window of
+//     AH_CAP predicates the workgroup collects those whose image meets the tile (image range by binary search in obj_off), stages up to SR
+//     embedding rows (more: read from global memory, same values in the same order) and every wavefront runs the dot products of the
+//     entries that meet its 32 slots.  Cells that no object owns (no-op tokens, columns >= n) get the default in a grid-stride pass.
+//   * activations saturate at H2_AMAX as in the pair kernel; an element beyond it (or NaN) ORs DFOL_RANGE_X_OVERFLOW into the status
+//     word - the bit the dense second layer raised for the same input.
+constexpr int AH_WAVES = 4, AH_MT = 2, AH_T = AH_WAVES * 64, AH_SLOTS = AH_WAVES * AH_MT * 16, AH_CAP = 512;
+
+template <int NB16>
+__global__ __launch_bounds__(AH_T) void attr_head_h2_kernel(const float* pre1, int64_t ld_pre1, int HID1, const u32x4* __restrict__ W2h,
+                                                            const float* __restrict__ b2, int HID2, const float* __restrict__ E, int64_t ld_e,
+                                                            const float* __restrict__ be, const int32_t* __restrict__ obj_off, int Q, int O,
+                                                            const int32_t* __restrict__ pred_q, const int32_t* __restrict__ pred_col, int P, int NS,
+                                                            float dflt, float* __restrict__ ll, uint32_t* __restrict__ status) {
+    constexpr int MT = AH_MT, ROWS = NB16 * 16, T = AH_T;
+    static_assert(NB16 > 16 && NB16 <= H2_TILES, "geometry");
+    __shared__ __attribute__((aligned(16))) u32x4 Bs[2 * H2_PIECES];          // two W2 chunks, both pieces (40 KB each)
+    constexpr int STAGE_FLOATS = 8192;                                        // bias / multiplier / embedding rows (32 KB)
+    __shared__ __attribute__((aligned(16))) float stage[STAGE_FLOATS];
+    __shared__ int32_t ent[4][AH_CAP];                                        // a window's entries: predicate, column, first and end object of its image
+    __shared__ int ent_n;
+    __shared__ int img_cnt[2];
+    constexpr int SR = STAGE_FLOATS / ROWS - 2;
+
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, kh = lane >> 4, r16 = lane & 15;
+    const int nchunk = HID1 / H2_CH;
+    const float* cf = reinterpret_cast<const float*>(W2h + (int64_t)nchunk * H2_PIECES);      // -log2(e) 2^-e_r per hidden column
+
+    auto fill_defaults = [&]() {      // cells without an object: the default (disjoint from the cells the dot products write)
+        for (int64_t idx = (int64_t)blockIdx.x * T + tid; idx < (int64_t)P * NS; idx += (int64_t)gridDim.x * T) {
+            const int p = (int)(idx / NS), o = (int)(idx - (int64_t)p * NS), q = pred_q[p];
+            if (pred_col[p] < 0 || o >= obj_off[q + 1] - obj_off[q]) ll[idx] = dflt;
+        }
+    };
+    const int g0 = blockIdx.x * AH_SLOTS;
+    if (g0 >= O) {                                                            // (uniform: the launcher's one workgroup of a batch without objects)
+        fill_defaults();
+        return;
+    }
+
+    auto dma_chunk = [&](int c, int buf) __attribute__((always_inline)) {      // all 256 threads: ten requests of 4 KiB, a wavefront's 1 KiB contiguous
+#pragma unroll
+        for (int i = 0; i < H2_PIECES / T; ++i)
+            __builtin_amdgcn_global_load_lds(W2h + (int64_t)c * H2_PIECES + T * i + tid,
+                                             (__attribute__((address_space(3))) void*)&Bs[buf * H2_PIECES + T * i + wave * 64], 16, 0, 0);
+    };
+    dma_chunk(0, 0);
+    // the lane's rows: slot r16 of the wavefront's slot tile m, k = 32 c + 16 t + 4 kh + 0..3 (h2_kperm); slots past the last object repeat it
+    const float* row[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) row[m] = pre1 + (int64_t)min(g0 + wave * (MT * 16) + m * 16 + r16, O - 1) * ld_pre1 + 4 * kh;
+    floatx4 ra[MT][2];
+    auto load_rows = [&](int c) __attribute__((always_inline)) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int t = 0; t < 2; ++t) ra[m][t] = *reinterpret_cast<const floatx4*>(row[m] + H2_CH * c + 16 * t);
+    };
+    load_rows(0);
+    // (chunk 0 and the first rows are in flight: the default cells and the tile's image range cost their own latency only)
+    fill_defaults();
+    // the images of the tile's first and last object: the largest q with obj_off[q] <= g = the number of q in [1, Q) with obj_off[q] <= g
+    // (an image without objects is never chosen), counted by all threads at once - a binary search is eight dependent trips to L2
+    if (tid < 2) img_cnt[tid] = 0;
+    __syncthreads();
+    {
+        const int g_last = min(g0 + AH_SLOTS, O) - 1;
+        int c_lo = 0, c_hi = 0;
+        for (int q = 1 + tid; q < Q; q += T) {
+            const int f = obj_off[q];
+            c_lo += f <= g0, c_hi += f <= g_last;
+        }
+        if (c_lo) atomicAdd(&img_cnt[0], c_lo);
+        if (c_hi) atomicAdd(&img_cnt[1], c_hi);
+    }
+    for (int i = tid; i < ROWS; i += T) {
+        stage[i] = H2_NL2E * (i < HID2 ? b2[i] : -1.0e30f);                  // Sigmoid(x + b) = 1 / (1 + 2^(-L2E x - L2E b)); padding columns: exactly 0
+        stage[ROWS + i] = i < HID2 ? cf[i] : 0.f;
+    }
+
+    floatx4 acc[MT][NB16];
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int i = 0; i < NB16; ++i) acc[m][i] = floatx4{0.f, 0.f, 0.f, 0.f};
+    u32x4 ap[MT][2];                                                         // [slot tile][piece h, l]
+    bool bad = false;
+    const int boff = r16 * 4 + (kh ^ dfol_swz(r16));                         // the lane's 16-byte piece inside a 16-row block
+    constexpr int PA3[3] = {1, 0, 0}, PB3[3] = {0, 1, 0};                    // al wh, ah wl, ah wh
+    for (int c = 0; c < nchunk; ++c) {
+        // chunk c (requested one iteration ago, under the MFMAs of chunk c - 1) and the rows have landed; behind the barrier every
+        // wavefront's part of it is visible and nobody reads the other buffer any more
+        __builtin_amdgcn_s_waitcnt(0x0F70);                                  // vmcnt(0): LDS-DMA completion is tracked per issuing wavefront
+        __syncthreads();
+        if (c + 1 < nchunk) dma_chunk(c + 1, (c + 1) & 1);
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int jp = 0; jp < 2; ++jp) {
+                    const float z0 = ra[m][t][2 * jp] * H2_L2E, z1 = ra[m][t][2 * jp + 1] * H2_L2E;
+                    bad |= !(z0 <= H2_AMAX) | !(z1 <= H2_AMAX);
+                    const float a0 = __builtin_amdgcn_fmed3f(z0, h2_elu_neg(z0), H2_AMAX);
+                    const float a1 = __builtin_amdgcn_fmed3f(z1, h2_elu_neg(z1), H2_AMAX);
+                    const uint32_t hh = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){a0, a1}, f16x2));
+                    const uint32_t lw = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){h2_resid<false>(a0, hh), h2_resid<true>(a1, hh)}, f16x2));
+                    ap[m][0][2 * t + jp] = hh;
+                    ap[m][1][2 * t + jp] = lw;
+                }
+        if (c + 1 < nchunk) load_rows(c + 1);
+        const int bbase = boff + (c & 1) * H2_PIECES;
+        constexpr int D = DFOL_H2_BDEPTH;
+        f16x8 bq[D + 1][2];
+        auto load_b = [&](int i, f16x8(&b)[2]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int p = 0; p < 2; ++p) b[p] = __builtin_bit_cast(f16x8, Bs[bbase + i * 64 + p * H2_ROWS * 4]);
+        };
+#pragma unroll
+        for (int d = 0; d < D; ++d) load_b(d, bq[d]);
+#pragma unroll
+        for (int i = 0; i < NB16; ++i) {
+            if (i + D < NB16) load_b(i + D, bq[(i + D) % (D + 1)]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+#pragma unroll
+                for (int x = 0; x < 3; ++x)
+                    acc[m][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, ap[m][PA3[x]]), bq[i % (D + 1)][PB3[x]], acc[m][i], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    }
+    if (status && __any(bad) && lane == 0) atomicOr(status, (uint32_t)DFOL_RANGE_X_OVERFLOW);
+
+    // Sigmoid of the hidden layer (the row scale of W2 folded into the exponent's multiplier)
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int i = 0; i < NB16; ++i) {
+            const float bv = stage[i * 16 + r16], cm = stage[ROWS + i * 16 + r16];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[m][i][e] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(fmaf(acc[m][i][e], cm, bv)));
+        }
+    const int q_lo = img_cnt[0], q_hi = img_cnt[1];                          // (published by the chunk loop's barriers)
+    const int w0 = g0 + wave * (MT * 16);                                    // the wavefront's first object
+    for (int pw = 0; pw < P; pw += AH_CAP) {
+        __syncthreads();                                                     // the previous window's readers of ent[] and stage[] are done
+        if (tid == 0) ent_n = 0;
+        __syncthreads();
+        for (int p = pw + tid; p < min(pw + AH_CAP, P); p += T) {
+            const int q = pred_q[p], col = pred_col[p];
+            if (col >= 0 && q >= q_lo && q <= q_hi) {
+                const int j = atomicAdd(&ent_n, 1);                          // (any order: every entry writes its own cells, staged or not the same values)
+                ent[0][j] = p, ent[1][j] = col, ent[2][j] = obj_off[q], ent[3][j] = obj_off[q + 1];
+            }
+        }
+        __syncthreads();
+        const int n_ent = ent_n;
+        if (n_ent == 0) continue;                                            // (uniform)
+        const int n_st = n_ent < SR ? n_ent : SR;
+        for (int j = 0; j < n_st; ++j) {
+            const float* erow = E + (int64_t)ent[1][j] * ld_e;
+            for (int i = tid; i < ROWS; i += T) stage[ROWS * (2 + j) + i] = i < HID2 ? erow[i] : 0.f;
+        }
+        __syncthreads();
+        for (int j = 0; j < n_ent; ++j) {
+            const int first = __builtin_amdgcn_readfirstlane(ent[2][j]), end = __builtin_amdgcn_readfirstlane(ent[3][j]);
+            if (end <= w0 || first >= w0 + MT * 16) continue;               // none of this wavefront's objects belongs to the entry's image
+            const int p = __builtin_amdgcn_readfirstlane(ent[0][j]), col = __builtin_amdgcn_readfirstlane(ent[1][j]);
+            float vm[MT];                                                    // the logit of slot 4 kh + r16 of slot tile m, in the lanes r16 < 4
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+                float part[4] = {0.f, 0.f, 0.f, 0.f};
+                if (j < SR) {
+                    const float* erow = stage + ROWS * (2 + j) + r16;
+#pragma unroll
+                    for (int i = 0; i < NB16; ++i) {
+                        const float ev = erow[i * 16];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) part[e] = fmaf(acc[m][i][e], ev, part[e]);
+                    }
+                } else {
+                    const float* erow = E + (int64_t)col * ld_e;
+#pragma unroll
+                    for (int i = 0; i < NB16; ++i) {
+                        const float ev = i * 16 + r16 < HID2 ? erow[i * 16 + r16] : 0.f;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) part[e] = fmaf(acc[m][i][e], ev, part[e]);
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) part[e] = dfol_group_sum<16>(part[e]);
+                vm[m] = r16 == 0 ? part[0] : (r16 == 1 ? part[1] : (r16 == 2 ? part[2] : part[3]));
+            }
+            // lanes r16 = 4..7 take the second slot tile's logits from the lanes r16 - 4 (DPP row_shr:4): one store for the wavefront's 32 objects
+            const float shifted = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(vm[1]), 0x114, 0xF, 0xF, false));
+            if (r16 < 8) {
+                const int hi = r16 >> 2;
+                const int g = w0 + hi * 16 + 4 * kh + (r16 & 3);
+                if (g >= first && g < end && g - first < NS) {
+                    const float x = (hi ? shifted : vm[0]) + (be ? be[col] : 0.f);
+                    ll[(int64_t)p * NS + (g - first)] = fminf(x, 0.f) - log1pf(expf(-fabsf(x)));       // nn.LogSigmoid, as attr_ll_kernel writes it
+                }
+            }
+        }
+    }
+}
+
 }  // namespace
 
 #ifdef DFOL_PAIR_TRACE
@@ -768,5 +988,32 @@ extern "C" int dfol_pair_train_fwd_h2_f32(const float* UV, int64_t ld_uv, int32_
     else DFOL_PAIR32T(20);
 #undef DFOL_PAIR32T
     DFOL_LAUNCH_CHECK("pair_train_fwd_h2");
+    return 0;
+}
+
+
+// The attribute head without its hidden table (include/dfol_vqa.h).  pre1: the first layer's pre-activations in plain units.
+extern "C" int dfol_attr_head_h2_f32(const float* pre1, int64_t ld_pre1, int32_t HID1, const void* W2_split, const float* b2, int32_t HID2,
+                                     const float* E, int64_t ld_e, const float* be, const int32_t* obj_off, int32_t Q, int32_t O,
+                                     const int32_t* pred_q, const int32_t* pred_col, int32_t P, int32_t NS, float default_ll, float* ll, void* stream) {
+    DFOL_REQUIRE(P >= 0 && Q >= 0 && O >= 0 && NS > 0 && NS % 4 == 0, "attr_head_h2: bad sizes P=%d Q=%d O=%d NS=%d", P, Q, O, NS);
+    DFOL_REQUIRE(HID1 > 0 && HID1 <= 256 && HID1 % H2_CH == 0 && ld_pre1 % 4 == 0 && ld_pre1 >= HID1,
+                 "attr_head_h2: HID1=%d must be a multiple of %d, <= 256, rows 16-byte aligned", HID1, H2_CH);
+    DFOL_REQUIRE(HID2 > 256 && HID2 <= 320, "attr_head_h2: HID2=%d must be in (256, 320]", HID2);
+    if (P == 0) return 0;
+    DFOL_REQUIRE(obj_off && pred_q && pred_col && ll && Q > 0, "attr_head_h2: null pointer (or requests without images)");
+    DFOL_REQUIRE(O == 0 || (pre1 && W2_split && b2 && E), "attr_head_h2: null pointer");
+    DFOL_REQUIRE(((uintptr_t)pre1 % 16 == 0) && ((uintptr_t)W2_split % 16 == 0), "attr_head_h2: operands must be 16-byte aligned");
+    const dim3 grid((unsigned)(O > 0 ? dfol_cdiv(O, AH_SLOTS) : 1));
+    uint32_t* status = dfol_range_status_ptr();
+#define DFOL_ATTR_HEAD(NBV)                                                                                                                      \
+    hipLaunchKernelGGL((attr_head_h2_kernel<NBV>), grid, dim3(AH_T), 0, (hipStream_t)stream, pre1, ld_pre1, HID1, (const u32x4*)W2_split, b2, HID2, E, \
+                       ld_e, be, obj_off, Q, O, pred_q, pred_col, P, NS, default_ll, ll, status)
+    if (HID2 <= 272) DFOL_ATTR_HEAD(17);
+    else if (HID2 <= 288) DFOL_ATTR_HEAD(18);
+    else if (HID2 <= 304) DFOL_ATTR_HEAD(19);
+    else DFOL_ATTR_HEAD(20);
+#undef DFOL_ATTR_HEAD
+    DFOL_LAUNCH_CHECK("attr_head_h2");
     return 0;
 }

@@ -98,6 +98,7 @@ inline void* at(void* base, int64_t off) { return off < 0 ? nullptr : static_cas
 
 int run_dense(const DfolDenseLayer& L, const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t M, void* stream) {
     // the dispatch of _lib.linear_act: the split-operand kernels for weights of >= 65536 elements when the input view allows it
+    DFOL_REQUIRE(L.kind != DFOL_DENSE_HEAD_F16X2, "run_program: a DFOL_DENSE_HEAD_F16X2 layer runs inside DFOL_OP_ATTR_HEAD, not as a dense product");
     const bool split_ok = L.kind != DFOL_DENSE_F32 && L.packed != nullptr && L.K % 4 == 0 && ldx % 2 == 0 && (reinterpret_cast<uintptr_t>(X) % 8 == 0);
     if (!split_ok) return dfol_linear_act_f32(X, ldx, L.weight, L.ldw, L.bias, Y, ldy, M, L.N, L.K, L.act, stream);
     switch (L.kind) {
@@ -129,7 +130,9 @@ extern "C" int dfol_run_program(const DfolProgramModel* model, const DfolProgram
                 const int32_t count = a[1] == 0 ? model->n_featurizer : (a[1] == 1 ? model->n_attribute : 1);
                 DFOL_REQUIRE(layers && a[2] >= 0 && a[2] < count, "run_program[%d]: dense layer %lld of set %lld does not exist", i, (long long)a[2], (long long)a[1]);
                 const float* X = a[3] == 0 ? scene->features + a[4] / 4 : static_cast<const float*>(at(workspace, a[4]));
-                rc = run_dense(layers[a[2]], X, a[3] == 0 ? scene->ld_features : a[5], static_cast<float*>(at(workspace, a[6])), a[7], static_cast<int32_t>(a[8]), stream);
+                DfolDenseLayer layer = layers[a[2]];
+                if (a[9]) layer.act = DFOL_ACT_NONE;
+                rc = run_dense(layer, X, a[3] == 0 ? scene->ld_features : a[5], static_cast<float*>(at(workspace, a[6])), a[7], static_cast<int32_t>(a[8]), stream);
                 break;
             }
             case DFOL_OP_BOX_POSITIONS:  // obj, ld_obj, pos_col
@@ -181,6 +184,15 @@ extern "C" int dfol_run_program(const DfolProgramModel* model, const DfolProgram
                                       static_cast<const int32_t*>(at(blob, a[3])), static_cast<const int32_t*>(at(blob, a[4])), static_cast<int32_t>(a[5]), NS, -30.0f,
                                       static_cast<float*>(at(workspace, a[6])), stream);
                 break;
+            case DFOL_OP_ATTR_HEAD: {    // pre1, ld_pre1, pred_img, cols, P, ll, scenes
+                DFOL_REQUIRE(model->n_attribute == 2 && model->attribute[1].kind == DFOL_DENSE_HEAD_F16X2 && model->attribute[1].packed && model->attribute[1].bias,
+                             "run_program[%d]: the model was not built for the fused attribute head", i);
+                const DfolDenseLayer& l2 = model->attribute[1];
+                rc = dfol_attr_head_h2_f32(static_cast<const float*>(at(workspace, a[1])), a[2], l2.K, l2.packed, l2.bias, l2.N, model->emb_w, model->ld_e, model->emb_b,
+                                           obj_off, static_cast<int32_t>(a[7]), scene->O, static_cast<const int32_t*>(at(blob, a[3])),
+                                           static_cast<const int32_t*>(at(blob, a[4])), static_cast<int32_t>(a[5]), NS, -30.0f, static_cast<float*>(at(workspace, a[6])), stream);
+                break;
+            }
             case DFOL_OP_OPTION_NORMALIZE:   // ll, seg_off, segments, pred_q, rank
                 rc = dfol_option_normalize_f32(static_cast<float*>(at(workspace, a[1])), static_cast<const int32_t*>(at(blob, a[2])), static_cast<int32_t>(a[3]),
                                                static_cast<const int32_t*>(at(blob, a[4])), n_obj, NS, static_cast<int32_t>(a[5]), stream);

@@ -72,6 +72,7 @@ class BatchWorld(object):
         IMAGE-level one the oracle kernels index (`_img_n_list`, `_img_n_obj`, `_obj_off`, `_pair_off`, `_pair_num`: object / pair rows
         are per scene), linked by `_q_img`.  Without sharing they coincide."""
         self._device = device
+        self._hidden_attr_table = None
         self._lazy = None                 # set by the oracle's needed-columns mode: hidden activations instead of tables
         self._rel_tiles = {}              # relation tiles computed ahead of the execution loop, keyed by id(lowered tokens)
         self._attribute_features = attribute_features
@@ -124,6 +125,18 @@ class BatchWorld(object):
     @_attribute_features.setter
     def _attribute_features(self, value):
         self._attr_table = value
+
+    # The attribute network's hidden activations [O, H].  With the fused attribute head (visual_oracle.prepare_scene) an inference scene
+    # holds the first layer's pre-activations only; the table is built for whoever still reads it.
+    @property
+    def _hidden_attr(self):
+        if self._hidden_attr_table is None and self._lazy is not None and getattr(self, "_obj", None) is not None:
+            self._hidden_attr_table = self._lazy._attribute_network(self._obj)
+        return self._hidden_attr_table
+
+    @_hidden_attr.setter
+    def _hidden_attr(self, value):
+        self._hidden_attr_table = value
 
     @property
     def _relation_features(self):

@@ -18,7 +18,7 @@ from . import _lib
 from . import native_plan as NP
 
 _p, _i32, _i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-DENSE_F32, DENSE_F16X2, DENSE_BF16X3, DENSE_BF16 = 0, 1, 2, 3
+DENSE_F32, DENSE_F16X2, DENSE_BF16X3, DENSE_BF16, DENSE_HEAD_F16X2 = 0, 1, 2, 3, 4
 PAIR_PLAIN, PAIR_PACKED, PAIR_BF16X3, PAIR_F16X2 = 0, 1, 2, 3
 
 
@@ -104,6 +104,19 @@ def calibrator(model):
     return fwd, bwd, out[0]
 
 
+def attr_head_on(model):
+    """The executor evaluates the attribute columns with the fused head (visual_oracle._attr_head: a two-layer attribute network, the default
+    two-piece fp16 arithmetic, DFOL_ATTR_HEAD not 0).  The arithmetic is the model's own `mlp_math` where it has one, so a spec made outside
+    a forward (a collater's) agrees with the one the forward makes."""
+    return attr_head_of(model) is not None
+
+
+def attr_head_of(model):
+    """visual_oracle._attr_head() evaluated in the model's own arithmetic: (first Linear, second Linear, packed image, bias) or None."""
+    with _lib.dense_math(getattr(model, "_mlp_math", None)):
+        return model._oracle._attr_head()
+
+
 def model_spec(model, calibrate=False):
     """native_plan.ModelSpec of an interpreter, or None when its modules are not the shapes the executor drives.  calibrate: the forward runs
     the attention-calibration passes (activate_attention_transfer, modulator_switch on)."""
@@ -128,7 +141,8 @@ def model_spec(model, calibrate=False):
             return None
         calib = dict(state_dim=int(nets[0].hidden_size), lstm_in=int(nets[0].input_size), ops_index=dict(model._OPS_INDEX))
     return NP.ModelSpec([l.out_features for l, _ in fl], [l.out_features for l, _ in al], lin1.out_features, fl[-1][0].out_features + 4,
-                        oracle._normalize, model._likelihood_threshold, oracle._ontology._relation_index, tile_bf16=tile_bf16, calib=calib)
+                        oracle._normalize, model._likelihood_threshold, oracle._ontology._relation_index, tile_bf16=tile_bf16, calib=calib,
+                        attr_head=len(al) == 2 and attr_head_on(model))
 
 
 class NativeModel(object):
@@ -138,7 +152,7 @@ class NativeModel(object):
     def __init__(self, model):
         feat, oracle = model._featurizer, model._oracle
         self._hold = []
-        math = _lib._dense_math()
+        math = getattr(model, "_mlp_math", None) or _lib._dense_math()      # (the model's own mode where it has one, as attr_head_of)
         kind, pieces = {"f16x2": (DENSE_F16X2, 2), "bf16x3": (DENSE_BF16X3, 3), "bf16": (DENSE_BF16, 1), "f32": (DENSE_F32, 0)}[math]
 
         def dense(weight, bias, act):
@@ -159,6 +173,12 @@ class NativeModel(object):
         fl, al = _layers(feat._featurizer_network._network), _layers(oracle._attribute_network._network)
         self._fl = (DenseLayer * len(fl))(*[dense(l.weight, l.bias, a) for l, a in fl])
         self._al = (DenseLayer * len(al))(*[dense(l.weight, l.bias, a) for l, a in al])
+        head = attr_head_of(model) if len(al) == 2 else None      # (taken once, in the scope attr_head_on decides in)
+        self.attr_head = head is not None
+        if self.attr_head:                                   # the last attribute layer runs inside DFOL_OP_ATTR_HEAD, from the pair kernel's image format
+            _, _, w2_img, b2_head = head
+            self._al[1].kind, self._al[1].packed, self._al[1].bias = DENSE_HEAD_F16X2, w2_img.data_ptr(), b2_head.data_ptr()
+            self._hold += [w2_img, b2_head]
         wuv, buv, wg, hid1, D = oracle._split_first_layer()
         w2p, b2, hid2, packed = oracle._padded_second_layer()
         emb = oracle._embedding_network.linear
@@ -203,7 +223,8 @@ class NativeModel(object):
         nets = calibrator(model)
         if nets is not None:
             params += [p for m in nets for p in m.parameters()]
-        return (tuple((p.data_ptr(), p._version) for p in params), _lib._dense_math(), _lib.pair_math(), str(params[0].device) if params else "")
+        return (tuple((p.data_ptr(), p._version) for p in params), _lib._dense_math(), _lib.pair_math(), str(params[0].device) if params else "",
+                attr_head_on(model))
 
 
 def native_model(model):

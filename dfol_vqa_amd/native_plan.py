@@ -24,7 +24,7 @@ from .host_util import flatten_list, get_lowered, lower_tokens, segments_of, unf
 # opcodes of include/dfol_vqa.h
 (OP_DENSE, OP_BOX_POSITIONS, OP_FILL, OP_PAIR_LL, OP_ATTR_LL, OP_OPTION_NORMALIZE, OP_FILTER, OP_RELATE_ONE, OP_RELATE, OP_QUANTIFY, OP_GATE,
  OP_LOGIC, OP_SEGMENT_SUM_ROWS, OP_SEGMENT_OR, OP_IMPLICATION, OP_COMPARE, OP_FIND_MAX_IND, OP_GATHER_TILES, OP_CALIB_FEATURES, OP_LSTM_CELL,
- OP_SELECT_ROWS, OP_ATT_MODULATIONS, OP_MODULATE, OP_CALIB_WALK) = range(24)
+ OP_SELECT_ROWS, OP_ATT_MODULATIONS, OP_MODULATE, OP_CALIB_WALK, OP_ATTR_HEAD) = range(25)
 WALK_FILL, WALK_SELECT, WALK_ADD, WALK_LSTM, WALK_ATT_MODULATIONS = range(5)      # steps of an OP_CALIB_WALK table
 INSTR_WIDTH = 16
 LOGIC_AND, LOGIC_OR, LOGIC_NOT = 0, 1, 2
@@ -69,7 +69,8 @@ class ModelSpec(object):
     """What the lowering must know about the model: widths (they size the workspace), the oracle's option normalisation and the
     interpreter's likelihood threshold.  Picklable (collate workers build plans)."""
 
-    def __init__(self, featurizer_widths, attribute_widths, hid1, D, normalize, likelihood_threshold, relation_index, tile_bf16=False, calib=None):
+    def __init__(self, featurizer_widths, attribute_widths, hid1, D, normalize, likelihood_threshold, relation_index, tile_bf16=False, calib=None,
+                 attr_head=False):
         self.featurizer_widths = [int(w) for w in featurizer_widths]      # output width of every featurizer layer (the last = D - 4)
         self.attribute_widths = [int(w) for w in attribute_widths]        # output width of every attribute-network layer
         self.hid1, self.D = int(hid1), int(D)
@@ -79,13 +80,16 @@ class ModelSpec(object):
         # relation tiles stored as bf16 where every consumer reads them directly (relation_tile_dtype: bf16 with a packed second layer of > 256 rows:
         # visual_oracle.prefetch_relations' rule); decided per batch below (NS % 8 == 0, no choose_rel)
         self.tile_bf16 = bool(tile_bf16)
+        # the attribute columns come from the fused head (dfol_attr_head_h2_f32) over the first layer's pre-activations: the network's last
+        # layer is not run as a dense product and its hidden table is not allocated (native_exec.attr_head_on: two layers, default arithmetic)
+        self.attr_head = bool(attr_head)
         # attention calibration (activate_attention_transfer with the modulator switched on): None, or {"state_dim": S, "lstm_in": 18 + token
         # embedding width, "ops_index": operator -> one-hot position (batch_gqa_interpreter.py:67-70)}
         self.calib = None if calib is None else dict(state_dim=int(calib["state_dim"]), lstm_in=int(calib["lstm_in"]), ops_index=dict(calib["ops_index"]))
 
     def key(self):
         return (tuple(self.featurizer_widths), tuple(self.attribute_widths), self.hid1, self.D, self.normalize, self.likelihood_threshold,
-                self.relation_index.tobytes(), self.tile_bf16,
+                self.relation_index.tobytes(), self.tile_bf16, self.attr_head,
                 None if self.calib is None else (self.calib["state_dim"], self.calib["lstm_in"], tuple(sorted(self.calib["ops_index"].items()))))
 
 
@@ -217,11 +221,11 @@ class _Builder(object):
             raise Unsupported("featurizer width")
         self.emit(OP_BOX_POSITIONS, self.obj, D, D - 4)
         x, ldx = self.obj, D
-        for i, w in enumerate(sp.attribute_widths):
+        for i, w in enumerate(sp.attribute_widths[:1] if sp.attr_head else sp.attribute_widths):
             y = self.alloc(O * w * 4)
-            self.emit(OP_DENSE, 1, i, 1, x, ldx, y, w, O)
+            self.emit(OP_DENSE, 1, i, 1, x, ldx, y, w, O, 1 if sp.attr_head else 0)      # (the fused head takes pre-activations)
             x, ldx = y, w
-        self.hidden, self.H = x, ldx
+        self.hidden, self.H = x, ldx                               # (with the fused head: the first layer's pre-activations)
         self.uv = self.alloc(O * 2 * sp.hid1 * 4)
         self.emit(OP_DENSE, 2, 0, 1, self.obj, D, self.uv, 2 * sp.hid1, O)
 
@@ -312,7 +316,10 @@ class _Builder(object):
         ll = self.block(total)
         cols = np.concatenate([low.cols for _, low, _ in todo]).astype(np.int32)
         pimg = np.concatenate([self.q_img[np.asarray(pq, np.int64)].astype(np.int32) for _, _, pq in todo])        # predicate -> scene
-        self.emit(OP_ATTR_LL, self.hidden, self.H, self.arr(pimg), self.arr(cols), total, ll)
+        if self.spec.attr_head:
+            self.emit(OP_ATTR_HEAD, self.hidden, self.H, self.arr(pimg), self.arr(cols), total, ll, self.n_img)
+        else:
+            self.emit(OP_ATTR_LL, self.hidden, self.H, self.arr(pimg), self.arr(cols), total, ll)
         base = 0
         for k, low, pq in todo:
             self.attr[k] = ll.at(base * self.NS * 4)

@@ -679,6 +679,42 @@ class ClassifierOracle(OracleBase):
             self._split_cache = (key, wuv, buv, wg, hid1, D)
         return L.keep_alive(self._split_cache)[1:]
 
+    def _attr_head(self):
+        """(first Linear, second Linear, packed image of the second, its bias) when the attribute columns of an inference forward come from
+        the fused head - a two-layer attribute network (Linear, ELU, Linear, Sigmoid) of the pair kernel's second-layer shapes, the default
+        two-piece fp16 arithmetic, DFOL_ATTR_HEAD not 0 - else None: the hidden table + dfol_attr_ll_f32."""
+        if os.environ.get("DFOL_ATTR_HEAD", "1") == "0" or _lib._dense_math() != "f16x2":
+            return None
+        net = None if self._attribute_network is None else self._attribute_network._network
+        if net is None:
+            return None
+        mods = [m for m in net if not isinstance(m, nn.Dropout)]
+        if len(mods) != 4 or not (isinstance(mods[0], nn.Linear) and isinstance(mods[1], nn.ELU) and isinstance(mods[2], nn.Linear) and isinstance(mods[3], nn.Sigmoid)):
+            return None
+        if any(isinstance(m, nn.Dropout) and m.training and m.p > 0 for m in net):
+            return None
+        lin1, lin2 = mods[0], mods[2]
+        w = lin2.weight
+        if lin2.bias is None or not w.is_cuda or w.dtype != torch.float32 or not L.attr_head_supported(w.shape[1], w.shape[0]):
+            return None
+        key = (w.data_ptr(), w._version, lin2.bias._version)
+        cache = getattr(self, "_attr_w2_cache", None)
+        if cache is None or cache[0] != key:                 # packed once per weight version, like the pair kernel's image
+            self._attr_w2_cache = cache = (key, L.pair_pack_w2_h2(w.detach().contiguous(), w.shape[0]), lin2.bias.detach().contiguous())
+        L.keep_alive(cache)
+        return lin1, lin2, cache[1], cache[2]
+
+    def _attr_columns(self, world, pred_img, cols):
+        """Attribute blocks [P, NS] of the requested (scene, concept) pairs: the fused head over the first layer's pre-activations, or
+        dfol_attr_ll_f32 over the hidden table."""
+        emb = self._embedding_network.linear
+        if getattr(world, "_attr_pre1", None) is not None:
+            # (the scene carries the image it was prepared with: a switch or arithmetic scope that changed since then does not reach it)
+            w2, b2, hid2 = world._attr_head_w2
+            _lib.note("attr_head")
+            return L.attr_head_h2(world._attr_pre1, w2, b2, hid2, emb.weight, emb.bias, world._obj_off, pred_img, cols, world._NS, -30.0)
+        return L.attr_ll(world._hidden_attr, emb.weight, emb.bias, world._obj_off, pred_img, cols, world._NS, -30.0)
+
     def _pair_kind(self):
         """Which fused pair kernel evaluates this oracle's relation tiles: "f16x2", "bf16x3", "packed" (fp32 pipe, packed W2) or "plain"."""
         packed = self._padded_second_layer()[3]
@@ -715,7 +751,17 @@ class ClassifierOracle(OracleBase):
         world._lazy = self
         world._obj = obj
         world._train = bool(train)
-        world._hidden_attr = self._attribute_network(obj)
+        # inference with the fused attribute head (csrc/dfol_pair_h2.hip: attr_head_h2_kernel): only the first layer's pre-activations are
+        # computed here; the hidden table [O, 300] is built when somebody reads world._hidden_attr (fol_types.BatchWorld), which the
+        # needed-columns routes below never do.  Training keeps the table: its backward reads it.
+        head = None if train else self._attr_head()
+        world._attr_pre1 = world._attr_head_w2 = None
+        if head is not None:
+            world._hidden_attr = None
+            world._attr_head_w2 = (head[2], head[3], head[1].weight.shape[0])      # packed second layer, its bias, its width
+            world._attr_pre1 = L.linear_act(obj, head[0].weight, head[0].bias, L.ACT_NONE)
+        else:
+            world._hidden_attr = self._attribute_network(obj)
         world._attr_table = None
         world._rel_table = None
         world._pair_h = None
@@ -1259,7 +1305,7 @@ class ClassifierOracle(OracleBase):
         emb = self._embedding_network.linear
         cols = upload(np.concatenate([low.cols for low in lows]), dev)
         pred_img = upload(np.tile(world._q_img.astype(np.int32), len(lows)), dev)          # predicate -> scene (= question without sharing)
-        ll = L.attr_ll(world._hidden_attr, emb.weight, emb.bias, world._obj_off, pred_img, cols, world._NS, -30.0)
+        ll = self._attr_columns(world, pred_img, cols)
         world._attr_blocks = {id(low): ll[i * Q:(i + 1) * Q] for i, low in enumerate(lows)}
 
     @staticmethod
@@ -1352,7 +1398,7 @@ class ClassifierOracle(OracleBase):
         elif token_type == TokenType.ATTRIBUTE:
             ll = getattr(world, "_attr_blocks", {}).get(id(low)) if pred_q is world._ident else None      # prefetch_attributes
             if ll is None:
-                ll = L.attr_ll(world._hidden_attr, emb.weight, emb.bias, world._obj_off, world.pred_img(pred_q), cols, world._NS, -30.0)
+                ll = self._attr_columns(world, world.pred_img(pred_q), cols)
         else:
             assert orientation == L.TILE_SUBJECT_ROWS
             hit = world._rel_tiles.get(id(low))

@@ -39,7 +39,11 @@ extern "C" {
 
 /* 3 (round 6): dfol_pair_ll_h2_f32 takes UV in units of ln 2 and dfol_pair_pack_w2_f16x2 folds ln 2 into W2 (the round-5 change of contract that
  * kept version 2: a caller written against 2 passes unscaled UV and must be refused, not answered wrongly); dfol_pair_ll_h2_f32 reports saturated
- * ELU outputs through the dfol_set_range_status word (DFOL_RANGE_PAIR_SATURATED); dfol_run_program knows the calibration instructions. */
+ * ELU outputs through the dfol_set_range_status word (DFOL_RANGE_PAIR_SATURATED); dfol_run_program knows the calibration instructions.
+ * The rule: the version changes when a caller written against the old one would be answered wrongly - an entry point whose arguments or units
+ * change, a struct whose layout changes.  Pure additions keep it: dfol_attr_head_h2_f32, DFOL_OP_ATTR_HEAD, DFOL_DENSE_HEAD_F16X2 and the ninth
+ * operand of DFOL_OP_DENSE (a slot that instruction tables written before it hold as zero = the layer's own activation) were added under 3;
+ * a caller that needs them checks for the symbol, and a table that names an opcode an older library lacks is refused by it ("unknown opcode"). */
 #define DFOL_ABI_VERSION 3
 
 /* ---- library ---------------------------------------------------------------------------------- */
@@ -689,6 +693,21 @@ int dfol_clip_adam_f32(float* g, const float* partials, const int64_t* param, co
 #define DFOL_RANGE_PAIR_SATURATED 2u /* dfol_pair_ll_h2_f32: a first-layer sum may exceed the ELU saturation point 6e4 / log2(e) = 4.16e4 (or is NaN) */
 int dfol_set_range_status(uint32_t* device_word);
 
+/* ---- the attribute head without its hidden table (needed columns only) ---------------------------------------------------------------
+ * ll[p][o] = LogSigmoid(Sigmoid(W2 ELU(pre1[first(q) + o]) + b2) . E[pred_col[p]] + be[pred_col[p]]) for every object o of image q = pred_q[p],
+ * default_ll where pred_col[p] < 0 and in the columns o >= n(q): what dfol_linear_act_h2_f32 (ELU), dfol_linear_act_h2_f32 (Sigmoid) and
+ * dfol_attr_ll_f32 compute together, in one launch that keeps the [O, HID2] hidden table in registers (the object-slot form of
+ * dfol_pair_ll_h2_f32's body: same packed image, same two fp16 pieces and three products, same saturation of the ELU outputs).
+ *   pre1      [O, ld_pre1] the attribute network's first-layer PRE-activations (bias included, no ELU), plain units; rows 16-byte aligned
+ *   W2_split  dfol_pair_pack_w2_f16x2 image of the attribute network's second layer [HID2, HID1]; HID1 % 32 == 0, <= 256; 256 < HID2 <= 320
+ *   obj_off   [Q + 1] first object row of every image; O = obj_off[Q] rows in all; n(q) <= NS
+ *   pred_q / pred_col [P] image and embedding row of every predicate, in ANY order (repeated columns allowed); 0 <= pred_q[p] < Q (not
+ *             checked, as in dfol_attr_ll_f32: obj_off[pred_q[p] + 1] is read); pred_col[p] < 0 = a no-op token, else a row of E
+ * An activation beyond the saturation point 6e4 / log2(e) (or NaN) ORs DFOL_RANGE_X_OVERFLOW into the dfol_set_range_status word. */
+int dfol_attr_head_h2_f32(const float* pre1, int64_t ld_pre1, int32_t HID1, const void* W2_split, const float* b2, int32_t HID2, const float* E,
+                          int64_t ld_e, const float* be, const int32_t* obj_off, int32_t Q, int32_t O, const int32_t* pred_q,
+                          const int32_t* pred_col, int32_t P, int32_t NS, float default_ll, float* ll, void* stream);
+
 /* ---- the native executor of a lowered ProgramBatch (round 5) -------------------------------------------------------------------------
  * Replaces the reference's per-operator Python dispatch for one ProgramBatch - BatchInterpreterBase.forward's build_scene call and execution
  * loop, batch_base_interpreter.py:45-70 and :145-172, with BatchGQAInterpreter._execute, batch_gqa_interpreter.py:72-78, and the operator
@@ -707,6 +726,8 @@ int dfol_set_range_status(uint32_t* device_word);
 #define DFOL_DENSE_F16X2 1  /* dfol_linear_act_h2_f32 on the dfol_linear_pack_w_f16x2 image */
 #define DFOL_DENSE_BF16X3 2 /* dfol_linear_act_split_f32 on the dfol_linear_pack_w_bf16x3 image */
 #define DFOL_DENSE_BF16 3   /* dfol_linear_act_bf16_f32 on the dfol_linear_pack_w_bf16 image */
+#define DFOL_DENSE_HEAD_F16X2 4 /* the attribute network's LAST layer when DFOL_OP_ATTR_HEAD evaluates it: `packed` is its dfol_pair_pack_w2_f16x2 image
+                                 * (dfol_attr_head_h2_f32); DFOL_OP_DENSE refuses such a layer */
 #define DFOL_PAIR_PLAIN 0   /* dfol_pair_ll_f32 */
 #define DFOL_PAIR_PACKED 1  /* dfol_pair_ll_packed_f32 */
 #define DFOL_PAIR_BF16X3 2  /* dfol_pair_ll_split_f32 */
@@ -764,7 +785,7 @@ typedef struct {            /* the scenes of one ProgramBatch (data_pipeline.py:
 } DfolProgramScene;
 
 /* opcodes (operand lists in csrc/dfol_program.hip, written by dfol_vqa_amd/native_plan.py) */
-#define DFOL_OP_DENSE 0
+#define DFOL_OP_DENSE 0              /* set, layer, x source, x, ldx, y, ldy, M, 1 = without the layer's activation (the pre-activations DFOL_OP_ATTR_HEAD takes) */
 #define DFOL_OP_BOX_POSITIONS 1
 #define DFOL_OP_FILL 2
 #define DFOL_OP_PAIR_LL 3
@@ -791,6 +812,8 @@ typedef struct {            /* the scenes of one ProgramBatch (data_pipeline.py:
 #define DFOL_OP_CALIB_WALK 23       /* table (blob: n steps of DFOL_INSTR_WIDTH int64, DFOL_WALK_* below), n, rows: a run of row-wise steps of the calibration
                                      * passes over states of `rows` rows in ONE launch - what DFOL_OP_FILL / SELECT_ROWS / LOGIC (add) / LSTM_CELL (token form) /
                                      * ATT_MODULATIONS launches in a row would compute, bit for bit (a workgroup owns 16 rows and walks the table) */
+#define DFOL_OP_ATTR_HEAD 24        /* pre1, ld_pre1, pred_img (blob), cols (blob), P, ll, scenes: dfol_attr_head_h2_f32 over the attribute network's last layer
+                                     * (a two-layer network whose last layer is DFOL_DENSE_HEAD_F16X2) - replaces that layer's DFOL_OP_DENSE and DFOL_OP_ATTR_LL */
 /* steps of a DFOL_OP_CALIB_WALK table; buffers are [planes][rows][width] floats in the workspace (an LSTM state is h then c: two planes) */
 #define DFOL_WALK_FILL 0            /* dst, planes, width, 32-bit pattern */
 #define DFOL_WALK_SELECT 1          /* x, y, flags (blob, uint8 [planes * rows]), planes, width, out: out = flags ? x : y per row */
