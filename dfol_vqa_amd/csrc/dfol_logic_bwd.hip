@@ -356,10 +356,14 @@ __global__ void option_normalize_bwd_kernel(const float* __restrict__ g_y, const
         gsum += g_y[p * stride + e];
         wsum += dfol_exp(y[p * stride + e]);
     }
-    const bool clamped = wsum < 0.5f;                       // sum of softmax weights is 1 unless log(max(Z, eps)) hit the floor
+    // The softmax weights sum to 1 (to fp32 rounding, 1e-5 at most) unless log(max(Z, eps)) hit the floor: then they sum to Z / eps < 1
+    // (a threshold of 0.5 took Z in [eps / 2, eps) for unclamped).  A lone option has y = 0 whatever x is, so dx = 0 exactly; e^y is 1 only
+    // to rounding.
+    const bool clamped = wsum < 0.99f;
+    const bool lone = p1 - p0 == 1;
     for (int p = p0; p < p1; ++p) {
         const float g = g_y[p * stride + e];
-        g_x[p * stride + e] = clamped ? g : g - dfol_exp(y[p * stride + e]) * gsum;
+        g_x[p * stride + e] = clamped ? g : (lone ? 0.f : g - dfol_exp(y[p * stride + e]) * gsum);
     }
 }
 

@@ -150,3 +150,165 @@ def g23_case(kind, arrays, meta):
     qs = [syn.question(q["question_id"], q["program"]["branches"], q["program"]["last_op"], q["answer"], syn.feature_scene(q["question_id"], q["n"], meta["feature_dim"]))
           for q in cm["questions"]]
     return qs, cm
+
+
+# ---------------------------------------------------------------------------------------------------
+# soft-logic gradients: a torch restatement of the block formulas, differentiated by torch autograd on the
+# CPU in float32 and float64, and the per-element tolerance policy of tests/test_logic_backward_gpu.py
+# ---------------------------------------------------------------------------------------------------
+EPS = 1e-20
+NEAR_FLOOR = 1e-4             # a float64 denominator within a factor 1 +- NEAR_FLOOR of EPS may be clamped in one precision and not the other
+GRAD_FLOOR = 2.0 ** -20       # dfol_exp scales x by log2(e) in fp32: e^x carries up to |x| 2^-24 (2.7e-6 at the clamp's x = -46); a gradient is a product of three such factors
+GRAD_TINY = 2.0 ** -106       # fp32's smallest normal number over GRAD_FLOOR: below it a kernel that flushes subnormals is off by more than the floor allows
+
+
+def t_slog(x):
+    import torch
+    return torch.log(x.clamp_min(EPS))
+
+
+def t_pnot(x, a):
+    import torch
+    return t_slog(a + (1 - 2 * a) * torch.exp(x))
+
+
+def t_near(x, a):
+    """Where the denominator of t_pnot(x, a) lies at the clamp's boundary (float64 inputs)."""
+    import torch
+    d = a + (1 - 2 * a) * torch.exp(x.detach())
+    return (d > EPS * (1 - NEAR_FLOOR)) & (d < EPS * (1 + NEAR_FLOOR))
+
+
+def t_prep(l, neg, any_neg):
+    """-relu(-l) (subgradient 0 at and above 0, as the reference's torch relu) and the optional negation."""
+    import torch
+    v = -torch.relu(-l)
+    return t_pnot(v, float(neg)) if any_neg else v
+
+
+def t_relate(a, b, l, qs, qo, neg, any_neg, lone_forall_identity=False, near=None):
+    """oracle.relate_block in torch: a, b [n]; l [n, n] the raw tile, subjects along rows.  `lone_forall_identity`: a FOR_ALL variable
+    takes the literal branch of a single predicate (no parametric not, no clamp).  `near` (a dict) receives the clamp-boundary masks."""
+    import torch
+    n = a.shape[0]
+    qs, qo = float(qs), float(qo)
+    v = t_prep(l, neg, any_neg)
+    off = 1 - torch.eye(n, dtype=l.dtype)
+    id_s, id_o = lone_forall_identity and qs == 0, lone_forall_identity and qo == 0
+    F_s = (lambda x: x) if id_s else (lambda x: t_pnot(x, qs))
+    F_o = (lambda x: x) if id_o else (lambda x: t_pnot(x, qo))
+    u1, u2 = v + b[None, :], v + a[:, None]
+    S, T = (F_o(u1) * off).sum(1), (F_s(u2) * off).sum(0)
+    if near is not None:
+        m = torch.zeros(n, n, dtype=torch.bool)
+        if any_neg:
+            m |= t_near(-torch.relu(-l), float(neg))
+        if not id_o:
+            m |= t_near(u1, qo) | t_near(S, qo)[:, None]
+        if not id_s:
+            m |= t_near(u2, qs) | t_near(T, qs)[None, :]
+        m &= off.bool()
+        near["tile"], near["s"], near["o"] = m, m.any(1), m.any(0)
+    return a + F_o(S), b + F_s(T)
+
+
+def t_filter(prior, ll, neg, any_neg):
+    return prior + t_prep(ll, neg, any_neg)
+
+
+def t_quantify(att, qf):
+    qf = float(qf)
+    return t_pnot(t_pnot(att, qf).sum(), qf)
+
+
+def t_lnot(x):
+    return t_pnot(x, 1.0)
+
+
+def t_or(a, b):
+    import torch
+    return t_slog(1 - (1 - torch.exp(a)) * (1 - torch.exp(b)))
+
+
+def t_segment_or(lp):
+    return t_lnot(t_lnot(lp).sum())
+
+
+def t_implication(prior, x):
+    return t_lnot(prior + t_lnot(x))
+
+
+def t_compare(lp1, lp2, is_less):
+    import torch
+    ls = torch.log_softmax(torch.stack([lp1, lp2], 1), 1)
+    return t_pnot(ls, is_less[:, None])
+
+
+def t_option_normalize(x):
+    """x [K, ...]: the K options of one segment."""
+    import torch
+    return x - t_slog(torch.exp(x).sum(0, keepdim=True))
+
+
+def autograd_pair(fn, inputs):
+    """fn(*tensors) -> scalar.  Gradients w.r.t. every input from torch autograd on the CPU, once in float32 and once in float64:
+    ([r32...], [r64...]) as float64 numpy arrays (an input that does not reach the result has gradient 0)."""
+    import torch
+    out = []
+    for dt in (torch.float32, torch.float64):
+        leaves = [torch.tensor(np.asarray(x), dtype=dt, requires_grad=True) for x in inputs]
+        fn(*leaves).backward()
+        out.append([np.zeros(t.shape) if t.grad is None else t.grad.numpy().astype(np.float64) for t in leaves])
+    return out[0], out[1]
+
+
+GRAD_TABLE = []               # (what, own, largest ratio, elements, left out) of every check_gradient call, for the printed table
+
+
+def check_gradient(got, r32, r64, what, owned=None, near=None, K=8.0, own=None, block_axis0=False, min_max=None, min_share=None,
+                   signed_zero_ok=False):
+    """A kernel's gradient against the float64 autograd of the restatement, element by element:
+
+        s_i = |r64_i| + 1e-3 max|r64|        (the max over the tensor; with block_axis0 over the element's slice along axis 0)
+        own = max(2^-20, max_i |r32_i - r64_i| / s_i)          (how much rounding noise the formula itself carries; may be given)
+        |got_i - r64_i| <= K own s_i
+
+    owned: the cells some object owns; every other cell must be exactly 0 (bit for bit: +0, unless signed_zero_ok).  near: cells at the clamp's boundary, left out
+    (at most 0.1 % of the owned ones).  min_max / min_share: the float64 gradient itself must be worth checking (largest magnitude;
+    share of the owned cells above 1e-6 of it).  Prints and records own and the largest observed ratio."""
+    got, r32, r64 = (np.asarray(x, np.float64) for x in (got, r32, r64))
+    assert got.shape == r32.shape == r64.shape, (what, got.shape, r32.shape, r64.shape)
+    assert np.all(np.isfinite(got)), "%s: %d non-finite values" % (what, int((~np.isfinite(got)).sum()))
+    assert np.all(np.isfinite(r64)) and np.all(np.isfinite(r32)), what
+    owned = np.ones(got.shape, bool) if owned is None else np.asarray(owned, bool)
+    if not owned.all():
+        stray = got[~owned]
+        assert not stray.any() and (signed_zero_ok or not np.signbit(stray).any()), "%s: %d cells nobody owns are not +0" % (what, int((stray != 0).sum()))
+        assert not r64[~owned].any(), what + ": the reference has a gradient in a cell nobody owns"
+    if min_max is not None:
+        top = np.abs(r64).max() if r64.size else 0.0
+        assert top >= min_max, "%s: the float64 gradient is at most %.3g: nothing to check" % (what, top)
+        share = (np.abs(r64[owned]) > 1e-6 * top).mean()
+        assert share >= min_share, "%s: only %.3g of the owned cells carry a gradient" % (what, share)
+    keep = owned.copy()
+    left_out = 0
+    if near is not None:
+        near = np.asarray(near, bool) & owned
+        left_out = int(near.sum())
+        assert left_out <= 1e-3 * owned.sum(), "%s: %d of %d cells at the clamp's boundary" % (what, left_out, int(owned.sum()))
+        keep &= ~near
+    if block_axis0 and r64.ndim > 1:
+        top = np.abs(r64).reshape(r64.shape[0], -1).max(1).reshape((-1,) + (1,) * (r64.ndim - 1))
+    else:
+        top = np.abs(r64).max() if r64.size else 0.0
+    s = np.abs(r64) + 1e-3 * top + GRAD_TINY
+    measured = float((np.abs(r32 - r64) / s)[keep].max()) if keep.any() else 0.0
+    own = max(GRAD_FLOOR, measured if own is None else own)
+    ratio = float((np.abs(got - r64) / s)[keep].max()) if keep.any() else 0.0
+    GRAD_TABLE.append((what, own, ratio, int(keep.sum()), left_out))
+    print("  %-78s own %.3g  ratio %.3g (%.3g of the bound)  n %d  left out %d" % (what, own, ratio, ratio / (K * own), int(keep.sum()), left_out))
+    if ratio > K * own:
+        bad = np.unravel_index(np.argmax(np.where(keep, np.abs(got - r64) / s, 0)), got.shape)
+        raise AssertionError("%s: |g - r64| / s = %.3g > %g * own (%.3g) at %s: got %.9g, r64 %.9g, r32 %.9g"
+                             % (what, ratio, K, own, bad, got[bad], r64[bad], r32[bad]))
+    return own, ratio
