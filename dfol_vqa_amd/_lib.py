@@ -189,6 +189,10 @@ SIGNATURES = {
     "dfol_pair_pack_w2_f16x2": [_p, _i64, _i32, _i32, _p, _p],
     "dfol_pair_ll_h2_f32": [_p, _i64, _i32, _p, _i64, _p, _p, _p, _i32, _p, _i64, _p, _p, _p, _i32, _i32, _p, _p, _p, _i32, _i32, _f,
                             _i32, _p, _p],
+    "dfol_pair_w2_f16_bytes": [_i32],
+    "dfol_pair_pack_w2_f16": [_p, _i64, _i32, _i32, _p, _p],
+    "dfol_pair_ll_h1_f32": [_p, _i64, _i32, _p, _i64, _p, _p, _p, _i32, _p, _i64, _p, _p, _p, _i32, _i32, _p, _p, _p, _i32, _i32, _f,
+                            _i32, _p, _p],
     "dfol_run_program": [_p, _p, _p, _i32, _p, _p, _p],
     "dfol_set_range_status": [_p],
 }
@@ -217,6 +221,7 @@ def load():
         fn.restype = ctypes.c_int
     lib.dfol_linear_wgrad_workspace.restype = ctypes.c_int64
     lib.dfol_pair_w2_f16x2_bytes.restype = ctypes.c_int64
+    lib.dfol_pair_w2_f16_bytes.restype = ctypes.c_int64
     lib.dfol_linear_w_f16x2_bytes.restype = ctypes.c_int64
     lib.dfol_pair_wgrad_fused_workspace.restype = ctypes.c_int64
     lib.dfol_pair_wgrad_fused_sums_workspace.restype = ctypes.c_int64
@@ -949,6 +954,32 @@ def pair_ll_h2(uv, hid1, pos, wg, w2_h2, b2, hid2, emb_w, emb_b, n_obj, obj_off,
     return tiles
 
 
+def pair_pack_w2_h1(w2, hid2=None):
+    """W2 [HID2(+padding), HID1] -> the one-piece fp16 image dfol_pair_ll_h1_f32 reads: the hi pieces of pair_pack_w2_h2's image (same row
+    scales, swizzle and tail), 20 KB per 32 k."""
+    hid1 = w2.shape[1]
+    hid2 = w2.shape[0] if hid2 is None else hid2
+    out = torch.empty(load().dfol_pair_w2_f16_bytes(hid1) // 2, dtype=torch.float16, device=w2.device)
+    call("dfol_pair_pack_w2_f16", _ptr(w2, F32), w2.stride(0), hid2, hid1, _ptr(out, torch.float16), _stream())
+    return out
+
+
+def pair_ll_h1(uv, hid1, pos, wg, w2_h1, b2, hid2, emb_w, emb_b, n_obj, obj_off, max_n, req_col, req_tile, req_orient, tiles,
+               default_ll=-30.0, uv_prescaled=False):
+    """As pair_ll_h2 in the opt-in reduced-precision mode (pair_math "f16"): operands rounded to fp16, ONE product per MAC, fp32
+    accumulation, on the image of pair_pack_w2_h1.  Same arguments, same units of `uv`, same saturation report."""
+    if not uv_prescaled:
+        uv = uv * LOG2E
+    K, Q = req_col.shape
+    NS = tiles.shape[1]
+    bf16 = tiles.dtype == torch.bfloat16
+    call("dfol_pair_ll_h1_f32", _dp(uv), uv.stride(0), hid1, _dp(pos), pos.stride(0), _ptr(wg, F32),
+         _ptr(w2_h1, torch.float16), _ptr(b2, F32), hid2, _dp(emb_w), emb_w.stride(0), _ptr(emb_b, F32, True), _ptr(n_obj, I32),
+         _ptr(obj_off, I32), Q, max_n, _ptr(req_col, I32), _ptr(req_tile, I32), _ptr(req_orient, U8, True), K, NS, default_ll,
+         TILE_BF16 if bf16 else TILE_F32, _ptr(tiles, torch.bfloat16 if bf16 else F32), _stream())
+    return tiles
+
+
 def pair_train_fwd_h2(uv_scaled, hid1, pos, wg, w2_h2, b2, hid2, n_obj, obj_off, pair_off, max_n, pairs, e_rows=None, req_row=None):
     """The forward of a train step's pair MLP in one launch (include/dfol_vqa.h: dfol_pair_train_fwd_h2_f32).  uv_scaled: U | V times log2(e).
     -> (Z [pairs, hid1], pre2 [pairs, hid2], geo [pairs, 4], x [K, pairs] or None).  req_row [K, Q] int32 (device): the row of e_rows
@@ -966,14 +997,40 @@ def pair_train_fwd_h2(uv_scaled, hid1, pos, wg, w2_h2, b2, hid2, n_obj, obj_off,
     return z, pre2, geo, x
 
 
+PAIR_MATH_MODES = ("f16x2", "bf16x3", "f32", "f16")
+_PAIR_MATH_OVERRIDE = None
+
+
 def pair_math():
     """Arithmetic of the fused pair kernel's second layer: "f16x2" (default: two fp16 pieces, three products), "bf16x3" (round 3's: three
-    bf16 pieces, six products) or "f32" (the fp32 matrix pipe) - all with fp32 results; DFOL_PAIR_MATH selects for A/B runs."""
+    bf16 pieces, six products) or "f32" (the fp32 matrix pipe) - all with fp32 results - or "f16": REDUCED precision, operands rounded to
+    fp16 and one product per MAC (a third of the matrix work; opt-in only, inference only: config key `pair_math: f16`).  A
+    pair_math_scope() takes precedence over the DFOL_PAIR_MATH environment variable, which takes precedence over the rule: "bf16x3" when
+    the dense math is, otherwise "f16x2" (`mlp_math: bf16` does not imply "f16")."""
     # (`mlp_math: bf16x3` / dense_math("bf16x3") - the remedy for activations beyond fp16's range - moves the pair kernel along with the dense layers)
-    m = os.environ.get("DFOL_PAIR_MATH") or ("bf16x3" if _dense_math() == "bf16x3" else "f16x2")
-    if m not in ("f16x2", "bf16x3", "f32"):
-        raise DfolError("DFOL_PAIR_MATH=%r (f16x2, bf16x3 or f32)" % m)
+    m = _PAIR_MATH_OVERRIDE or os.environ.get("DFOL_PAIR_MATH") or ("bf16x3" if _dense_math() == "bf16x3" else "f16x2")
+    if m not in PAIR_MATH_MODES:
+        raise DfolError("DFOL_PAIR_MATH=%r (f16x2, bf16x3, f32, or f16: reduced precision, one fp16 product per MAC)" % m)
     return m
+
+
+class pair_math_scope:
+    """with pair_math_scope("f16"): ...   - the pair kernel's arithmetic inside the block (None: no change), as dense_math for the dense layers."""
+
+    def __init__(self, mode):
+        if mode is not None and mode not in PAIR_MATH_MODES:
+            raise DfolError("unknown pair math mode %r (%s)" % (mode, ", ".join(PAIR_MATH_MODES)))
+        self.mode = mode
+
+    def __enter__(self):
+        global _PAIR_MATH_OVERRIDE
+        self.saved, _PAIR_MATH_OVERRIDE = _PAIR_MATH_OVERRIDE, (self.mode or _PAIR_MATH_OVERRIDE)
+        return self
+
+    def __exit__(self, *exc):
+        global _PAIR_MATH_OVERRIDE
+        _PAIR_MATH_OVERRIDE = self.saved
+        return False
 
 
 # ---- training path of the pair MLP (csrc/dfol_pair_train.hip) ------------------------------------------------------

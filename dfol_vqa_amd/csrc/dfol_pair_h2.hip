@@ -54,6 +54,12 @@ __device__ long long dfol_h2_trace_buf[8 * 8 * 64];
 #ifndef DFOL_H2_BDEPTH
 #define DFOL_H2_BDEPTH 2
 #endif
+// the same distance for the one-piece kernel (NP = 1): a tile is two MFMAs there, 32 cycles of the pipe, so the same time ahead is more tiles
+// (four fragments in flight are 20 registers, fewer than the 24 of the two-piece form).  NOT MEASURED against 2 or 3: the value follows
+// from that arithmetic alone.  Cross-compiled, NP = 1 <19> takes 240 / 244 / 248 VGPRs at depth 2 / 3 / 4, no scratch at any of them.
+#ifndef DFOL_H1_BDEPTH
+#define DFOL_H1_BDEPTH 4
+#endif
 // Y's chunk requests as inline asm (1): in flight across the build tick's closing barrier
 #ifndef DFOL_H2_DMA_ASM
 #define DFOL_H2_DMA_ASM 1
@@ -74,6 +80,7 @@ constexpr float H2_NL2E = -1.44269504088896340736f;         // -log2(e)
 constexpr int H2_CH = 32;                                   // K per chunk = one v_mfma_f32_16x16x32_f16
 constexpr int H2_ROWS = 320, H2_TILES = 20;                 // rows (hidden columns) of the packed image
 constexpr int H2_PIECES = 2 * H2_ROWS * 4;                  // 16-byte pieces per chunk: 2560 = 40 KB
+constexpr int H1_PIECES = H2_ROWS * 4;                      // ... of the one-piece image (pair_math "f16"): 1280 = 20 KB
 constexpr float H2_AMAX = 60000.0f;                         // activations saturate here (fp16 max 65504); in units of 1 / ln 2 (see make_a): ELU outputs of 41 589
 constexpr float H2_L2E = 1.44269504088896340736f;           // log2(e) = 1 / ln 2
 constexpr float H2_LN2 = 0.69314718055994530942f;
@@ -119,12 +126,14 @@ __global__ void h2_row_scale_kernel(const float* __restrict__ W2, int64_t ld_w2,
     }
 }
 
-// One thread per 16-byte piece of the packed image.
+// One thread per 16-byte piece of the packed image.  NP = 2: [hi pieces][lo pieces] per chunk; NP = 1: the hi pieces alone (the same bits).
+template <int NP>
 __global__ void h2_pack_w2_kernel(const float* __restrict__ W2, int64_t ld_w2, int HID2, int HID1, const float* __restrict__ tail,
                                   u32x4* __restrict__ out) {
+    constexpr int PIECES = NP * H2_ROWS * 4;
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (HID1 / H2_CH) * H2_PIECES) return;
-    const int c = idx / H2_PIECES, rem = idx - c * H2_PIECES;
+    if (idx >= (HID1 / H2_CH) * PIECES) return;
+    const int c = idx / PIECES, rem = idx - c * PIECES;
     const int p = rem / (H2_ROWS * 4), rr = rem - p * H2_ROWS * 4, r = rr >> 2, slot = rr & 3;
     const int kq = slot ^ dfol_swz(r);
     const int e = reinterpret_cast<const int32_t*>(tail)[H2_ROWS + r];
@@ -161,7 +170,9 @@ struct H2Train {
 // 32 of them (two 16-slot tiles) and all NB16 column tiles (2 x NB16 accumulator tiles: 152 registers at NB16 = 19).  A workgroup runs
 // wg_tiles consecutive pair tiles (tile = image * tiles_per_image + tb, the order of the T = 1 grid) one after the other: the geometry
 // weights are staged once, the epilogue's rows once per image, and the next tile's start runs under the current one's end (see the tile loop).
-template <int NB16, bool TBF16, bool TRAIN = false>
+// NP: fp16 pieces per operand.  2 = the three products above (fp32 accuracy); 1 = the opt-in reduced mode (pair_math "f16": A = fp16(a), the
+// one-piece W2 image, ONE product per MAC - 38 MFMAs and 19 fragment reads per chunk, 20 KB chunk buffers; everything else is the same body).
+template <int NB16, bool TBF16, bool TRAIN = false, int NP = 2>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void pair_ll32h_kernel(
     const float* UV_ /* not __restrict__: see load_uv */, int64_t ld_uv_, int HID1, const float* __restrict__ pos_, int64_t ld_pos_,
     const float* __restrict__ Wg_, const u32x4* __restrict__ W2h_, const float* __restrict__ b2_, int HID2,
@@ -172,7 +183,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     constexpr int MT = 2, WAVES = 8;
     constexpr int ROWS = NB16 * 16, T = WAVES * 64, SLOTS = MT * 16 * WAVES;
     static_assert(NB16 > 16 && NB16 <= H2_TILES, "geometry");
-    __shared__ __attribute__((aligned(16))) u32x4 Bs[2 * H2_PIECES];          // two W2 chunks, both pieces (40 KB each)
+    static_assert(NP == 2 || (NP == 1 && !TRAIN), "pieces per operand (the train forward keeps both)");
+    constexpr int PIECES = NP * H2_ROWS * 4;                                  // 16-byte pieces of a W2 chunk
+    __shared__ __attribute__((aligned(16))) u32x4 Bs[2 * PIECES];             // two W2 chunks, all pieces (40 KB each; NP = 1: 20 KB)
     __shared__ __attribute__((aligned(16))) u32x4 WgA[(256 / H2_CH) * 2 * 64];      // the geometry weights as MFMA A fragments: [chunk][k-tile][lane], 16 KB
     constexpr int STAGE_FLOATS = 8192;                          // the epilogue's bias / multiplier / embedding rows (32 KB)
     __shared__ __attribute__((aligned(16))) float stage[STAGE_FLOATS];
@@ -190,8 +203,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
 #pragma unroll
-        for (int i = 0; i < H2_PIECES / T; ++i)
-            __builtin_amdgcn_global_load_lds(W2h + T * i + tid, (__attribute__((address_space(3))) void*)&Bs[T * i + wave * 64], 16, 0, 0);
+        for (int i = 0; i < (PIECES + T - 1) / T; ++i)              // (NP = 1: 2.5 passes - the last one by the wavefronts 0-3)
+            if (PIECES % T == 0 || T * i + wave * 64 < PIECES)      // (wave-uniform)
+                __builtin_amdgcn_global_load_lds(W2h + T * i + tid, (__attribute__((address_space(3))) void*)&Bs[T * i + wave * 64], 16, 0, 0);
     };
     bool started = false;           // a tile has run: WgA is staged, stage[] holds the rows of image stage_q, the buffers hold W2 chunks
     bool b0 = false;                // buffer 0 holds chunk 0 again: half X requested it at the end of the previous tile (W2 is the same for every tile)
@@ -218,7 +232,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
         const int lane = tid & 63, kh = lane >> 4, r16 = lane & 15;
-        const float* cf = reinterpret_cast<const float*>(W2h + (int64_t)nchunk * H2_PIECES);      // -log2(e) 2^-e_r per hidden column
+        const float* cf = reinterpret_cast<const float*>(W2h + (int64_t)nchunk * PIECES);      // -log2(e) 2^-e_r per hidden column
 
         TRACE(0);
         // chunk 0 is requested before anything else: it lands under the geometry arithmetic below
@@ -265,9 +279,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         // offset - it advances the global and the LDS address alike - so one pointer / M0 setting serves four requests: three settings per chunk
         // instead of ten.  Y's build tick is paced by its instruction count, and every request used to come with five address instructions.)
         auto dma_chunk = [&](int c, int buf, int w, int ln) __attribute__((always_inline)) {
-            constexpr int PER_WAVE = H2_PIECES / 4;                                 // 16-byte pieces of a wavefront's quarter (640 = ten requests)
-            const u32x4* src = W2h + (int64_t)c * H2_PIECES + w * PER_WAVE + ln;
-            u32x4* dst = &Bs[buf * H2_PIECES + w * PER_WAVE];
+            constexpr int PER_WAVE = PIECES / 4;                                    // 16-byte pieces of a wavefront's quarter (640 = ten requests; NP = 1: 320 = five)
+            const u32x4* src = W2h + (int64_t)c * PIECES + w * PER_WAVE + ln;
+            u32x4* dst = &Bs[buf * PIECES + w * PER_WAVE];
 #pragma unroll
             for (int g = 0; g < PER_WAVE / 64; g += 4) {
 #if DFOL_H2_DMA_ASM
@@ -282,7 +296,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"
                 const uint32_t m0v = __builtin_amdgcn_readfirstlane(d);
-                const int rem = PER_WAVE / 64 - g;                      // requests of this group (compile-time after unrolling): 4, 4, 2
+                const int rem = PER_WAVE / 64 - g;                      // requests of this group (compile-time after unrolling): 4, 4, 2; NP = 1: 4, 1
                 if (rem >= 4)
                     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off\n\tglobal_load_lds_dwordx4 %0, off offset:1024\n\t"
                                  "global_load_lds_dwordx4 %0, off offset:2048\n\tglobal_load_lds_dwordx4 %0, off offset:3072" ::"v"(sp), "s"(m0v) : "memory", "m0");
@@ -322,7 +336,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     rv[m][half] = *reinterpret_cast<const floatx4*>(base + voff[m] + 64 * half);
                 }
         };
-        u32x4 ap[MT][2];                                                // [slot][piece h, l]
+        u32x4 ap[MT][NP];                                               // [slot][piece h, l]
         // A pieces of chunk c.  The first layer's sums z = U[s] + V[o] + Wg geo(s, o) come out of the matrix pipe: per k-tile t (16 k) one MFMA
         // per slot tile with the geometry weights as A (rows = k), the pair geometry as B (columns = slots) and U + V as the C operand - twelve
         // contraction slots hold the three piece products wg_h geo_h + wg_h geo_l + wg_l geo_h.  With the k order of h2_kperm its result
@@ -348,9 +362,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                         const float a0 = __builtin_amdgcn_fmed3f(z0, h2_elu_neg(z0), H2_AMAX);
                         const float a1 = __builtin_amdgcn_fmed3f(z1, h2_elu_neg(z1), H2_AMAX);
                         const uint32_t hh = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){a0, a1}, f16x2));
-                        const uint32_t ll = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){h2_resid<false>(a0, hh), h2_resid<true>(a1, hh)}, f16x2));
                         ap[m][0][2 * t + jp] = hh;
-                        ap[m][1][2 * t + jp] = ll;
+                        if constexpr (NP == 2)
+                            ap[m][1][2 * t + jp] = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){h2_resid<false>(a0, hh), h2_resid<true>(a1, hh)}, f16x2));
                         if (TRAIN) z[m][t][2 * jp] = a0 * H2_LN2, z[m][t][2 * jp + 1] = a1 * H2_LN2;       // the activations themselves, back in plain units
                     }
             if (TRAIN && !(DFOL_H2T_SKIP & 1)) {
@@ -367,17 +381,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         };
         const int boff = r16 * 4 + (kh ^ dfol_swz(r16));                  // the lane's 16-byte piece inside a 16-row block
         int bbase = boff;                                               // + the chunk buffer's offset
-        auto load_b = [&](int i, f16x8 (&b)[2]) __attribute__((always_inline)) {
+        auto load_b = [&](int i, f16x8 (&b)[NP]) __attribute__((always_inline)) {
 #pragma unroll
-            for (int p = 0; p < 2; ++p) b[p] = __builtin_bit_cast(f16x8, Bs[bbase + i * 64 + p * H2_ROWS * 4]);
+            for (int p = 0; p < NP; ++p) b[p] = __builtin_bit_cast(f16x8, Bs[bbase + i * 64 + p * H2_ROWS * 4]);
         };
         // The MFMAs of a chunk: the B fragments of tile i+1 are requested before the MFMAs of tile i, and the scheduler may not move anything
         // across tiles (left alone it hoists the reads of all tiles to the top and spills).  The three products of one accumulator are issued
         // back to back, smallest first: a dependent MFMA takes its C operand from the previous result without a register-file read.
         constexpr int PA3[3] = {1, 0, 0}, PB3[3] = {0, 1, 0};           // al wh, ah wl, ah wh
         auto chunk_mfma = [&]() __attribute__((always_inline)) {
-            constexpr int D = DFOL_H2_BDEPTH;                           // tiles of B fragments in flight ahead of the MFMAs
-            f16x8 bq[D + 1][2];
+            constexpr int D = NP == 2 ? DFOL_H2_BDEPTH : DFOL_H1_BDEPTH;  // tiles of B fragments in flight ahead of the MFMAs
+            f16x8 bq[D + 1][NP];
 #pragma unroll
             for (int d = 0; d < D; ++d) load_b(d, bq[d]);
 #pragma unroll
@@ -387,7 +401,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
                 for (int m = 0; m < MT; ++m) {
 #pragma unroll
-                    for (int x = 0; x < 3; ++x)
+                    for (int x = NP == 2 ? 0 : 2; x < 3; ++x)   // (one piece: ah wh alone)
                         acc[m][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, ap[m][PA3[x]]), bq[i % (D + 1)][PB3[x]], acc[m][i], 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -473,7 +487,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
                 for (int m = 0; m < MT; ++m)
 #pragma unroll
-                    for (int p = 0; p < 2; ++p) asm volatile("" : "+v"(ap[m][p]));
+                    for (int p = 0; p < NP; ++p) asm volatile("" : "+v"(ap[m][p]));
                 __builtin_amdgcn_sched_barrier(0);
                 if (Y && DFOL_H2_DMA_LATE && c >= 1 && c < lastc) dma_chunk(c + 1, (c + 1) & 1, wave - 4, lane);
                 TRACE(3 + 4 * c);
@@ -486,7 +500,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 __syncthreads();
                 __builtin_amdgcn_sched_barrier(0);
                 TRACE(4 + 4 * c);
-                bbase = boff + (c & 1) * H2_PIECES;
+                bbase = boff + (c & 1) * PIECES;
                 if (DFOL_H2_PREFETCH && c < lastc) load_uv(c + 1);      // lands under the MFMAs
                 chunk_mfma();
                 if (Y) __builtin_amdgcn_s_waitcnt(0x0F70);      // the chunk requested in the build tick has landed
@@ -903,18 +917,63 @@ static int h2_wg_tiles() {
 }
 
 extern "C" int64_t dfol_pair_w2_f16x2_bytes(int32_t HID1) { return (int64_t)(HID1 / H2_CH) * H2_PIECES * 16 + 2 * H2_ROWS * 4; }
+extern "C" int64_t dfol_pair_w2_f16_bytes(int32_t HID1) { return (int64_t)(HID1 / H2_CH) * H1_PIECES * 16 + 2 * H2_ROWS * 4; }
 
-extern "C" int dfol_pair_pack_w2_f16x2(const float* W2, int64_t ld_w2, int32_t HID2, int32_t HID1, void* W2_split, void* stream) {
-    DFOL_REQUIRE(HID1 > 0 && HID1 <= 256 && HID1 % H2_CH == 0, "pair_pack_w2_f16x2: HID1=%d must be a multiple of %d, <= 256", HID1, H2_CH);
-    DFOL_REQUIRE(HID2 > 256 && HID2 <= 320, "pair_pack_w2_f16x2: HID2=%d must be in (256, 320]", HID2);
-    DFOL_REQUIRE(W2 && W2_split && ld_w2 >= HID1, "pair_pack_w2_f16x2: null pointer or ld_w2 < HID1");
-    DFOL_REQUIRE((uintptr_t)W2_split % 16 == 0, "pair_pack_w2_f16x2: output must be 16-byte aligned");
-    const int total = (HID1 / H2_CH) * H2_PIECES;
+// NP = 2: the two-piece image; NP = 1: its hi pieces alone (same row scales, same tail)
+template <int NP>
+static int h2_pack_w2(const char* name, const float* W2, int64_t ld_w2, int32_t HID2, int32_t HID1, void* W2_split, void* stream) {
+    DFOL_REQUIRE(HID1 > 0 && HID1 <= 256 && HID1 % H2_CH == 0, "%s: HID1=%d must be a multiple of %d, <= 256", name, HID1, H2_CH);
+    DFOL_REQUIRE(HID2 > 256 && HID2 <= 320, "%s: HID2=%d must be in (256, 320]", name, HID2);
+    DFOL_REQUIRE(W2 && W2_split && ld_w2 >= HID1, "%s: null pointer or ld_w2 < HID1", name);
+    DFOL_REQUIRE((uintptr_t)W2_split % 16 == 0, "%s: output must be 16-byte aligned", name);
+    const int total = (HID1 / H2_CH) * NP * H2_ROWS * 4;
     float* tail = reinterpret_cast<float*>(reinterpret_cast<u32x4*>(W2_split) + total);
     hipLaunchKernelGGL(h2_row_scale_kernel, dim3(H2_ROWS / 4), dim3(256), 0, (hipStream_t)stream, W2, ld_w2, HID2, HID1, tail);
-    hipLaunchKernelGGL(h2_pack_w2_kernel, dim3(dfol_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, W2, ld_w2, HID2, HID1, (const float*)tail,
+    hipLaunchKernelGGL(h2_pack_w2_kernel<NP>, dim3(dfol_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, W2, ld_w2, HID2, HID1, (const float*)tail,
                        (u32x4*)W2_split);
-    DFOL_LAUNCH_CHECK("pair_pack_w2_f16x2");
+    DFOL_LAUNCH_CHECK(name);
+    return 0;
+}
+
+extern "C" int dfol_pair_pack_w2_f16x2(const float* W2, int64_t ld_w2, int32_t HID2, int32_t HID1, void* W2_split, void* stream) {
+    return h2_pack_w2<2>("pair_pack_w2_f16x2", W2, ld_w2, HID2, HID1, W2_split, stream);
+}
+
+extern "C" int dfol_pair_pack_w2_f16(const float* W2, int64_t ld_w2, int32_t HID2, int32_t HID1, void* W2_split, void* stream) {
+    return h2_pack_w2<1>("pair_pack_w2_f16", W2, ld_w2, HID2, HID1, W2_split, stream);
+}
+
+// dfol_pair_ll_h2_f32 (NP = 2) and dfol_pair_ll_h1_f32 (NP = 1): the same checks, the same range kernel in front, the same grid
+template <int NP>
+static int h2_pair_ll(const char* name, const float* UV, int64_t ld_uv, int32_t HID1, const float* pos, int64_t ld_pos, const float* Wg,
+                      const void* W2_split, const float* b2, int32_t HID2, const float* E, int64_t ld_e, const float* be, const int32_t* n_obj,
+                      const int32_t* obj_off, int32_t Q, int32_t max_n, const int32_t* req_col, const int32_t* req_tile, const uint8_t* req_orient,
+                      int32_t K, int32_t NS, float default_ll, int32_t tile_dtype, void* tiles_v, void* stream) {
+    DFOL_REQUIRE(tile_dtype == DFOL_TILE_F32 || (tile_dtype == DFOL_TILE_BF16 && NS % 8 == 0), "%s: tile_dtype=%d (bf16 tiles need NS %% 8 == 0)", name, tile_dtype);
+    DFOL_REQUIRE(Q >= 0 && K >= 0 && NS > 0 && NS % 4 == 0 && max_n >= 0 && max_n <= NS, "%s: bad sizes Q=%d K=%d NS=%d max_n=%d", name, Q, K, NS, max_n);
+    DFOL_REQUIRE(HID1 > 0 && HID1 <= 256 && HID1 % H2_CH == 0 && ld_uv % 4 == 0, "%s: HID1=%d must be a multiple of %d, <= 256, UV rows 16-byte aligned", name, HID1, H2_CH);
+    DFOL_REQUIRE(HID2 > 256 && HID2 <= 320, "%s: HID2=%d must be in (256, 320]", name, HID2);
+    if (Q == 0 || K == 0 || max_n < 2) return 0;
+    DFOL_REQUIRE(UV && pos && Wg && W2_split && b2 && E && n_obj && obj_off && req_col && req_tile && tiles_v, "%s: null pointer", name);
+    DFOL_REQUIRE(((uintptr_t)UV % 16 == 0) && ((uintptr_t)W2_split % 16 == 0) && ((uintptr_t)Wg % 16 == 0), "%s: operands must be 16-byte aligned", name);
+    hipStream_t st = (hipStream_t)stream;
+    const int tpi = dfol_cdiv((int64_t)max_n * (max_n - 1), 256);
+    DFOL_REQUIRE((int64_t)Q * tpi < ((int64_t)1 << 31), "%s: too many tiles", name);
+    DFOL_REQUIRE((int64_t)max_n * ld_uv * 4 < ((int64_t)1 << 31), "%s: an image's U / V rows must span less than 2 GB", name);
+    const int wgt = h2_wg_tiles();
+    const dim3 grid((unsigned)dfol_cdiv((int64_t)Q * tpi, wgt));
+    if (uint32_t* status = dfol_range_status_ptr())           // (dfol_set_range_status: saturated ELU outputs are reported, not answered with)
+        hipLaunchKernelGGL(h2_uv_range_kernel, dim3((unsigned)Q), dim3(512), 0, st, UV, ld_uv, HID1, pos, ld_pos, Wg, n_obj, obj_off, status);
+    const H2Train none = {nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr};
+#define DFOL_PAIR32H(NBV, BF)                                                                                                       \
+    hipLaunchKernelGGL((pair_ll32h_kernel<NBV, BF, false, NP>), grid, dim3(512), 0, st, UV, ld_uv, HID1, pos, ld_pos, Wg, (const u32x4*)W2_split, b2, HID2, \
+                       E, ld_e, be, n_obj, obj_off, Q, tpi, wgt, req_col, req_tile, req_orient, K, NS, default_ll, tiles_v, none)
+    if (HID2 <= 272) { if (tile_dtype == DFOL_TILE_BF16) DFOL_PAIR32H(17, true); else DFOL_PAIR32H(17, false); }
+    else if (HID2 <= 288) { if (tile_dtype == DFOL_TILE_BF16) DFOL_PAIR32H(18, true); else DFOL_PAIR32H(18, false); }
+    else if (HID2 <= 304) { if (tile_dtype == DFOL_TILE_BF16) DFOL_PAIR32H(19, true); else DFOL_PAIR32H(19, false); }
+    else { if (tile_dtype == DFOL_TILE_BF16) DFOL_PAIR32H(20, true); else DFOL_PAIR32H(20, false); }
+#undef DFOL_PAIR32H
+    DFOL_LAUNCH_CHECK(name);
     return 0;
 }
 
@@ -923,32 +982,18 @@ extern "C" int dfol_pair_ll_h2_f32(const float* UV, int64_t ld_uv, int32_t HID1,
                                    const float* be, const int32_t* n_obj, const int32_t* obj_off, int32_t Q, int32_t max_n,
                                    const int32_t* req_col, const int32_t* req_tile, const uint8_t* req_orient, int32_t K,
                                    int32_t NS, float default_ll, int32_t tile_dtype, void* tiles_v, void* stream) {
-    DFOL_REQUIRE(tile_dtype == DFOL_TILE_F32 || (tile_dtype == DFOL_TILE_BF16 && NS % 8 == 0), "pair_ll_h2: tile_dtype=%d (bf16 tiles need NS %% 8 == 0)", tile_dtype);
-    DFOL_REQUIRE(Q >= 0 && K >= 0 && NS > 0 && NS % 4 == 0 && max_n >= 0 && max_n <= NS, "pair_ll_h2: bad sizes Q=%d K=%d NS=%d max_n=%d", Q, K, NS, max_n);
-    DFOL_REQUIRE(HID1 > 0 && HID1 <= 256 && HID1 % H2_CH == 0 && ld_uv % 4 == 0, "pair_ll_h2: HID1=%d must be a multiple of %d, <= 256, UV rows 16-byte aligned", HID1, H2_CH);
-    DFOL_REQUIRE(HID2 > 256 && HID2 <= 320, "pair_ll_h2: HID2=%d must be in (256, 320]", HID2);
-    if (Q == 0 || K == 0 || max_n < 2) return 0;
-    DFOL_REQUIRE(UV && pos && Wg && W2_split && b2 && E && n_obj && obj_off && req_col && req_tile && tiles_v, "pair_ll_h2: null pointer");
-    DFOL_REQUIRE(((uintptr_t)UV % 16 == 0) && ((uintptr_t)W2_split % 16 == 0) && ((uintptr_t)Wg % 16 == 0), "pair_ll_h2: operands must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const int tpi = dfol_cdiv((int64_t)max_n * (max_n - 1), 256);
-    DFOL_REQUIRE((int64_t)Q * tpi < ((int64_t)1 << 31), "pair_ll_h2: too many tiles");
-    DFOL_REQUIRE((int64_t)max_n * ld_uv * 4 < ((int64_t)1 << 31), "pair_ll_h2: an image's U / V rows must span less than 2 GB");
-    const int wgt = h2_wg_tiles();
-    const dim3 grid((unsigned)dfol_cdiv((int64_t)Q * tpi, wgt));
-    if (uint32_t* status = dfol_range_status_ptr())           // (dfol_set_range_status: saturated ELU outputs are reported, not answered with)
-        hipLaunchKernelGGL(h2_uv_range_kernel, dim3((unsigned)Q), dim3(512), 0, st, UV, ld_uv, HID1, pos, ld_pos, Wg, n_obj, obj_off, status);
-    const H2Train none = {nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr};
-#define DFOL_PAIR32H(NBV, BF)                                                                                                       \
-    hipLaunchKernelGGL((pair_ll32h_kernel<NBV, BF>), grid, dim3(512), 0, st, UV, ld_uv, HID1, pos, ld_pos, Wg, (const u32x4*)W2_split, b2, HID2, \
-                       E, ld_e, be, n_obj, obj_off, Q, tpi, wgt, req_col, req_tile, req_orient, K, NS, default_ll, tiles_v, none)
-    if (HID2 <= 272) { if (tile_dtype == DFOL_TILE_BF16) DFOL_PAIR32H(17, true); else DFOL_PAIR32H(17, false); }
-    else if (HID2 <= 288) { if (tile_dtype == DFOL_TILE_BF16) DFOL_PAIR32H(18, true); else DFOL_PAIR32H(18, false); }
-    else if (HID2 <= 304) { if (tile_dtype == DFOL_TILE_BF16) DFOL_PAIR32H(19, true); else DFOL_PAIR32H(19, false); }
-    else { if (tile_dtype == DFOL_TILE_BF16) DFOL_PAIR32H(20, true); else DFOL_PAIR32H(20, false); }
-#undef DFOL_PAIR32H
-    DFOL_LAUNCH_CHECK("pair_ll_h2");
-    return 0;
+    return h2_pair_ll<2>("pair_ll_h2", UV, ld_uv, HID1, pos, ld_pos, Wg, W2_split, b2, HID2, E, ld_e, be, n_obj, obj_off, Q, max_n, req_col, req_tile, req_orient, K,
+                         NS, default_ll, tile_dtype, tiles_v, stream);
+}
+
+// The opt-in reduced-precision form (pair_math "f16"): ONE fp16 product per MAC on the dfol_pair_pack_w2_f16 image.
+extern "C" int dfol_pair_ll_h1_f32(const float* UV, int64_t ld_uv, int32_t HID1, const float* pos, int64_t ld_pos, const float* Wg,
+                                   const void* W2_f16, const float* b2, int32_t HID2, const float* E, int64_t ld_e,
+                                   const float* be, const int32_t* n_obj, const int32_t* obj_off, int32_t Q, int32_t max_n,
+                                   const int32_t* req_col, const int32_t* req_tile, const uint8_t* req_orient, int32_t K,
+                                   int32_t NS, float default_ll, int32_t tile_dtype, void* tiles_v, void* stream) {
+    return h2_pair_ll<1>("pair_ll_h1", UV, ld_uv, HID1, pos, ld_pos, Wg, W2_f16, b2, HID2, E, ld_e, be, n_obj, obj_off, Q, max_n, req_col, req_tile, req_orient, K,
+                         NS, default_ll, tile_dtype, tiles_v, stream);
 }
 
 

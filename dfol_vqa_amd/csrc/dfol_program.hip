@@ -160,6 +160,10 @@ extern "C" int dfol_run_program(const DfolProgramModel* model, const DfolProgram
                         rc = dfol_pair_ll_h2_f32(uv, a[2], model->hid1, pos, a[4], model->wg, model->w2, model->b2, model->hid2, model->emb_w, model->ld_e, model->emb_b,
                                                  img_n_obj, obj_off, Qimg, scene->max_n, rc_, rt, ro, K, NS, -30.0f, tdt, tiles, stream);
                         break;
+                    case DFOL_PAIR_F16:
+                        rc = dfol_pair_ll_h1_f32(uv, a[2], model->hid1, pos, a[4], model->wg, model->w2, model->b2, model->hid2, model->emb_w, model->ld_e, model->emb_b,
+                                                 img_n_obj, obj_off, Qimg, scene->max_n, rc_, rt, ro, K, NS, -30.0f, tdt, tiles, stream);
+                        break;
                     case DFOL_PAIR_BF16X3:
                         rc = dfol_pair_ll_split_f32(uv, a[2], model->hid1, pos, a[4], model->wg, model->w2, model->b2, model->hid2, model->emb_w, model->ld_e, model->emb_b,
                                                     img_n_obj, obj_off, Qimg, scene->max_n, rc_, rt, ro, K, NS, -30.0f, tdt, tiles, stream);

@@ -85,6 +85,12 @@ def build_interpreter(config, neural_dict, ontology):           # gqa_interprete
         model._mlp_math = 'bf16x3'
     elif mlp_math not in ('fp32', 'float32', 'f32'):
         raise ValueError("mlp_math must be fp32, bf16x3 or bf16, got %r" % (config.get('mlp_math'),))
+    pair_math = config.get('pair_math')                                                    # an extra key of this build: the fused pair kernel's arithmetic
+    if pair_math is not None:
+        if str(pair_math).lower() not in ('f16x2', 'f16'):
+            raise ValueError("pair_math must be f16x2 (the default: fp32 accuracy) or f16 (reduced precision: one fp16 product per MAC, "
+                             "inference only), got %r" % (pair_math,))
+        model._pair_math = str(pair_math).lower()
     return model
 
 

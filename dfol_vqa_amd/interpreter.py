@@ -318,7 +318,9 @@ class BatchInterpreterBase(nn.Module):
             from . import _lib
             dev0 = program_batch_list[0].device if program_batch_list else None
             watch = _lib.RangeWatch(dev0) if dev0 is not None and torch.device(dev0).type == "cuda" else None
-            with _lib.dense_math(getattr(self, "_mlp_math", None)):
+            # `_pair_math` (config key `pair_math`): "f16" runs the fused pair kernel of an INFERENCE forward with one fp16 product per MAC
+            # (reduced precision, opt-in); a train step's pair branch stays on the default (visual_oracle._train_pair_math)
+            with _lib.dense_math(getattr(self, "_mlp_math", None)), _lib.pair_math_scope(getattr(self, "_pair_math", None)):
                 all_results, all_traces, device = self._run_batches(program_batch_list, is_training, modulator_switch, return_trace)
             if watch is not None:
                 check = watch.finish()                           # (runs after the answers' read-backs: raises if a kernel left fp16's range)

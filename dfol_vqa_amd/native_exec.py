@@ -19,7 +19,7 @@ from . import native_plan as NP
 
 _p, _i32, _i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
 DENSE_F32, DENSE_F16X2, DENSE_BF16X3, DENSE_BF16, DENSE_HEAD_F16X2 = 0, 1, 2, 3, 4
-PAIR_PLAIN, PAIR_PACKED, PAIR_BF16X3, PAIR_F16X2 = 0, 1, 2, 3
+PAIR_PLAIN, PAIR_PACKED, PAIR_BF16X3, PAIR_F16X2, PAIR_F16 = 0, 1, 2, 3, 4
 
 
 class DenseLayer(ctypes.Structure):
@@ -187,7 +187,7 @@ class NativeModel(object):
         m.featurizer, m.attribute = self._fl, self._al
         m.uv = dense(wuv, buv, _lib.ACT_NONE)
         if isinstance(packed, tuple):
-            m.pair_kind, w2 = (PAIR_F16X2 if packed[0] == "f16x2" else PAIR_BF16X3), packed[1]
+            m.pair_kind, w2 = {"f16x2": PAIR_F16X2, "f16": PAIR_F16, "bf16x3": PAIR_BF16X3}[packed[0]], packed[1]
         elif packed is not None:
             m.pair_kind, w2 = PAIR_PACKED, packed
         else:
@@ -228,10 +228,12 @@ class NativeModel(object):
 
 
 def native_model(model):
-    key = NativeModel.version_key(model)
-    hit = model.__dict__.get("_native_model")
-    if hit is None or hit[0] != key:
-        hit = model.__dict__["_native_model"] = (key, NativeModel(model))
+    # (the pair arithmetic is the model's own `pair_math` where it has one - the scope its forward runs in - as attr_head_of does for `mlp_math`)
+    with _lib.pair_math_scope(getattr(model, "_pair_math", None)):
+        key = NativeModel.version_key(model)
+        hit = model.__dict__.get("_native_model")
+        if hit is None or hit[0] != key:
+            hit = model.__dict__["_native_model"] = (key, NativeModel(model))
     return hit[1]
 
 

@@ -665,7 +665,7 @@ class ClassifierOracle(OracleBase):
         # The fp16x2 pair kernel (csrc/dfol_pair_h2.hip) takes U | V in units of ln 2, i.e. multiplied by log2(e): its ELU then needs no multiply in
         # front of the hardware exponential (a build tick of that kernel is paced by its instruction count).  The factor goes into the stacked
         # weight and bias here, once per weight version; the kernel scales the geometry columns itself and its pack kernel folds ln 2 into W2.
-        scaled = self._pair_kind() == "f16x2"
+        scaled = self._pair_kind() in ("f16x2", "f16")           # (the one-piece form is the same kernel body: same units)
         key = (lin.weight.data_ptr(), lin.weight._version, None if lin.bias is None else lin.bias._version, scaled)
         if self._split_cache is None or self._split_cache[0] != key:
             w = lin.weight.detach()
@@ -716,18 +716,33 @@ class ClassifierOracle(OracleBase):
         return L.attr_ll(world._hidden_attr, emb.weight, emb.bias, world._obj_off, pred_img, cols, world._NS, -30.0)
 
     def _pair_kind(self):
-        """Which fused pair kernel evaluates this oracle's relation tiles: "f16x2", "bf16x3", "packed" (fp32 pipe, packed W2) or "plain"."""
+        """Which fused pair kernel evaluates this oracle's relation tiles: "f16x2", "f16" (opt-in reduced precision), "bf16x3", "packed" (fp32
+        pipe, packed W2) or "plain"."""
         packed = self._padded_second_layer()[3]
         if isinstance(packed, tuple):
             return packed[0]
         return "plain" if packed is None else "packed"
 
-    def _padded_second_layer(self):
-        """W2 zero-padded to a multiple of 32 rows, so the fused pair kernel's main loop needs no bounds checks."""
+    @staticmethod
+    def _train_pair_math():
+        """The pair arithmetic of a train step: the reduced mode "f16" is an inference mode, training stays on the default it replaces."""
+        m = L.pair_math()
+        return "f16x2" if m == "f16" else m
+
+    def _padded_second_layer(self, math=None):
+        """W2 zero-padded to a multiple of 32 rows, so the fused pair kernel's main loop needs no bounds checks.  math: the pair arithmetic
+        the packed image is for (default: L.pair_math())."""
         lin = [m for m in self._relation_network._network if isinstance(m, nn.Linear)][1]
-        key = (lin.weight.data_ptr(), lin.weight._version, lin.bias._version, L.pair_math())
+        math = L.pair_math() if math is None else math
+        key = (lin.weight.data_ptr(), lin.weight._version, lin.bias._version, math)
         cache = getattr(self, "_w2_cache", None)
+        # (a second entry for the same weights under another arithmetic: inside a `pair_math: f16` scope the train gate asks for the f16x2
+        # image between requests for the f16 one; with one entry every such switch would pack W2 again.  Clearing _w2_cache drops both.)
+        other = getattr(self, "_w2_cache_other", None) if cache is not None else None
+        if cache is not None and cache[0] != key and other is not None and other[0] == key:
+            self._w2_cache, self._w2_cache_other = cache, other = other, cache
         if cache is None or cache[0] != key:
+            self._w2_cache_other = cache if cache is not None and cache[0][:3] == key[:3] else None
             w = lin.weight.detach()
             rows = (w.shape[0] + 31) // 32 * 32
             wp = torch.zeros(rows, w.shape[1], dtype=w.dtype, device=w.device)
@@ -738,9 +753,15 @@ class ClassifierOracle(OracleBase):
                 packed = L.pair_pack_w2(wp, w.shape[0])      # the layout of the occupancy-2 pair kernel (csrc/dfol_pair.hip)
                 # full-size second layer: fp32 results from the fp16 matrix pipe (two fp16 pieces per operand, three products:
                 # csrc/dfol_pair_h2.hip) or, DFOL_PAIR_MATH=bf16x3, from the bf16 pipe (three pieces, six products: csrc/dfol_pair_split.hip);
-                # DFOL_PAIR_MATH=f32 keeps the fp32 matrix pipe
-                if L.pair_split_supported(w.shape[1], w.shape[0]) and L.pair_math() != "f32":
-                    packed = ("f16x2", L.pair_pack_w2_h2(wp, w.shape[0])) if L.pair_math() == "f16x2" else ("bf16x3", L.pair_pack_w2_split(wp, w.shape[0]))
+                # DFOL_PAIR_MATH=f32 keeps the fp32 matrix pipe; `pair_math: f16` (opt-in, reduced precision) takes the hi pieces alone: one
+                # product per MAC on the same kernel body
+                if L.pair_split_supported(w.shape[1], w.shape[0]) and math != "f32":
+                    if math == "f16x2":
+                        packed = ("f16x2", L.pair_pack_w2_h2(wp, w.shape[0]))
+                    elif math == "f16":
+                        packed = ("f16", L.pair_pack_w2_h1(wp, w.shape[0]))
+                    else:
+                        packed = ("bf16x3", L.pair_pack_w2_split(wp, w.shape[0]))
             self._w2_cache = (key, wp, lin.bias.detach().contiguous(), w.shape[0], packed)
         return L.keep_alive(self._w2_cache)[1:]
 
@@ -857,13 +878,13 @@ class ClassifierOracle(OracleBase):
         if os.environ.get("DFOL_TRAIN_FWD_FUSED", "1") == "0" or V is not None or store != torch.float32 or not U.is_cuda:
             return None
         hid1, hid2 = lin1.weight.shape[0], lin2.weight.shape[0]
-        if _lib._dense_math() != "f16x2" or L.pair_math() != "f16x2" or not L.pair_split_supported(hid1, hid2):
+        if _lib._dense_math() != "f16x2" or self._train_pair_math() != "f16x2" or not L.pair_split_supported(hid1, hid2):
             return None
         if os.environ.get("DFOL_TRAIN_HEAD_FUSED", "1") == "0" or not L.pair_head_fused_supported(hid1, hid2) or not torch.is_grad_enabled():
             return None
         if not bool(L.load().dfol_pair_hidden1_bwd_recompute_supported(int(max(world._n_list)), int(hid1))) or os.environ.get("DFOL_H1B_RECOMPUTE", "1") == "0":
             return None
-        packed = self._padded_second_layer()[3]
+        packed = self._padded_second_layer(self._train_pair_math())[3]
         if not (isinstance(packed, tuple) and packed[0] == "f16x2"):
             return None
         return {"w2h": packed[1], "b2": lin2.bias.detach().contiguous(), "hid2": int(hid2), "first": first}
@@ -1139,6 +1160,9 @@ class ClassifierOracle(OracleBase):
         ro = None if req_orient is None else up(req_orient)
         if isinstance(packed, tuple) and packed[0] == "f16x2":
             L.pair_ll_h2(world._uv, hid1, world._obj[:, D - 4:], wg, packed[1], b2, hid2, emb.weight, emb.bias, world._img_n_obj,
+                         world._obj_off, max(world._n_list), rc, rt, ro, tiles, -30.0, uv_prescaled=True)
+        elif isinstance(packed, tuple) and packed[0] == "f16":
+            L.pair_ll_h1(world._uv, hid1, world._obj[:, D - 4:], wg, packed[1], b2, hid2, emb.weight, emb.bias, world._img_n_obj,
                          world._obj_off, max(world._n_list), rc, rt, ro, tiles, -30.0, uv_prescaled=True)
         elif isinstance(packed, tuple):
             L.pair_ll_split(world._uv, hid1, world._obj[:, D - 4:], wg, packed[1], b2, hid2, emb.weight, emb.bias, world._img_n_obj,

@@ -42,7 +42,8 @@ extern "C" {
  * ELU outputs through the dfol_set_range_status word (DFOL_RANGE_PAIR_SATURATED); dfol_run_program knows the calibration instructions.
  * The rule: the version changes when a caller written against the old one would be answered wrongly - an entry point whose arguments or units
  * change, a struct whose layout changes.  Pure additions keep it: dfol_attr_head_h2_f32, DFOL_OP_ATTR_HEAD, DFOL_DENSE_HEAD_F16X2 and the ninth
- * operand of DFOL_OP_DENSE (a slot that instruction tables written before it hold as zero = the layer's own activation) were added under 3;
+ * operand of DFOL_OP_DENSE (a slot that instruction tables written before it hold as zero = the layer's own activation) were added under 3,
+ * and so were dfol_pair_ll_h1_f32, dfol_pair_pack_w2_f16, dfol_pair_w2_f16_bytes and DFOL_PAIR_F16 (an older library refuses the kind);
  * a caller that needs them checks for the symbol, and a table that names an opcode an older library lacks is refused by it ("unknown opcode"). */
 #define DFOL_ABI_VERSION 3
 
@@ -456,6 +457,21 @@ int dfol_pair_ll_h2_f32(const float* UV, int64_t ld_uv, int32_t HID1, const floa
                         const int32_t* req_tile, const uint8_t* req_orient, int32_t K, int32_t NS, float default_ll,
                         int32_t tile_dtype, void* tiles, void* stream);
 
+/* The same relation tiles in the OPT-IN reduced-precision mode (`pair_math: f16` / DFOL_PAIR_MATH=f16; never the default): ONE fp16 product per
+ * MAC.  The kernel of dfol_pair_ll_h2_f32 with one piece per operand - A = fp16(ELU output) rounded to nearest even, W2 = the hi pieces of the
+ * two-piece image (dfol_pair_pack_w2_f16: per 32 k a 20 KB chunk [320 rows][4 k-groups] x 16 bytes, same row scales, swizzle, k order and
+ * 640-word tail; bit for bit the hi half of dfol_pair_pack_w2_f16x2's image; dfol_pair_w2_f16_bytes(HID1) bytes, 16-byte aligned) - so 38 MFMAs
+ * per 32-wide chunk instead of 114.  Operands carry 11 significand bits (bf16: 8), accumulation is fp32: every operand is off by at most
+ * 2^-11 of its value (the error measured against float64 is in DESIGN 3.4).  Units of UV, saturation and its DFOL_RANGE_PAIR_SATURATED report, arguments and limits exactly as
+ * dfol_pair_ll_h2_f32.  There is no train forward in this mode. */
+int64_t dfol_pair_w2_f16_bytes(int32_t HID1);
+int dfol_pair_pack_w2_f16(const float* W2, int64_t ld_w2, int32_t HID2, int32_t HID1, void* W2_f16, void* stream);
+int dfol_pair_ll_h1_f32(const float* UV, int64_t ld_uv, int32_t HID1, const float* pos, int64_t ld_pos, const float* Wg,
+                        const void* W2_f16, const float* b2, int32_t HID2, const float* E, int64_t ld_e, const float* be,
+                        const int32_t* n_obj, const int32_t* obj_off, int32_t Q, int32_t max_n, const int32_t* req_col,
+                        const int32_t* req_tile, const uint8_t* req_orient, int32_t K, int32_t NS, float default_ll,
+                        int32_t tile_dtype, void* tiles, void* stream);
+
 /* The FORWARD of a train step's pair MLP in one launch (round 6; csrc/dfol_pair_h2.hip, the kernel of dfol_pair_ll_h2_f32 with its operands'
  * layout: UV in units of ln 2, W2_split from dfol_pair_pack_w2_f16x2): per ordered pair row (image-major, subject-major: util.py:87-103;
  * pair_off[q] = first row of image q)
@@ -732,6 +748,7 @@ int dfol_attr_head_h2_f32(const float* pre1, int64_t ld_pre1, int32_t HID1, cons
 #define DFOL_PAIR_PACKED 1  /* dfol_pair_ll_packed_f32 */
 #define DFOL_PAIR_BF16X3 2  /* dfol_pair_ll_split_f32 */
 #define DFOL_PAIR_F16X2 3   /* dfol_pair_ll_h2_f32 */
+#define DFOL_PAIR_F16 4     /* dfol_pair_ll_h1_f32 on the dfol_pair_pack_w2_f16 image (opt-in reduced precision) */
 
 typedef struct {            /* one nn.Linear + activation of gqa_interpreter_experiments.py:18-36 */
     int32_t kind;           /* DFOL_DENSE_*: the arithmetic of weights >= 65536 elements; smaller ones always run dfol_linear_act_f32 */
