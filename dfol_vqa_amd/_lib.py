@@ -99,6 +99,7 @@ SIGNATURES = {
     "dfol_relate_one_fwd_f32": [_p, _p, _p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _p],
     "dfol_gate_f32": [_p, _p, _p, _p, _p, _i32, _i32, _p, _p, _p],
     "dfol_gather_rows_f32": [_p, _p, _i32, _i32, _p, _p],
+    "dfol_gather_object_rows_f32": [_p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _p],
     "dfol_segment_sum_rows_f32": [_p, _p, _i32, _i32, _p, _p],
     "dfol_logic_f32": [_i32, _p, _p, _i64, _p, _p],
     "dfol_parametric_not_f32": [_p, _p, _i32, _i32, _p, _p],
@@ -533,6 +534,19 @@ def gather_rows(src, idx):
     P, width = idx.numel(), src2.shape[1]
     out = torch.empty((P,) + tuple(src.shape[1:]), dtype=F32, device=src.device)
     call("dfol_gather_rows_f32", _ptr(src2, F32), _ptr(idx, I32), P, width, _ptr(out), _stream())
+    return out
+
+
+def gather_object_rows(features, boxes, sizes, slot, obj_off, out):
+    """out[obj_off[i] + j] = [features[slot[i]][j], W, H, x1, y1, x2 - x1, y2 - y1] (csrc/dfol_store.hip); features [S, max_obj, F], boxes
+    [S, max_obj, 4], sizes [S, 2]; slot [I] and obj_off [I + 1] int32 on the device; out [O, >= F + 6] rows of unit column stride."""
+    S, max_obj, F = features.shape
+    if tuple(boxes.shape) != (S, max_obj, 4) or tuple(sizes.shape) != (S, 2) or obj_off.numel() != slot.numel() + 1:
+        raise DfolError("gather_object_rows: store tensors / index arrays of mismatched shapes")
+    if out.dim() != 2 or out.dtype != F32 or not out.is_cuda or (out.shape[0] > 1 and out.stride(1) != 1) or out.shape[1] < F + 6:
+        raise DfolError("gather_object_rows: out must be fp32 device rows of at least F + 6 = %d columns" % (F + 6))
+    call("dfol_gather_object_rows_f32", _ptr(features, F32), _ptr(boxes, F32), _ptr(sizes, F32), _ptr(slot, I32), _ptr(obj_off, I32),
+         slot.numel(), max_obj, F, _dp(out), out.stride(0), _stream())
     return out
 
 

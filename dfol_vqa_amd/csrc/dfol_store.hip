@@ -1,0 +1,107 @@
+// The device-resident object-feature store's one kernel (dfol_vqa_amd/feature_store.py): the [O, F + 6] object matrix of a batch, which
+// BatchGQABoxFeaturesCollator.collate_object_features builds on the host from the chunk files and ships over PCIe (822 KB per question at
+// 100 objects x 2048 features), written on the device from a store that holds the corpus' features, boxes and image sizes.
+//
+//   out[obj_off[i] + j] = [features[slot[i]][j][0:F], W, H, x1, y1, x2 - x1, y2 - y1]       j < obj_off[i + 1] - obj_off[i]
+//
+// A pure copy, bound by HBM: one workgroup column per image, a wavefront per row (8 KB at F = 2048), 16-byte loads with four in flight per
+// lane.  Output rows have a stride of F + 6 floats, so they are 16-byte aligned at best every other row: the store width (16, 8 or 4 bytes)
+// follows the row's actual address, which is uniform over the wavefront.  The two subtractions are single fp32 subtractions, as numpy's on
+// the host, so the matrix is bit-equal to the collator's.  No LDS, no atomics.
+#include "dfol_common.h"
+
+namespace {
+
+constexpr int ST_WAVES = 4;                 // wavefronts of a workgroup = rows in flight per workgroup
+constexpr int ST_TARGET_WAVES = 4096;       // wavefronts of a launch when the batch has the rows for it: 16 per CU
+
+template <int SW>
+__device__ __forceinline__ void st_store(float* d, const float4& v) {
+    if (SW == 4) {
+        *reinterpret_cast<float4*>(d) = v;
+    } else if (SW == 2) {
+        *reinterpret_cast<float2*>(d) = make_float2(v.x, v.y);
+        *reinterpret_cast<float2*>(d + 2) = make_float2(v.z, v.w);
+    } else {
+        d[0] = v.x, d[1] = v.y, d[2] = v.z, d[3] = v.w;
+    }
+}
+
+// n4 16-byte pieces of one row, the wavefront's lanes side by side; SW = floats per store instruction
+template <int SW>
+__device__ __forceinline__ void st_copy_row(const float4* __restrict__ src, float* __restrict__ dst, int n4, int lane) {
+    int c = lane;
+    for (; c + 192 < n4; c += 256) {
+        const float4 a = src[c], b = src[c + 64], e = src[c + 128], f = src[c + 192];
+        st_store<SW>(dst + 4 * c, a);
+        st_store<SW>(dst + 4 * (c + 64), b);
+        st_store<SW>(dst + 4 * (c + 128), e);
+        st_store<SW>(dst + 4 * (c + 192), f);
+    }
+    for (; c < n4; c += 64) st_store<SW>(dst + 4 * c, src[c]);
+}
+
+// grid (I, row slices): workgroup (i, y) writes the rows j = 4 y + wave, + 4 gridDim.y, ... of image i
+template <bool VEC>
+__global__ __launch_bounds__(ST_WAVES * 64) void gather_object_rows_kernel(const float* __restrict__ feats, const float* __restrict__ boxes,
+                                                                           const float* __restrict__ sizes, const int32_t* __restrict__ slot,
+                                                                           const int32_t* __restrict__ obj_off, int max_obj, int F,
+                                                                           float* __restrict__ out, int64_t ld_out) {
+    const int i = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int first = obj_off[i];
+    const int n = min(obj_off[i + 1] - first, max_obj);              // (an image has at most max_obj rows in the store)
+    const int s = slot[i];
+    const int64_t img = (int64_t)s * max_obj;
+    for (int j = blockIdx.y * ST_WAVES + wave; j < n; j += gridDim.y * ST_WAVES) {
+        const float* src = feats + (img + j) * F;
+        float* dst = out + (int64_t)(first + j) * ld_out;
+        if (VEC) {
+            const float4* src4 = reinterpret_cast<const float4*>(src);
+            const unsigned mis = (unsigned)(reinterpret_cast<uintptr_t>(dst) & 15);
+            if (mis == 0)
+                st_copy_row<4>(src4, dst, F >> 2, lane);
+            else if (mis == 8)
+                st_copy_row<2>(src4, dst, F >> 2, lane);
+            else
+                st_copy_row<1>(src4, dst, F >> 2, lane);
+        } else {
+            for (int c = lane; c < F; c += 64) dst[c] = src[c];
+        }
+        if (lane < 6) {                                              // [W, H, x, y, w, h]  (batch_gqa_boxfeatures_pipeline.py:57-71)
+            const float* b = boxes + (img + j) * 4;
+            float v;
+            if (lane < 2)
+                v = sizes[2 * (int64_t)s + lane];
+            else if (lane < 4)
+                v = b[lane - 2];
+            else
+                v = b[lane - 2] - b[lane - 4];
+            dst[F + lane] = v;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int dfol_gather_object_rows_f32(const float* store_features, const float* store_boxes, const float* store_sizes, const int32_t* slot,
+                                           const int32_t* obj_off, int32_t I, int32_t max_obj, int32_t F, float* out, int64_t ld_out,
+                                           void* stream) {
+    DFOL_REQUIRE(I >= 0 && F > 0 && max_obj > 0, "gather_object_rows: bad sizes I=%d max_obj=%d F=%d", I, max_obj, F);
+    DFOL_REQUIRE(ld_out >= (int64_t)F + 6, "gather_object_rows: ld_out=%lld is less than F + 6 = %d", (long long)ld_out, F + 6);
+    if (I == 0) return 0;
+    DFOL_REQUIRE(store_features && store_boxes && store_sizes && slot && obj_off && out, "gather_object_rows: null pointer");
+    const int rows = dfol_cdiv(max_obj, ST_WAVES);
+    int slices = dfol_cdiv(ST_TARGET_WAVES / ST_WAVES, I);
+    slices = slices < rows ? slices : rows;
+    slices = slices < 65535 ? slices : 65535;
+    const dim3 grid(I, slices), block(ST_WAVES * 64);
+    const bool vec = F % 4 == 0 && (reinterpret_cast<uintptr_t>(store_features) & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL(gather_object_rows_kernel<true>, grid, block, 0, (hipStream_t)stream, store_features, store_boxes, store_sizes, slot,
+                           obj_off, max_obj, F, out, ld_out);
+    else
+        hipLaunchKernelGGL(gather_object_rows_kernel<false>, grid, block, 0, (hipStream_t)stream, store_features, store_boxes, store_sizes, slot,
+                           obj_off, max_obj, F, out, ld_out);
+    DFOL_LAUNCH_CHECK("gather_object_rows");
+    return 0;
+}

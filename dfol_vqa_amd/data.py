@@ -19,6 +19,7 @@ import re
 import numpy as np
 import torch
 
+from .feature_store import DeviceFeatureStore, FeatureStoreIndex, ObjectFeatureRef  # noqa: F401
 from .program import ProgramCollaterBase
 
 _NEG = re.compile(r"not\((\w|\s)+\)")
@@ -276,9 +277,14 @@ class BatchGQABoxFeaturesCollator(ProgramCollaterBase):
 
     Chunk i is `<prefix>_<i>.npz` (or `.h5`) with `features [chunk, max_obj, F]` and `bboxes [chunk, max_obj, 4]` (x1, y1, x2, y2);
     `object_info_json_path` maps image id -> {objectsNum, width, height, idx, file}.  Produces the reference's
-    `object_features [O, F + 6]` = [features, W, H, x, y, w, h] (:57-71) plus the host-side object counts."""
+    `object_features [O, F + 6]` = [features, W, H, x, y, w, h] (:57-71) plus the host-side object counts.
 
-    def __init__(self, object_h5_path, file_prefix, chunk_num, object_info_json_path, ontology, split_num, lower=True, share_scenes=False):
+    device_store (a DeviceFeatureStore's `.index`, never the store itself: collators travel to DataLoader workers): a batch whose images
+    are all resident carries an ObjectFeatureRef instead of the matrix, and opens no chunk file; ProgramBatch.to_cuda gathers the matrix
+    on the device.  Any other batch takes the host route below and is marked `_feature_source = "host"`."""
+
+    def __init__(self, object_h5_path, file_prefix, chunk_num, object_info_json_path, ontology, split_num, lower=True, share_scenes=False, *,
+                 device_store=None):
         super(BatchGQABoxFeaturesCollator, self).__init__('select', 'relate', 'filter', split_num, ontology=ontology if lower else None,
                                                           share_scenes=share_scenes)
         self._object_h5_path = object_h5_path
@@ -290,6 +296,13 @@ class BatchGQABoxFeaturesCollator(ProgramCollaterBase):
         self._gqa_ontology = ontology
         first = self._chunk(0)
         self._chunck_size, self._max_object_per_image, self._feature_dim = first['features'].shape
+        if device_store is not None:
+            if not isinstance(device_store, FeatureStoreIndex):
+                raise TypeError("device_store= takes a DeviceFeatureStore's .index (host-only, picklable), not %s" % type(device_store).__name__)
+            if (device_store.max_obj, device_store.F) != (self._max_object_per_image, self._feature_dim):
+                raise ValueError("device_store holds [%d, %d] images, the chunk files [%d, %d]"
+                                 % (device_store.max_obj, device_store.F, self._max_object_per_image, self._feature_dim))
+        self._device_store = device_store
 
     def _chunk_path(self, i):
         base = os.path.join(self._object_h5_path, "%s_%d" % (self._file_prefix, i))
@@ -302,6 +315,10 @@ class BatchGQABoxFeaturesCollator(ProgramCollaterBase):
         return _open_arrays(self._chunk_path(i))
 
     def collate_object_features(self, questions):
+        if self._device_store is not None:
+            ref = self._device_store.ref([q['image_id'] for q in questions])
+            if ref is not None:
+                return ref, torch.from_numpy(np.repeat(np.arange(len(ref.counts)), ref.counts).astype(np.int64))
         if self._file_handles is None:                  # opened lazily in each DataLoader worker (:38-39)
             self._file_handles = [self._chunk(i) for i in range(self._chunk_num)]
         info = [self._object_info[q['image_id']] for q in questions]
@@ -318,6 +335,14 @@ class BatchGQABoxFeaturesCollator(ProgramCollaterBase):
             counts.append(n)
         batch_ind = torch.from_numpy(np.repeat(np.arange(len(counts)), counts).astype(np.int64))
         return torch.from_numpy(np.concatenate(feats, 0)), batch_ind
+
+    def collate(self, questions):
+        result = super(BatchGQABoxFeaturesCollator, self).collate(questions)
+        if self._device_store is not None:
+            for pb in result:
+                if not isinstance(pb._object_features, ObjectFeatureRef):
+                    pb._feature_source = "host"             # (an image of the batch is not resident: ProgramBatch.to_cuda counts the miss)
+        return result
 
     def collate_meta_data(self, questions):             # :75-92 (the direct-supervision extras are out of scope)
         tokens = sorted({t for q in questions for t in q['tokens']}, key=str)

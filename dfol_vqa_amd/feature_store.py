@@ -1,0 +1,242 @@
+"""Device-resident object-feature store: batches name images, a kernel gathers their rows (csrc/dfol_store.hip).
+
+`BatchGQABoxFeaturesCollator.collate_object_features` reads every image's features out of the chunk files, concatenates
+`[features, W, H, x, y, w, h]` on the host and the batch ships that matrix to the GPU: 822 KB per question at 100 objects x 2048 features,
+which binds a stream of unseen batches to PCIe.  The store holds the chunk files' `features`, `bboxes` and the per-image `(W, H)` on the
+device instead - the whole GQA corpus is ~122 GB of fp32, one MI355X has 288 GB - and a batch carries only an `ObjectFeatureRef`: the store
+slot and object count of each of its images.  `ProgramBatch.to_cuda` resolves the ref into the same `[O, F + 6]` matrix, bit for bit.
+
+Three kinds of object, by who may hold them:
+  DeviceFeatureStore   main process only: the device tensors, `gather`.  Registers itself by id in this process' table.
+  FeatureStoreIndex    `store.index`: host-only and picklable, image id -> (slot or -1, object count).  This is what a collator - and so
+                       every DataLoader worker - gets; no device tensor is reachable from it.
+  ObjectFeatureRef     what a collator puts in a ProgramBatch's `_object_features` when every image of the batch is resident.
+"""
+
+import json
+import os
+import uuid
+import weakref
+import zipfile
+
+import numpy as np
+import torch
+
+from . import _lib
+
+_STORES = weakref.WeakValueDictionary()        # store id -> DeviceFeatureStore of THIS process
+
+
+class ObjectFeatureRef(object):
+    """The images of one batch as rows of a store: `slots` [I] int32 (any order, repeats allowed) and `counts` [I] int32 objects each."""
+
+    __slots__ = ("store_id", "slots", "counts", "_pinned")
+
+    def __init__(self, store_id, slots, counts):
+        self.store_id = store_id
+        self.slots = np.ascontiguousarray(slots, np.int32)
+        self.counts = np.ascontiguousarray(counts, np.int32)
+        self._pinned = None
+
+    def index_array(self):
+        """[slot (I) | first output row of every image (I + 1)] int32: what the kernel reads, one upload."""
+        off = np.zeros(len(self.counts) + 1, np.int64)
+        np.cumsum(self.counts, out=off[1:])
+        if off[-1] >= 2 ** 31:
+            raise _lib.DfolError("feature store: %d object rows in one batch" % off[-1])
+        return np.concatenate([self.slots, off.astype(np.int32)])
+
+    def pin_memory(self):
+        self._pinned = torch.from_numpy(self.index_array()).pin_memory()
+        return self
+
+    def __getstate__(self):                     # (the pinned copy stays in the process that made it)
+        return (self.store_id, self.slots, self.counts)
+
+    def __setstate__(self, state):
+        self.store_id, self.slots, self.counts = state
+        self._pinned = None
+
+
+class FeatureStoreIndex(object):
+    """Which images a store holds, and where: host-only, picklable, safe to hand to DataLoader workers."""
+
+    def __init__(self, store_id, feature_dim, max_obj, table):
+        self.store_id, self.F, self.max_obj = store_id, int(feature_dim), int(max_obj)
+        self._table = table                     # image id -> (slot or -1, object count)
+
+    def __len__(self):
+        return len(self._table)
+
+    def __contains__(self, image_id):
+        return self._table.get(image_id, (-1, 0))[0] >= 0
+
+    def get(self, image_id):
+        return self._table.get(image_id, (-1, 0))
+
+    def ref(self, image_ids):
+        """ObjectFeatureRef of a batch's images, or None when one of them is not resident (the batch then takes the host route)."""
+        entries = [self._table.get(im, (-1, 0)) for im in image_ids]
+        if any(slot < 0 for slot, _ in entries):
+            return None
+        return ObjectFeatureRef(self.store_id, [slot for slot, _ in entries], [n for _, n in entries])
+
+
+def _chunk_path(directory, prefix, i):
+    base = os.path.join(directory, "%s_%d" % (prefix, i))
+    for ext in (".npz", ".h5"):
+        if os.path.exists(base + ext):
+            return base + ext
+    raise FileNotFoundError(base + ".npz|.h5")
+
+
+def _array_shape(path, arrays, name):
+    """Shape of one array of a container without reading it (an .npz member's header; an .h5 dataset knows its shape)."""
+    if path.endswith(".npz"):
+        with zipfile.ZipFile(path) as z, z.open(name + ".npy") as fh:
+            version = np.lib.format.read_magic(fh)
+            read = np.lib.format.read_array_header_1_0 if version == (1, 0) else np.lib.format.read_array_header_2_0
+            return tuple(read(fh)[0])
+    return tuple(arrays[name].shape)
+
+
+class StoreLayout(object):
+    """The host half of building a store: the chunk files' shapes (read from their headers, no array is loaded) and the info JSON."""
+
+    def __init__(self, object_h5_path, file_prefix, chunk_num, object_info_json_path):
+        from .data import _open_arrays
+        with open(object_info_json_path, "r") as f:
+            self.info = json.load(f)
+        self.paths = [_chunk_path(object_h5_path, file_prefix, i) for i in range(chunk_num)]
+        self.shapes = []
+        for p in self.paths:
+            arrays = _open_arrays(p)
+            self.shapes.append(tuple(int(d) for d in _array_shape(p, arrays, "features")))
+            if hasattr(arrays, "close"):
+                arrays.close()
+        self.max_obj, self.F = self.shapes[0][1:]
+        if any(s[1:] != (self.max_obj, self.F) for s in self.shapes):
+            raise _lib.DfolError("feature store: chunk files of different [max_obj, F]: %s" % sorted(set(s[1:] for s in self.shapes)))
+        self.row_bytes = 4 * (self.max_obj * self.F + self.max_obj * 4 + 2)          # features, boxes and (W, H) of one image
+        self.chunk_bytes = [s[0] * self.row_bytes for s in self.shapes]
+
+    def index(self, store_id, max_bytes=None):
+        """-> (FeatureStoreIndex, sizes [S, 2] fp32, first slot of every resident chunk [resident + 1]).  max_bytes: whole chunks in file
+        order for as long as they fit; None: every chunk."""
+        resident, used = 0, 0
+        while resident < len(self.paths) and (max_bytes is None or used + self.chunk_bytes[resident] <= max_bytes):
+            used += self.chunk_bytes[resident]
+            resident += 1
+        base = np.concatenate([[0], np.cumsum([s[0] for s in self.shapes[:resident]])]).astype(np.int64)
+        sizes = np.zeros((int(base[-1]), 2), np.float32)
+        table = {}
+        for image_id, inf in self.info.items():
+            c, n = int(inf["file"]), int(inf["objectsNum"])
+            if c < resident:
+                if not (0 <= int(inf["idx"]) < self.shapes[c][0] and 0 <= n <= self.max_obj):
+                    raise _lib.DfolError("feature store: image %s (idx %s, %d objects) does not fit chunk %d %s"
+                                         % (image_id, inf["idx"], n, c, self.shapes[c]))
+                slot = int(base[c]) + int(inf["idx"])
+                sizes[slot] = (inf["width"], inf["height"])
+                table[image_id] = (slot, n)
+            else:
+                table[image_id] = (-1, n)
+        return FeatureStoreIndex(store_id, self.F, self.max_obj, table), sizes, base
+
+
+class DeviceFeatureStore(object):
+    """The chunk files of a BatchGQABoxFeaturesCollator (`<prefix>_<i>.npz|.h5`: `features [chunk, max_obj, F]`, `bboxes [chunk, max_obj, 4]`
+    as x1, y1, x2, y2; the info JSON: image id -> {objectsNum, width, height, idx, file}) resident on `device` as three fp32 tensors:
+    `features [S, max_obj, F]`, `boxes [S, max_obj, 4]` as stored, `sizes [S, 2]`; slot = rows of the chunks before the image's + `idx`.
+
+    max_bytes=None: the whole corpus, which must fit in 80 % of the device memory that is free now - otherwise DfolError, nothing is
+    allocated.  max_bytes=N: whole chunks in file order for as long as they fit in N bytes; batches that name an image of a later chunk
+    take the host route (FeatureStoreIndex.ref -> None)."""
+
+    def __init__(self, object_h5_path, file_prefix, chunk_num, object_info_json_path, device, max_bytes=None):
+        from .data import _open_arrays
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.DfolError("a feature store lives on a GPU (got device %s)" % (device,))
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        lay = StoreLayout(object_h5_path, file_prefix, chunk_num, object_info_json_path)
+        if max_bytes is None:
+            need, free = sum(lay.chunk_bytes), int(torch.cuda.mem_get_info(self.device)[0])
+            if need > 0.8 * free:
+                raise _lib.DfolError("feature store: the corpus needs %d bytes, 80 %% of the free device memory is %d bytes (%d free); "
+                                     "pass max_bytes= for a partial store" % (need, int(0.8 * free), free))
+        self.id = uuid.uuid4().hex
+        self.index, sizes, base = lay.index(self.id, max_bytes)
+        S, max_obj, F = int(base[-1]), lay.max_obj, lay.F
+        self.features = torch.empty((S, max_obj, F), dtype=torch.float32, device=self.device)
+        self.boxes = torch.empty((S, max_obj, 4), dtype=torch.float32, device=self.device)
+        for c in range(len(base) - 1):             # one chunk on the host at a time
+            arrays = _open_arrays(lay.paths[c])
+            self.features[base[c]:base[c + 1]].copy_(torch.from_numpy(np.ascontiguousarray(arrays["features"][...], np.float32)))
+            self.boxes[base[c]:base[c + 1]].copy_(torch.from_numpy(np.ascontiguousarray(arrays["bboxes"][...], np.float32)))
+            if hasattr(arrays, "close"):
+                arrays.close()
+        self.sizes = torch.from_numpy(sizes).to(self.device)
+        self.S, self.max_obj, self.F = S, max_obj, F
+        self.nbytes = S * lay.row_bytes
+        self.resident_chunks = len(base) - 1
+        _STORES[self.id] = self
+
+    def upload_index(self, ref):
+        """The ref's index arrays on the device, checked against the store first (the kernel trusts them): -> int32 [slot (I) | obj_off (I + 1)].
+        A few hundred bytes, from the ref's own pinned copy (ProgramBatch.pin_memory) or through the pinned staging ring.  Not inside a stream
+        capture: a graph would bake in one batch's images - its owner gathers between replays."""
+        if ref.store_id != self.id:
+            raise _lib.DfolError("feature store %s asked for a ref of store %s" % (self.id, ref.store_id))
+        slots, counts = ref.slots, ref.counts
+        I = len(slots)
+        if len(counts) != I or (I and (slots.min() < 0 or slots.max() >= self.S or counts.min() < 0 or counts.max() > self.max_obj)):
+            raise _lib.DfolError("feature store: a ref outside the store (S = %d, max_obj = %d)" % (self.S, self.max_obj))
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.DfolError("feature store: gather uploads the batch's index arrays and cannot run inside a stream capture; "
+                                 "call it between replays, with out= the captured batch's feature buffer")
+        with torch.cuda.device(self.device):
+            idx = torch.empty(2 * I + 1, dtype=torch.int32, device=self.device)
+            if ref._pinned is not None:
+                idx.copy_(ref._pinned, non_blocking=True)
+            elif I:
+                host = ref.index_array()
+                if host.nbytes <= (1 << 20):
+                    from . import host_util
+                    host_util.ring_for(self.device).copy_to(idx.view(torch.uint8), host)
+                else:
+                    idx.copy_(torch.from_numpy(host))
+            else:
+                idx.zero_()
+        return idx
+
+    def gather(self, ref, out=None, index=None):
+        """The batch's `[O, F + 6]` object matrix on the store's device, launched on the current stream.  out=: written into that buffer
+        (rows of unit column stride, at least F + 6 columns, O rows) - how the owner of a GraphedForward / GraphedTrainStep serves new scenes
+        into its captured batch, BETWEEN replays (see upload_index).  index=: the result of an earlier upload_index(ref)."""
+        O = int(ref.counts.sum(dtype=np.int64))
+        if out is None:
+            out = torch.empty((O, self.F + 6), dtype=torch.float32, device=self.device)
+        elif out.dim() != 2 or out.shape[0] != O or out.shape[1] < self.F + 6 or out.device != self.device:
+            raise _lib.DfolError("feature store: out= must be [%d, >= %d] on %s, got %s on %s" % (O, self.F + 6, self.device, tuple(out.shape), out.device))
+        idx = self.upload_index(ref) if index is None else index
+        I = len(ref.slots)
+        if idx.numel() != 2 * I + 1:
+            raise _lib.DfolError("feature store: index= is not this ref's")
+        if O == 0:
+            return out
+        with torch.cuda.device(self.device):
+            _lib.gather_object_rows(self.features, self.boxes, self.sizes, idx[:I], idx[I:], out)
+        return out
+
+
+def resolve(ref, device):
+    """ProgramBatch.to_cuda's step: the ref's matrix from the store registered under its id in this process."""
+    store = _STORES.get(ref.store_id)
+    if store is None:
+        raise _lib.DfolError("no feature store %s in this process (a store serves the process that built it)" % ref.store_id)
+    dev = torch.device(device)
+    if dev.type != "cuda" or (dev.index is not None and dev.index != store.device.index):
+        raise _lib.DfolError("feature store %s lives on %s, the batch goes to %s" % (ref.store_id, store.device, device))
+    return store.gather(ref)

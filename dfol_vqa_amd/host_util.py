@@ -75,6 +75,14 @@ class Lowered(object):
         self.all_valid = bool(self.valid.all())
         self._dev = {}
 
+    # pickled without its device copies: an ontology keeps these objects (`_lower_cache`), and a collator that travels to a spawned DataLoader
+    # worker takes its ontology along - device tensors in it would make the worker open the GPU just to receive them
+    def __getstate__(self):
+        return (self.cols, self.neg, self.valid)
+
+    def __setstate__(self, state):
+        self.__init__(*state)
+
     def on(self, device):
         key = str(device)
         if key not in self._dev:

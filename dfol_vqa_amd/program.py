@@ -293,12 +293,21 @@ class ProgramBatch(object):
         return self
 
     def to_cuda(self, device, non_blocking=True):
+        from . import _lib, feature_store
+
         def move(obj):
             if isinstance(obj, torch.Tensor):
                 return obj.cuda(device, non_blocking=non_blocking)
+            if isinstance(obj, feature_store.ObjectFeatureRef):        # the images' rows of the device-resident store, gathered by a kernel
+                return feature_store.resolve(obj, device)
             if isinstance(obj, dict):
                 return {k: move(v) for k, v in obj.items()}
             return obj
+        def count():                                                  # (after the move: a ref that does not resolve raises uncounted)
+            if isinstance(self._object_features, feature_store.ObjectFeatureRef):
+                _lib.note("feature_store_batch")
+            elif getattr(self, "_feature_source", None) == "host":    # a store-backed collator's batch with an image the store does not hold
+                _lib.note("feature_store_miss")
         plan = getattr(self, "_native_plan", None)
         if plan is not None and not isinstance(self._op_batch_list, _LazyOps):
             # Lowered for the native executor (native_plan.build_plan, at collate time): everything its launches read travels in the plan's
@@ -308,13 +317,16 @@ class ProgramBatch(object):
             pb = ProgramBatch.__new__(ProgramBatch)
             pb.__dict__.update(self.__dict__)
             pb._op_batch_list, pb._device = ops, device
+            pb.__dict__.pop("_feature_source", None)                # (counted once, here)
             pb._object_features, pb._object_batch_index, pb._meta_data = move(self._object_features), move(self._object_batch_index), move(self._meta_data)
+            count()
             return pb
         pb = ProgramBatch(device, [ob.to_cuda(device, non_blocking) for ob in self._op_batch_list], self._dependencies, self._answers,
                           move(self._object_features), move(self._object_batch_index), self._original_dicts, move(self._meta_data),
                           object_nums=self._object_nums, question_image=self._question_image)
         if hasattr(self, "_native_plan"):                      # (None: lowered, and found to have a shape the executor does not take)
             pb._native_plan = self._native_plan
+        count()
         return pb
 
     def terminal_op_name(self):
@@ -329,7 +341,7 @@ class ProgramBatch(object):
         return self
 
     def pin_memory(self):
-        if isinstance(self._object_features, torch.Tensor):
+        if hasattr(self._object_features, "pin_memory"):              # (a tensor, or a feature store's ObjectFeatureRef: its two index arrays)
             self._object_features = self._object_features.pin_memory()
         if isinstance(self._meta_data, dict):
             for k, v in self._meta_data.items():

@@ -43,7 +43,8 @@ extern "C" {
  * The rule: the version changes when a caller written against the old one would be answered wrongly - an entry point whose arguments or units
  * change, a struct whose layout changes.  Pure additions keep it: dfol_attr_head_h2_f32, DFOL_OP_ATTR_HEAD, DFOL_DENSE_HEAD_F16X2 and the ninth
  * operand of DFOL_OP_DENSE (a slot that instruction tables written before it hold as zero = the layer's own activation) were added under 3,
- * and so were dfol_pair_ll_h1_f32, dfol_pair_pack_w2_f16, dfol_pair_w2_f16_bytes and DFOL_PAIR_F16 (an older library refuses the kind);
+ * and so were dfol_pair_ll_h1_f32, dfol_pair_pack_w2_f16, dfol_pair_w2_f16_bytes and DFOL_PAIR_F16 (an older library refuses the kind) and
+ * dfol_gather_object_rows_f32;
  * a caller that needs them checks for the symbol, and a table that names an opcode an older library lacks is refused by it ("unknown opcode"). */
 #define DFOL_ABI_VERSION 3
 
@@ -205,6 +206,19 @@ int dfol_gate_f32(const float* x_att, const float* y_att, const float* x_quant, 
 /* Row gather: out[p][:] = src[idx[p]][:]  (the reference's mm(predicate_question_map, X), e.g.
  * batch_base_ops.py:75,343 and batch_gqa_ops.py:588) for rows of `width` floats. */
 int dfol_gather_rows_f32(const float* src, const int32_t* idx, int32_t P, int32_t width, float* out, void* stream);
+
+/* Object matrix of a batch from a device-resident feature store (dfol_vqa_amd/feature_store.py), what
+ * BatchGQABoxFeaturesCollator.collate_object_features builds on the host (batch_gqa_boxfeatures_pipeline.py:57-71):
+ *   out[obj_off[i] + j][:] = [store_features[slot[i]][j][0:F], W, H, x1, y1, x2 - x1, y2 - y1]      0 <= j < obj_off[i + 1] - obj_off[i]
+ *   store_features [S, max_obj, F], store_boxes [S, max_obj, 4] as stored (x1, y1, x2, y2), store_sizes [S, 2] (W, H): device pointers
+ *   slot    [I] store slot of every image of the batch, in any order, repeats allowed; 0 <= slot[i] < S is NOT checked (device array)
+ *   obj_off [I + 1] first output row of every image; an image's row count is at most max_obj (more are not written)
+ *   out     [O, ld_out], O = obj_off[I], ld_out >= F + 6; columns beyond F + 6 are left as they are
+ * The two differences are single fp32 subtractions: every bit of `out` equals the host collator's.  Neither index array is read on the
+ * host; I == 0 returns without a launch (a caller that knows O == 0 does not call).  16-byte loads when F % 4 == 0 and store_features is
+ * 16-byte aligned, any F otherwise; the store width follows each output row's own alignment. */
+int dfol_gather_object_rows_f32(const float* store_features, const float* store_boxes, const float* store_sizes, const int32_t* slot,
+                                const int32_t* obj_off, int32_t I, int32_t max_obj, int32_t F, float* out, int64_t ld_out, void* stream);
 
 /* Segmented row sum: out[q][:] = sum_{p in seg q} src[p][:]   (mm(pqm^T, X), batch_gqa_ops.py:457). */
 int dfol_segment_sum_rows_f32(const float* src, const int32_t* seg_off, int32_t Q, int32_t width, float* out,

@@ -1,0 +1,268 @@
+#!/usr/bin/env python3
+"""What the device-resident feature store (dfol_vqa_amd/feature_store.py, csrc/dfol_store.hip) buys a stream of unseen batches.
+
+Synthetic chunk files in the collator's layout (default 2048 images x 100 objects x 2048 features, .npz, in a temporary directory), then a
+stream of unseen 256-question batches - DataLoader workers collate and lower them to plans, this process uploads, launches the native
+executor and decodes the answers - with the object features arriving three ways:
+
+  pool    already on the device (a pool of two feature sets, `value_fresh_programs`'s form): the upper bound
+  store   an ObjectFeatureRef per batch, gathered from the store by ProgramBatch.to_cuda
+  host    today's route: the worker builds [O, F + 6] from the chunk files, the matrix travels to this process, is pinned and uploaded
+
+The legs alternate in one process, `--runs` runs each (a difference counts only when the ranges are apart).  The gather kernel
+alone is timed by HIP events beside a device-to-device copy_ of the same byte count.  Prints one JSON line.
+
+usage: python tools/bench_feature_store.py [--images 2048] [--objects 100] [--features 2048] [--batch 256] [--batches 24] [--runs 4] [--workers 5]
+"""
+import argparse
+import collections
+import json
+import os
+import shutil
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import dfol_vqa_amd as D  # noqa: E402
+from dfol_vqa_amd import data, experiment  # noqa: E402
+from dfol_vqa_amd import synthetic as syn  # noqa: E402
+
+KINDS = ["exist", "verify_rel", "choose_attr", "and", "query_attr", "verify_attrs", "or", "choose_rel"]
+
+
+class HostCollator(data.BatchGQABoxFeaturesCollator):
+    """The host route over .npz chunks: every chunk is read ONCE per process (numpy re-reads a whole .npz member on every access; the
+    reference's .h5 chunks are read row by row)."""
+
+    def _chunk(self, i):
+        arrays = data._open_arrays(self._chunk_path(i))
+        return {k: np.asarray(arrays[k]) for k in ("features", "bboxes")}
+
+
+class PoolCollator(D.ProgramCollaterBase):
+    """No features at all: the launching process points every batch at a device-resident feature set."""
+
+    def __init__(self, ontology, counts):
+        super(PoolCollator, self).__init__("select", "relate", "filter", 1, ontology=ontology)
+        self._counts = counts
+
+    def collate_object_features(self, questions):
+        return None, torch.from_numpy(np.repeat(np.arange(len(questions)), [self._counts[q["image_id"]] for q in questions]).astype(np.int64))
+
+    def collate_meta_data(self, questions):
+        return {"index": {}, "embedding": torch.zeros(1, 1)}
+
+
+class Collate(object):
+    """A DataLoader worker's collate function: collate -> lower -> plan -> sparse maps (the worker never opens the GPU)."""
+
+    def __init__(self, collator):
+        self.collator = collator
+
+    def __call__(self, questions):
+        pbs = self.collator.collate(questions)
+        for pb in pbs:
+            pb.create_sparse_tensors()
+        return pbs
+
+
+def one_thread(_):
+    torch.set_num_threads(1)
+
+
+def write_corpus(directory, images, objects, features, per_chunk, seed=3):
+    rng = np.random.default_rng(seed)
+    info, chunks = {}, (images + per_chunk - 1) // per_chunk
+    for c in range(chunks):
+        n = min(per_chunk, images - c * per_chunk)
+        feats = rng.random((n, objects, features), dtype=np.float32)
+        boxes = np.empty((n, objects, 4), np.float32)
+        boxes[..., 0] = rng.random((n, objects), dtype=np.float32) * 500
+        boxes[..., 1] = rng.random((n, objects), dtype=np.float32) * 400
+        boxes[..., 2:] = boxes[..., :2] + 5 + rng.random((n, objects, 2), dtype=np.float32) * 100
+        np.savez(os.path.join(directory, "objs_%d.npz" % c), features=feats, bboxes=boxes)
+        for i in range(n):
+            info["img%05d" % (c * per_chunk + i)] = {"objectsNum": objects, "width": 640, "height": 480, "idx": i, "file": c}
+    path = os.path.join(directory, "objs_info.json")
+    with open(path, "w") as f:
+        json.dump(info, f)
+    return chunks, path, info
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--images", type=int, default=2048)
+    ap.add_argument("--objects", type=int, default=100)
+    ap.add_argument("--features", type=int, default=2048)
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--batches", type=int, default=24, help="unseen batches per run of a leg (at least 4)")
+    ap.add_argument("--runs", type=int, default=4, help="runs of every leg, alternating (at least four for a comparison)")
+    ap.add_argument("--workers", type=int, default=5)
+    ap.add_argument("--per-chunk", type=int, default=256, help="images per chunk file")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_feature_store: needs a GPU (there is no CPU form of this measurement)")
+    import bench
+    from dfol_vqa_amd import _lib, native_exec, training
+    device = torch.device("cuda", 0)
+    tmp = tempfile.mkdtemp(prefix="dfol_store_bench_")
+    loaders = {}
+    try:
+        paths, names = syn.write_synthetic_ontology(os.path.join(tmp, "ontology"))
+        cfg = syn.reference_config(paths)
+        ontology = experiment.build_ontology(cfg)
+        torch.manual_seed(0)
+        model = experiment.build_model(cfg, ontology)
+        bench.init_weights(model)
+        model = model.to(device).eval()
+        spec = native_exec.model_spec(model) if native_exec.enabled() else None
+        t0 = time.perf_counter()
+        chunks, info_path, info = write_corpus(tmp, args.images, args.objects, args.features, args.per_chunk)
+        write_s = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        store = data.DeviceFeatureStore(tmp, "objs", chunks, info_path, device)
+        torch.cuda.synchronize()
+        build_s = time.perf_counter() - t0
+
+        with open(paths["attribute_file"]) as f:
+            cats = json.load(f)
+        rng = np.random.RandomState(9)
+        questions = []
+        for b in range(args.batches):                        # every batch other programs on other images
+            qs = syn.full_size_questions(KINDS[b % len(KINDS)], args.batch, args.objects, args.objects, names, cats, 7000 + b, with_scene=False)
+            for q in qs:
+                q["image_id"] = "img%05d" % rng.randint(args.images)
+            questions += qs
+        sampler = [list(range(b * args.batch, (b + 1) * args.batch)) for b in range(args.batches)]
+
+        collators = {"pool": PoolCollator(ontology, {k: v["objectsNum"] for k, v in info.items()}),
+                     "store": HostCollator(tmp, "objs", chunks, info_path, ontology, 1, device_store=store.index),
+                     "host": HostCollator(tmp, "objs", chunks, info_path, ontology, 1)}
+        for c in collators.values():
+            c._native_spec = spec
+        batch_bytes = args.batch * args.objects * (args.features + 6) * 4
+        # the host leg's matrices cross from the workers through shared memory: as many workers as it has room for, else this process collates
+        shm_free = shutil.disk_usage("/dev/shm").free if os.path.isdir("/dev/shm") else 0
+        host_workers = int(max(0, min(args.workers, shm_free // (3 * batch_bytes))))
+        for leg, c in collators.items():
+            w = host_workers if leg == "host" else args.workers
+            kw = dict(multiprocessing_context="spawn", persistent_workers=True, worker_init_fn=one_thread, prefetch_factor=1 if leg == "host" else 2) if w else {}
+            # (pinning is the host leg's: the reference's pin_memory DataLoader for the feature matrix; a store batch's few hundred bytes of
+            # index arrays go through the pinned staging ring)
+            loaders[leg] = torch.utils.data.DataLoader(questions, batch_sampler=sampler, num_workers=w, collate_fn=Collate(c), pin_memory=leg == "host", **kw)
+
+        refs = [store.index.ref([q["image_id"] for q in questions[i * args.batch:(i + 1) * args.batch]]) for i in range(min(8, args.batches))]
+        pool = [store.gather(r) for r in refs[:2]]
+        first_lp = {}
+
+        def run(leg):
+            """One pass over the stream: -> (seconds, host seconds spent in to_cuda)."""
+            inflight, k, to_cuda_s = collections.deque(), 0, 0.0
+
+            def finish():
+                pbs, pending = inflight.popleft()
+                res = pending.result()
+                training.compute_evaluation_metrics(pbs, res)
+                return res
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for pbs in loaders[leg]:
+                h0 = time.perf_counter()
+                if leg == "pool":
+                    for pb in pbs:
+                        pb._object_features = pool[k % len(pool)]
+                dev = [pb.to_cuda(device) for pb in pbs]
+                to_cuda_s += time.perf_counter() - h0
+                inflight.append((dev, model.forward_async(dev, False)))
+                if len(inflight) > 2:                        # two batches in flight, as value_fresh_programs
+                    res = finish()
+                    if k == 2 and leg not in first_lp:
+                        first_lp[leg] = res["log_probability"].cpu().numpy().copy()
+                k += 1
+            while inflight:
+                finish()
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0, to_cuda_s
+
+        legs = ("pool", "store", "host")
+        with torch.no_grad():
+            for leg in legs:                                 # warm-up: workers up, allocator, weight images
+                run(leg)
+            _lib.PATH_COUNTS.clear()
+            times = {leg: [] for leg in legs}
+            to_cuda = {leg: [] for leg in legs}
+            for _ in range(args.runs):
+                for leg in legs:
+                    dt, h = run(leg)
+                    times[leg].append(dt / args.batches * 1e3)
+                    to_cuda[leg].append(h / args.batches * 1e3)
+        counts = {k: v for k, v in _lib.PATH_COUNTS.items() if k in ("native_program", "python_program", "feature_store_batch", "feature_store_miss")}
+
+        # the gather alone, and a device-to-device copy of the same bytes, by HIP events in the same session
+        out = torch.empty_like(pool[0])
+        src = pool[1]
+
+        def event_ms(fn, n=20):
+            for i in range(3):
+                fn(i)
+            evs = []
+            for i in range(n):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn(i)
+                b.record()
+                evs.append((a, b))
+            torch.cuda.synchronize()
+            return sorted(a.elapsed_time(b) for a, b in evs)
+        # (the kernel alone: every ref's index arrays are on the device before the first event, nothing is allocated between the events)
+        on_dev = [store.upload_index(r) for r in refs]
+        torch.cuda.synchronize()
+        gather_ms = event_ms(lambda i: store.gather(refs[i % len(refs)], out=out, index=on_dev[i % len(refs)]))
+        copy_ms = event_ms(lambda i: out.copy_(src))
+        same = bool(np.array_equal(first_lp["store"].view(np.uint32), first_lp["host"].view(np.uint32)))
+    finally:
+        for ld in loaders.values():                          # (persistent workers: stop them before the files go)
+            it = getattr(ld, "_iterator", None)
+            if it is not None:
+                it._shutdown_workers()
+        shutil.rmtree(tmp, ignore_errors=True)
+
+    def span(xs):
+        return {"min": min(xs), "median": float(np.median(xs)), "max": max(xs)}
+
+    def apart(a, b):
+        """a against b in ms per batch, by the rule that a difference counts only when the ranges of the runs are apart."""
+        return "faster, ranges apart" if a["max"] < b["min"] else "slower, ranges apart" if a["min"] > b["max"] else "ranges overlap: no difference shown"
+    ms = {leg: span(times[leg]) for leg in legs}
+    qps = {leg: {"min": args.batch / ms[leg]["max"] * 1e3, "median": args.batch / ms[leg]["median"] * 1e3, "max": args.batch / ms[leg]["min"] * 1e3} for leg in legs}
+    g, c = float(np.median(gather_ms)), float(np.median(copy_ms))
+    extra = ms["store"]["median"] - ms["pool"]["median"]
+    moved = 2.0 * batch_bytes
+    result = {
+        "tool": "bench_feature_store", "shape": {"images": args.images, "objects": args.objects, "features": args.features, "batch": args.batch,
+                                                 "batches_per_run": args.batches, "runs": args.runs, "workers": args.workers, "host_leg_workers": host_workers},
+        "store": {"bytes": store.nbytes, "slots": store.S, "chunks": chunks, "write_files_s": write_s, "build_s": build_s},
+        "ms_per_batch": ms, "questions_per_s": qps, "to_cuda_host_ms_per_batch": {leg: span(to_cuda[leg]) for leg in legs},
+        "store_vs_host": apart(ms["store"], ms["host"]), "store_vs_pool": apart(ms["store"], ms["pool"]),
+        "store_over_pool_questions_per_s": qps["store"]["median"] / qps["pool"]["median"],
+        "store_over_host_questions_per_s": qps["store"]["median"] / qps["host"]["median"],
+        "gather_kernel": {"ms": span(gather_ms), "GBps_read_plus_written": moved / g / 1e6, "bytes_read_plus_written": moved},
+        "copy_d2d": {"ms": span(copy_ms), "GBps_read_plus_written": moved / c / 1e6},
+        "gather_over_copy": g / c,
+        "store_step_beyond_pool": {"ms_per_batch": extra, "gather_kernel_ms": g, "not_explained_by_the_gather_ms": extra - g,
+                                   "to_cuda_host_ms_store_minus_pool": float(np.median(to_cuda["store"]) - np.median(to_cuda["pool"])),
+                                   "named": "the gather runs on the launch stream ahead of the batch's featurizer (nothing overlaps it), and to_cuda of a "
+                                            "store batch allocates the [O, F + 6] matrix, uploads the index arrays and launches on the launching thread: "
+                                            "to_cuda_host_ms_store_minus_pool is that host share"},
+        "routes": counts, "store_equals_host_bitwise_first_batch": same,
+    }
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
