@@ -132,6 +132,8 @@ SIGNATURES = {
     "dfol_lstm_pointwise_f32": [_p, _p, _p, _i32, _i32, _p, _p, _p],
     "dfol_lstm_cell_train_f32": [_p, _i64, _i32, _p, _i64, _p, _p, _i64, _p, _i64, _p, _p, _i32, _i32, _p, _p, _p, _p],
     "dfol_lstm_cell_bwd_f32": [_p, _p, _p, _p, _p, _i32, _i32, _p, _p, _p],
+    "dfol_lstm_cell_supported": [_i32, _i32],               # returns 0 / 1, not a status: called directly
+    "dfol_calib_walk_supported": [_i32, _i32],
     "dfol_modulate_bwd_f32": [_p, _p, _p, _p, _p, _i32, _i32, _p, _p, _p],
     "dfol_attr_ll_f32": [_p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _i32, _i32, _f, _p, _p],
     "dfol_attr_head_h2_f32": [_p, _i64, _i32, _p, _p, _i32, _p, _i64, _p, _p, _i32, _i32, _p, _p, _i32, _i32, _f, _p, _p],
@@ -772,6 +774,16 @@ def linear_act(x, weight, bias, act, out=None):
     call("dfol_linear_act_f32", _dp(x), x.stride(0), _dp(weight), weight.stride(0), _ptr(bias, F32, True),
          _dp(out), out.stride(0), M, N, K, act, _stream())
     return out
+
+
+def lstm_cell_supported(KX, H):
+    """The one-launch cell (lstm_cell / lstm_cell_tokens / lstm_cell_train) takes this input and state width: KX + H <= 496, the kernel's own rule."""
+    return bool(load().dfol_lstm_cell_supported(int(KX), int(H)))
+
+
+def calib_walk_supported(KX, H):
+    """DFOL_OP_CALIB_WALK takes a calibrator of these widths: KX + 9 H + 2 <= 1024, the walk kernel's own rule."""
+    return bool(load().dfol_calib_walk_supported(int(KX), int(H)))
 
 
 def lstm_pointwise(igates, hgates, c):

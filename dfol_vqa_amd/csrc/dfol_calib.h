@@ -31,6 +31,10 @@ struct LcCell {
     LcTokens tk;
 };
 __host__ __device__ inline size_t lc_lds_floats(int KX, int H) { return (size_t)LC_ROWS * ((size_t)KX + H + (size_t)LC_SLICES * LC_PS); }
+// What a launch may ask of LDS (64 KB a workgroup) decides the widths a cell takes: 16 * (KX + H + 16 * 33) * 4 <= 65536, i.e. KX + H <= 496.  The one
+// formula behind dfol_lstm_cell_supported, the entry points' own refusal and the host's choice of the two-product + pointwise route.
+constexpr size_t LC_LDS_BYTES = 64 * 1024;
+inline bool lc_cell_fits(int KX, int H) { return KX > 0 && H > 0 && sizeof(float) * lc_lds_floats(KX, H) <= LC_LDS_BYTES; }
 
 // Stage the inputs of rows r0 .. r0 + LC_ROWS - 1 as in_s[k][row] (no barrier).  A lane keeps its row and walks k (four consecutive k per wavefront:
 // 16-byte pieces of sixteen rows, LDS stores without bank conflicts - lanes along k, the first version, put 32 lanes on one bank).
@@ -121,6 +125,8 @@ __device__ __forceinline__ void lc_units(const LcCell& p, int r0, int j0, const 
 // sum in slice order - so that a gate is (slices 0..7) + (slices 8..15), the bits of lc_units.  part_s: [2][LC_ROWS][4H + 1] floats.  One barrier
 // inside (the caller puts one between the staging and this call).
 __host__ __device__ inline size_t lc_wide_lds_floats(int KX, int H) { return (size_t)LC_ROWS * ((size_t)KX + H + 2 * ((size_t)4 * H + 1)); }
+// (16 * (KX + H + 2 * (4 H + 1)) * 4 <= 65536, i.e. KX + 9 H + 2 <= 1024: dfol_calib_walk_supported, run_calib_walk's refusal, native_plan.fold_runs)
+inline bool lc_walk_fits(int KX, int H) { return KX > 0 && H > 0 && sizeof(float) * lc_wide_lds_floats(KX, H) <= LC_LDS_BYTES; }
 __device__ __forceinline__ void lc_wide(const LcCell& p, int r0, const float* __restrict__ in_s, float* __restrict__ part_s) {
     static_assert(LC_SLICES % 2 == 0 && LC_THREADS == 512, "lstm_cell: two halves of the K slices");
     const int tid = threadIdx.x, K = p.KX + p.H, H = p.H, KX = p.KX, G = 4 * H, PS = G + 1;

@@ -1692,8 +1692,8 @@ static int lstm_cell_launch(const char* what, const float* x, int64_t ld_x, int3
                             const float* Wih, int64_t ld_wih, const float* Whh, int64_t ld_whh, const float* bih, const float* bhh, int32_t rows, int32_t H,
                             float* h_out, float* c_out, float* gates, void* stream) {
     DFOL_REQUIRE(rows >= 0 && H > 0 && KX > 0, "%s: bad sizes rows=%d H=%d KX=%d", what, rows, H, KX);
+    DFOL_REQUIRE(lc_cell_fits(KX, H), "%s: input width %d + hidden %d too large for the staging buffer (KX + H <= 496: dfol_lstm_cell_supported)", what, KX, H);
     const size_t lds = sizeof(float) * lc_lds_floats(KX, H);
-    DFOL_REQUIRE(lds <= 64 * 1024, "%s: input width %d + hidden %d too large for the staging buffer", what, KX, H);
     if (rows == 0) return 0;
     DFOL_REQUIRE(h && c && Wih && Whh && h_out && c_out, "%s: null pointer", what);
     hipLaunchKernelGGL(lstm_cell_kernel, dim3(dfol_cdiv(rows, LC_ROWS), dfol_cdiv(H, LC_UNITS)), dim3(LC_THREADS), lds, (hipStream_t)stream,
@@ -1701,6 +1701,8 @@ static int lstm_cell_launch(const char* what, const float* x, int64_t ld_x, int3
     DFOL_LAUNCH_CHECK(what);
     return 0;
 }
+
+extern "C" int dfol_lstm_cell_supported(int32_t KX, int32_t H) { return lc_cell_fits(KX, H) ? 1 : 0; }
 
 extern "C" int dfol_lstm_cell_f32(const float* x, int64_t ld_x, int32_t KX, const float* h, int64_t ld_h, const float* c, const float* Wih,
                                   int64_t ld_wih, const float* Whh, int64_t ld_whh, const float* bih, const float* bhh, int32_t rows,

@@ -85,8 +85,10 @@ int run_calib_walk(const DfolProgramModel* model, const int64_t* table_dev, int3
     DFOL_REQUIRE(model->lstm_wih_t[0] && model->lstm_whh_t[0] && model->lstm_wih_t[1] && model->lstm_whh_t[1] && model->lstm_h > 0 && model->lstm_kx > 0 &&
                      model->att_out_w && model->att_out_n > 0,
                  "calib_walk: the model has no calibration networks");
+    DFOL_REQUIRE(lc_walk_fits(model->lstm_kx, model->lstm_h),
+                 "calib_walk: input width %d + hidden %d too large for the staging buffer (KX + 9 H + 2 <= 1024: dfol_calib_walk_supported)", model->lstm_kx,
+                 model->lstm_h);
     const size_t lds = sizeof(float) * lc_wide_lds_floats(model->lstm_kx, model->lstm_h);
-    DFOL_REQUIRE(lds <= 64 * 1024, "calib_walk: input width %d + hidden %d too large for the staging buffer", model->lstm_kx, model->lstm_h);
     hipLaunchKernelGGL(calib_walk_kernel, dim3(dfol_cdiv(rows, LC_ROWS)), dim3(LC_THREADS), lds, (hipStream_t)stream, table_dev, n_steps, rows,
                        static_cast<char*>(workspace), static_cast<const char*>(blob), *model);
     DFOL_LAUNCH_CHECK("calib_walk");
@@ -111,6 +113,8 @@ int run_dense(const DfolDenseLayer& L, const float* X, int64_t ldx, float* Y, in
 }
 
 }  // namespace
+
+extern "C" int dfol_calib_walk_supported(int32_t KX, int32_t H) { return lc_walk_fits(KX, H) ? 1 : 0; }
 
 extern "C" int dfol_run_program(const DfolProgramModel* model, const DfolProgramScene* scene, const int64_t* instr_host, int32_t n_instr,
                                 const void* blob, void* workspace, void* stream) {

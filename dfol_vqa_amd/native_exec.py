@@ -97,8 +97,8 @@ def calibrator(model):
             and isinstance(out[0], nn.Linear) and isinstance(out[1], nn.Sigmoid)):
         return None
     S, KX = fwd.hidden_size, fwd.input_size
-    if (bwd.hidden_size, bwd.input_size) != (S, KX) or out[0].in_features != 2 * S or out[0].out_features != 4 or 4 * (KX + 5 * S) * 4 > 65536:
-        return None
+    if (bwd.hidden_size, bwd.input_size) != (S, KX) or out[0].in_features != 2 * S or out[0].out_features != 4 or not _lib.lstm_cell_supported(KX, S):
+        return None                                          # (KX + S > 496: the Python loop runs such cells as two products + the pointwise kernel)
     if not all(p.is_cuda and p.dtype == torch.float32 for m in (fwd, bwd, out) for p in m.parameters()):
         return None
     return fwd, bwd, out[0]

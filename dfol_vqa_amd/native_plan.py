@@ -570,11 +570,15 @@ class _Calibration(object):
 
     def fold_runs(self, resolve):
         """DFOL_CALIB_WALK=1 (opt-in): runs of row-wise launches over states of one size -> one OP_CALIB_WALK each (the workgroup that owns 16 rows walks
-        the run: csrc/dfol_program.hip calib_walk_kernel; same device code, bit-identical results).  Measured SLOWER than the launches it replaces
+        the run: csrc/dfol_program.hip calib_walk_kernel; same device code, bit-identical results), for the calibrator widths the walk kernel takes
+        (dfol_calib_walk_supported; others keep the separate launches).  Measured SLOWER than the launches it replaces
         (256 questions: 1.89 against 1.70 ms per batch): a workgroup then pulls all 294 KB of a cell's weights through one CU's L1, which
         the stand-alone cell spreads over 112 CUs - so the default keeps the separate launches."""
         import os
         if os.environ.get("DFOL_CALIB_WALK", "0") != "1" or not self._walk:
+            return
+        from . import _lib
+        if not _lib.calib_walk_supported(self.c["lstm_in"], self.S):       # (lstm_in + 9 S + 2 > 1024: the walk kernel's LDS; the separate launches stay)
             return
         instrs, out, k = self.b.instrs, [], 0
         first = self._walk[0][0]

@@ -182,8 +182,9 @@ class CalibrationLSTMCell(nn.LSTMCell):
         return L.keep_alive(self._wt)
 
     def forward(self, x, state=None):
+        # (the one-launch cell stages 16 rows of [x | h] in LDS: input + state width <= 496, asked of the library - dfol_lstm_cell_supported)
         fits = state is not None and x.is_cuda and x.dtype == torch.float32 and x.stride(-1) == 1 and state[0].stride(-1) == 1 and \
-            4 * (x.shape[1] + 5 * state[0].shape[1]) * 4 <= 65536
+            L.lstm_cell_supported(x.shape[1], state[0].shape[1])
         grads = torch.is_grad_enabled() and (x.requires_grad or (state is not None and (state[0].requires_grad or state[1].requires_grad)) or
                                              any(p.requires_grad for p in self.parameters()))
         if grads and fits and os.environ.get("DFOL_LSTM_BWD", "hip") != "torch":
@@ -191,11 +192,15 @@ class CalibrationLSTMCell(nn.LSTMCell):
             h, c = state
             return _LSTMCellFn.apply(x, h.contiguous(), c.contiguous(), self.weight_ih, self.weight_hh, self.bias_ih, self.bias_hh, wt[1], wt[2])
         if state is None or not x.is_cuda or grads:
+            if grads and not fits and state is not None and x.is_cuda:
+                _lib.fallback("calibration LSTM cell (training)", "input width %d + state width %d beyond the one-launch cell's 496, or a strided / "
+                              "non-fp32 input" % (x.shape[1], state[0].shape[1]))
             return super(CalibrationLSTMCell, self).forward(x, state)
         h, c = state
         if fits:
             wt = self._transposed()
             return L.lstm_cell(x, h, c.contiguous(), wt[1], wt[2], self.bias_ih, self.bias_hh)          # one launch
+        _lib.note("lstm_pointwise")                              # two gate products on the dense kernels + the pointwise stage
         ig = L.linear_act(x.contiguous(), self.weight_ih, self.bias_ih, L.ACT_NONE)
         hg = L.linear_act(h.contiguous(), self.weight_hh, self.bias_hh, L.ACT_NONE)
         return L.lstm_pointwise(ig, hg, c.contiguous())

@@ -44,7 +44,7 @@ extern "C" {
  * change, a struct whose layout changes.  Pure additions keep it: dfol_attr_head_h2_f32, DFOL_OP_ATTR_HEAD, DFOL_DENSE_HEAD_F16X2 and the ninth
  * operand of DFOL_OP_DENSE (a slot that instruction tables written before it hold as zero = the layer's own activation) were added under 3,
  * and so were dfol_pair_ll_h1_f32, dfol_pair_pack_w2_f16, dfol_pair_w2_f16_bytes and DFOL_PAIR_F16 (an older library refuses the kind) and
- * dfol_gather_object_rows_f32;
+ * dfol_gather_object_rows_f32, and the two size queries dfol_lstm_cell_supported and dfol_calib_walk_supported;
  * a caller that needs them checks for the symbol, and a table that names an opcode an older library lacks is refused by it ("unknown opcode"). */
 #define DFOL_ABI_VERSION 3
 
@@ -334,13 +334,19 @@ int dfol_lstm_pointwise_f32(const float* igates, const float* hgates, const floa
 /* The whole LSTM cell in one launch (gate products, biases, pointwise stage): x [rows, ld_x] (KX used), h [rows, ld_h], c [rows, H],
  * Wih = W_ih^T [KX, ld_wih >= 4H], Whh = W_hh^T [H, ld_whh >= 4H] (TRANSPOSED weights: coalesced across the gate threads),
  * b_ih / b_hh [4H] or NULL -> h_out, c_out [rows, H].  What the calibration passes run.
+ * LIMIT (this entry point, dfol_lstm_cell_tokens_f32 and dfol_lstm_cell_train_f32): a workgroup stages 16 rows of [x | h] and the 16 K slices' partial
+ * gates in LDS, 16 * (KX + H + 16 * 33) * 4 <= 65536 bytes, i.e. KX + H <= 496 (the default 318 + 50 takes 57 KB).  dfol_lstm_cell_supported(KX, H)
+ * answers 1 / 0 from that formula; wider cells are refused with an error ("too large for the staging buffer") before any device call and run as
+ * two dfol_linear_act_f32 launches + dfol_lstm_pointwise_f32.
  */
+int dfol_lstm_cell_supported(int32_t KX, int32_t H);
 int dfol_lstm_cell_f32(const float* x, int64_t ld_x, int32_t KX, const float* h, int64_t ld_h, const float* c, const float* Wih,
                        int64_t ld_wih, const float* Whh, int64_t ld_whh, const float* bih, const float* bhh, int32_t rows, int32_t H,
                        float* h_out, float* c_out, void* stream);
 /* The same cell on an operator's TOKENS: row p of x is built while it is staged - [head (n_head floats: operator one-hot, token-type flag) |
  * table[idx[p]] (E floats: token embedding)], all zeros where idx[p] < 0 - what dfol_calib_features_f32 would write (batch_base_ops.py:265-273,
  * 437-446, 628-637), without the round trip through memory; KX = n_head + E.  Bit-identical to dfol_calib_features_f32 + dfol_lstm_cell_f32.
+ * LIMIT: n_head + E + H <= 496 (dfol_lstm_cell_supported), as dfol_lstm_cell_f32.
  */
 int dfol_lstm_cell_tokens_f32(const float* head, int32_t n_head, const float* table, int32_t E, const int32_t* idx, const float* h, int64_t ld_h,
                               const float* c, const float* Wih, int64_t ld_wih, const float* Whh, int64_t ld_whh, const float* bih, const float* bhh,
@@ -363,7 +369,8 @@ int dfol_attention_modulations_f32(const float* fs, const float* bs, const float
  * stores the ACTIVATED gates [rows, 4H] (sigmoid(i), sigmoid(f), tanh(g), sigmoid(o)); dfol_lstm_cell_bwd_f32 is the backward of the
  * pointwise stage (torch's lstm_cell_backward): -> d_gates [rows, 4H] w.r.t. the PRE-activation gates and d_c_prev [rows, H]; d_hy / d_cy
  * may be NULL (no gradient through that output).  The weight / input products of the backward are dfol_linear_act_f32 and
- * dfol_linear_wgrad_bias_f32 calls on d_gates.
+ * dfol_linear_wgrad_bias_f32 calls on d_gates.  LIMIT of dfol_lstm_cell_train_f32: KX + H <= 496 (dfol_lstm_cell_supported), as dfol_lstm_cell_f32;
+ * dfol_lstm_cell_bwd_f32 is pointwise and takes any H.
  */
 int dfol_lstm_cell_train_f32(const float* x, int64_t ld_x, int32_t KX, const float* h, int64_t ld_h, const float* c, const float* Wih,
                              int64_t ld_wih, const float* Whh, int64_t ld_whh, const float* bih, const float* bhh, int32_t rows, int32_t H,
@@ -842,7 +849,11 @@ typedef struct {            /* the scenes of one ProgramBatch (data_pipeline.py:
 #define DFOL_OP_MODULATE 22         /* att, mods, pred_q (blob), P, out */
 #define DFOL_OP_CALIB_WALK 23       /* table (blob: n steps of DFOL_INSTR_WIDTH int64, DFOL_WALK_* below), n, rows: a run of row-wise steps of the calibration
                                      * passes over states of `rows` rows in ONE launch - what DFOL_OP_FILL / SELECT_ROWS / LOGIC (add) / LSTM_CELL (token form) /
-                                     * ATT_MODULATIONS launches in a row would compute, bit for bit (a workgroup owns 16 rows and walks the table) */
+                                     * ATT_MODULATIONS launches in a row would compute, bit for bit (a workgroup owns 16 rows and walks the table).
+                                     * LIMIT: the workgroup stages 16 rows of [x | h] and two halves of ALL 4 lstm_h gate columns in LDS,
+                                     * 16 * (lstm_kx + lstm_h + 2 * (4 lstm_h + 1)) * 4 <= 65536 bytes, i.e. lstm_kx + 9 lstm_h + 2 <= 1024
+                                     * (dfol_calib_walk_supported; 318 + 50 fits, a state width of 100 does not); a wider model is refused
+                                     * ("too large for the staging buffer") and keeps the separate launches */
 #define DFOL_OP_ATTR_HEAD 24        /* pre1, ld_pre1, pred_img (blob), cols (blob), P, ll, scenes: dfol_attr_head_h2_f32 over the attribute network's last layer
                                      * (a two-layer network whose last layer is DFOL_DENSE_HEAD_F16X2) - replaces that layer's DFOL_OP_DENSE and DFOL_OP_ATTR_LL */
 /* steps of a DFOL_OP_CALIB_WALK table; buffers are [planes][rows][width] floats in the workspace (an LSTM state is h then c: two planes) */
@@ -852,6 +863,7 @@ typedef struct {            /* the scenes of one ProgramBatch (data_pipeline.py:
 #define DFOL_WALK_LSTM 3            /* which, h, c, h_out, c_out, head (blob), n_head, table (blob), E, idx (blob) */
 #define DFOL_WALK_ATT_MODULATIONS 4 /* forward state h, backward state h, out [rows, att_out_n] */
 
+int dfol_calib_walk_supported(int32_t KX, int32_t H); /* 1 / 0: DFOL_OP_CALIB_WALK takes a calibrator of input width KX and state width H */
 int dfol_run_program(const DfolProgramModel* model, const DfolProgramScene* scene, const int64_t* instr_host, int32_t n_instr,
                      const void* blob, void* workspace, void* stream);
 
