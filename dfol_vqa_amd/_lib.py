@@ -100,6 +100,7 @@ SIGNATURES = {
     "dfol_gate_f32": [_p, _p, _p, _p, _p, _i32, _i32, _p, _p, _p],
     "dfol_gather_rows_f32": [_p, _p, _i32, _i32, _p, _p],
     "dfol_gather_object_rows_f32": [_p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _p],
+    "dfol_store_rows_f32": [_p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p],
     "dfol_segment_sum_rows_f32": [_p, _p, _i32, _i32, _p, _p],
     "dfol_logic_f32": [_i32, _p, _p, _i64, _p, _p],
     "dfol_parametric_not_f32": [_p, _p, _i32, _i32, _p, _p],
@@ -188,6 +189,7 @@ SIGNATURES = {
     "dfol_grad_sqnorm_f32": [_p, _i64, _p, _p],
     "dfol_clip_adam_f32": [_p, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _i32, _p, _f, _f, _f, _f, _f, _f, _f, _p, _p],
     "dfol_linear_wide_h2_f32": [_p, _i64, _p, _p, _p, _i64, _i32, _i32, _i32, _i32, _p],
+    "dfol_linear_wide_rows_h2_f32": [_p, _i64, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _i32, _p],
     "dfol_pair_w2_f16x2_bytes": [_i32],
     "dfol_pair_pack_w2_f16x2": [_p, _i64, _i32, _i32, _p, _p],
     "dfol_pair_ll_h2_f32": [_p, _i64, _i32, _p, _i64, _p, _p, _p, _i32, _p, _i64, _p, _p, _p, _i32, _i32, _p, _p, _p, _i32, _i32, _f,
@@ -198,6 +200,7 @@ SIGNATURES = {
                             _i32, _p, _p],
     "dfol_run_program": [_p, _p, _p, _i32, _p, _p, _p],
     "dfol_set_range_status": [_p],
+    "dfol_set_feature_rows": [_p, _p],
 }
 
 
@@ -552,6 +555,19 @@ def gather_object_rows(features, boxes, sizes, slot, obj_off, out):
     return out
 
 
+def store_rows(boxes, sizes, slot, obj_off, src_row, box6):
+    """The index form of a store-backed batch (csrc/dfol_store.hip): src_row[obj_off[i] + j] = slot[i] * max_obj + j and box6 = the gather's last
+    six columns, written into src_row [O] int32 and box6 [O, 6] fp32; boxes [S, max_obj, 4], sizes [S, 2]."""
+    S, max_obj = boxes.shape[0], boxes.shape[1]
+    if tuple(boxes.shape) != (S, max_obj, 4) or tuple(sizes.shape) != (S, 2) or obj_off.numel() != slot.numel() + 1:
+        raise DfolError("store_rows: store tensors / index arrays of mismatched shapes")
+    if src_row.dim() != 1 or box6.dim() != 2 or tuple(box6.shape) != (src_row.numel(), 6):
+        raise DfolError("store_rows: src_row [O] int32 and box6 [O, 6] fp32")
+    call("dfol_store_rows_f32", _ptr(boxes, F32), _ptr(sizes, F32), _ptr(slot, I32), _ptr(obj_off, I32), slot.numel(), S, max_obj,
+         _ptr(src_row, I32), _ptr(box6, F32), _stream())
+    return src_row, box6
+
+
 def segment_sum_rows(src, seg_off):
     Q, width = seg_off.numel() - 1, src.shape[1]
     out = torch.empty(Q, width, dtype=F32, device=src.device)
@@ -681,6 +697,25 @@ def linear_wide(x, weight, bias, act, out=None):
         out = torch.empty(M, N, dtype=F32, device=x.device)
     call("dfol_linear_wide_h2_f32", _dp(x), x.stride(0), _ptr(linear_pack_w_split(weight, False, 2), torch.bfloat16), _ptr(bias, F32, True), _dp(out),
          out.stride(0), M, N, K, act, _stream())
+    return out
+
+
+def linear_wide_supported(M, N, K):
+    """dfol_linear_wide_supported: the persistent wide kernel takes the shape and it pays (DFOL_DENSE_WIDE: 0 never, 2 whenever taken)."""
+    return bool(load().dfol_linear_wide_supported(int(M), int(N), int(K)))
+
+
+def linear_wide_rows(table, src_row, weight, bias, act, out=None):
+    """linear_wide over indexed rows: y[r] = act(table[src_row[r]] @ weight.T + bias), table [rows, K] fp32 (a feature store's features as a
+    matrix), src_row [M] int32.  Bit for bit linear_wide(table[src_row]) without the gathered copy (csrc/dfol_dense_wide.hip, ROWS)."""
+    M, K = src_row.numel(), table.shape[1]
+    N = weight.shape[0]
+    if weight.shape[1] != K or table.dtype != F32 or table.stride(1) != 1:
+        raise DfolError("linear_wide_rows: table [rows, %d] fp32 with unit column stride, weight [N, %d]" % (K, K))
+    if out is None:
+        out = torch.empty(M, N, dtype=F32, device=table.device)
+    call("dfol_linear_wide_rows_h2_f32", _dp(table), table.stride(0), _ptr(src_row, I32), _ptr(linear_pack_w_split(weight, False, 2), torch.bfloat16),
+         _ptr(bias, F32, True), _dp(out), out.stride(0), M, N, K, act, _stream())
     return out
 
 

@@ -34,10 +34,13 @@ constexpr int WD_NMAX = 512;
 constexpr size_t WD_LDS = (size_t)6 * WD_TILE * 16 + 2 * WD_NMAX * 4 + 8 * 4096;  // A0, A1, B0 (two column blocks), B1; row scales and bias; the epilogue's 4 KB per wavefront
 
 // XV: floats per X load (4: rows 16-byte aligned; 2: rows 8-byte aligned - the 2054-column raw feature matrix)
-template <int ACT, int XV>
+// ROWS: row r of the product is row src_row[r] of X (dfol_linear_wide_rows_h2_f32: X is a feature store's table, src_row from dfol_store_rows_f32).
+// The index is read where a row's address is formed - at the start and at each block transition of load_x, never per k-step - and nothing
+// else differs: the instantiations without ROWS never touch src_row and compile to the code they had before it existed.
+template <int ACT, int XV, bool ROWS = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void wide_h2_kernel(
     const float* __restrict__ X, int64_t ldx, const u32x4* __restrict__ Wp, const float* __restrict__ bias, float* __restrict__ Y, int64_t ldy, int M,
-    int N, int K, int ksteps, int nbn, uint32_t* __restrict__ status) {
+    int N, int K, int ksteps, int nbn, uint32_t* __restrict__ status, const int32_t* __restrict__ src_row) {
     extern __shared__ __attribute__((aligned(16))) u32x4 wd_sm[];
     constexpr int A0 = 0, B0 = 2 * WD_TILE;                            // A buffer b at b * WD_TILE; B buffer b at B0 + b * 2 * WD_TILE
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), kh = lane >> 4, r16 = lane & 15;
@@ -58,7 +61,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // ---- X rows: a ring of WD_XD register sets; the loader's position runs ahead of the multiplier's across block boundaries
     float4 xa[WD_XD][2];
     int lb = first, lks = 0;
-    const float* xrow = X + (int64_t)min(lb * WD_BM + arow, M - 1) * ldx + aq * 8;
+    const int r0 = min(lb * WD_BM + arow, M - 1);                      // (clamped: the index read stays inside src_row [M], the row inside X)
+    const float* xrow = X + (int64_t)(ROWS ? src_row[r0] : r0) * ldx + aq * 8;
     auto load_x = [&](auto set_tag) __attribute__((always_inline)) {
         constexpr int S = decltype(set_tag)::value;
         const int k = lks * WD_BK + aq * 8;
@@ -73,7 +77,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         if (++lks == ksteps) {                                         // (uniform) on to the next block of this workgroup; past the last: clamped rows, never used
             lks = 0;
             lb += stride;
-            xrow = X + (int64_t)min((int64_t)lb * WD_BM + arow, (int64_t)M - 1) * ldx + aq * 8;
+            const int64_t r = min((int64_t)lb * WD_BM + arow, (int64_t)M - 1);
+            xrow = X + (ROWS ? (int64_t)src_row[r] : r) * ldx + aq * 8;
         }
     };
     // ---- weight tiles: the two column blocks of a half, one half-step ahead in registers
@@ -252,35 +257,53 @@ extern "C" int dfol_linear_wide_supported(int64_t M, int32_t N, int32_t K) {
     return on == 2 || 4 * blocks >= 3 * rounds * wd_cus();
 }
 
+// one launch path for both forms: src_row == nullptr is the plain product over X's own rows
+static int wd_launch(const char* name, const float* X, int64_t ldx, const int32_t* src_row, const void* W_split, const float* bias, float* Y, int64_t ldy,
+                     int32_t M, int32_t N, int32_t K, int32_t act, void* stream);
+
 extern "C" int dfol_linear_wide_h2_f32(const float* X, int64_t ldx, const void* W_split, const float* bias, float* Y, int64_t ldy, int32_t M, int32_t N,
                                        int32_t K, int32_t act, void* stream) {
+    return wd_launch("linear_wide_h2", X, ldx, nullptr, W_split, bias, Y, ldy, M, N, K, act, stream);
+}
+
+extern "C" int dfol_linear_wide_rows_h2_f32(const float* X_table, int64_t ld_table, const int32_t* src_row, const void* W_split, const float* bias,
+                                            float* Y, int64_t ldy, int32_t M, int32_t N, int32_t K, int32_t act, void* stream) {
+    DFOL_REQUIRE(src_row, "linear_wide_rows_h2: null pointer");
+    return wd_launch("linear_wide_rows_h2", X_table, ld_table, src_row, W_split, bias, Y, ldy, M, N, K, act, stream);
+}
+
+static int wd_launch(const char* name, const float* X, int64_t ldx, const int32_t* src_row, const void* W_split, const float* bias, float* Y, int64_t ldy,
+                     int32_t M, int32_t N, int32_t K, int32_t act, void* stream) {
     DFOL_REQUIRE(M > 0 && N > 256 && N <= WD_NMAX && K >= 4 * WD_BK && K % 4 == 0 && ldx % 2 == 0 && ldx >= K && ldy >= N,
-                 "linear_wide_h2: bad sizes M=%d N=%d K=%d (256 < N <= 512, K >= 128, K %% 4, ldx %% 2)", M, N, K);
-    DFOL_REQUIRE(X && W_split && Y, "linear_wide_h2: null pointer");
-    DFOL_REQUIRE(((uintptr_t)X % 8 == 0) && ((uintptr_t)W_split % 16 == 0), "linear_wide_h2: X must be 8-byte and W_split 16-byte aligned");
+                 "%s: bad sizes M=%d N=%d K=%d (256 < N <= 512, K >= 128, K %% 4, ldx %% 2)", name, M, N, K);
+    DFOL_REQUIRE(X && W_split && Y, "%s: null pointer", name);
+    DFOL_REQUIRE(((uintptr_t)X % 8 == 0) && ((uintptr_t)W_split % 16 == 0), "%s: X must be 8-byte and W_split 16-byte aligned", name);
     const bool x16 = (uintptr_t)X % 16 == 0 && ldx % 4 == 0;
     const int ksteps = dfol_cdiv(K, WD_BK), nbn = dfol_cdiv(N, 128);
     const int grid = std::min(dfol_cdiv(M, WD_BM), wd_cus());
     uint32_t* status = dfol_range_status_ptr();
     hipStream_t st = (hipStream_t)stream;
-#define DFOL_WD_K(A, XVV)                                                                                                                   \
+#define DFOL_WD_K(A, XVV, R)                                                                                                                \
     {                                                                                                                                      \
-        static const hipError_t ok = hipFuncSetAttribute((const void*)wide_h2_kernel<A, XVV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WD_LDS); \
-        DFOL_REQUIRE(ok == hipSuccess, "linear_wide_h2: cannot reserve %zu bytes of LDS (%s)", WD_LDS, hipGetErrorString(ok));              \
-        hipLaunchKernelGGL((wide_h2_kernel<A, XVV>), dim3(grid), dim3(512), WD_LDS, st, X, ldx, (const u32x4*)W_split, bias, Y, ldy, M, N, K, ksteps, \
-                           nbn, status);                                                                                                   \
+        static const hipError_t ok = hipFuncSetAttribute((const void*)wide_h2_kernel<A, XVV, R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WD_LDS); \
+        DFOL_REQUIRE(ok == hipSuccess, "%s: cannot reserve %zu bytes of LDS (%s)", name, WD_LDS, hipGetErrorString(ok));                    \
+        hipLaunchKernelGGL((wide_h2_kernel<A, XVV, R>), dim3(grid), dim3(512), WD_LDS, st, X, ldx, (const u32x4*)W_split, bias, Y, ldy, M, N, K, ksteps, \
+                           nbn, status, src_row);                                                                                          \
     }
+#define DFOL_WD_X(A, R)                                                                                                                     \
+    if (x16) DFOL_WD_K(A, 4, R) else DFOL_WD_K(A, 2, R)
 #define DFOL_WD(A)                                                                                                                          \
-    if (x16) DFOL_WD_K(A, 4) else DFOL_WD_K(A, 2)
+    if (src_row) { DFOL_WD_X(A, true) } else { DFOL_WD_X(A, false) }
     switch (act) {
         case DFOL_ACT_NONE: DFOL_WD(DFOL_ACT_NONE); break;
         case DFOL_ACT_SIGMOID: DFOL_WD(DFOL_ACT_SIGMOID); break;
         case DFOL_ACT_ELU: DFOL_WD(DFOL_ACT_ELU); break;
         case DFOL_ACT_LOGSIGMOID: DFOL_WD(DFOL_ACT_LOGSIGMOID); break;
-        default: DFOL_REQUIRE(false, "linear_wide_h2: unknown activation %d", act);
+        default: DFOL_REQUIRE(false, "%s: unknown activation %d", name, act);
     }
 #undef DFOL_WD
+#undef DFOL_WD_X
 #undef DFOL_WD_K
-    DFOL_LAUNCH_CHECK("linear_wide_h2");
+    DFOL_LAUNCH_CHECK(name);
     return 0;
 }

@@ -112,12 +112,27 @@ int run_dense(const DfolDenseLayer& L, const float* X, int64_t ldx, float* Y, in
     return 1;
 }
 
+// dfol_set_feature_rows: the index form of the NEXT dfol_run_program's scene on this thread
+thread_local const int32_t* g_feature_src_row = nullptr;
+thread_local const float* g_feature_box6 = nullptr;
+
 }  // namespace
+
+extern "C" int dfol_set_feature_rows(const int32_t* src_row, const float* box6) {
+    DFOL_REQUIRE((src_row == nullptr) == (box6 == nullptr), "set_feature_rows: src_row and box6 come together");
+    g_feature_src_row = src_row;
+    g_feature_box6 = box6;
+    return 0;
+}
 
 extern "C" int dfol_calib_walk_supported(int32_t KX, int32_t H) { return lc_walk_fits(KX, H) ? 1 : 0; }
 
 extern "C" int dfol_run_program(const DfolProgramModel* model, const DfolProgramScene* scene, const int64_t* instr_host, int32_t n_instr,
                                 const void* blob, void* workspace, void* stream) {
+    const int32_t* src_row = g_feature_src_row;                      // (taken and cleared first: an early return must not leave it to the next batch)
+    const float* box6 = g_feature_box6;
+    g_feature_src_row = nullptr;
+    g_feature_box6 = nullptr;
     DFOL_REQUIRE(model && scene && instr_host && blob && workspace, "run_program: null pointer");
     DFOL_REQUIRE(n_instr >= 0 && scene->NS > 0 && scene->NS % 4 == 0, "run_program: bad sizes (n_instr %d, NS %d)", n_instr, scene->NS);
     const int32_t NS = scene->NS;
@@ -136,10 +151,23 @@ extern "C" int dfol_run_program(const DfolProgramModel* model, const DfolProgram
                 const float* X = a[3] == 0 ? scene->features + a[4] / 4 : static_cast<const float*>(at(workspace, a[4]));
                 DfolDenseLayer layer = layers[a[2]];
                 if (a[9]) layer.act = DFOL_ACT_NONE;
+                if (a[3] == 0 && src_row != nullptr) {              // the scene in index form: the featurizer's first product reads the store's rows
+                    const int32_t M = static_cast<int32_t>(a[8]);
+                    DFOL_REQUIRE(a[4] == 0 && layer.kind == DFOL_DENSE_F16X2 && layer.packed != nullptr && dfol_linear_wide_supported(M, layer.N, layer.K),
+                                 "run_program[%d]: a scene in index form (dfol_set_feature_rows) needs a two-piece fp16 product of a shape "
+                                 "dfol_linear_wide_supported takes (M %d N %d K %d kind %d): hand over the gathered matrix", i, M, layer.N, layer.K, layer.kind);
+                    rc = dfol_linear_wide_rows_h2_f32(scene->features, scene->ld_features, src_row, layer.packed, layer.bias,
+                                                      static_cast<float*>(at(workspace, a[6])), a[7], M, layer.N, layer.K, layer.act, stream);
+                    break;
+                }
                 rc = run_dense(layer, X, a[3] == 0 ? scene->ld_features : a[5], static_cast<float*>(at(workspace, a[6])), a[7], static_cast<int32_t>(a[8]), stream);
                 break;
             }
             case DFOL_OP_BOX_POSITIONS:  // obj, ld_obj, pos_col
+                if (box6 != nullptr) {                              // (index form: the six box columns travel beside the row numbers)
+                    rc = dfol_box_positions_f32(box6, 6, 6, scene->O, static_cast<float*>(at(workspace, a[1])), a[2], static_cast<int32_t>(a[3]), stream);
+                    break;
+                }
                 rc = dfol_box_positions_f32(scene->features, scene->ld_features, scene->raw_cols, scene->O, static_cast<float*>(at(workspace, a[1])), a[2],
                                             static_cast<int32_t>(a[3]), stream);
                 break;

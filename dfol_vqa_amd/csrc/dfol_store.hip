@@ -1,4 +1,4 @@
-// The device-resident object-feature store's one kernel (dfol_vqa_amd/feature_store.py): the [O, F + 6] object matrix of a batch, which
+// The device-resident object-feature store's kernels (dfol_vqa_amd/feature_store.py).  The gather: the [O, F + 6] object matrix of a batch, which
 // BatchGQABoxFeaturesCollator.collate_object_features builds on the host from the chunk files and ships over PCIe (822 KB per question at
 // 100 objects x 2048 features), written on the device from a store that holds the corpus' features, boxes and image sizes.
 //
@@ -8,6 +8,9 @@
 // lane.  Output rows have a stride of F + 6 floats, so they are 16-byte aligned at best every other row: the store width (16, 8 or 4 bytes)
 // follows the row's actual address, which is uniform over the wavefront.  The two subtractions are single fp32 subtractions, as numpy's on
 // the host, so the matrix is bit-equal to the collator's.  No LDS, no atomics.
+//
+// The index form (a `direct` store): the same batch as O row numbers into the store's [S * max_obj, F] table and its six box columns - 28 bytes
+// per object instead of 4 (F + 6) - for the consumer that reads the table's rows itself (dfol_linear_wide_rows_h2_f32).
 #include "dfol_common.h"
 
 namespace {
@@ -81,7 +84,43 @@ __global__ __launch_bounds__(ST_WAVES * 64) void gather_object_rows_kernel(const
     }
 }
 
+// grid (I, row slices of SR_THREADS): thread (i, j) writes row obj_off[i] + j - its table row and (W, H, x1, y1, x2 - x1, y2 - y1), the gather's own
+// six values by the gather's own subtractions
+constexpr int SR_THREADS = 128;
+
+__global__ __launch_bounds__(SR_THREADS) void store_rows_kernel(const float* __restrict__ boxes, const float* __restrict__ sizes,
+                                                                const int32_t* __restrict__ slot, const int32_t* __restrict__ obj_off, int max_obj,
+                                                                int32_t* __restrict__ src_row, float* __restrict__ box6) {
+    const int i = blockIdx.x, j = blockIdx.y * SR_THREADS + threadIdx.x;
+    const int first = obj_off[i];
+    const int n = min(obj_off[i + 1] - first, max_obj);              // (an image has at most max_obj rows in the store)
+    if (j >= n) return;
+    const int s = slot[i];
+    const int64_t row = (int64_t)s * max_obj + j;                    // (< 2^31: the host checked S * max_obj)
+    const float* b = boxes + row * 4;
+    const float x1 = b[0], y1 = b[1], x2 = b[2], y2 = b[3];
+    src_row[first + j] = (int32_t)row;
+    float* d = box6 + (int64_t)(first + j) * 6;
+    d[0] = sizes[2 * (int64_t)s], d[1] = sizes[2 * (int64_t)s + 1];
+    d[2] = x1, d[3] = y1, d[4] = x2 - x1, d[5] = y2 - y1;
+}
+
 }  // namespace
+
+extern "C" int dfol_store_rows_f32(const float* store_boxes, const float* store_sizes, const int32_t* slot, const int32_t* obj_off, int32_t I, int32_t S,
+                                   int32_t max_obj, int32_t* src_row, float* box6, void* stream) {
+    DFOL_REQUIRE(I >= 0 && S > 0 && max_obj > 0, "store_rows: bad sizes I=%d S=%d max_obj=%d", I, S, max_obj);
+    DFOL_REQUIRE((int64_t)S * max_obj < (1ll << 31), "store_rows: S * max_obj = %lld rows do not fit the int32 row numbers (< 2^31)",
+                 (long long)S * max_obj);
+    if (I == 0) return 0;
+    DFOL_REQUIRE(store_boxes && store_sizes && slot && obj_off && src_row && box6, "store_rows: null pointer");
+    const int slices = dfol_cdiv(max_obj, SR_THREADS);
+    DFOL_REQUIRE(slices <= 65535, "store_rows: max_obj=%d is more than a launch's %d rows per image", max_obj, 65535 * SR_THREADS);
+    hipLaunchKernelGGL(store_rows_kernel, dim3(I, slices), dim3(SR_THREADS), 0, (hipStream_t)stream, store_boxes, store_sizes, slot, obj_off, max_obj,
+                       src_row, box6);
+    DFOL_LAUNCH_CHECK("store_rows");
+    return 0;
+}
 
 extern "C" int dfol_gather_object_rows_f32(const float* store_features, const float* store_boxes, const float* store_sizes, const int32_t* slot,
                                            const int32_t* obj_off, int32_t I, int32_t max_obj, int32_t F, float* out, int64_t ld_out,

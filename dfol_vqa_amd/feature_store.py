@@ -6,6 +6,10 @@ which binds a stream of unseen batches to PCIe.  The store holds the chunk files
 device instead - the whole GQA corpus is ~122 GB of fp32, one MI355X has 288 GB - and a batch carries only an `ObjectFeatureRef`: the store
 slot and object count of each of its images.  `ProgramBatch.to_cuda` resolves the ref into the same `[O, F + 6]` matrix, bit for bit.
 
+A store built with `direct=True` resolves a ref into a `StoreRows` instead: the row numbers of the batch in the store's own table and its
+six box columns (28 bytes per object).  The featurizer's first product then reads the table through the row numbers
+(csrc/dfol_dense_wide.hip, ROWS) and the `[O, F + 6]` matrix is never written; whoever needs the matrix calls `StoreRows.materialize()`.
+
 Three kinds of object, by who may hold them:
   DeviceFeatureStore   main process only: the device tensors, `gather`.  Registers itself by id in this process' table.
   FeatureStoreIndex    `store.index`: host-only and picklable, image id -> (slot or -1, object count).  This is what a collator - and so
@@ -46,6 +50,15 @@ class ObjectFeatureRef(object):
             raise _lib.DfolError("feature store: %d object rows in one batch" % off[-1])
         return np.concatenate([self.slots, off.astype(np.int32)])
 
+    def source_rows(self, max_obj):
+        """[O] int32: the store-table row (slot * max_obj + j) behind every object row of the batch, images in the ref's order - what
+        dfol_store_rows_f32 writes on the device, restated on the host."""
+        check_row_space(int(self.slots.max()) + 1 if len(self.slots) else 1, max_obj)
+        counts = np.minimum(self.counts.astype(np.int64), int(max_obj))
+        first = np.repeat(self.slots.astype(np.int64) * int(max_obj), counts)
+        within = np.arange(int(counts.sum()), dtype=np.int64) - np.repeat(np.cumsum(counts) - counts, counts)
+        return (first + within).astype(np.int32)
+
     def pin_memory(self):
         self._pinned = torch.from_numpy(self.index_array()).pin_memory()
         return self
@@ -56,6 +69,13 @@ class ObjectFeatureRef(object):
     def __setstate__(self, state):
         self.store_id, self.slots, self.counts = state
         self._pinned = None
+
+
+def check_row_space(S, max_obj):
+    """The index form names a store row by ONE int32 (slot * max_obj + j): a store of 2^31 rows or more is refused, as the kernel's host does."""
+    if int(S) * int(max_obj) >= 2 ** 31:
+        raise _lib.DfolError("feature store: S * max_obj = %d x %d rows do not fit int32 row numbers (< 2^31); build the store without direct=True"
+                             % (int(S), int(max_obj)))
 
 
 class FeatureStoreIndex(object):
@@ -151,9 +171,13 @@ class DeviceFeatureStore(object):
 
     max_bytes=None: the whole corpus, which must fit in 80 % of the device memory that is free now - otherwise DfolError, nothing is
     allocated.  max_bytes=N: whole chunks in file order for as long as they fit in N bytes; batches that name an image of a later chunk
-    take the host route (FeatureStoreIndex.ref -> None)."""
+    take the host route (FeatureStoreIndex.ref -> None).
 
-    def __init__(self, object_h5_path, file_prefix, chunk_num, object_info_json_path, device, max_bytes=None):
+    direct=True (opt-in; recorded on the store only - index, refs and collators are the same): `resolve`, i.e. ProgramBatch.to_cuda, hands the
+    batch on as a StoreRows (`rows`) and the featurizer reads the store's rows in place where its first product is one the wide kernel takes;
+    every other consumer materialises the matrix as before."""
+
+    def __init__(self, object_h5_path, file_prefix, chunk_num, object_info_json_path, device, max_bytes=None, direct=False):
         from .data import _open_arrays
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -179,6 +203,9 @@ class DeviceFeatureStore(object):
                 arrays.close()
         self.sizes = torch.from_numpy(sizes).to(self.device)
         self.S, self.max_obj, self.F = S, max_obj, F
+        self.direct = bool(direct)
+        if self.direct:
+            check_row_space(S, max_obj)
         self.nbytes = S * lay.row_bytes
         self.resident_chunks = len(base) - 1
         _STORES[self.id] = self
@@ -231,12 +258,78 @@ class DeviceFeatureStore(object):
         return out
 
 
+    def rows(self, ref, out=None, index=None):
+        """The batch in index form -> StoreRows (src_row [O] int32, box6 [O, 6], this store's table), one small launch on the current stream.
+        out=: an existing StoreRows of this store with the same image and object counts, rewritten in place - how the owner of a captured forward
+        serves a new scene BETWEEN replays: like upload_index, not inside a stream capture.  index=: an earlier upload_index(ref)."""
+        check_row_space(self.S, self.max_obj)
+        O, I = int(ref.counts.sum(dtype=np.int64)), len(ref.slots)
+        idx = self.upload_index(ref) if index is None else index
+        if idx.numel() != 2 * I + 1:
+            raise _lib.DfolError("feature store: index= is not this ref's")
+        if out is None:
+            out = StoreRows(self, torch.empty(O, dtype=torch.int32, device=self.device), torch.empty((O, 6), dtype=torch.float32, device=self.device), idx)
+        else:
+            if not isinstance(out, StoreRows) or out.store is not self or out._index is None or out.O != O or out._index.numel() != 2 * I + 1:
+                raise _lib.DfolError("feature store: out= must be a StoreRows of this store with %d images and %d objects" % (I, O))
+            if torch.cuda.is_current_stream_capturing():
+                raise _lib.DfolError("feature store: rows(out=) rewrites a captured batch's rows and cannot run inside a stream capture; "
+                                     "call it between replays")
+            out._index.copy_(idx)                      # (materialize() gathers through it)
+        if O:
+            with torch.cuda.device(self.device):
+                _lib.store_rows(self.boxes, self.sizes, idx[:I], idx[I:], out.src_row, out.box6)
+        return out
+
+
+class StoreRows(object):
+    """A batch's objects as rows of a `direct` store: `src_row` [O] int32 rows of `table` (the store's features viewed as [S * max_obj, F]) and
+    `box6` [O, 6] = (W, H, x, y, w, h), the matrix's last six columns.  Stands where the `[O, F + 6]` matrix stood in a ProgramBatch: it has its
+    shape, device and dtype for the size checks, and `materialize()` for every consumer that needs the tensor."""
+
+    def __init__(self, store, src_row, box6, index, parent=None, picked=None):
+        self.store, self.src_row, self.box6 = store, src_row, box6
+        self.table = store.features.view(store.S * store.max_obj, store.F)
+        self.O = int(src_row.numel())
+        self._index = index                                # device [slot (I) | obj_off (I + 1)] of the ref, or None: a selection of `parent`'s rows
+        self._parent, self._picked = parent, picked
+
+    shape = property(lambda self: (self.O, self.store.F + 6))
+    device = property(lambda self: self.store.device)
+    dtype = torch.float32
+    is_cuda = True
+
+    def size(self, dim=None):
+        return torch.Size(self.shape) if dim is None else self.shape[dim]
+
+    def materialize(self, out=None):
+        """The `[O, F + 6]` matrix, bit for bit `store.gather(ref)` (the same kernel through the same index arrays)."""
+        st = self.store
+        if self._index is None:                            # selected rows: the parent's matrix, then the selection - what build_scene did before
+            m = self._parent.materialize().index_select(0, self._picked)
+            return m if out is None else out.copy_(m)
+        if out is None:
+            out = torch.empty((self.O, st.F + 6), dtype=torch.float32, device=st.device)
+        elif out.dim() != 2 or out.shape[0] != self.O or out.shape[1] < st.F + 6 or out.device != st.device:
+            raise _lib.DfolError("feature store: out= must be [%d, >= %d] on %s, got %s on %s" % (self.O, st.F + 6, st.device, tuple(out.shape), out.device))
+        I = (self._index.numel() - 1) // 2
+        if self.O:
+            with torch.cuda.device(st.device):
+                _lib.gather_object_rows(st.features, st.boxes, st.sizes, self._index[:I], self._index[I:], out)
+        return out
+
+    def select_rows(self, rows):
+        """The StoreRows of rows `rows` (int64 device tensor, repeats allowed) of this one: the two small arrays composed, no feature row moved."""
+        return StoreRows(self.store, self.src_row.index_select(0, rows), self.box6.index_select(0, rows), None, parent=self, picked=rows)
+
+
 def resolve(ref, device):
-    """ProgramBatch.to_cuda's step: the ref's matrix from the store registered under its id in this process."""
+    """ProgramBatch.to_cuda's step: the ref's matrix - or, from a `direct` store, its StoreRows - from the store registered under its id in this
+    process."""
     store = _STORES.get(ref.store_id)
     if store is None:
         raise _lib.DfolError("no feature store %s in this process (a store serves the process that built it)" % ref.store_id)
     dev = torch.device(device)
     if dev.type != "cuda" or (dev.index is not None and dev.index != store.device.index):
         raise _lib.DfolError("feature store %s lives on %s, the batch goes to %s" % (ref.store_id, store.device, device))
-    return store.gather(ref)
+    return store.rows(ref) if store.direct else store.gather(ref)

@@ -42,7 +42,46 @@ class BatchGQABoxFeaturizer(nn.Module):
         super(BatchGQABoxFeaturizer, self).__init__()
         self._featurizer_network = featurizer_network
 
+    def _store_layers(self, rows):
+        """The featurizer's layers [(Linear, activation)] when its FIRST product can read a direct feature store's rows in place (a StoreRows):
+        inference, the two-piece fp16 arithmetic on a weight of the split kernels' size, the store's feature width, and a shape the wide kernel
+        takes and pays for (dfol_linear_wide_supported - the same question the tiled kernel asks before it forwards there, so either route runs
+        the same kernel body on the same rows).  None: the caller materialises the matrix and goes on as ever."""
+        from . import _lib, native_exec
+        net = self._featurizer_network
+        if net is None or getattr(net, "_network", None) is None or not hasattr(net, "output_width") or rows.O == 0:
+            return None
+        if torch.is_grad_enabled() and any(p.requires_grad for p in net.parameters()):
+            return None
+        layers = native_exec._layers(net._network)
+        if not layers or _lib._dense_math() != "f16x2":
+            return None
+        w = layers[0][0].weight
+        N, K = w.shape
+        if N * K < _lib.SPLIT_MIN_WEIGHT or w.stride(1) != 1 or K != rows.store.F or not _lib.linear_wide_supported(rows.O, N, K):
+            return None
+        return layers
+
     def featurize_scene(self, device, objects_list, batch_index, meta_data, world_geometry=None):
+        from . import _lib
+        from .feature_store import StoreRows
+        if isinstance(objects_list, StoreRows):
+            layers = self._store_layers(objects_list)
+            if layers is not None:
+                # the index form of a store-backed batch: the first product gathers the store's rows through src_row, the rest is as below
+                rows, net = objects_list, self._featurizer_network
+                D = net.output_width() + 4
+                obj = torch.empty(rows.O, D, dtype=torch.float32, device=device)
+                x = None
+                for k, (lin, act) in enumerate(layers):
+                    out = obj[:, :D - 4] if k == len(layers) - 1 else None
+                    x = _lib.linear_wide_rows(rows.table, rows.src_row, lin.weight, lin.bias, act, out) if k == 0 else \
+                        L.linear_act(x, lin.weight, lin.bias, act, out)
+                L.box_positions(rows.box6, obj, D - 4)
+                _lib.note("feature_store_direct")
+                return self._with_pairs(obj, D, rows.O, world_geometry)
+            objects_list = objects_list.materialize()             # training, another arithmetic, a narrow first layer, a small batch: the matrix
+            _lib.note("feature_store_direct_materialized")
         object_num = objects_list.size()[0]
         raw_cols = objects_list.size()[1]
         feat = objects_list[:, :raw_cols - 6]                    # a strided view: the GEMM reads it in place
@@ -60,6 +99,9 @@ class BatchGQABoxFeaturizer(nn.Module):
             obj = torch.empty(object_num, D, dtype=torch.float32, device=device)
             obj[:, :D - 4] = f
         L.box_positions(objects_list, obj, D - 4)                # :208-211
+        return self._with_pairs(obj, D, object_num, world_geometry)
+
+    def _with_pairs(self, obj, D, object_num, world_geometry):
         geo = world_geometry
         pair = None
         if geo is not None and geo._pair_num > 0:
@@ -279,7 +321,8 @@ class BatchInterpreterBase(nn.Module):
                 object_nums = torch.bincount(bi.to(torch.int64).cpu()).tolist()
             off = np.concatenate([[0], np.cumsum(object_nums)])
             rows = np.concatenate([np.arange(off[i], off[i + 1]) for i in question_image]) if len(question_image) else np.zeros(0, np.int64)
-            object_features = object_features.index_select(0, torch.as_tensor(rows, dtype=torch.int64).to(object_features.device))
+            rows = torch.as_tensor(rows, dtype=torch.int64).to(object_features.device)
+            object_features = object_features.select_rows(rows) if hasattr(object_features, "select_rows") else object_features.index_select(0, rows)
             object_nums = [int(object_nums[i]) for i in question_image]
             batch_index = torch.as_tensor(np.repeat(np.arange(len(object_nums)), object_nums).astype(np.int64)).to(object_features.device)
             question_image = None
@@ -373,7 +416,8 @@ class BatchInterpreterBase(nn.Module):
         device = program_batch_list[0].device
         spec = self._native_spec(is_training, modulator_switch, return_trace)
         for program_batch in program_batch_list:
-            if spec is not None and isinstance(program_batch._object_features, torch.Tensor) and program_batch._object_features.is_cuda:
+            feats = program_batch._object_features
+            if spec is not None and (isinstance(feats, torch.Tensor) or hasattr(feats, "materialize")) and feats.is_cuda:
                 from . import gqa_ops, native_exec
                 plan = native_exec.plan_for(self, program_batch, spec)
                 if plan is not None:

@@ -284,9 +284,24 @@ def run(model, program_batch, plan, queue, give_answer=True):
     """Enqueue the batch; -> the result dict, its answers filled by a closure appended to `queue` (the interpreter's deferred read-back)."""
     feats = program_batch._object_features
     device = feats.device
-    if feats.dtype != torch.float32 or feats.stride(1) != 1 or feats.shape[0] != plan.scene["O"]:
-        raise _lib.DfolError("native executor: object features must be fp32 rows, one per object of the batch")
     nm = native_model(model)
+    rows = None
+    if hasattr(feats, "materialize"):
+        # A direct feature store's batch (feature_store.StoreRows).  The plan is lowered as for any batch; where the featurizer's first product
+        # is one the wide kernel takes - the question BatchGQABoxFeaturizer._store_layers asks - the executor reads the store's rows in place
+        # (dfol_set_feature_rows), otherwise it gets the gathered matrix.
+        first = nm.struct.featurizer[0]
+        if feats.O and first.kind == DENSE_F16X2 and first.K == feats.store.F and _lib.linear_wide_supported(feats.O, first.N, first.K):
+            rows = feats
+            _lib.note("feature_store_direct")
+        else:
+            feats = feats.materialize()
+            _lib.note("feature_store_direct_materialized")
+    if rows is not None:
+        if rows.O != plan.scene["O"]:
+            raise _lib.DfolError("native executor: object features must be fp32 rows, one per object of the batch")
+    elif feats.dtype != torch.float32 or feats.stride(1) != 1 or feats.shape[0] != plan.scene["O"]:
+        raise _lib.DfolError("native executor: object features must be fp32 rows, one per object of the batch")
     if feats.shape[1] - 6 != nm.struct.featurizer[0].K:
         raise _lib.DfolError("native executor: feature width %d does not match the featurizer (%d + 6)" % (feats.shape[1], nm.struct.featurizer[0].K))
     blob = blob_on(plan, device)
@@ -295,7 +310,11 @@ def run(model, program_batch, plan, queue, give_answer=True):
     gran = (1 << 25) if plan.ws_bytes >= (1 << 25) else (1 << 20)
     ws = torch.empty((plan.ws_bytes + gran - 1) // gran * gran, dtype=torch.uint8, device=device)
     sc = ProgramScene()
-    sc.features, sc.ld_features, sc.raw_cols, sc.O = feats.data_ptr(), feats.stride(0), feats.shape[1], plan.scene["O"]
+    if rows is not None:
+        sc.features, sc.ld_features, sc.raw_cols, sc.O = rows.table.data_ptr(), rows.table.stride(0), rows.shape[1], plan.scene["O"]
+        _lib.call("dfol_set_feature_rows", rows.src_row.data_ptr(), rows.box6.data_ptr())        # (picked up, and cleared, by the call below)
+    else:
+        sc.features, sc.ld_features, sc.raw_cols, sc.O = feats.data_ptr(), feats.stride(0), feats.shape[1], plan.scene["O"]
     sc.NS, sc.max_n = plan.scene["NS"], plan.scene["max_n"]
     sc.n_obj, sc.img_n_obj, sc.obj_off = plan.scene["n_obj"], plan.scene["img_n_obj"], plan.scene["obj_off"]
     instrs = plan.instrs

@@ -44,7 +44,8 @@ extern "C" {
  * change, a struct whose layout changes.  Pure additions keep it: dfol_attr_head_h2_f32, DFOL_OP_ATTR_HEAD, DFOL_DENSE_HEAD_F16X2 and the ninth
  * operand of DFOL_OP_DENSE (a slot that instruction tables written before it hold as zero = the layer's own activation) were added under 3,
  * and so were dfol_pair_ll_h1_f32, dfol_pair_pack_w2_f16, dfol_pair_w2_f16_bytes and DFOL_PAIR_F16 (an older library refuses the kind) and
- * dfol_gather_object_rows_f32, and the two size queries dfol_lstm_cell_supported and dfol_calib_walk_supported;
+ * dfol_gather_object_rows_f32, and the two size queries dfol_lstm_cell_supported and dfol_calib_walk_supported, and the index form of a store-backed
+ * batch: dfol_store_rows_f32, dfol_linear_wide_rows_h2_f32 and dfol_set_feature_rows (no struct and no instruction table changes for it);
  * a caller that needs them checks for the symbol, and a table that names an opcode an older library lacks is refused by it ("unknown opcode"). */
 #define DFOL_ABI_VERSION 3
 
@@ -220,6 +221,14 @@ int dfol_gather_rows_f32(const float* src, const int32_t* idx, int32_t P, int32_
 int dfol_gather_object_rows_f32(const float* store_features, const float* store_boxes, const float* store_sizes, const int32_t* slot,
                                 const int32_t* obj_off, int32_t I, int32_t max_obj, int32_t F, float* out, int64_t ld_out, void* stream);
 
+/* The same batch in INDEX form (a store built with direct=True): instead of the matrix, which of the store's rows it is made of, for a consumer
+ * that reads the store's [S * max_obj, F] table itself (dfol_linear_wide_rows_h2_f32) - 28 bytes per object instead of 4 (F + 6).
+ *   src_row [O] int32  src_row[obj_off[i] + j] = slot[i] * max_obj + j                                0 <= j < obj_off[i + 1] - obj_off[i]
+ *   box6    [O, 6]     (W, H, x1, y1, x2 - x1, y2 - y1): bit for bit the last six columns dfol_gather_object_rows_f32 writes
+ * slot / obj_off / the row limit max_obj as there; S * max_obj < 2^31 (refused otherwise); I == 0 returns without a launch. */
+int dfol_store_rows_f32(const float* store_boxes, const float* store_sizes, const int32_t* slot, const int32_t* obj_off, int32_t I, int32_t S,
+                        int32_t max_obj, int32_t* src_row, float* box6, void* stream);
+
 /* Segmented row sum: out[q][:] = sum_{p in seg q} src[p][:]   (mm(pqm^T, X), batch_gqa_ops.py:457). */
 int dfol_segment_sum_rows_f32(const float* src, const int32_t* seg_off, int32_t Q, int32_t width, float* out,
                               void* stream);
@@ -288,6 +297,13 @@ int dfol_linear_act_h2_f32(const float* X, int64_t ldx, const void* W_split, con
 int dfol_linear_wide_supported(int64_t M, int32_t N, int32_t K);
 int dfol_linear_wide_h2_f32(const float* X, int64_t ldx, const void* W_split, const float* bias, float* Y, int64_t ldy, int32_t M,
                             int32_t N, int32_t K, int32_t act, void* stream);
+/* The wide product over INDEXED rows: row r of the product is row src_row[r] of X_table ([rows, ld_table], K used; src_row [M] int32 from
+ * dfol_store_rows_f32, every entry a row of the table - not checked, a device array).  The same kernel with the row's address formed through
+ * the index (read once per 128-row block, not per k-step): results - and the DFOL_RANGE_X_OVERFLOW report, which covers the indexed rows
+ * only - are bit for bit those of dfol_linear_wide_h2_f32 over the gathered matrix.  Limits as dfol_linear_wide_h2_f32, on X_table / ld_table;
+ * it takes every M (the caller asks dfol_linear_wide_supported whether the shape pays). */
+int dfol_linear_wide_rows_h2_f32(const float* X_table, int64_t ld_table, const int32_t* src_row, const void* W_split, const float* bias, float* Y,
+                                 int64_t ldy, int32_t M, int32_t N, int32_t K, int32_t act, void* stream);
 
 /* The bf16 mode of the same kernel (BASELINE configs[3] "bf16 fwd / fp32 logic"; config key `mlp_math: bf16`): both operands rounded to
  * bf16 (nearest even), ONE product per operand pair, fp32 accumulation, fp32 output.  NOT the reference's numerics (relative error
@@ -864,6 +880,12 @@ typedef struct {            /* the scenes of one ProgramBatch (data_pipeline.py:
 #define DFOL_WALK_ATT_MODULATIONS 4 /* forward state h, backward state h, out [rows, att_out_n] */
 
 int dfol_calib_walk_supported(int32_t KX, int32_t H); /* 1 / 0: DFOL_OP_CALIB_WALK takes a calibrator of input width KX and state width H */
+/* The NEXT dfol_run_program of the calling thread reads its scene in index form (a thread-local setting like dfol_set_range_status, cleared by that
+ * call whether it succeeds or not; NULL, NULL clears it): scene->features / ld_features describe the feature store's [S * max_obj, K] table
+ * (raw_cols is ignored), src_row [O] and box6 [O, 6] are dfol_store_rows_f32's.  The source-0 DFOL_OP_DENSE runs dfol_linear_wide_rows_h2_f32 - it
+ * must be a DFOL_DENSE_F16X2 layer of a shape dfol_linear_wide_supported(O, N, K) takes: the caller asks that first and hands over the gathered
+ * matrix otherwise; any other source-0 product is refused - and DFOL_OP_BOX_POSITIONS reads box6.  Plans are lowered as ever. */
+int dfol_set_feature_rows(const int32_t* src_row, const float* box6);
 int dfol_run_program(const DfolProgramModel* model, const DfolProgramScene* scene, const int64_t* instr_host, int32_t n_instr,
                      const void* blob, void* workspace, void* stream);
 

@@ -3,14 +3,17 @@
 
 Synthetic chunk files in the collator's layout (default 2048 images x 100 objects x 2048 features, .npz, in a temporary directory), then a
 stream of unseen 256-question batches - DataLoader workers collate and lower them to plans, this process uploads, launches the native
-executor and decodes the answers - with the object features arriving three ways:
+executor and decodes the answers - with the object features arriving four ways:
 
-  pool    already on the device (a pool of two feature sets, `value_fresh_programs`'s form): the upper bound
-  store   an ObjectFeatureRef per batch, gathered from the store by ProgramBatch.to_cuda
-  host    today's route: the worker builds [O, F + 6] from the chunk files, the matrix travels to this process, is pinned and uploaded
+  pool          already on the device (a pool of two feature sets, `value_fresh_programs`'s form): the upper bound
+  store         an ObjectFeatureRef per batch, gathered from the store by ProgramBatch.to_cuda
+  store_direct  the same refs and workers with the store in its index form (`direct=True`): to_cuda writes row numbers and box columns, the
+                featurizer's first product reads the store's rows in place (csrc/dfol_dense_wide.hip, ROWS) - no [O, F + 6] matrix
+  host          today's route: the worker builds [O, F + 6] from the chunk files, the matrix travels to this process, is pinned and uploaded
 
 The legs alternate in one process, `--runs` runs each (a difference counts only when the ranges are apart).  The gather kernel
-alone is timed by HIP events beside a device-to-device copy_ of the same byte count.  Prints one JSON line.
+alone is timed by HIP events beside a device-to-device copy_ of the same byte count, and the featurizer's first product both ways: gather +
+dfol_linear_wide_h2_f32 against dfol_store_rows_f32 + dfol_linear_wide_rows_h2_f32, alternating.  Prints one JSON line.
 
 usage: python tools/bench_feature_store.py [--images 2048] [--objects 100] [--features 2048] [--batch 256] [--batches 24] [--runs 4] [--workers 5]
 """
@@ -94,6 +97,11 @@ def write_corpus(directory, images, objects, features, per_chunk, seed=3):
     return chunks, path, info
 
 
+def load_wide(_lib, O, N, K):
+    """The wide kernel takes the featurizer's first product at this shape (what both routes of the product comparison run)."""
+    return 256 < N <= 512 and K >= 128 and K % 4 == 0 and _lib.linear_wide_supported(O, N, K)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=2048)
@@ -169,9 +177,10 @@ def main():
                 res = pending.result()
                 training.compute_evaluation_metrics(pbs, res)
                 return res
+            store.direct = leg == "store_direct"             # (recorded on the store only: the same index, refs, collator and workers)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            for pbs in loaders[leg]:
+            for pbs in loaders["store" if leg == "store_direct" else leg]:
                 h0 = time.perf_counter()
                 if leg == "pool":
                     for pb in pbs:
@@ -187,9 +196,10 @@ def main():
             while inflight:
                 finish()
             torch.cuda.synchronize()
+            store.direct = False
             return time.perf_counter() - t0, to_cuda_s
 
-        legs = ("pool", "store", "host")
+        legs = ("pool", "store", "store_direct", "host")
         with torch.no_grad():
             for leg in legs:                                 # warm-up: workers up, allocator, weight images
                 run(leg)
@@ -201,7 +211,8 @@ def main():
                     dt, h = run(leg)
                     times[leg].append(dt / args.batches * 1e3)
                     to_cuda[leg].append(h / args.batches * 1e3)
-        counts = {k: v for k, v in _lib.PATH_COUNTS.items() if k in ("native_program", "python_program", "feature_store_batch", "feature_store_miss")}
+        counts = {k: v for k, v in _lib.PATH_COUNTS.items() if k in ("native_program", "python_program", "feature_store_batch", "feature_store_miss",
+                                                                     "feature_store_direct", "feature_store_direct_materialized")}
 
         # the gather alone, and a device-to-device copy of the same bytes, by HIP events in the same session
         out = torch.empty_like(pool[0])
@@ -225,6 +236,37 @@ def main():
         gather_ms = event_ms(lambda i: store.gather(refs[i % len(refs)], out=out, index=on_dev[i % len(refs)]))
         copy_ms = event_ms(lambda i: out.copy_(src))
         same = bool(np.array_equal(first_lp["store"].view(np.uint32), first_lp["host"].view(np.uint32)))
+        same_direct = bool(np.array_equal(first_lp["store_direct"].view(np.uint32), first_lp["store"].view(np.uint32)))
+
+        # the featurizer's first product both ways, alternating in `runs` rounds: the matrix route (gather + the wide product over the matrix) against
+        # the index route (row numbers and box columns + the wide product over the store's rows); index arrays uploaded and buffers allocated before
+        first = [m for m in model._featurizer._featurizer_network._network if isinstance(m, torch.nn.Linear)][0]
+        O, N = out.shape[0], first.out_features
+        product = None
+        if first.in_features == args.features and _lib._dense_math() == "f16x2" and load_wide(_lib, O, N, args.features):
+            rows = [store.rows(r, index=i) for r, i in zip(refs, on_dev)]
+            y = torch.empty(O, N, device=device)
+            act = _lib.ACT_SIGMOID
+
+            def matrix_route(i):
+                store.gather(refs[i % len(refs)], out=out, index=on_dev[i % len(refs)])
+                _lib.linear_wide(out[:, :args.features], first.weight, first.bias, act, out=y)
+
+            def index_route(i):
+                r = rows[i % len(refs)]
+                store.rows(refs[i % len(refs)], out=r, index=on_dev[i % len(refs)])
+                _lib.linear_wide_rows(r.table, r.src_row, first.weight, first.bias, act, out=y)
+            matrix_route(0)
+            y_matrix = y.clone()
+            index_route(0)
+            product = {"same_bits": bool(torch.equal(y, y_matrix)), "matrix_route_ms": [], "index_route_ms": [], "wide_over_matrix_ms": [], "wide_over_rows_ms": []}
+            for _ in range(args.runs):
+                product["matrix_route_ms"].append(float(np.median(event_ms(matrix_route))))
+                product["index_route_ms"].append(float(np.median(event_ms(index_route))))
+                product["wide_over_matrix_ms"].append(float(np.median(event_ms(
+                    lambda i: _lib.linear_wide(out[:, :args.features], first.weight, first.bias, act, out=y)))))
+                product["wide_over_rows_ms"].append(float(np.median(event_ms(
+                    lambda i: _lib.linear_wide_rows(rows[i % len(refs)].table, rows[i % len(refs)].src_row, first.weight, first.bias, act, out=y)))))
     finally:
         for ld in loaders.values():                          # (persistent workers: stop them before the files go)
             it = getattr(ld, "_iterator", None)
@@ -259,7 +301,13 @@ def main():
                                    "named": "the gather runs on the launch stream ahead of the batch's featurizer (nothing overlaps it), and to_cuda of a "
                                             "store batch allocates the [O, F + 6] matrix, uploads the index arrays and launches on the launching thread: "
                                             "to_cuda_host_ms_store_minus_pool is that host share"},
-        "routes": counts, "store_equals_host_bitwise_first_batch": same,
+        "store_direct_vs_store": apart(ms["store_direct"], ms["store"]), "store_direct_vs_pool": apart(ms["store_direct"], ms["pool"]),
+        "store_direct_over_store_questions_per_s": qps["store_direct"]["median"] / qps["store"]["median"],
+        "featurizer_first_product": None if product is None else dict(
+            product, matrix_route=span(product["matrix_route_ms"]), index_route=span(product["index_route_ms"]),
+            index_vs_matrix=apart(span(product["index_route_ms"]), span(product["matrix_route_ms"])),
+            wide_rows_vs_wide=apart(span(product["wide_over_rows_ms"]), span(product["wide_over_matrix_ms"]))),
+        "routes": counts, "store_equals_host_bitwise_first_batch": same, "store_direct_equals_store_bitwise_first_batch": same_direct,
     }
     print(json.dumps(result))
 
