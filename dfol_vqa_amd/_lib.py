@@ -929,32 +929,20 @@ def pair_ll(uv, hid1, pos, wg, w2, b2, emb_w, emb_b, n_obj, obj_off, max_n, req_
 
 
 PACKED_W2_ROWS, PACKED_W2_CHUNK = 320, 16
-
-
-def pair_pack_w2(w2, hid2=None):
-    """W2 [HID2(+padding), HID1] -> the packed image dfol_pair_ll_packed_f32 reads ([HID1/16][320][16], swizzled)."""
-    hid1 = w2.shape[1]
-    hid2 = w2.shape[0] if hid2 is None else hid2
-    out = torch.empty((hid1 // PACKED_W2_CHUNK) * PACKED_W2_ROWS * PACKED_W2_CHUNK, dtype=F32, device=w2.device)
-    call("dfol_pair_pack_w2_f32", _ptr(w2, F32), w2.stride(0), hid2, hid1, _ptr(out), _stream())
-    return out
-
-
-def pair_ll_packed(uv, hid1, pos, wg, w2_packed, b2, hid2, emb_w, emb_b, n_obj, obj_off, max_n, req_col, req_tile, req_orient, tiles,
-                   default_ll=-30.0):
-    """As pair_ll, with the second layer packed by pair_pack_w2 (hid1 % 16 == 0, hid2 <= 320).  `tiles` may be bfloat16
-    (TILE_BF16 storage for relate_one_fwd_bf16; needs hid2 > 256 and NS % 8 == 0)."""
-    K, Q = req_col.shape
-    NS = tiles.shape[1]
-    bf16 = tiles.dtype == torch.bfloat16
-    call("dfol_pair_ll_packed_f32", _dp(uv), uv.stride(0), hid1, _dp(pos), pos.stride(0), _ptr(wg, F32), _ptr(w2_packed, F32),
-         _ptr(b2, F32), hid2, _dp(emb_w), emb_w.stride(0), _ptr(emb_b, F32, True), _ptr(n_obj, I32), _ptr(obj_off, I32), Q, max_n,
-         _ptr(req_col, I32), _ptr(req_tile, I32), _ptr(req_orient, U8, True), K, NS, default_ll, TILE_BF16 if bf16 else TILE_F32,
-         _ptr(tiles, torch.bfloat16 if bf16 else F32), _stream())
-    return tiles
-
-
 SPLIT_W2_CHUNK_BYTES = 3 * 320 * 32 * 2                        # three bf16 pieces of 20 column tiles x 32 k
+LOG2E = 1.4426950408889634
+
+# The forms in which the pair network's second layer W2 reaches the fused pair kernel, one row each: the executor's code (include/dfol_vqa.h:
+# DFOL_PAIR_*), the names of this module's pack and launch wrappers, the image's dtype, whether the kernel takes U | V in units of ln 2
+# (multiplied by log2 e), whether it can write bf16 tiles.  A new form is one row here, one pack kernel and one entry point.
+PairKind = _collections.namedtuple("PairKind", "code pack launch dtype ln2_units bf16_tiles")
+PAIR_KINDS = {
+    "f16x2": PairKind(3, "pair_pack_w2_h2", "pair_ll_h2", torch.float16, True, True),
+    "f16": PairKind(4, "pair_pack_w2_h1", "pair_ll_h1", torch.float16, True, True),
+    "bf16x3": PairKind(2, "pair_pack_w2_split", "pair_ll_split", torch.bfloat16, False, True),
+    "packed": PairKind(1, "pair_pack_w2", "pair_ll_packed", F32, False, True),
+    "plain": PairKind(0, None, "pair_ll", F32, False, False),      # (no image: the zero-padded weight itself)
+}
 
 
 def pair_split_supported(hid1, hid2):
@@ -962,39 +950,73 @@ def pair_split_supported(hid1, hid2):
     return hid1 % 32 == 0 and 0 < hid1 <= 256 and 256 < hid2 <= 320
 
 
+def pair_kind_for(math, hid1, hid2):
+    """The PAIR_KINDS row that evaluates a HID1 -> HID2 second layer under the pair arithmetic `math` (pair_math()): the packed layout of the
+    occupancy-2 kernel (csrc/dfol_pair.hip) where the shape allows it and DFOL_PAIR_PACKED is not 0; on a full-size layer fp32 results from
+    the fp16 matrix pipe ("f16x2": two pieces per operand, three products; "f16": opt-in reduced precision, the hi pieces alone, one
+    product per MAC on the same kernel body: csrc/dfol_pair_h2.hip) or from the bf16 pipe ("bf16x3": three pieces, six products:
+    csrc/dfol_pair_split.hip); "f32" keeps the fp32 matrix pipe."""
+    if not (hid1 % PACKED_W2_CHUNK == 0 and hid1 <= 256 and hid2 <= PACKED_W2_ROWS) or os.environ.get("DFOL_PAIR_PACKED", "1") == "0":
+        return "plain"
+    return "packed" if math == "f32" or not pair_split_supported(hid1, hid2) else math
+
+
+def pair_tiles_bf16_ok(hid1, hid2):
+    """bf16 tile storage (config key relation_tile_dtype: bf16) is possible: the pair kernels that write bf16 tiles are the packed ones over a
+    second layer of more than 256 rows.  The weight's shape decides, not its values or the arithmetic."""
+    return hid2 > 256 and PAIR_KINDS[pair_kind_for("f32", hid1, hid2)].bf16_tiles
+
+
+def _pair_pack(entry, dtype, nbytes, w2, hid2):
+    out = torch.empty(nbytes // dtype.itemsize, dtype=dtype, device=w2.device)
+    call(entry, _ptr(w2, F32), w2.stride(0), w2.shape[0] if hid2 is None else hid2, w2.shape[1], _ptr(out, dtype), _stream())
+    return out
+
+
+def _pair_ll_image(entry, dtype, scale_uv, uv, hid1, pos, wg, image, b2, hid2, emb_w, emb_b, n_obj, obj_off, max_n, req_col, req_tile, req_orient,
+                   tiles, default_ll):
+    """The four entry points that take a packed image of W2 (same argument list).  scale_uv: `uv` is still in natural units and the kernel
+    takes it multiplied by log2(e)."""
+    if scale_uv:
+        uv = uv * LOG2E
+    K, Q = req_col.shape
+    NS = tiles.shape[1]
+    bf16 = tiles.dtype == torch.bfloat16
+    call(entry, _dp(uv), uv.stride(0), hid1, _dp(pos), pos.stride(0), _ptr(wg, F32), _ptr(image, dtype), _ptr(b2, F32), hid2, _dp(emb_w),
+         emb_w.stride(0), _ptr(emb_b, F32, True), _ptr(n_obj, I32), _ptr(obj_off, I32), Q, max_n, _ptr(req_col, I32), _ptr(req_tile, I32),
+         _ptr(req_orient, U8, True), K, NS, default_ll, TILE_BF16 if bf16 else TILE_F32, _ptr(tiles, torch.bfloat16 if bf16 else F32), _stream())
+    return tiles
+
+
+def pair_pack_w2(w2, hid2=None):
+    """W2 [HID2(+padding), HID1] -> the packed image dfol_pair_ll_packed_f32 reads ([HID1/16][320][16], swizzled)."""
+    return _pair_pack("dfol_pair_pack_w2_f32", F32, (w2.shape[1] // PACKED_W2_CHUNK) * PACKED_W2_ROWS * PACKED_W2_CHUNK * 4, w2, hid2)
+
+
+def pair_ll_packed(uv, hid1, pos, wg, w2_packed, b2, hid2, emb_w, emb_b, n_obj, obj_off, max_n, req_col, req_tile, req_orient, tiles,
+                   default_ll=-30.0):
+    """As pair_ll, with the second layer packed by pair_pack_w2 (hid1 % 16 == 0, hid2 <= 320).  `tiles` may be bfloat16
+    (TILE_BF16 storage for relate_one_fwd_bf16; needs hid2 > 256 and NS % 8 == 0)."""
+    return _pair_ll_image("dfol_pair_ll_packed_f32", F32, False, uv, hid1, pos, wg, w2_packed, b2, hid2, emb_w, emb_b, n_obj, obj_off, max_n,
+                          req_col, req_tile, req_orient, tiles, default_ll)
+
+
 def pair_pack_w2_split(w2, hid2=None):
     """W2 [HID2(+padding), HID1] -> the bf16x3 image dfol_pair_ll_split_f32 reads (SPLIT_W2_CHUNK_BYTES per 32 k, swizzled)."""
-    hid1 = w2.shape[1]
-    hid2 = w2.shape[0] if hid2 is None else hid2
-    out = torch.empty((hid1 // 32) * SPLIT_W2_CHUNK_BYTES // 2, dtype=torch.bfloat16, device=w2.device)
-    call("dfol_pair_pack_w2_bf16x3", _ptr(w2, F32), w2.stride(0), hid2, hid1, _ptr(out, torch.bfloat16), _stream())
-    return out
+    return _pair_pack("dfol_pair_pack_w2_bf16x3", torch.bfloat16, (w2.shape[1] // 32) * SPLIT_W2_CHUNK_BYTES, w2, hid2)
 
 
 def pair_ll_split(uv, hid1, pos, wg, w2_split, b2, hid2, emb_w, emb_b, n_obj, obj_off, max_n, req_col, req_tile, req_orient, tiles,
                   default_ll=-30.0):
     """As pair_ll_packed, with the second layer split by pair_pack_w2_split: bf16 matrix pipes, fp32 results."""
-    K, Q = req_col.shape
-    NS = tiles.shape[1]
-    bf16 = tiles.dtype == torch.bfloat16
-    call("dfol_pair_ll_split_f32", _dp(uv), uv.stride(0), hid1, _dp(pos), pos.stride(0), _ptr(wg, F32),
-         _ptr(w2_split, torch.bfloat16), _ptr(b2, F32), hid2, _dp(emb_w), emb_w.stride(0), _ptr(emb_b, F32, True), _ptr(n_obj, I32),
-         _ptr(obj_off, I32), Q, max_n, _ptr(req_col, I32), _ptr(req_tile, I32), _ptr(req_orient, U8, True), K, NS, default_ll,
-         TILE_BF16 if bf16 else TILE_F32, _ptr(tiles, torch.bfloat16 if bf16 else F32), _stream())
-    return tiles
+    return _pair_ll_image("dfol_pair_ll_split_f32", torch.bfloat16, False, uv, hid1, pos, wg, w2_split, b2, hid2, emb_w, emb_b, n_obj, obj_off,
+                          max_n, req_col, req_tile, req_orient, tiles, default_ll)
 
 
 def pair_pack_w2_h2(w2, hid2=None):
     """W2 [HID2(+padding), HID1] -> the fp16x2 image dfol_pair_ll_h2_f32 reads (rows scaled by powers of two, two fp16 pieces, swizzled;
     the per-column multipliers of the epilogue behind the chunks)."""
-    hid1 = w2.shape[1]
-    hid2 = w2.shape[0] if hid2 is None else hid2
-    out = torch.empty(load().dfol_pair_w2_f16x2_bytes(hid1) // 2, dtype=torch.float16, device=w2.device)
-    call("dfol_pair_pack_w2_f16x2", _ptr(w2, F32), w2.stride(0), hid2, hid1, _ptr(out, torch.float16), _stream())
-    return out
-
-
-LOG2E = 1.4426950408889634
+    return _pair_pack("dfol_pair_pack_w2_f16x2", torch.float16, load().dfol_pair_w2_f16x2_bytes(w2.shape[1]), w2, hid2)
 
 
 def pair_ll_h2(uv, hid1, pos, wg, w2_h2, b2, hid2, emb_w, emb_b, n_obj, obj_off, max_n, req_col, req_tile, req_orient, tiles,
@@ -1003,42 +1025,22 @@ def pair_ll_h2(uv, hid1, pos, wg, w2_h2, b2, hid2, emb_w, emb_b, n_obj, obj_off,
     (csrc/dfol_pair_h2.hip).  Ordered pairs only: `tiles` must be pre-filled with default_ll (diagonal and padding keep the fill).
     The kernel takes U | V MULTIPLIED BY log2(e) (include/dfol_vqa.h): uv_prescaled=True says `uv` already is (the oracle scales the stacked
     first-layer weight once per weight version); otherwise it is scaled here, with one extra pass over it (tests, lab scripts)."""
-    if not uv_prescaled:
-        uv = uv * LOG2E
-    K, Q = req_col.shape
-    NS = tiles.shape[1]
-    bf16 = tiles.dtype == torch.bfloat16
-    call("dfol_pair_ll_h2_f32", _dp(uv), uv.stride(0), hid1, _dp(pos), pos.stride(0), _ptr(wg, F32),
-         _ptr(w2_h2, torch.float16), _ptr(b2, F32), hid2, _dp(emb_w), emb_w.stride(0), _ptr(emb_b, F32, True), _ptr(n_obj, I32),
-         _ptr(obj_off, I32), Q, max_n, _ptr(req_col, I32), _ptr(req_tile, I32), _ptr(req_orient, U8, True), K, NS, default_ll,
-         TILE_BF16 if bf16 else TILE_F32, _ptr(tiles, torch.bfloat16 if bf16 else F32), _stream())
-    return tiles
+    return _pair_ll_image("dfol_pair_ll_h2_f32", torch.float16, not uv_prescaled, uv, hid1, pos, wg, w2_h2, b2, hid2, emb_w, emb_b, n_obj, obj_off,
+                          max_n, req_col, req_tile, req_orient, tiles, default_ll)
 
 
 def pair_pack_w2_h1(w2, hid2=None):
     """W2 [HID2(+padding), HID1] -> the one-piece fp16 image dfol_pair_ll_h1_f32 reads: the hi pieces of pair_pack_w2_h2's image (same row
     scales, swizzle and tail), 20 KB per 32 k."""
-    hid1 = w2.shape[1]
-    hid2 = w2.shape[0] if hid2 is None else hid2
-    out = torch.empty(load().dfol_pair_w2_f16_bytes(hid1) // 2, dtype=torch.float16, device=w2.device)
-    call("dfol_pair_pack_w2_f16", _ptr(w2, F32), w2.stride(0), hid2, hid1, _ptr(out, torch.float16), _stream())
-    return out
+    return _pair_pack("dfol_pair_pack_w2_f16", torch.float16, load().dfol_pair_w2_f16_bytes(w2.shape[1]), w2, hid2)
 
 
 def pair_ll_h1(uv, hid1, pos, wg, w2_h1, b2, hid2, emb_w, emb_b, n_obj, obj_off, max_n, req_col, req_tile, req_orient, tiles,
                default_ll=-30.0, uv_prescaled=False):
     """As pair_ll_h2 in the opt-in reduced-precision mode (pair_math "f16"): operands rounded to fp16, ONE product per MAC, fp32
     accumulation, on the image of pair_pack_w2_h1.  Same arguments, same units of `uv`, same saturation report."""
-    if not uv_prescaled:
-        uv = uv * LOG2E
-    K, Q = req_col.shape
-    NS = tiles.shape[1]
-    bf16 = tiles.dtype == torch.bfloat16
-    call("dfol_pair_ll_h1_f32", _dp(uv), uv.stride(0), hid1, _dp(pos), pos.stride(0), _ptr(wg, F32),
-         _ptr(w2_h1, torch.float16), _ptr(b2, F32), hid2, _dp(emb_w), emb_w.stride(0), _ptr(emb_b, F32, True), _ptr(n_obj, I32),
-         _ptr(obj_off, I32), Q, max_n, _ptr(req_col, I32), _ptr(req_tile, I32), _ptr(req_orient, U8, True), K, NS, default_ll,
-         TILE_BF16 if bf16 else TILE_F32, _ptr(tiles, torch.bfloat16 if bf16 else F32), _stream())
-    return tiles
+    return _pair_ll_image("dfol_pair_ll_h1_f32", torch.float16, not uv_prescaled, uv, hid1, pos, wg, w2_h1, b2, hid2, emb_w, emb_b, n_obj, obj_off,
+                          max_n, req_col, req_tile, req_orient, tiles, default_ll)
 
 
 def pair_train_fwd_h2(uv_scaled, hid1, pos, wg, w2_h2, b2, hid2, n_obj, obj_off, pair_off, max_n, pairs, e_rows=None, req_row=None):

@@ -112,6 +112,17 @@ int run_dense(const DfolDenseLayer& L, const float* X, int64_t ldx, float* Y, in
     return 1;
 }
 
+// DFOL_OP_PAIR_LL: the entry points that take a packed image of W2, by DFOL_PAIR_* (DFOL_PAIR_PLAIN reads the weight itself: another argument list)
+using PairImageEntry = int (*)(const float*, int64_t, int32_t, const float*, int64_t, const float*, const void*, const float*, int32_t, const float*, int64_t,
+                               const float*, const int32_t*, const int32_t*, int32_t, int32_t, const int32_t*, const int32_t*, const uint8_t*, int32_t, int32_t,
+                               float, int32_t, void*, void*);
+template <class... Rest>       // (the fp32 image alone is declared const float*)
+int pair_ll_packed(const float* uv, int64_t ld_uv, int32_t hid1, const float* pos, int64_t ld_pos, const float* wg, const void* w2, Rest... rest) {
+    return dfol_pair_ll_packed_f32(uv, ld_uv, hid1, pos, ld_pos, wg, static_cast<const float*>(w2), rest...);
+}
+constexpr PairImageEntry kPairImageEntry[] = {nullptr, pair_ll_packed, dfol_pair_ll_split_f32, dfol_pair_ll_h2_f32, dfol_pair_ll_h1_f32};
+static_assert(DFOL_PAIR_PACKED == 1 && DFOL_PAIR_BF16X3 == 2 && DFOL_PAIR_F16X2 == 3 && DFOL_PAIR_F16 == 4, "kPairImageEntry is indexed by DFOL_PAIR_*");
+
 // dfol_set_feature_rows: the index form of the NEXT dfol_run_program's scene on this thread
 thread_local const int32_t* g_feature_src_row = nullptr;
 thread_local const float* g_feature_box6 = nullptr;
@@ -187,32 +198,18 @@ extern "C" int dfol_run_program(const DfolProgramModel* model, const DfolProgram
                 void* tiles = at(workspace, a[9]);
                 const int32_t K = static_cast<int32_t>(a[8]), Qimg = static_cast<int32_t>(a[10]), tdt = static_cast<int32_t>(a[11]);
                 DFOL_REQUIRE(tdt == DFOL_TILE_F32 || model->pair_kind != DFOL_PAIR_PLAIN, "run_program[%d]: bf16 tiles need a packed second layer", i);
-                switch (model->pair_kind) {
-                    case DFOL_PAIR_F16X2:
-                        rc = dfol_pair_ll_h2_f32(uv, a[2], model->hid1, pos, a[4], model->wg, model->w2, model->b2, model->hid2, model->emb_w, model->ld_e, model->emb_b,
-                                                 img_n_obj, obj_off, Qimg, scene->max_n, rc_, rt, ro, K, NS, -30.0f, tdt, tiles, stream);
-                        break;
-                    case DFOL_PAIR_F16:
-                        rc = dfol_pair_ll_h1_f32(uv, a[2], model->hid1, pos, a[4], model->wg, model->w2, model->b2, model->hid2, model->emb_w, model->ld_e, model->emb_b,
-                                                 img_n_obj, obj_off, Qimg, scene->max_n, rc_, rt, ro, K, NS, -30.0f, tdt, tiles, stream);
-                        break;
-                    case DFOL_PAIR_BF16X3:
-                        rc = dfol_pair_ll_split_f32(uv, a[2], model->hid1, pos, a[4], model->wg, model->w2, model->b2, model->hid2, model->emb_w, model->ld_e, model->emb_b,
-                                                    img_n_obj, obj_off, Qimg, scene->max_n, rc_, rt, ro, K, NS, -30.0f, tdt, tiles, stream);
-                        break;
-                    case DFOL_PAIR_PACKED:
-                        rc = dfol_pair_ll_packed_f32(uv, a[2], model->hid1, pos, a[4], model->wg, static_cast<const float*>(model->w2), model->b2, model->hid2, model->emb_w,
-                                                     model->ld_e, model->emb_b, img_n_obj, obj_off, Qimg, scene->max_n, rc_, rt, ro, K, NS, -30.0f, tdt, tiles, stream);
-                        break;
-                    case DFOL_PAIR_PLAIN:
-                        rc = dfol_pair_ll_f32(uv, a[2], model->hid1, pos, a[4], model->wg, static_cast<const float*>(model->w2), model->ld_w2, model->w2_rows, model->b2,
-                                              model->hid2, model->emb_w, model->ld_e, model->emb_b, img_n_obj, obj_off, Qimg, scene->max_n, rc_, rt, ro, K, NS, -30.0f,
-                                              static_cast<float*>(tiles), stream);
-                        break;
-                    default:
-                        dfol_set_error("run_program[%d]: unknown pair kernel kind %d", i, model->pair_kind);
-                        return 1;
+                if (model->pair_kind == DFOL_PAIR_PLAIN) {
+                    rc = dfol_pair_ll_f32(uv, a[2], model->hid1, pos, a[4], model->wg, static_cast<const float*>(model->w2), model->ld_w2, model->w2_rows, model->b2,
+                                          model->hid2, model->emb_w, model->ld_e, model->emb_b, img_n_obj, obj_off, Qimg, scene->max_n, rc_, rt, ro, K, NS, -30.0f,
+                                          static_cast<float*>(tiles), stream);
+                    break;
                 }
+                if (model->pair_kind < 0 || model->pair_kind > DFOL_PAIR_F16) {
+                    dfol_set_error("run_program[%d]: unknown pair kernel kind %d", i, model->pair_kind);
+                    return 1;
+                }
+                rc = kPairImageEntry[model->pair_kind](uv, a[2], model->hid1, pos, a[4], model->wg, model->w2, model->b2, model->hid2, model->emb_w, model->ld_e,
+                                                       model->emb_b, img_n_obj, obj_off, Qimg, scene->max_n, rc_, rt, ro, K, NS, -30.0f, tdt, tiles, stream);
                 break;
             }
             case DFOL_OP_ATTR_LL:        // hidden, ld_hidden, pred_img, cols, P, ll

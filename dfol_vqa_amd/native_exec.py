@@ -19,7 +19,6 @@ from . import native_plan as NP
 
 _p, _i32, _i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
 DENSE_F32, DENSE_F16X2, DENSE_BF16X3, DENSE_BF16, DENSE_HEAD_F16X2 = 0, 1, 2, 3, 4
-PAIR_PLAIN, PAIR_PACKED, PAIR_BF16X3, PAIR_F16X2, PAIR_F16 = 0, 1, 2, 3, 4
 
 
 class DenseLayer(ctypes.Structure):
@@ -112,7 +111,7 @@ def attr_head_on(model):
 
 
 def attr_head_of(model):
-    """visual_oracle._attr_head() evaluated in the model's own arithmetic: (first Linear, second Linear, packed image, bias) or None."""
+    """visual_oracle._attr_head() evaluated in the model's own arithmetic: (first Linear, second Linear, PairImage of the second) or None."""
     with _lib.dense_math(getattr(model, "_mlp_math", None)):
         return model._oracle._attr_head()
 
@@ -130,10 +129,7 @@ def model_spec(model, calibrate=False):
     if not fl or not al:
         return None
     lin1, lin2 = [m for m in oracle._relation_network._network if isinstance(m, nn.Linear)][:2]
-    # bf16 tile storage (config key relation_tile_dtype: bf16): the pair kernels that write bf16 tiles are the packed ones over a second layer of
-    # more than 256 rows (visual_oracle.prefetch_relations' rule; the weight's shape decides, not its values)
-    tile_bf16 = getattr(oracle, "_tile_dtype", torch.float32) == torch.bfloat16 and 256 < lin2.out_features <= 320 and lin1.out_features <= 256 and \
-        lin1.out_features % 16 == 0 and os.environ.get("DFOL_PAIR_PACKED", "1") != "0"
+    tile_bf16 = getattr(oracle, "_tile_dtype", torch.float32) == torch.bfloat16 and _lib.pair_tiles_bf16_ok(lin1.out_features, lin2.out_features)
     calib = None
     if calibrate:
         nets = calibrator(model)
@@ -176,29 +172,24 @@ class NativeModel(object):
         head = attr_head_of(model) if len(al) == 2 else None      # (taken once, in the scope attr_head_on decides in)
         self.attr_head = head is not None
         if self.attr_head:                                   # the last attribute layer runs inside DFOL_OP_ATTR_HEAD, from the pair kernel's image format
-            _, _, w2_img, b2_head = head
-            self._al[1].kind, self._al[1].packed, self._al[1].bias = DENSE_HEAD_F16X2, w2_img.data_ptr(), b2_head.data_ptr()
-            self._hold += [w2_img, b2_head]
+            self._al[1].kind, self._al[1].packed, self._al[1].bias = DENSE_HEAD_F16X2, head[2].image.data_ptr(), head[2].b2.data_ptr()
+            self._hold.append(head[2])
         wuv, buv, wg, hid1, D = oracle._split_first_layer()
-        w2p, b2, hid2, packed = oracle._padded_second_layer()
+        img = oracle._pair_image()
         emb = oracle._embedding_network.linear
         m = ProgramModel()
         m.n_featurizer, m.n_attribute = len(fl), len(al)
         m.featurizer, m.attribute = self._fl, self._al
         m.uv = dense(wuv, buv, _lib.ACT_NONE)
-        if isinstance(packed, tuple):
-            m.pair_kind, w2 = {"f16x2": PAIR_F16X2, "f16": PAIR_F16, "bf16x3": PAIR_BF16X3}[packed[0]], packed[1]
-        elif packed is not None:
-            m.pair_kind, w2 = PAIR_PACKED, packed
-        else:
-            m.pair_kind, w2 = PAIR_PLAIN, w2p
-        m.hid1, m.hid2, m.w2_rows = int(hid1), int(hid2), int(w2p.shape[0])
-        m.wg, m.w2, m.ld_w2, m.b2 = wg.data_ptr(), w2.data_ptr(), w2p.stride(0), b2.data_ptr()
+        m.pair_kind = _lib.PAIR_KINDS[img.kind].code
+        w2 = img.image if img.image is not None else img.w2_padded
+        m.hid1, m.hid2, m.w2_rows = int(hid1), int(img.hid2), int(img.w2_padded.shape[0])
+        m.wg, m.w2, m.ld_w2, m.b2 = wg.data_ptr(), w2.data_ptr(), img.w2_padded.stride(0), img.b2.data_ptr()
         ew = emb.weight.detach()
         m.emb_w, m.ld_e = ew.data_ptr(), ew.stride(0)
         m.emb_b = None if emb.bias is None else emb.bias.detach().data_ptr()
         m.emb_in, m.D = int(ew.shape[1]), int(D)
-        self._hold += [wuv, buv, wg, w2p, b2, w2, ew, emb.bias]
+        self._hold += [wuv, buv, wg, img, ew, emb.bias]
         nets = calibrator(model)
         if nets is not None:
             for k, cell in enumerate(nets[:2]):

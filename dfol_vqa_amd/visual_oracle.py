@@ -7,6 +7,7 @@ cached tables by csrc/dfol_logic.hip.  Parameter names match the reference's sta
 (`_network.1.weight`, ...) so its checkpoints load with strict=False.
 """
 
+import collections
 import contextlib
 import os
 
@@ -18,6 +19,10 @@ from . import _lib
 from . import ops as L
 from .fol_types import TokenType
 from .host_util import flatten_list, get_lowered, lower_tokens, segments_of, upload
+
+# A second layer W2 as the fused pair kernel reads it: kind (a key of L.PAIR_KINDS), its packed image (None for "plain"), the weight zero-padded
+# to a multiple of 32 rows (None for the attribute head, which reads the image alone), the bias, the true output width.
+PairImage = collections.namedtuple("PairImage", "kind image w2_padded b2 hid2")
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -670,7 +675,7 @@ class ClassifierOracle(OracleBase):
         # The fp16x2 pair kernel (csrc/dfol_pair_h2.hip) takes U | V in units of ln 2, i.e. multiplied by log2(e): its ELU then needs no multiply in
         # front of the hardware exponential (a build tick of that kernel is paced by its instruction count).  The factor goes into the stacked
         # weight and bias here, once per weight version; the kernel scales the geometry columns itself and its pack kernel folds ln 2 into W2.
-        scaled = self._pair_kind() in ("f16x2", "f16")           # (the one-piece form is the same kernel body: same units)
+        scaled = L.PAIR_KINDS[self._pair_kind()].ln2_units       # (the one-piece form is the same kernel body: same units)
         key = (lin.weight.data_ptr(), lin.weight._version, None if lin.bias is None else lin.bias._version, scaled)
         if self._split_cache is None or self._split_cache[0] != key:
             w = lin.weight.detach()
@@ -685,7 +690,7 @@ class ClassifierOracle(OracleBase):
         return L.keep_alive(self._split_cache)[1:]
 
     def _attr_head(self):
-        """(first Linear, second Linear, packed image of the second, its bias) when the attribute columns of an inference forward come from
+        """(first Linear, second Linear, PairImage of the second) when the attribute columns of an inference forward come from
         the fused head - a two-layer attribute network (Linear, ELU, Linear, Sigmoid) of the pair kernel's second-layer shapes, the default
         two-piece fp16 arithmetic, DFOL_ATTR_HEAD not 0 - else None: the hidden table + dfol_attr_ll_f32."""
         if os.environ.get("DFOL_ATTR_HEAD", "1") == "0" or _lib._dense_math() != "f16x2":
@@ -705,9 +710,9 @@ class ClassifierOracle(OracleBase):
         key = (w.data_ptr(), w._version, lin2.bias._version)
         cache = getattr(self, "_attr_w2_cache", None)
         if cache is None or cache[0] != key:                 # packed once per weight version, like the pair kernel's image
-            self._attr_w2_cache = cache = (key, L.pair_pack_w2_h2(w.detach().contiguous(), w.shape[0]), lin2.bias.detach().contiguous())
-        L.keep_alive(cache)
-        return lin1, lin2, cache[1], cache[2]
+            self._attr_w2_cache = cache = (key, PairImage("f16x2", L.pair_pack_w2_h2(w.detach().contiguous(), w.shape[0]), None,
+                                                          lin2.bias.detach().contiguous(), w.shape[0]))
+        return lin1, lin2, L.keep_alive(cache)[1]
 
     def _attr_columns(self, world, pred_img, cols):
         """Attribute blocks [P, NS] of the requested (scene, concept) pairs: the fused head over the first layer's pre-activations, or
@@ -715,18 +720,14 @@ class ClassifierOracle(OracleBase):
         emb = self._embedding_network.linear
         if getattr(world, "_attr_pre1", None) is not None:
             # (the scene carries the image it was prepared with: a switch or arithmetic scope that changed since then does not reach it)
-            w2, b2, hid2 = world._attr_head_w2
+            img = world._attr_head_w2
             _lib.note("attr_head")
-            return L.attr_head_h2(world._attr_pre1, w2, b2, hid2, emb.weight, emb.bias, world._obj_off, pred_img, cols, world._NS, -30.0)
+            return L.attr_head_h2(world._attr_pre1, img.image, img.b2, img.hid2, emb.weight, emb.bias, world._obj_off, pred_img, cols, world._NS, -30.0)
         return L.attr_ll(world._hidden_attr, emb.weight, emb.bias, world._obj_off, pred_img, cols, world._NS, -30.0)
 
     def _pair_kind(self):
-        """Which fused pair kernel evaluates this oracle's relation tiles: "f16x2", "f16" (opt-in reduced precision), "bf16x3", "packed" (fp32
-        pipe, packed W2) or "plain"."""
-        packed = self._padded_second_layer()[3]
-        if isinstance(packed, tuple):
-            return packed[0]
-        return "plain" if packed is None else "packed"
+        """Which fused pair kernel evaluates this oracle's relation tiles: a key of L.PAIR_KINDS."""
+        return self._pair_image().kind
 
     @staticmethod
     def _train_pair_math():
@@ -734,41 +735,27 @@ class ClassifierOracle(OracleBase):
         m = L.pair_math()
         return "f16x2" if m == "f16" else m
 
-    def _padded_second_layer(self, math=None):
-        """W2 zero-padded to a multiple of 32 rows, so the fused pair kernel's main loop needs no bounds checks.  math: the pair arithmetic
-        the packed image is for (default: L.pair_math())."""
+    def _pair_image(self, math=None):
+        """The relation network's second layer as a PairImage for the pair arithmetic `math` (default: L.pair_math()): W2 zero-padded to a
+        multiple of 32 rows, so the fused pair kernel's main loop needs no bounds checks, and the image of L.pair_kind_for's kind."""
         lin = [m for m in self._relation_network._network if isinstance(m, nn.Linear)][1]
         math = L.pair_math() if math is None else math
-        key = (lin.weight.data_ptr(), lin.weight._version, lin.bias._version, math)
+        key = (lin.weight.data_ptr(), lin.weight._version, lin.bias._version)
         cache = getattr(self, "_w2_cache", None)
-        # (a second entry for the same weights under another arithmetic: inside a `pair_math: f16` scope the train gate asks for the f16x2
-        # image between requests for the f16 one; with one entry every such switch would pack W2 again.  Clearing _w2_cache drops both.)
-        other = getattr(self, "_w2_cache_other", None) if cache is not None else None
-        if cache is not None and cache[0] != key and other is not None and other[0] == key:
-            self._w2_cache, self._w2_cache_other = cache, other = other, cache
         if cache is None or cache[0] != key:
-            self._w2_cache_other = cache if cache is not None and cache[0][:3] == key[:3] else None
+            # one image per arithmetic of this weight version: inside a `pair_math: f16` scope the train gate asks for the f16x2 image between
+            # requests for the f16 one, and no such switch packs W2 again.  A new weight version (or clearing _w2_cache) drops them all.
+            self._w2_cache = cache = (key, {})
+        img = cache[1].get(math)
+        if img is None:
             w = lin.weight.detach()
-            rows = (w.shape[0] + 31) // 32 * 32
-            wp = torch.zeros(rows, w.shape[1], dtype=w.dtype, device=w.device)
+            wp = torch.zeros((w.shape[0] + 31) // 32 * 32, w.shape[1], dtype=w.dtype, device=w.device)
             wp[:w.shape[0]] = w
-            packed = None
-            if w.shape[1] % L.PACKED_W2_CHUNK == 0 and w.shape[1] <= 256 and w.shape[0] <= L.PACKED_W2_ROWS \
-                    and os.environ.get("DFOL_PAIR_PACKED", "1") != "0":
-                packed = L.pair_pack_w2(wp, w.shape[0])      # the layout of the occupancy-2 pair kernel (csrc/dfol_pair.hip)
-                # full-size second layer: fp32 results from the fp16 matrix pipe (two fp16 pieces per operand, three products:
-                # csrc/dfol_pair_h2.hip) or, DFOL_PAIR_MATH=bf16x3, from the bf16 pipe (three pieces, six products: csrc/dfol_pair_split.hip);
-                # DFOL_PAIR_MATH=f32 keeps the fp32 matrix pipe; `pair_math: f16` (opt-in, reduced precision) takes the hi pieces alone: one
-                # product per MAC on the same kernel body
-                if L.pair_split_supported(w.shape[1], w.shape[0]) and math != "f32":
-                    if math == "f16x2":
-                        packed = ("f16x2", L.pair_pack_w2_h2(wp, w.shape[0]))
-                    elif math == "f16":
-                        packed = ("f16", L.pair_pack_w2_h1(wp, w.shape[0]))
-                    else:
-                        packed = ("bf16x3", L.pair_pack_w2_split(wp, w.shape[0]))
-            self._w2_cache = (key, wp, lin.bias.detach().contiguous(), w.shape[0], packed)
-        return L.keep_alive(self._w2_cache)[1:]
+            kind = L.pair_kind_for(math, w.shape[1], w.shape[0])
+            pack = L.PAIR_KINDS[kind].pack
+            img = cache[1][math] = PairImage(kind, None if pack is None else getattr(L, pack)(wp, w.shape[0]), wp, lin.bias.detach().contiguous(),
+                                             w.shape[0])
+        return L.keep_alive(img)
 
     def prepare_scene(self, world, obj, train=False):
         """Hidden activations of a scene: attribute hidden [O, H] and the per-object halves of the pair MLP's first layer.
@@ -784,7 +771,7 @@ class ClassifierOracle(OracleBase):
         world._attr_pre1 = world._attr_head_w2 = None
         if head is not None:
             world._hidden_attr = None
-            world._attr_head_w2 = (head[2], head[3], head[1].weight.shape[0])      # packed second layer, its bias, its width
+            world._attr_head_w2 = head[2]
             world._attr_pre1 = L.linear_act(obj, head[0].weight, head[0].bias, L.ACT_NONE)
         else:
             world._hidden_attr = self._attribute_network(obj)
@@ -889,10 +876,10 @@ class ClassifierOracle(OracleBase):
             return None
         if not bool(L.load().dfol_pair_hidden1_bwd_recompute_supported(int(max(world._n_list)), int(hid1))) or os.environ.get("DFOL_H1B_RECOMPUTE", "1") == "0":
             return None
-        packed = self._padded_second_layer(self._train_pair_math())[3]
-        if not (isinstance(packed, tuple) and packed[0] == "f16x2"):
+        img = self._pair_image(self._train_pair_math())
+        if img.kind != "f16x2":
             return None
-        return {"w2h": packed[1], "b2": lin2.bias.detach().contiguous(), "hid2": int(hid2), "first": first}
+        return {"w2h": img.image, "b2": lin2.bias.detach().contiguous(), "hid2": int(hid2), "first": first}
 
     def _head_fused(self, world, z, lin1, lin2):
         """The deferred head backward applies: fused training kernels, fp32-stored activations on the split-operand pipes, widths the one-workgroup
@@ -1157,27 +1144,18 @@ class ClassifierOracle(OracleBase):
 
     def _launch_pairs(self, world, req_col, req_tile, tiles, req_orient=None):
         _, _, wg, hid1, D = self._split_first_layer()
-        w2p, b2, hid2, packed = self._padded_second_layer()
+        img = self._pair_image()
         emb = self._embedding_network.linear
         dev = world._device
         up = lambda a: a if isinstance(a, torch.Tensor) else torch.as_tensor(a).to(dev)
-        rc, rt = up(req_col), up(req_tile)
-        ro = None if req_orient is None else up(req_orient)
-        if isinstance(packed, tuple) and packed[0] == "f16x2":
-            L.pair_ll_h2(world._uv, hid1, world._obj[:, D - 4:], wg, packed[1], b2, hid2, emb.weight, emb.bias, world._img_n_obj,
-                         world._obj_off, max(world._n_list), rc, rt, ro, tiles, -30.0, uv_prescaled=True)
-        elif isinstance(packed, tuple) and packed[0] == "f16":
-            L.pair_ll_h1(world._uv, hid1, world._obj[:, D - 4:], wg, packed[1], b2, hid2, emb.weight, emb.bias, world._img_n_obj,
-                         world._obj_off, max(world._n_list), rc, rt, ro, tiles, -30.0, uv_prescaled=True)
-        elif isinstance(packed, tuple):
-            L.pair_ll_split(world._uv, hid1, world._obj[:, D - 4:], wg, packed[1], b2, hid2, emb.weight, emb.bias, world._img_n_obj,
-                            world._obj_off, max(world._n_list), rc, rt, ro, tiles, -30.0)
-        elif packed is not None:
-            L.pair_ll_packed(world._uv, hid1, world._obj[:, D - 4:], wg, packed, b2, hid2, emb.weight, emb.bias, world._img_n_obj,
-                             world._obj_off, max(world._n_list), rc, rt, ro, tiles, -30.0)
+        rest = (emb.weight, emb.bias, world._img_n_obj, world._obj_off, max(world._n_list), up(req_col), up(req_tile),
+                None if req_orient is None else up(req_orient), tiles, -30.0)
+        if img.image is None:
+            L.pair_ll(world._uv, hid1, world._obj[:, D - 4:], wg, img.w2_padded, img.b2, *rest, hid2=img.hid2)
         else:
-            L.pair_ll(world._uv, hid1, world._obj[:, D - 4:], wg, w2p, b2, emb.weight, emb.bias, world._img_n_obj,
-                      world._obj_off, max(world._n_list), rc, rt, ro, tiles, -30.0, hid2=hid2)
+            kind = L.PAIR_KINDS[img.kind]       # (the wrapper is looked up on L at call time: one name, whoever replaced it)
+            getattr(L, kind.launch)(world._uv, hid1, world._obj[:, D - 4:], wg, img.image, img.b2, img.hid2, *rest,
+                                    **({"uv_prescaled": True} if kind.ln2_units else {}))
 
     def _new_tiles(self, world, count, dtype=torch.float32):
         # the pair kernels write the real ordered pairs (the bf16x3 kernel not even the diagonal): absent everywhere else
@@ -1239,8 +1217,10 @@ class ClassifierOracle(OracleBase):
             return
         total = sum(len(e[0].cols) for e in entries)
         # bf16 storage only when every consumer is the fused single-posterior kernel (relate / verify_rel), which reads it directly
-        bf16 = self._tile_dtype == torch.bfloat16 and world._NS % 8 == 0 and self._padded_second_layer()[3] is not None and \
-            self._padded_second_layer()[2] > 256 and all(ob._op_name != "choose_rel" for ob in program_batch._op_batch_list)
+        bf16 = self._tile_dtype == torch.bfloat16 and world._NS % 8 == 0 and all(ob._op_name != "choose_rel" for ob in program_batch._op_batch_list)
+        if bf16:
+            img = self._pair_image()
+            bf16 = L.pair_tiles_bf16_ok(img.w2_padded.shape[1], img.hid2)
         if world._shared:
             return self._prefetch_relations_shared(world, program_batch, entries, torch.bfloat16 if bf16 else torch.float32, fused)
         tiles = self._new_tiles(world, total, torch.bfloat16 if bf16 else torch.float32)

@@ -382,7 +382,7 @@ def test_through_the_interpreter(models, shared, monkeypatch):
         assert torch.equal(fresh.view(torch.int16), img.view(torch.int16))
         again = real_h1(uv, hid1, pos, wg, fresh, b2, hid2, ew, eb, n_obj, off, max_n, rc, rt, ro, torch.full_like(tiles, -30.0), **kw)
         assert torch.equal(again.view(torch.int32), produced.view(torch.int32))
-        img2 = by_key["f16"]._oracle._padded_second_layer("f16x2")[3][1]
+        img2 = by_key["f16"]._oracle._pair_image("f16x2").image
         two = real_h2(uv, hid1, pos, wg, img2, b2, hid2, ew, eb, n_obj, off, max_n, rc, rt, ro, torch.full_like(tiles, -30.0), **kw)
         differs |= not torch.equal(two, produced)
         assert (two - produced).abs().max().item() < 1e-2
@@ -437,7 +437,7 @@ def test_training_ignores_the_key(models, monkeypatch):
 
 def test_both_images_stay_packed_inside_the_scope(models, monkeypatch):
     """Inside a `pair_math: f16` scope the train gate asks for the f16x2 image between requests for the f16 one: W2 is packed once per
-    arithmetic, not once per switch, and clearing `_w2_cache` drops both entries."""
+    arithmetic, not once per switch, and clearing `_w2_cache` drops every entry."""
     from dfol_vqa_amd import _lib, ops
     oracle = models[0]["f16"]._oracle
     monkeypatch.delenv("DFOL_PAIR_MATH", raising=False)
@@ -447,10 +447,99 @@ def test_both_images_stay_packed_inside_the_scope(models, monkeypatch):
         monkeypatch.setattr(ops, name, lambda *a, _real=real, _name=name, **k: (packs.append(_name), _real(*a, **k))[1])
     oracle._w2_cache = None
     with _lib.pair_math_scope("f16"):
-        first = oracle._padded_second_layer()[3]
-        two = oracle._padded_second_layer("f16x2")[3]
+        first = oracle._pair_image()
+        two = oracle._pair_image("f16x2")
         for _ in range(3):
-            assert oracle._padded_second_layer()[3][1] is first[1] and oracle._padded_second_layer("f16x2")[3][1] is two[1]
-    assert (first[0], two[0]) == ("f16", "f16x2") and sorted(packs) == ["pair_pack_w2_h1", "pair_pack_w2_h2"], packs
+            assert oracle._pair_image().image is first.image and oracle._pair_image("f16x2").image is two.image
+    assert (first.kind, two.kind) == ("f16", "f16x2") and sorted(packs) == ["pair_pack_w2_h1", "pair_pack_w2_h2"], packs
     oracle._w2_cache = None
-    assert oracle._padded_second_layer()[3][0] == "f16x2" and oracle._w2_cache_other is None
+    assert oracle._pair_image().kind == "f16x2"
+    assert [(math, img.kind) for math, img in oracle._w2_cache[1].items()] == [("f16x2", "f16x2")]      # exactly one entry: the f16x2 image
+
+
+# ---- every form of the second layer through the one launch path -----------------------------------------------------------------------------
+# kind -> (pair_math scope, DFOL_PAIR_PACKED, the _lib wrapper that launches it, the _lib wrapper that packs its image, U | V prescaled by log2 e);
+# written out here, not read from _lib.PAIR_KINDS: the table is what is under test
+FORMS = {"f16x2": ("f16x2", None, "pair_ll_h2", "pair_pack_w2_h2", True), "f16": ("f16", None, "pair_ll_h1", "pair_pack_w2_h1", True),
+         "bf16x3": ("bf16x3", None, "pair_ll_split", "pair_pack_w2_split", False), "packed": ("f32", None, "pair_ll_packed", "pair_pack_w2", False),
+         "plain": ("f32", "0", "pair_ll", None, False)}
+
+
+def test_every_kind_launches_its_own_wrapper(models, monkeypatch):
+    """One shared-scene batch of three images with 1, 2 and 9 objects (no pair; the smallest image with an ordered pair; 72 pairs, so a
+    workgroup's 256 slots straddle images), two relation columns per image, in each of the five kinds in turn: the tiles _launch_pairs
+    writes are bit for bit those of the kind's _lib wrapper called directly on an image packed here from the model's own W2; the
+    executor's log-probabilities are the Python loop's bit for bit; the executor's model struct carries the header's code of the kind."""
+    import re
+    from dfol_vqa_amd import _lib, native_exec
+    from dfol_vqa_amd import synthetic as syn
+    from test_interpreter_gpu import DEV, TableCollater
+    by_key, ont, names, _ = models
+    model = by_key["default"]
+    oracle = model._oracle
+    monkeypatch.delenv("DFOL_PAIR_MATH", raising=False)
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "dfol_vqa.h")).read()
+    codes = {name.lower(): int(value) for name, value in re.findall(r"#define\s+DFOL_PAIR_([A-Z0-9]+)\s+(\d+)", header)}
+    assert set(codes) == set(FORMS)
+    nouns, attrs, rels = names["nouns"][:4], names["attributes"][:3], names["relations"][:2]
+    scenes = [syn.feature_scene(4300 + i, n, 2048) for i, n in enumerate((1, 2, 9))]
+    qs = []
+    for i in range(6):                                           # two questions per image, one relation each: K = 2 distinct requests per image
+        br = [[syn.op("select", nouns[i % 4]), syn.op("filter", attrs[i % 3]), syn.op("relate", rels[i // 3], True, nouns[(i + 1) % 4])]]
+        qs.append(dict(syn.question(i, br, syn.op("exist"), "yes" if i % 2 else "no", scenes[i % 3]), image_id="img%d" % (i % 3)))
+
+    def pbs_of():
+        return [pb.to_cuda(DEV) for pb in TableCollater(1, ont, "X", share_scenes=True).collate([dict(q) for q in qs])]
+
+    launches = []
+    real_launch = oracle._launch_pairs
+
+    def spy(world, req_col, req_tile, tiles, req_orient=None):
+        real_launch(world, req_col, req_tile, tiles, req_orient)
+        launches.append((world, req_col, req_tile, req_orient, tiles.clone()))
+
+    monkeypatch.setattr(oracle, "_launch_pairs", spy)
+    lin1, lin2 = [m for m in oracle._relation_network._network if isinstance(m, torch.nn.Linear)]
+    w1, w2 = lin1.weight.detach(), lin2.weight.detach()
+    D = (w1.shape[1] - 4) // 2
+    assert tuple(w2.shape) == (HID2, HID1)
+    wg, b2 = w1[:, 2 * D:].contiguous(), lin2.bias.detach().contiguous()
+    w2_padded = torch.zeros(320, HID1, device=w2.device)
+    w2_padded[:HID2] = w2
+    emb = oracle._embedding_network.linear
+
+    def forget():                                                # (neither cache is keyed by DFOL_PAIR_PACKED)
+        oracle._w2_cache = None
+        model.__dict__.pop("_native_model", None)
+
+    results = {}
+    try:
+        for kind, (math, packed_env, launch, pack, prescaled) in FORMS.items():
+            if packed_env is not None:
+                monkeypatch.setenv("DFOL_PAIR_PACKED", packed_env)
+            forget()
+            del launches[:]
+            with _lib.pair_math_scope(math):
+                results[kind] = _both_routes(model, pbs_of, monkeypatch)["log_probability"]
+                assert oracle._pair_kind() == kind
+                assert native_exec.native_model(model).struct.pair_kind == codes[kind], kind
+            assert len(launches) == 1, (kind, len(launches))     # the Python loop's one launch (the executor calls C directly)
+            world, rc, rt, ro, produced = launches[0]
+            assert tuple(rc.shape) == (2, 3) and world._img_n_list == [1, 2, 9] and produced.dtype == torch.float32
+            head = (world._uv, HID1, world._obj[:, D - 4:], wg)
+            rest = (emb.weight, emb.bias, world._img_n_obj, world._obj_off, 9, rc, rt, ro, torch.full_like(produced, -30.0), -30.0)
+            if pack is None:
+                again = _lib.pair_ll(*head, w2_padded, b2, *rest, hid2=HID2)
+            else:
+                image = getattr(_lib, pack)(w2_padded, HID2)
+                again = getattr(_lib, launch)(*head, image, b2, HID2, *rest, **({"uv_prescaled": True} if prescaled else {}))
+            assert torch.equal(again.view(torch.int32), produced.view(torch.int32)), kind
+            wrote = (produced != -30.0).flatten(1).sum(1).cpu().numpy()[rt.cpu().numpy()]          # [K, images]
+            assert (wrote[:, 0] == 0).all() and (wrote[:, 1] == 2).all() and (wrote[:, 2] == 72).all(), (kind, wrote)
+    finally:
+        monkeypatch.delenv("DFOL_PAIR_PACKED", raising=False)
+        forget()
+    # the arithmetics are different kernels: the reduced mode and the default do not answer with the same bits, and all stay close
+    assert not torch.equal(results["f16"], results["f16x2"])
+    for kind, lp in results.items():
+        assert (lp - results["packed"]).abs().max().item() < 1e-2, kind

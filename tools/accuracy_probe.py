@@ -175,7 +175,7 @@ def main():
                         "torch32": stats(st["hidden_attr"], s64["hidden_attr"])}
     # (the fp16x2 pair kernel takes U | V in units of ln 2: the oracle scales the stacked first-layer weight by log2 e)
     with L.pair_math_scope(getattr(model, "_pair_math", None)):
-        scaled = model._oracle._pair_kind() in ("f16x2", "f16")
+        scaled = L.PAIR_KINDS[model._oracle._pair_kind()].ln2_units
     uv_hip = world._uv.cpu().numpy() / (1.4426950408889634 if scaled else 1.0)
     S["uv"] = {"hip": stats(uv_hip, s64["uv"]), "numpy32": stats(s32["uv"], s64["uv"])}
     S["hidden_rel"] = {"numpy32": stats(s32["hidden_rel"], s64["hidden_rel"]), "torch32": stats(st["hidden_rel"], s64["hidden_rel"])}
