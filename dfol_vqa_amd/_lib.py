@@ -6,6 +6,7 @@ There is no CPU fallback: if `libdfolvqa.so` is missing, or a tensor is not a co
 
 import ctypes
 import os
+import threading
 
 import torch
 
@@ -101,6 +102,7 @@ SIGNATURES = {
     "dfol_gather_rows_f32": [_p, _p, _i32, _i32, _p, _p],
     "dfol_gather_object_rows_f32": [_p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _p],
     "dfol_store_rows_f32": [_p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p],
+    "dfol_store_objects_f32": [_p, _i64, _p, _p, _i32, _i32, _p, _i64, _p],
     "dfol_segment_sum_rows_f32": [_p, _p, _i32, _i32, _p, _p],
     "dfol_logic_f32": [_i32, _p, _p, _i64, _p, _p],
     "dfol_parametric_not_f32": [_p, _p, _i32, _i32, _p, _p],
@@ -201,6 +203,7 @@ SIGNATURES = {
     "dfol_run_program": [_p, _p, _p, _i32, _p, _p, _p],
     "dfol_set_range_status": [_p],
     "dfol_set_feature_rows": [_p, _p],
+    "dfol_set_feature_cache": [_p, _i64, _i32, _p, _p],
 }
 
 
@@ -313,6 +316,7 @@ RANGE_X_OVERFLOW = 1
 RANGE_PAIR_SATURATED = 2
 _RANGE_WORDS = {}
 _RANGE_RING = 8
+_RANGE_ACTIVE = threading.local()    # .word: the status word of this thread's open RangeWatch (a watch opened inside another hands it back)
 
 
 class RangeWatch(object):
@@ -334,6 +338,7 @@ class RangeWatch(object):
             word = ring[0][ring[1] % _RANGE_RING:ring[1] % _RANGE_RING + 1]
             ring[1] += 1
         self.word, self.device = word, dev
+        self._outer, _RANGE_ACTIVE.word = getattr(_RANGE_ACTIVE, "word", None), word
         load().dfol_set_range_status(word.data_ptr())           # (thread-local in the library: the launches of THIS thread carry it)
 
     def finish(self):
@@ -348,7 +353,9 @@ class RangeWatch(object):
         # starts from a clean word instead of inheriting this one's flag until the host gets round to its check
         self.word.zero_()
         # the library's pointer is a thread-local of THIS thread: later direct calls - possibly on another device - must not OR into this word
-        load().dfol_set_range_status(None)
+        # (a watch opened inside another one - the feature store building its cache on a forward's first use - hands the outer word back)
+        _RANGE_ACTIVE.word = self._outer
+        load().dfol_set_range_status(None if self._outer is None else self._outer.data_ptr())
         word, dev = self.word, self.device
         # (an event behind the copy: waiting for the STREAM would also wait for whatever was queued after this forward - the next batch of a
         # pipelined loop; a captured forward has no event of its own: its replay's owner waits for the stream)
@@ -378,6 +385,12 @@ class RangeWatch(object):
                                 "DFOL_DENSE_MATH=bf16x3 / DFOL_PAIR_MATH=bf16x3, or normalise the features." % "; ".join(what))
         check.range_check = True
         return check
+
+
+def range_status_off():
+    """No status word on this thread: what a forward does on its way out, also when it raised before its watch finished."""
+    _RANGE_ACTIVE.word = None
+    load().dfol_set_range_status(None)
 
 
 _RANGE_HOSTS = []
@@ -566,6 +579,21 @@ def store_rows(boxes, sizes, slot, obj_off, src_row, box6):
     call("dfol_store_rows_f32", _ptr(boxes, F32), _ptr(sizes, F32), _ptr(slot, I32), _ptr(obj_off, I32), slot.numel(), S, max_obj,
          _ptr(src_row, I32), _ptr(box6, F32), _stream())
     return src_row, box6
+
+
+def store_objects(cache, src_row, box6, out=None):
+    """The object matrix of a store-backed batch from cached featurizer outputs (csrc/dfol_store.hip): out[r] = [cache[src_row[r]], box positions
+    of box6[r]], [O, W + 4]; cache [rows, W] fp32 with unit column stride, src_row [O] int32 and box6 [O, 6] from store_rows.  out=: rows of
+    unit column stride and at least W + 4 columns; columns beyond W + 4 are left alone."""
+    O, W = src_row.numel(), cache.shape[1]
+    if cache.dim() != 2 or cache.dtype != F32 or cache.stride(1) != 1 or src_row.dim() != 1 or tuple(box6.shape) != (O, 6):
+        raise DfolError("store_objects: cache [rows, W] fp32 with unit column stride, src_row [O] int32 and box6 [O, 6] fp32")
+    if out is None:
+        out = torch.empty(O, W + 4, dtype=F32, device=cache.device)
+    elif out.dim() != 2 or out.shape[0] != O or out.dtype != F32 or out.stride(1) != 1 or out.device != cache.device:
+        raise DfolError("store_objects: out= must be [%d, >= %d] fp32 rows of unit column stride on %s" % (O, W + 4, cache.device))
+    call("dfol_store_objects_f32", _dp(cache), cache.stride(0), _ptr(src_row, I32), _ptr(box6, F32), O, W, _dp(out), out.stride(0), _stream())
+    return out
 
 
 def segment_sum_rows(src, seg_off):

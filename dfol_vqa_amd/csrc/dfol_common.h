@@ -78,6 +78,11 @@ __device__ __forceinline__ float dfol_act(float x) {
     return x;
 }
 
+// ---- box positions ----------------------------------------------------------------------------------------------------------------
+// batch_gqa_boxfeatures_pipeline.py:208-211: position column k of {x, y, w, h} / max({W, H, W, H}, 1) from t = (W, H, x, y, w, h); one fp32
+// division per column, shared by box_positions_kernel and the feature store's cached-row kernel so the two agree bit for bit
+__device__ __forceinline__ float dfol_box_position(const float* t, int k) { return t[2 + k] / fmaxf(t[k & 1], 1.f); }
+
 // ---- object pairs -----------------------------------------------------------------------------------------------------------------
 // batch_gqa_boxfeatures_pipeline.py:263-279: {distance, angle, sign dx, sign dy} of subject box ps and object box po ({x, y, w, h})
 __device__ __forceinline__ float4 dfol_pair_geometry(const float* ps, const float* po) {

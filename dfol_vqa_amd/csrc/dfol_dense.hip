@@ -209,12 +209,9 @@ __global__ void box_positions_kernel(const float* __restrict__ raw, int64_t ld_r
     const int o = blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= O) return;
     const float* t = raw + (int64_t)o * ld_raw + raw_cols - 6;      // (W, H, x, y, w, h)
-    const float Wc = fmaxf(t[0], 1.f), Hc = fmaxf(t[1], 1.f);      // clamp(1), batch_gqa_boxfeatures_pipeline.py:209
     float* d = obj + (int64_t)o * ld_obj + pos_col;
-    d[0] = t[2] / Wc;
-    d[1] = t[3] / Hc;
-    d[2] = t[4] / Wc;
-    d[3] = t[5] / Hc;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) d[k] = dfol_box_position(t, k);    // clamp(1) and divide, batch_gqa_boxfeatures_pipeline.py:209
 }
 
 extern "C" int dfol_box_positions_f32(const float* raw, int64_t ld_raw, int32_t raw_cols, int32_t O, float* obj, int64_t ld_obj,

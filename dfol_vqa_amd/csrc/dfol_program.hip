@@ -126,8 +126,24 @@ static_assert(DFOL_PAIR_PACKED == 1 && DFOL_PAIR_BF16X3 == 2 && DFOL_PAIR_F16X2 
 // dfol_set_feature_rows: the index form of the NEXT dfol_run_program's scene on this thread
 thread_local const int32_t* g_feature_src_row = nullptr;
 thread_local const float* g_feature_box6 = nullptr;
+// dfol_set_feature_cache: the cached form of the same (the featurizer's outputs instead of its inputs)
+struct FeatureCache {
+    const float* cache;
+    int64_t ld;
+    int32_t W;
+    const int32_t* src_row;
+    const float* box6;
+};
+thread_local FeatureCache g_feature_cache = {nullptr, 0, 0, nullptr, nullptr};
 
 }  // namespace
+
+extern "C" int dfol_set_feature_cache(const float* cache, int64_t ld_cache, int32_t W, const int32_t* src_row, const float* box6) {
+    DFOL_REQUIRE((cache == nullptr) == (src_row == nullptr) && (cache == nullptr) == (box6 == nullptr), "set_feature_cache: cache, src_row and box6 come together");
+    DFOL_REQUIRE(cache == nullptr || (W > 0 && ld_cache >= W), "set_feature_cache: bad sizes W=%d ld_cache=%lld", W, (long long)ld_cache);
+    g_feature_cache = FeatureCache{cache, ld_cache, W, src_row, box6};
+    return 0;
+}
 
 extern "C" int dfol_set_feature_rows(const int32_t* src_row, const float* box6) {
     DFOL_REQUIRE((src_row == nullptr) == (box6 == nullptr), "set_feature_rows: src_row and box6 come together");
@@ -144,6 +160,8 @@ extern "C" int dfol_run_program(const DfolProgramModel* model, const DfolProgram
     const float* box6 = g_feature_box6;
     g_feature_src_row = nullptr;
     g_feature_box6 = nullptr;
+    const FeatureCache cached = g_feature_cache;
+    g_feature_cache = FeatureCache{nullptr, 0, 0, nullptr, nullptr};
     DFOL_REQUIRE(model && scene && instr_host && blob && workspace, "run_program: null pointer");
     DFOL_REQUIRE(n_instr >= 0 && scene->NS > 0 && scene->NS % 4 == 0, "run_program: bad sizes (n_instr %d, NS %d)", n_instr, scene->NS);
     const int32_t NS = scene->NS;
@@ -159,6 +177,7 @@ extern "C" int dfol_run_program(const DfolProgramModel* model, const DfolProgram
                 const DfolDenseLayer* layers = a[1] == 0 ? model->featurizer : (a[1] == 1 ? model->attribute : &model->uv);
                 const int32_t count = a[1] == 0 ? model->n_featurizer : (a[1] == 1 ? model->n_attribute : 1);
                 DFOL_REQUIRE(layers && a[2] >= 0 && a[2] < count, "run_program[%d]: dense layer %lld of set %lld does not exist", i, (long long)a[2], (long long)a[1]);
+                if (a[1] == 0 && cached.cache != nullptr) break;    // the featurizer's output comes from the cache (DFOL_OP_BOX_POSITIONS writes it)
                 const float* X = a[3] == 0 ? scene->features + a[4] / 4 : static_cast<const float*>(at(workspace, a[4]));
                 DfolDenseLayer layer = layers[a[2]];
                 if (a[9]) layer.act = DFOL_ACT_NONE;
@@ -175,6 +194,13 @@ extern "C" int dfol_run_program(const DfolProgramModel* model, const DfolProgram
                 break;
             }
             case DFOL_OP_BOX_POSITIONS:  // obj, ld_obj, pos_col
+                if (cached.cache != nullptr) {                      // (cached form: the object matrix's feature columns and its positions in one launch)
+                    DFOL_REQUIRE(a[3] == cached.W, "run_program[%d]: cached featurizer rows of %d columns for an object matrix of %lld + 4", i, cached.W,
+                                 (long long)a[3]);
+                    rc = dfol_store_objects_f32(cached.cache, cached.ld, cached.src_row, cached.box6, scene->O, cached.W, static_cast<float*>(at(workspace, a[1])),
+                                                a[2], stream);
+                    break;
+                }
                 if (box6 != nullptr) {                              // (index form: the six box columns travel beside the row numbers)
                     rc = dfol_box_positions_f32(box6, 6, 6, scene->O, static_cast<float*>(at(workspace, a[1])), a[2], static_cast<int32_t>(a[3]), stream);
                     break;

@@ -11,6 +11,9 @@
 //
 // The index form (a `direct` store): the same batch as O row numbers into the store's [S * max_obj, F] table and its six box columns - 28 bytes
 // per object instead of 4 (F + 6) - for the consumer that reads the table's rows itself (dfol_linear_wide_rows_h2_f32).
+//
+// The cached form (a `featurized` store): the batch's object matrix [O, W + 4] from the cached OUTPUT of a frozen featurizer for every table
+// row - the indexed rows of the cache beside their box positions, one launch instead of the featurizer's products (store_objects_kernel).
 #include "dfol_common.h"
 
 namespace {
@@ -105,7 +108,71 @@ __global__ __launch_bounds__(SR_THREADS) void store_rows_kernel(const float* __r
     d[2] = x1, d[3] = y1, d[4] = x2 - x1, d[5] = y2 - y1;
 }
 
+// The cached form (a `featurized` store): object row r = [cache[src_row[r]][0:W], box positions of box6[r]] - the featurizer's output for a
+// frozen featurizer, read back instead of recomputed.  As the gather: a pure copy, a wavefront per row and 16-byte loads; rows of W <= 128
+// take LPR = 8 .. 32 lanes each (a power of two >= W / 4: one 16-byte piece per lane), 64 / LPR rows per wavefront.  An output row starts
+// at any multiple of 4 bytes, so the store width follows the row's address (uniform over the row's lanes).  Lanes 0 .. 3 of a row write
+// its position columns by dfol_box_position, box_positions_kernel's arithmetic.  src_row is trusted, as in wide_h2_kernel<ROWS>.
+template <bool VEC>
+__global__ __launch_bounds__(ST_WAVES * 64) void store_objects_kernel(const float* __restrict__ cache, int64_t ld_cache,
+                                                                      const int32_t* __restrict__ src_row, const float* __restrict__ box6, int O,
+                                                                      int W, int lpr, float* __restrict__ out, int64_t ld_out) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int rpw = 64 / lpr, sub = lane / lpr, l = lane & (lpr - 1);
+    const int64_t step = (int64_t)gridDim.x * ST_WAVES * rpw;
+    for (int64_t r = ((int64_t)blockIdx.x * ST_WAVES + wave) * rpw + sub; r < O; r += step) {
+        const float* src = cache + (int64_t)src_row[r] * ld_cache;
+        float* dst = out + r * ld_out;
+        if (VEC) {
+            const float4* src4 = reinterpret_cast<const float4*>(src);
+            const unsigned mis = (unsigned)(reinterpret_cast<uintptr_t>(dst) & 15);
+            const int n4 = W >> 2;
+            if (lpr == 64) {
+                if (mis == 0)
+                    st_copy_row<4>(src4, dst, n4, lane);
+                else if (mis == 8)
+                    st_copy_row<2>(src4, dst, n4, lane);
+                else
+                    st_copy_row<1>(src4, dst, n4, lane);
+            } else if (l < n4) {                                     // (n4 <= lpr: the host chose lpr so)
+                const float4 v = src4[l];
+                if (mis == 0)
+                    st_store<4>(dst + 4 * l, v);
+                else if (mis == 8)
+                    st_store<2>(dst + 4 * l, v);
+                else
+                    st_store<1>(dst + 4 * l, v);
+            }
+            if (l < (W & 3)) dst[4 * n4 + l] = src[4 * n4 + l];      // (a table whose row stride, but not W, is a multiple of four floats)
+        } else {
+            for (int c = l; c < W; c += lpr) dst[c] = src[c];
+        }
+        if (l < 4) dst[W + l] = dfol_box_position(box6 + r * 6, l);
+    }
+}
+
 }  // namespace
+
+extern "C" int dfol_store_objects_f32(const float* cache, int64_t ld_cache, const int32_t* src_row, const float* box6, int32_t O, int32_t W, float* out,
+                                      int64_t ld_out, void* stream) {
+    DFOL_REQUIRE(O >= 0 && W > 0 && ld_cache >= W, "store_objects: bad sizes O=%d W=%d ld_cache=%lld", O, W, (long long)ld_cache);
+    DFOL_REQUIRE(ld_out >= (int64_t)W + 4, "store_objects: ld_out=%lld is less than W + 4 = %d", (long long)ld_out, W + 4);
+    if (O == 0) return 0;
+    DFOL_REQUIRE(cache && src_row && box6 && out, "store_objects: null pointer");
+    int lpr = 8;                                                     // lanes per row: a 16-byte piece each up to W = 128, then the whole wavefront
+    while (lpr < 64 && 4 * lpr < W) lpr *= 2;
+    const int waves = dfol_cdiv(O, 64 / lpr);
+    int blocks = dfol_cdiv(waves, ST_WAVES);
+    blocks = blocks < ST_TARGET_WAVES / ST_WAVES ? blocks : ST_TARGET_WAVES / ST_WAVES;
+    const dim3 grid(blocks), block(ST_WAVES * 64);
+    const bool vec = ld_cache % 4 == 0 && (reinterpret_cast<uintptr_t>(cache) & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL(store_objects_kernel<true>, grid, block, 0, (hipStream_t)stream, cache, ld_cache, src_row, box6, O, W, lpr, out, ld_out);
+    else
+        hipLaunchKernelGGL(store_objects_kernel<false>, grid, block, 0, (hipStream_t)stream, cache, ld_cache, src_row, box6, O, W, lpr, out, ld_out);
+    DFOL_LAUNCH_CHECK("store_objects");
+    return 0;
+}
 
 extern "C" int dfol_store_rows_f32(const float* store_boxes, const float* store_sizes, const int32_t* slot, const int32_t* obj_off, int32_t I, int32_t S,
                                    int32_t max_obj, int32_t* src_row, float* box6, void* stream) {

@@ -10,6 +10,11 @@ A store built with `direct=True` resolves a ref into a `StoreRows` instead: the 
 six box columns (28 bytes per object).  The featurizer's first product then reads the table through the row numbers
 (csrc/dfol_dense_wide.hip, ROWS) and the `[O, F + 6]` matrix is never written; whoever needs the matrix calls `StoreRows.materialize()`.
 
+A store built with `featurized=True` (which implies the index form) also keeps the OUTPUT of a frozen featurizer for every row of its table:
+`featurize(net)` runs the network over the table once, `StoreRows.objects(cache)` gathers a batch's cached rows beside their box positions
+(dfol_store_objects_f32) and no featurizer product runs per batch.  The cache is keyed by the network's weight versions; `release_raw()`
+then frees the raw features (a quarter of the memory is left at 2048 -> 512).
+
 Three kinds of object, by who may hold them:
   DeviceFeatureStore   main process only: the device tensors, `gather`.  Registers itself by id in this process' table.
   FeatureStoreIndex    `store.index`: host-only and picklable, image id -> (slot or -1, object count).  This is what a collator - and so
@@ -76,6 +81,40 @@ def check_row_space(S, max_obj):
     if int(S) * int(max_obj) >= 2 ** 31:
         raise _lib.DfolError("feature store: S * max_obj = %d x %d rows do not fit int32 row numbers (< 2^31); build the store without direct=True"
                              % (int(S), int(max_obj)))
+
+
+def featurizer_key(net):
+    """What a cache of `net`'s outputs depends on: every parameter's storage and version (an optimizer step, a load_state_dict or any other
+    in-place update bumps the version) and the arithmetic of the dense products."""
+    return (tuple((p.data_ptr(), p._version) for p in net.parameters()), _lib._dense_math())
+
+
+class FeaturizedRows(object):
+    """The host side of a featurized store's cache: the rows, the key they were computed under, and whether the raw features behind them are
+    still there.  No device call: a DeviceFeatureStore owns one and asks it."""
+
+    def __init__(self):
+        self.rows, self.key, self.raw_released, self.builds = None, None, False, 0
+
+    def valid_for(self, net):
+        return self.rows is not None and self.key == featurizer_key(net)
+
+    def set(self, net, rows):
+        self.rows, self.key = rows, featurizer_key(net)
+        self.builds += 1
+        return rows
+
+    def release_raw(self):
+        if self.rows is None:
+            raise _lib.DfolError("feature store: release_raw() before featurize(net): there is no cache to serve batches from")
+        self.raw_released = True
+
+    def need_raw(self, what):
+        if self.raw_released:
+            raise _lib.DfolError("feature store: %s needs the raw features, which release_raw() has freed; build the store again" % what)
+
+
+FEATURIZE_BLOCK_ROWS = 32768                   # rows per product of featurize(): 256 of the wide kernel's 128-row blocks, a shape it takes by default
 
 
 class FeatureStoreIndex(object):
@@ -175,9 +214,13 @@ class DeviceFeatureStore(object):
 
     direct=True (opt-in; recorded on the store only - index, refs and collators are the same): `resolve`, i.e. ProgramBatch.to_cuda, hands the
     batch on as a StoreRows (`rows`) and the featurizer reads the store's rows in place where its first product is one the wide kernel takes;
-    every other consumer materialises the matrix as before."""
+    every other consumer materialises the matrix as before.
 
-    def __init__(self, object_h5_path, file_prefix, chunk_num, object_info_json_path, device, max_bytes=None, direct=False):
+    featurized=True (opt-in; implies direct=True): the store also caches a frozen featurizer's output for every row of its table - `featurize`,
+    `cached_for` - and a batch whose featurizer does not train gets its object matrix from the cache (`StoreRows.objects`); `release_raw()` then
+    frees the raw features."""
+
+    def __init__(self, object_h5_path, file_prefix, chunk_num, object_info_json_path, device, max_bytes=None, direct=False, featurized=False):
         from .data import _open_arrays
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -203,7 +246,10 @@ class DeviceFeatureStore(object):
                 arrays.close()
         self.sizes = torch.from_numpy(sizes).to(self.device)
         self.S, self.max_obj, self.F = S, max_obj, F
-        self.direct = bool(direct)
+        self.featurized = bool(featurized)
+        self.direct = bool(direct) or self.featurized
+        self._featurized = FeaturizedRows()
+        self.cache_nbytes = 0                              # (the cache of featurize(), beside `nbytes` of chunk data)
         if self.direct:
             check_row_space(S, max_obj)
         self.nbytes = S * lay.row_bytes
@@ -242,6 +288,7 @@ class DeviceFeatureStore(object):
         """The batch's `[O, F + 6]` object matrix on the store's device, launched on the current stream.  out=: written into that buffer
         (rows of unit column stride, at least F + 6 columns, O rows) - how the owner of a GraphedForward / GraphedTrainStep serves new scenes
         into its captured batch, BETWEEN replays (see upload_index).  index=: the result of an earlier upload_index(ref)."""
+        self._featurized.need_raw("gather")
         O = int(ref.counts.sum(dtype=np.int64))
         if out is None:
             out = torch.empty((O, self.F + 6), dtype=torch.float32, device=self.device)
@@ -257,6 +304,66 @@ class DeviceFeatureStore(object):
             _lib.gather_object_rows(self.features, self.boxes, self.sizes, idx[:I], idx[I:], out)
         return out
 
+
+    # ---- the cache of a frozen featurizer's rows (featurized=True) -----------------------------------------------------------------------
+    def featurize(self, net):
+        """Run the featurizer network `net` (BatchGQABoxFeaturizer._featurizer_network) over every row of the store's table -> the cache
+        [S * max_obj, W] fp32, kept under the key of net's weight versions.  Blocks of FEATURIZE_BLOCK_ROWS rows: the first layer by the direct
+        route's own product (linear_wide_rows over the table, an identity row block), later layers by linear_act - a row's result does not depend
+        on the rows beside it, so a batch's cached rows are the direct route's.  Refused (DfolError) where the direct route would step aside -
+        no network, another first-layer width, another arithmetic - inside a stream capture, and after release_raw().  An fp16 range flag
+        raises as it would from a forward."""
+        from . import ops as L
+        from .interpreter import store_layers_of
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.DfolError("feature store: featurize() builds the cache of featurizer rows and cannot run inside a stream capture; build it "
+                                 "(or run one eager forward) before the capture")
+        self._featurized.need_raw("featurize() for new featurizer weights")
+        layers, why = store_layers_of(net, self.F, FEATURIZE_BLOCK_ROWS)
+        if layers is None:
+            raise _lib.DfolError("feature store: featurize(): %s" % why)
+        rows, W = self.S * self.max_obj, int(layers[-1][0].weight.shape[0])
+        table = self.features.view(rows, self.F)
+        with torch.no_grad(), torch.cuda.device(self.device):
+            cache = torch.empty((rows, W), dtype=torch.float32, device=self.device)
+            ident = torch.arange(min(rows, FEATURIZE_BLOCK_ROWS), dtype=torch.int32, device=self.device)
+            watch = _lib.RangeWatch(self.device)
+            try:
+                for r0 in range(0, rows, FEATURIZE_BLOCK_ROWS):
+                    n = min(FEATURIZE_BLOCK_ROWS, rows - r0)
+                    x = None
+                    for k, (lin, act) in enumerate(layers):
+                        out = cache[r0:r0 + n] if k == len(layers) - 1 else None
+                        x = _lib.linear_wide_rows(table[r0:], ident[:n], lin.weight, lin.bias, act, out) if k == 0 else \
+                            L.linear_act(x, lin.weight, lin.bias, act, out)
+            finally:
+                check = watch.finish()
+            check()                                        # (waits for the products: the cache is whole, and in range, when this returns)
+        _lib.note("feature_store_featurize")
+        self.cache_nbytes = rows * W * 4
+        return self._featurized.set(net, cache)
+
+    def cached_for(self, net, build=False):
+        """The cache if it was computed with net's current weights, else None.  build=True: a missing or stale cache is built first (once per
+        weight version) - None then means that featurize() does not take this network; after release_raw() that, like a stale cache, raises."""
+        if self._featurized.valid_for(net):
+            return self._featurized.rows
+        if not build:
+            return None
+        from .interpreter import store_layers_of
+        if store_layers_of(net, self.F, FEATURIZE_BLOCK_ROWS)[0] is None and not self._featurized.raw_released:
+            return None                                    # (the batch goes on as a direct store's)
+        return self.featurize(net)                         # (raises inside a capture and after release_raw())
+
+    def release_raw(self):
+        """Free the raw features once a cache exists: the store then serves frozen-featurizer batches only, in a quarter of the memory at
+        2048 -> 512.  Explicit and one-way: `gather`, `StoreRows.materialize`, a featurizer that trains and `featurize` for new weights raise a
+        DfolError naming this call."""
+        self._featurized.release_raw()
+        if self.features is not None:
+            self.nbytes -= self.features.numel() * 4
+            self.features = None
+        return self
 
     def rows(self, ref, out=None, index=None):
         """The batch in index form -> StoreRows (src_row [O] int32, box6 [O, 6], this store's table), one small launch on the current stream.
@@ -289,7 +396,7 @@ class StoreRows(object):
 
     def __init__(self, store, src_row, box6, index, parent=None, picked=None):
         self.store, self.src_row, self.box6 = store, src_row, box6
-        self.table = store.features.view(store.S * store.max_obj, store.F)
+        self.table = None if store.features is None else store.features.view(store.S * store.max_obj, store.F)      # (None: release_raw())
         self.O = int(src_row.numel())
         self._index = index                                # device [slot (I) | obj_off (I + 1)] of the ref, or None: a selection of `parent`'s rows
         self._parent, self._picked = parent, picked
@@ -305,6 +412,7 @@ class StoreRows(object):
     def materialize(self, out=None):
         """The `[O, F + 6]` matrix, bit for bit `store.gather(ref)` (the same kernel through the same index arrays)."""
         st = self.store
+        st._featurized.need_raw("StoreRows.materialize() (a featurizer that trains, a stale cache, or a consumer of the [O, F + 6] matrix)")
         if self._index is None:                            # selected rows: the parent's matrix, then the selection - what build_scene did before
             m = self._parent.materialize().index_select(0, self._picked)
             return m if out is None else out.copy_(m)
@@ -317,6 +425,15 @@ class StoreRows(object):
             with torch.cuda.device(st.device):
                 _lib.gather_object_rows(st.features, st.boxes, st.sizes, self._index[:I], self._index[I:], out)
         return out
+
+    def objects(self, cache, out=None):
+        """The object matrix `[O, W + 4]` of the batch from a featurized store's cache (`store.featurize(net)` / `cached_for(net)`): the cached
+        rows of src_row beside the box positions of box6, one launch (dfol_store_objects_f32).  A selection of rows has it too."""
+        st = self.store
+        if cache.dim() != 2 or cache.shape[0] != st.S * st.max_obj or cache.device != st.device:
+            raise _lib.DfolError("feature store: cache must be [%d, W] on %s, got %s on %s" % (st.S * st.max_obj, st.device, tuple(cache.shape), cache.device))
+        with torch.cuda.device(st.device):
+            return _lib.store_objects(cache, self.src_row, self.box6, out)
 
     def select_rows(self, rows):
         """The StoreRows of rows `rows` (int64 device tensor, repeats allowed) of this one: the two small arrays composed, no feature row moved."""

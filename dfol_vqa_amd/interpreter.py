@@ -32,6 +32,33 @@ def gather_results(outputs, target_device=None, is_cuda=True):
             'answer_log_probability': answer_log_probability}
 
 
+def featurizer_trains(net):
+    """A gradient reaches the featurizer network's weights under the current grad mode: its output is then part of the graph, not a constant."""
+    return torch.is_grad_enabled() and any(p.requires_grad for p in net.parameters())
+
+
+def store_layers_of(net, F, M):
+    """-> (the featurizer network's layers [(Linear, activation)], None) when its first product can read M rows of a feature store of width F in
+    place - the two-piece fp16 arithmetic on a weight of the split kernels' size, the store's width, a shape the wide kernel takes and pays for
+    (dfol_linear_wide_supported) - else (None, why not).  ONE predicate for the direct route (M = the batch's rows), the executor and the store's
+    cache builder (M = its row block)."""
+    from . import _lib, native_exec
+    if net is None or getattr(net, "_network", None) is None or not hasattr(net, "output_width"):
+        return None, "the featurizer has no network"
+    layers = native_exec._layers(net._network)
+    if not layers:
+        return None, "the featurizer network is not a chain of Linear layers and activations (or a Dropout is active)"
+    if _lib._dense_math() != "f16x2":
+        return None, "the dense arithmetic is %r, not 'f16x2'" % _lib._dense_math()
+    w = layers[0][0].weight
+    N, K = w.shape
+    if K != F:
+        return None, "the featurizer's first layer takes %d features, the store holds %d" % (K, F)
+    if N * K < _lib.SPLIT_MIN_WEIGHT or w.stride(1) != 1 or not _lib.linear_wide_supported(M, N, K):
+        return None, "the wide kernel does not take a %d -> %d product over %d rows" % (K, N, M)
+    return layers, None
+
+
 class BatchGQABoxFeaturizer(nn.Module):
     """Object and pair features of a scene (batch_gqa_boxfeatures_pipeline.py:193-281).
 
@@ -47,25 +74,30 @@ class BatchGQABoxFeaturizer(nn.Module):
         inference, the two-piece fp16 arithmetic on a weight of the split kernels' size, the store's feature width, and a shape the wide kernel
         takes and pays for (dfol_linear_wide_supported - the same question the tiled kernel asks before it forwards there, so either route runs
         the same kernel body on the same rows).  None: the caller materialises the matrix and goes on as ever."""
-        from . import _lib, native_exec
         net = self._featurizer_network
-        if net is None or getattr(net, "_network", None) is None or not hasattr(net, "output_width") or rows.O == 0:
+        if rows.O == 0 or (net is not None and featurizer_trains(net)):
             return None
-        if torch.is_grad_enabled() and any(p.requires_grad for p in net.parameters()):
+        return store_layers_of(net, rows.store.F, rows.O)[0]
+
+    def _cached_objects(self, rows):
+        """The object matrix of a `featurized` store's batch from the store's cached featurizer rows (feature_store.DeviceFeatureStore.featurize:
+        built on first use, rebuilt once when a weight's version has changed), or None: a store without a cache, a featurizer that trains under
+        the current grad mode (its output is no constant), or a network the cache cannot be built for - the caller goes on as for a direct store."""
+        net = self._featurizer_network
+        if not getattr(rows.store, "featurized", False) or net is None or featurizer_trains(net):
             return None
-        layers = native_exec._layers(net._network)
-        if not layers or _lib._dense_math() != "f16x2":
-            return None
-        w = layers[0][0].weight
-        N, K = w.shape
-        if N * K < _lib.SPLIT_MIN_WEIGHT or w.stride(1) != 1 or K != rows.store.F or not _lib.linear_wide_supported(rows.O, N, K):
-            return None
-        return layers
+        cache = rows.store.cached_for(net, build=True)
+        return None if cache is None else rows.objects(cache)
 
     def featurize_scene(self, device, objects_list, batch_index, meta_data, world_geometry=None):
         from . import _lib
         from .feature_store import StoreRows
         if isinstance(objects_list, StoreRows):
+            obj = self._cached_objects(objects_list)
+            if obj is not None:
+                # a frozen featurizer over a featurized store: its rows were computed once, the batch's are gathered beside their box positions
+                _lib.note("feature_store_featurized")
+                return self._with_pairs(obj, obj.shape[1], objects_list.O, world_geometry)
             layers = self._store_layers(objects_list)
             if layers is not None:
                 # the index form of a store-backed batch: the first product gathers the store's rows through src_row, the rest is as below
@@ -374,7 +406,7 @@ class BatchInterpreterBase(nn.Module):
         finally:
             gqa_ops.DEFERRED.queue = outer
             if watch is not None:
-                _lib.load().dfol_set_range_status(None)          # (also when the forward raised before watch.finish())
+                _lib.range_status_off()                          # (also when the forward raised before watch.finish())
         if outer is None:
             for fill in queue:
                 fill()

@@ -276,8 +276,17 @@ def run(model, program_batch, plan, queue, give_answer=True):
     feats = program_batch._object_features
     device = feats.device
     nm = native_model(model)
-    rows = None
-    if hasattr(feats, "materialize"):
+    rows = cache = None
+    if hasattr(feats, "materialize") and getattr(feats.store, "featurized", False):
+        # A featurized store's batch: the featurizer's rows come from the store's cache (built on first use, rebuilt once per weight version) -
+        # the question BatchGQABoxFeaturizer._cached_objects asks; the executor skips the featurizer's products (dfol_set_feature_cache).
+        from .interpreter import featurizer_trains
+        net = model._featurizer._featurizer_network
+        cache = None if featurizer_trains(net) else feats.store.cached_for(net, build=True)
+    if cache is not None:
+        rows = feats
+        _lib.note("feature_store_featurized")
+    elif hasattr(feats, "materialize"):
         # A direct feature store's batch (feature_store.StoreRows).  The plan is lowered as for any batch; where the featurizer's first product
         # is one the wide kernel takes - the question BatchGQABoxFeaturizer._store_layers asks - the executor reads the store's rows in place
         # (dfol_set_feature_rows), otherwise it gets the gathered matrix.
@@ -301,7 +310,10 @@ def run(model, program_batch, plan, queue, give_answer=True):
     gran = (1 << 25) if plan.ws_bytes >= (1 << 25) else (1 << 20)
     ws = torch.empty((plan.ws_bytes + gran - 1) // gran * gran, dtype=torch.uint8, device=device)
     sc = ProgramScene()
-    if rows is not None:
+    if cache is not None:
+        sc.features, sc.ld_features, sc.raw_cols, sc.O = None, rows.shape[1], rows.shape[1], plan.scene["O"]      # (no raw feature is read)
+        _lib.call("dfol_set_feature_cache", cache.data_ptr(), cache.stride(0), cache.shape[1], rows.src_row.data_ptr(), rows.box6.data_ptr())
+    elif rows is not None:
         sc.features, sc.ld_features, sc.raw_cols, sc.O = rows.table.data_ptr(), rows.table.stride(0), rows.shape[1], plan.scene["O"]
         _lib.call("dfol_set_feature_rows", rows.src_row.data_ptr(), rows.box6.data_ptr())        # (picked up, and cleared, by the call below)
     else:

@@ -45,7 +45,8 @@ extern "C" {
  * operand of DFOL_OP_DENSE (a slot that instruction tables written before it hold as zero = the layer's own activation) were added under 3,
  * and so were dfol_pair_ll_h1_f32, dfol_pair_pack_w2_f16, dfol_pair_w2_f16_bytes and DFOL_PAIR_F16 (an older library refuses the kind) and
  * dfol_gather_object_rows_f32, and the two size queries dfol_lstm_cell_supported and dfol_calib_walk_supported, and the index form of a store-backed
- * batch: dfol_store_rows_f32, dfol_linear_wide_rows_h2_f32 and dfol_set_feature_rows (no struct and no instruction table changes for it);
+ * batch: dfol_store_rows_f32, dfol_linear_wide_rows_h2_f32 and dfol_set_feature_rows (no struct and no instruction table changes for it), and
+ * its cached form: dfol_store_objects_f32 and dfol_set_feature_cache (likewise);
  * a caller that needs them checks for the symbol, and a table that names an opcode an older library lacks is refused by it ("unknown opcode"). */
 #define DFOL_ABI_VERSION 3
 
@@ -228,6 +229,16 @@ int dfol_gather_object_rows_f32(const float* store_features, const float* store_
  * slot / obj_off / the row limit max_obj as there; S * max_obj < 2^31 (refused otherwise); I == 0 returns without a launch. */
 int dfol_store_rows_f32(const float* store_boxes, const float* store_sizes, const int32_t* slot, const int32_t* obj_off, int32_t I, int32_t S,
                         int32_t max_obj, int32_t* src_row, float* box6, void* stream);
+
+/* The object matrix of the same batch from CACHED featurizer outputs (a store built with featurized=True; phases whose featurizer is frozen):
+ *   out[r][:] = [cache[src_row[r]][0:W], (x, y, w, h) / max((W, H, W, H), 1) of box6[r]]                0 <= r < O
+ *   cache   [rows, ld_cache] fp32, ld_cache >= W: the featurizer's output for every row of the store's table
+ *   src_row [O] int32, box6 [O, 6]: dfol_store_rows_f32's; every src_row entry a row of `cache` - NOT checked (a device array)
+ *   out     [O, ld_out], ld_out >= W + 4; columns beyond W + 4 are left as they are
+ * The four position columns are bit for bit dfol_box_positions_f32's on box6.  O == 0 returns without a launch.  16-byte loads when
+ * ld_cache % 4 == 0 and cache is 16-byte aligned, any W >= 1 and any ld_out otherwise; the store width follows each output row's alignment. */
+int dfol_store_objects_f32(const float* cache, int64_t ld_cache, const int32_t* src_row, const float* box6, int32_t O, int32_t W, float* out,
+                           int64_t ld_out, void* stream);
 
 /* Segmented row sum: out[q][:] = sum_{p in seg q} src[p][:]   (mm(pqm^T, X), batch_gqa_ops.py:457). */
 int dfol_segment_sum_rows_f32(const float* src, const int32_t* seg_off, int32_t Q, int32_t width, float* out,
@@ -886,6 +897,11 @@ int dfol_calib_walk_supported(int32_t KX, int32_t H); /* 1 / 0: DFOL_OP_CALIB_WA
  * must be a DFOL_DENSE_F16X2 layer of a shape dfol_linear_wide_supported(O, N, K) takes: the caller asks that first and hands over the gathered
  * matrix otherwise; any other source-0 product is refused - and DFOL_OP_BOX_POSITIONS reads box6.  Plans are lowered as ever. */
 int dfol_set_feature_rows(const int32_t* src_row, const float* box6);
+/* The same for a scene whose featurizer output is CACHED (a frozen featurizer; dfol_store_objects_f32): the NEXT dfol_run_program of the calling
+ * thread runs no featurizer product - every DFOL_OP_DENSE of set 0 is skipped, scene->features is not read and may be NULL - and its
+ * DFOL_OP_BOX_POSITIONS writes the whole object matrix: cache rows src_row [O] of cache [rows, ld_cache] (W = the instruction's pos_col columns,
+ * else refused) and the positions of box6 [O, 6].  Cleared by that call; all NULL / 0 clears it.  It takes precedence over dfol_set_feature_rows. */
+int dfol_set_feature_cache(const float* cache, int64_t ld_cache, int32_t W, const int32_t* src_row, const float* box6);
 int dfol_run_program(const DfolProgramModel* model, const DfolProgramScene* scene, const int64_t* instr_host, int32_t n_instr,
                      const void* blob, void* workspace, void* stream);
 

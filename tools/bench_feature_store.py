@@ -3,17 +3,21 @@
 
 Synthetic chunk files in the collator's layout (default 2048 images x 100 objects x 2048 features, .npz, in a temporary directory), then a
 stream of unseen 256-question batches - DataLoader workers collate and lower them to plans, this process uploads, launches the native
-executor and decodes the answers - with the object features arriving four ways:
+executor and decodes the answers - with the object features arriving five ways:
 
   pool          already on the device (a pool of two feature sets, `value_fresh_programs`'s form): the upper bound
   store         an ObjectFeatureRef per batch, gathered from the store by ProgramBatch.to_cuda
   store_direct  the same refs and workers with the store in its index form (`direct=True`): to_cuda writes row numbers and box columns, the
                 featurizer's first product reads the store's rows in place (csrc/dfol_dense_wide.hip, ROWS) - no [O, F + 6] matrix
+  store_featurized  the same refs and workers with the store's cache of featurizer rows (`featurized=True`, built once before the runs): to_cuda
+                writes row numbers and box columns, one launch gathers the batch's cached [O, 512] rows beside their box positions
+                (csrc/dfol_store.hip, dfol_store_objects_f32) - no featurizer product per batch
   host          today's route: the worker builds [O, F + 6] from the chunk files, the matrix travels to this process, is pinned and uploaded
 
 The legs alternate in one process, `--runs` runs each (a difference counts only when the ranges are apart).  The gather kernel
 alone is timed by HIP events beside a device-to-device copy_ of the same byte count, and the featurizer's first product both ways: gather +
-dfol_linear_wide_h2_f32 against dfol_store_rows_f32 + dfol_linear_wide_rows_h2_f32, alternating.  Prints one JSON line.
+dfol_linear_wide_h2_f32 against dfol_store_rows_f32 + dfol_linear_wide_rows_h2_f32, alternating; the cached-row kernel likewise beside a copy_
+of its bytes, with the one-off featurize() time and the cache's size.  Prints one JSON line.
 
 usage: python tools/bench_feature_store.py [--images 2048] [--objects 100] [--features 2048] [--batch 256] [--batches 24] [--runs 4] [--workers 5]
 """
@@ -167,6 +171,13 @@ def main():
         refs = [store.index.ref([q["image_id"] for q in questions[i * args.batch:(i + 1) * args.batch]]) for i in range(min(8, args.batches))]
         pool = [store.gather(r) for r in refs[:2]]
         first_lp = {}
+        # the cache of featurizer rows, built once (the model's featurizer is frozen: reference_config); the store's flags are set per leg
+        fnet = model._featurizer._featurizer_network
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        cache = store.featurize(fnet)
+        torch.cuda.synchronize()
+        featurize_s = time.perf_counter() - t0
 
         def run(leg):
             """One pass over the stream: -> (seconds, host seconds spent in to_cuda)."""
@@ -177,10 +188,11 @@ def main():
                 res = pending.result()
                 training.compute_evaluation_metrics(pbs, res)
                 return res
-            store.direct = leg == "store_direct"             # (recorded on the store only: the same index, refs, collator and workers)
+            store.featurized = leg == "store_featurized"     # (recorded on the store only: the same index, refs, collator and workers)
+            store.direct = leg in ("store_direct", "store_featurized")
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            for pbs in loaders["store" if leg == "store_direct" else leg]:
+            for pbs in loaders["store" if leg.startswith("store_") else leg]:
                 h0 = time.perf_counter()
                 if leg == "pool":
                     for pb in pbs:
@@ -196,10 +208,10 @@ def main():
             while inflight:
                 finish()
             torch.cuda.synchronize()
-            store.direct = False
+            store.direct = store.featurized = False
             return time.perf_counter() - t0, to_cuda_s
 
-        legs = ("pool", "store", "store_direct", "host")
+        legs = ("pool", "store", "store_direct", "store_featurized", "host")
         with torch.no_grad():
             for leg in legs:                                 # warm-up: workers up, allocator, weight images
                 run(leg)
@@ -212,7 +224,8 @@ def main():
                     times[leg].append(dt / args.batches * 1e3)
                     to_cuda[leg].append(h / args.batches * 1e3)
         counts = {k: v for k, v in _lib.PATH_COUNTS.items() if k in ("native_program", "python_program", "feature_store_batch", "feature_store_miss",
-                                                                     "feature_store_direct", "feature_store_direct_materialized")}
+                                                                     "feature_store_direct", "feature_store_direct_materialized",
+                                                                     "feature_store_featurized", "feature_store_featurize")}
 
         # the gather alone, and a device-to-device copy of the same bytes, by HIP events in the same session
         out = torch.empty_like(pool[0])
@@ -237,6 +250,16 @@ def main():
         copy_ms = event_ms(lambda i: out.copy_(src))
         same = bool(np.array_equal(first_lp["store"].view(np.uint32), first_lp["host"].view(np.uint32)))
         same_direct = bool(np.array_equal(first_lp["store_direct"].view(np.uint32), first_lp["store"].view(np.uint32)))
+        same_featurized = bool(np.array_equal(first_lp["store_featurized"].view(np.uint32), first_lp["store"].view(np.uint32)))
+
+        # the cached-row kernel alone (row numbers and box columns on the device before the first event), and a device-to-device copy of the bytes it
+        # writes - it reads four columns per row fewer, from rows scattered over the cache
+        batch_rows = [store.rows(r, index=i) for r, i in zip(refs, on_dev)]
+        obj = torch.empty(batch_rows[0].O, cache.shape[1] + 4, device=device)
+        obj_src = torch.rand_like(obj)
+        objects_ms = event_ms(lambda i: batch_rows[i % len(refs)].objects(cache, out=obj))
+        objects_copy_ms = event_ms(lambda i: obj.copy_(obj_src))
+        objects_bytes = obj.numel() * 4 + batch_rows[0].O * cache.shape[1] * 4
 
         # the featurizer's first product both ways, alternating in `runs` rounds: the matrix route (gather + the wide product over the matrix) against
         # the index route (row numbers and box columns + the wide product over the store's rows); index arrays uploaded and buffers allocated before
@@ -307,7 +330,17 @@ def main():
             product, matrix_route=span(product["matrix_route_ms"]), index_route=span(product["index_route_ms"]),
             index_vs_matrix=apart(span(product["index_route_ms"]), span(product["matrix_route_ms"])),
             wide_rows_vs_wide=apart(span(product["wide_over_rows_ms"]), span(product["wide_over_matrix_ms"]))),
+        "store_featurized_vs_store_direct": apart(ms["store_featurized"], ms["store_direct"]),
+        "store_featurized_vs_store": apart(ms["store_featurized"], ms["store"]), "store_featurized_vs_pool": apart(ms["store_featurized"], ms["pool"]),
+        "store_featurized_over_store_direct_questions_per_s": qps["store_featurized"]["median"] / qps["store_direct"]["median"],
+        "featurized_cache": {"featurize_s": featurize_s, "bytes": store.cache_nbytes, "rows": int(cache.shape[0]), "width": int(cache.shape[1]),
+                             "raw_feature_bytes": store.S * store.max_obj * store.F * 4},
+        "objects_kernel": {"ms": span(objects_ms), "bytes_read_plus_written": objects_bytes,
+                           "GBps_read_plus_written": objects_bytes / float(np.median(objects_ms)) / 1e6},
+        "objects_copy_d2d": {"ms": span(objects_copy_ms), "GBps_read_plus_written": 2.0 * obj.numel() * 4 / float(np.median(objects_copy_ms)) / 1e6},
+        "objects_over_copy": float(np.median(objects_ms)) / float(np.median(objects_copy_ms)),
         "routes": counts, "store_equals_host_bitwise_first_batch": same, "store_direct_equals_store_bitwise_first_batch": same_direct,
+        "store_featurized_equals_store_bitwise_first_batch": same_featurized,
     }
     print(json.dumps(result))
 
