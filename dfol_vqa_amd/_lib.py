@@ -76,13 +76,13 @@ def note(route):
     PATH_COUNTS[route] += 1
 
 
-def fallback(route, why):
-    """Count a step that left the HIP kernels and say so once per route."""
+def fallback(route, why, what="runs on torch / vendor-library operators instead of this library's HIP kernels"):
+    """Count a step that left the route it was meant to take and say so once per route.  what: the clause after the route's name, for a step that
+    stays on this library's kernels but not on the ones asked for (range_rerun: the same forward again, on the wide-range arithmetic)."""
     PATH_COUNTS["fallback:" + route] += 1
     if route not in _WARNED:
         _WARNED.add(route)
-        _warnings.warn("dfol_vqa_amd: %s runs on torch / vendor-library operators instead of this library's HIP kernels (%s)" % (route, why),
-                       RuntimeWarning, stacklevel=3)
+        _warnings.warn("dfol_vqa_amd: %s %s (%s)" % (route, what, why), RuntimeWarning, stacklevel=3)
 
 
 _p, _i32, _i64, _f = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
@@ -319,6 +319,19 @@ _RANGE_RING = 8
 _RANGE_ACTIVE = threading.local()    # .word: the status word of this thread's open RangeWatch (a watch opened inside another hands it back)
 
 
+def range_message(flags):
+    """What a non-zero fp16-range status word says, and the remedy: the text of the error a forward raises, and of the warning of a forward that
+    runs the batch again instead (`range_overflow: rerun`)."""
+    what = []
+    if flags & RANGE_X_OVERFLOW:
+        what.append("an input of a dense layer (object features, or a hidden activation) is beyond fp16's largest finite value 65504 or NaN")
+    if flags & RANGE_PAIR_SATURATED:
+        what.append("a first-layer sum of the relation MLP reaches the fused pair kernel's saturation point (ELU outputs beyond 4.16e4) or is NaN")
+    return ("fp16 range exceeded in the two-piece fp16 arithmetic (dense math 'f16x2', the default): %s. The results of this "
+            "forward are not valid. Use `mlp_math: bf16x3` (config key; three bf16 pieces, fp32's exponent range) or "
+            "DFOL_DENSE_MATH=bf16x3 / DFOL_PAIR_MATH=bf16x3, or normalise the features." % "; ".join(what))
+
+
 class RangeWatch(object):
     """One forward's watch on the fp16-range status word of its device.  The default dense arithmetic ("f16x2") splits activations into two
     UNSCALED fp16 pieces: an object feature beyond 65504 would come back as NaN log-probabilities.  The dense kernels flag that in a device word; `finish()` queues its copy behind the forward's launches (pinned, asynchronous - no
@@ -364,9 +377,10 @@ class RangeWatch(object):
             done = torch.cuda.Event()
             done.record()
 
-        def check(sync=True, value=None):
+        def check(sync=True, value=None, throw=True):
             """sync=False: look at what has arrived so far (a replayed train step checks the step BEFORE it: no host wait per step); value: the word
-            as the caller read it back itself (a pipelined graph replay)."""
+            as the caller read it back itself (a pipelined graph replay); throw=False: hand the flags back (0: in range) instead of raising - the
+            caller re-runs the batch on the wide-range arithmetic (interpreter: `range_overflow: rerun`)."""
             if sync and value is None:
                 if done is not None:
                     done.synchronize()
@@ -375,14 +389,10 @@ class RangeWatch(object):
             v = int(host[0]) if value is None else int(value)
             if v:
                 word.zero_()
-                what = []
-                if v & RANGE_X_OVERFLOW:
-                    what.append("an input of a dense layer (object features, or a hidden activation) is beyond fp16's largest finite value 65504 or NaN")
-                if v & RANGE_PAIR_SATURATED:
-                    what.append("a first-layer sum of the relation MLP reaches the fused pair kernel's saturation point (ELU outputs beyond 4.16e4) or is NaN")
-                raise DfolError("fp16 range exceeded in the two-piece fp16 arithmetic (dense math 'f16x2', the default): %s. The results of this "
-                                "forward are not valid. Use `mlp_math: bf16x3` (config key; three bf16 pieces, fp32's exponent range) or "
-                                "DFOL_DENSE_MATH=bf16x3 / DFOL_PAIR_MATH=bf16x3, or normalise the features." % "; ".join(what))
+                if throw:
+                    raise DfolError(range_message(v))
+            if not throw:
+                return v
         check.range_check = True
         return check
 

@@ -91,6 +91,13 @@ def build_interpreter(config, neural_dict, ontology):           # gqa_interprete
             raise ValueError("pair_math must be f16x2 (the default: fp32 accuracy) or f16 (reduced precision: one fp16 product per MAC, "
                              "inference only), got %r" % (pair_math,))
         model._pair_math = str(pair_math).lower()
+    # an extra key of this build: what an inference forward does when the default two-piece fp16 arithmetic leaves fp16's range - raise
+    # (the default), or run that batch again on bf16x3 (interpreter.range_rerun); training raises under either
+    range_overflow = str(config.get('range_overflow', 'raise')).lower()
+    if range_overflow not in ('raise', 'rerun'):
+        raise ValueError("range_overflow must be raise (the default) or rerun (a flagged inference batch runs again on bf16x3), got %r"
+                         % (config.get('range_overflow'),))
+    model._range_overflow = range_overflow
     return model
 
 

@@ -152,20 +152,78 @@ class _LazyGather(object):
         return gather_results(self.results, self.device, True)
 
 
+def _range_flags(queue, value=None):
+    """`range_overflow: rerun`: run a finished forward's deferred closures (the answers' read-backs, then its fp16-range check) with the check
+    handing its flags back instead of raising -> the forward's status word (0: in range).  value: the word as the caller read it back itself (a
+    pipelined replay).  (Under `raise` the owners run their queues as they always have.)"""
+    flags = 0
+    for fill in queue:
+        if getattr(fill, "range_check", False):
+            flags |= fill(value is None, value, False)
+        else:
+            fill()
+    return flags
+
+
+def range_rerun(model, program_batch_list, flags, return_trace=False, modulator_switch=True):
+    """`range_overflow: rerun`: the inference forward of `program_batch_list` again, on the wide-range arithmetic - what this model returns for the
+    batch with `mlp_math: bf16x3` - after its first run left fp16's range (`flags`: its status word).  Eager, on the current stream, under
+    no_grad; the caller has waited for the first run and discards its results.  The model's own modes are set for the duration (restored on
+    the way out), so that everything that asks the model - the forward's scopes, the executor's model cache and spec, the attribute head's
+    predicate - agrees: dense AND pair arithmetic "bf16x3" (a `pair_math: f16` or DFOL_PAIR_MATH left in place would saturate again).  The re-run
+    has a watch of its own and raises like any forward.  Its log-probabilities, and the object features it read, must be finite (a NaN or inf
+    feature is beyond any arithmetic): DfolError otherwise; an error of the re-run itself propagates with the range error as its cause."""
+    from . import _lib
+    why = _lib.range_message(flags)
+    _lib.note("range_rerun")
+    _lib.fallback("range_rerun", why, "ran a batch again on the 'bf16x3' arithmetic, dense layers and pair kernel (every such batch costs one extra forward)")
+    saved = [(k, k in model.__dict__, model.__dict__.get(k)) for k in ("_mlp_math", "_pair_math")]
+    try:
+        model._mlp_math = model._pair_math = "bf16x3"
+        with torch.no_grad():
+            out = model._forward(program_batch_list, False, return_trace, modulator_switch, rerun=False)
+    except Exception as err:
+        raise err from _lib.DfolError(why)
+    finally:
+        for k, had, v in saved:
+            if had:
+                model.__dict__[k] = v
+            else:
+                model.__dict__.pop(k, None)
+    # (the features are looked at too: the logic kernels clamp log-likelihoods at 0 with fminf, which drops a NaN - an object whose features hold
+    # one would come back as a certain match, finite and wrong.  A re-run is rare: two small reductions and a host wait do not matter here)
+    res = out[0] if return_trace else out
+    feats = [pb._object_features for pb in program_batch_list if isinstance(pb._object_features, torch.Tensor)]
+    if not all(bool(torch.isfinite(t).all()) for t in [res['log_probability']] + feats):
+        raise _lib.DfolError(why + " The re-run on 'bf16x3' (`range_overflow: rerun`) did not help: the object features or the re-run's "
+                             "log-probabilities are not all finite (a NaN or infinite feature is beyond every arithmetic).")
+    return out
+
+
 class PendingForward(object):
     """A forward whose launches are enqueued but whose answers have not been read back (`BatchInterpreterBase.forward_async`): the host
     is free - to collate the next ProgramBatch, say - while the device runs this one; `result()` waits for the device, reads the terminal
-    operators' log-probabilities back and returns what `forward` would have."""
+    operators' log-probabilities back and returns what `forward` would have.  rerun = (model, program_batch_list, modulator_switch) of a forward
+    under `range_overflow: rerun`: a flagged forward is run again inside `result()` (range_rerun), on the stream current THERE, behind this
+    forward - a forward queued after this one keeps its own tensors and status word."""
 
-    def __init__(self, lazy, queue):
-        self._lazy, self._queue, self._result = lazy, queue, None
+    def __init__(self, lazy, queue, rerun=None):
+        self._lazy, self._queue, self._result, self._rerun = lazy, queue, None, rerun
 
     def result(self):
         if self._result is None:
-            for fill in self._queue:
-                fill()
-            self._result = self._lazy.gather()
-            self._lazy = self._queue = None
+            flags = 0
+            if self._rerun is None:
+                for fill in self._queue:
+                    fill()
+            else:
+                flags = _range_flags(self._queue)
+            if flags:
+                model, pbs, modulator_switch = self._rerun
+                self._result = range_rerun(model, pbs, flags, modulator_switch=modulator_switch)
+            else:
+                self._result = self._lazy.gather()
+            self._lazy = self._queue = self._rerun = None
         return self._result
 
 
@@ -217,6 +275,12 @@ class GraphedForward(object):
 
     def __call__(self):
         self._graph.replay()
+        if getattr(self._model, "_range_overflow", "raise") == "rerun":      # (a captured forward is an inference forward under no_grad)
+            flags = _range_flags(self._queue)                    # (the range check waits for the replay's stream)
+            if flags:
+                # the replay is discarded; the batch runs again eagerly - outside any capture, behind the replay
+                return range_rerun(self._model, self._pbs, flags)
+            return self._lazy.gather()
         for fill in self._queue:
             fill()
         return self._lazy.gather()
@@ -237,25 +301,40 @@ class GraphedForward(object):
             h.copy_(t, non_blocking=True)
         slot["event"].record()
         slot["busy"] = True
+        slot["serial"] = self._next                              # (collect: no submit since - the ProgramBatches still hold this replay's features)
         return slot
 
     def collect(self, ticket):
         """Wait for that replay (only), decode its answers from its own copies and return what `forward` would have - with the log-probabilities
-        as a host tensor (the device buffers belong to the replays behind it)."""
+        as a host tensor (the device buffers belong to the replays behind it).  `range_overflow: rerun`: a flagged replay is run again eagerly
+        over the ProgramBatches (range_rerun, on the current stream, after the wait for the ticket's event) - while they still hold that replay's
+        features, that is with no `submit` on this graph since the ticket's; otherwise the range error is raised as under `raise`."""
         from . import gqa_ops
         ticket["event"].synchronize()
         snap = {id(t): h.numpy() for t, h in zip(self._outputs, ticket["host"])}
         gqa_ops.DEFERRED.snapshot = snap
+        flags = 0
         try:
-            for fill in self._queue:
-                if getattr(fill, "range_check", False):
-                    fill(False, int(snap[id(self._range_dev)][0]))
-                else:
-                    fill()
-            res = self._lazy.gather()
+            if getattr(self._model, "_range_overflow", "raise") == "rerun":
+                flags = _range_flags(self._queue, int(snap[id(self._range_dev)][0]))
+            else:
+                for fill in self._queue:
+                    if getattr(fill, "range_check", False):
+                        fill(False, int(snap[id(self._range_dev)][0]))
+                    else:
+                        fill()
+            res = None if flags else self._lazy.gather()
         finally:
             gqa_ops.DEFERRED.snapshot = None
             ticket["busy"] = False
+        if flags:
+            from . import _lib
+            if ticket["serial"] != self._next:
+                raise _lib.DfolError(_lib.range_message(flags) + " `range_overflow: rerun` could not run this batch again: a later submit() on the "
+                                     "same graph may have replaced its features in the ProgramBatches.")
+            res = dict(range_rerun(self._model, self._pbs, flags))
+            res['log_probability'] = res['log_probability'].cpu()
+            return res
         res = dict(res)
         res['answer'] = [list(a) for a in res['answer']]         # (the queued closures refill the same lists at every replay)
         res['answer_log_probability'] = [list(a) for a in res['answer_log_probability']]
@@ -378,9 +457,29 @@ class BatchInterpreterBase(nn.Module):
         geometry._relation_features = relation_features
         return geometry
 
+    # `range_overflow` (config key, experiment.build_interpreter): what an INFERENCE forward does when a kernel of the default two-piece fp16
+    # arithmetic left fp16's range - "raise" (DfolError naming the remedy) or "rerun" (that batch again on "bf16x3": range_rerun).  A forward a
+    # gradient reaches - training.train_batch, GraphedTrainStep - raises under either: by the time the flag is read its backward has run, and
+    # the optimizer step may have; DeviceFeatureStore.featurize() raises too: it speaks for a whole corpus, not for one batch.
+    _range_overflow = "raise"
+
+    def _may_rerun(self, program_batch_list, is_training):
+        """This forward may be run again when it leaves fp16's range: the switch is on, and no gradient reaches the forward."""
+        if self._range_overflow != "rerun":
+            return False
+        return not is_training and not (torch.is_grad_enabled() and (
+            any(p.requires_grad for p in self.parameters()) or
+            any(getattr(pb._object_features, "requires_grad", False) for pb in program_batch_list)))
+
     def forward(self, program_batch_list, is_training, return_trace=False, modulator_switch=True):
         """batch_base_interpreter.py:72-183.  Terminal operators defer reading their log-probabilities back until every
-        ProgramBatch has been enqueued: one device->host synchronisation per forward."""
+        ProgramBatch has been enqueued: one device->host synchronisation per forward.  Under `range_overflow: rerun` an inference forward
+        that no gradient reaches and that left fp16's range is run again on the wide-range arithmetic (range_rerun) instead of raising."""
+        return self._forward(program_batch_list, is_training, return_trace, modulator_switch, rerun=self._may_rerun(program_batch_list, is_training))
+
+    def _forward(self, program_batch_list, is_training, return_trace, modulator_switch, rerun):
+        """rerun: this forward reads its own answers back (no outer queue) and may run the batch again when its range check flags it; a forward
+        whose read-backs an owner runs - forward_async, a graph capture - leaves that to the owner."""
         from . import gqa_ops
         outer = gqa_ops.DEFERRED.queue
         queue = [] if outer is None else outer                 # (a graph capture installs its own queue, see GraphedForward)
@@ -408,8 +507,13 @@ class BatchInterpreterBase(nn.Module):
             if watch is not None:
                 _lib.range_status_off()                          # (also when the forward raised before watch.finish())
         if outer is None:
-            for fill in queue:
-                fill()
+            if rerun:
+                flags = _range_flags(queue)
+                if flags:
+                    return range_rerun(self, program_batch_list, flags, return_trace, modulator_switch)
+            else:
+                for fill in queue:
+                    fill()
         result = gather_results(all_results, device, True) if outer is None else _LazyGather(all_results, device)
         return (result, all_traces) if return_trace else result
 
@@ -422,10 +526,10 @@ class BatchInterpreterBase(nn.Module):
         queue = []
         gqa_ops.DEFERRED.queue = queue
         try:
-            lazy = self.forward(program_batch_list, is_training, modulator_switch=modulator_switch)
+            lazy = self._forward(program_batch_list, is_training, False, modulator_switch, rerun=False)
         finally:
             gqa_ops.DEFERRED.queue = None
-        return PendingForward(lazy, queue)
+        return PendingForward(lazy, queue, (self, program_batch_list, modulator_switch) if self._may_rerun(program_batch_list, is_training) else None)
 
     def _native_spec(self, is_training, modulator_switch, return_trace):
         """The lowering spec when this forward may run on the native executor (native_exec / native_plan: one C call per ProgramBatch instead
