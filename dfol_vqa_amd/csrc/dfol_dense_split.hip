@@ -14,7 +14,7 @@
 // Workgroup: 256 threads = 2 x 2 wavefronts, 128 x 128 output tile, wavefront tile 64 x 64 (16 accumulator tiles, 64 registers);
 // 48 KB of LDS: two workgroups per CU.  Consecutive workgroups of one XCD share the X row block (blockIdx is re-mapped so that the
 // column blocks of a row block run on the same XCD and hit its L2).
-// -DDFOL_DENSE_TRACE: clock64 stamps of one workgroup (tools/scratch/trace_dense.py).
+// -DDFOL_DENSE_TRACE: clock64 stamps of one workgroup (tools/lab/trace_dense.py).
 #include "dfol_common.h"
 #include "dfol_split.h"
 
@@ -32,26 +32,6 @@ __device__ long long dfol_dense_trace_buf[4 * 64];
 namespace {
 
 constexpr int LS_BM = 128, LS_BN = 128, LS_BK = 32;
-// Two measured variants of the step loop for the two-piece kernels, both OFF: -DLS_DOUBLE_BUFFER=1 (two LDS buffers, one barrier per step)
-// and with it -DLS_XRING=4 (four steps of X rows in flight instead of two).  At the train step's tall products (2.5 M rows, K = 256 / 300;
-// tools/lab/time_tall.py) the single-buffered loop takes 1.96 / 2.13 ms, the double-buffered one 2.02 / 2.27 ms, with the deeper ring
-// 2.14 / 2.35 ms: these products move 5.6 GB each at ~2.8 TB/s and neither barriers nor the depth of the prefetch bound them (rocprofv3
-// counters, tools/lab/pmc_tall.sh: 46 % of the wavefront cycles wait on memory counters, 15 % issue MFMAs; without the MFMAs the
-// kernels are 0.15 ms faster, without the stores 0.5 ms).
-#ifndef LS_DOUBLE_BUFFER
-#define LS_DOUBLE_BUFFER 0
-#endif
-// -DLS_B_GLOBAL=1 (two-piece kernels): the B fragments go from the packed image (it is in fragment order) straight into the MFMA operand
-// registers, one step ahead - no LDS traffic for B.  The step loop of the two-piece kernels is LDS-bound otherwise: per step and
-// wavefront 8 writes and 24 reads of 16 bytes x 64 lanes for 48 MFMAs, 256 KB per CU and step pair = 2048 cycles of the LDS pipe against
-// 1536 of the matrix pipe (without any global traffic the forward tall product still takes 1.38 of its 1.96 ms).
-// (measured at the same two products: 1.92 / 2.39 ms against 1.95 / 2.13 - the producer kernel spills with the fragment registers; OFF)
-#ifndef LS_B_GLOBAL
-#define LS_B_GLOBAL 0
-#endif
-#ifndef LS_XRING
-#define LS_XRING 2                // steps of X rows in flight in the double-buffered form (register sets of 16 per 128-row block)
-#endif
 
 // NP = 2, round 4: TWO fp16 pieces per operand (dfol_split2h) and THREE products xl wh + xh wl + xh wh on v_mfma_f32_16x16x32_f16; every
 // row of W is scaled by its own power of two at pack time (dfol_scale_exp) and the epilogue multiplies the accumulator by 2^-e_n.  X is
@@ -148,10 +128,11 @@ template <int ACT, int XV, int NT, int NP, int RT, bool BIO, int MODE = 0>
 __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restrict__ Bs, const void* __restrict__ Xv, int64_t ldx,
                                         const u32x4* __restrict__ Wp, const float* __restrict__ bias, void* __restrict__ Yv, int64_t ldy, int M, int N,
                                         int K, int ksteps, int mb, int nb, int nbn, const LsProducer& prod = LsProducer(), float* __restrict__ Rs = nullptr) {
+    // One step loop: single LDS buffer, B one step ahead, X two steps ahead, last three steps peeled.  Three other forms (two LDS buffers,
+    // four steps of X in flight, B fragments straight from the packed image) were measured slower at the tall products and are not here:
+    // DESIGN_HISTORY.md ("the tiled kernel's step loop, three variants") has the numbers and the commit that holds their code.
     static_assert(!BIO || NP == 1, "bf16 storage belongs to the bf16 mode");
     constexpr bool PROD = MODE == 1, LOGIT = MODE == 2;
-    constexpr bool BG = LS_B_GLOBAL && !LS_DOUBLE_BUFFER && NP == 2 && !BIO;     // B fragments straight from the packed image
-    constexpr bool DB = LS_DOUBLE_BUFFER && NP == 2 && !BIO;          // two LDS buffers (2 x 32 KB for a 128-row block: still two workgroups per CU)
     static_assert(!LOGIT || (!BIO && ACT == DFOL_ACT_NONE), "the logit partial sums belong to the fp32 pre-activation output");
     static_assert(!PROD || (NP == 2 && !BIO && XV == 4 && ACT == DFOL_ACT_NONE), "the produced operand is two fp16 pieces of fp32 rows");
     typedef typename std::conditional<BIO, uint16_t, float>::type TX;
@@ -193,8 +174,7 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
     // X registers: two steps in flight (HBM latency is longer than one step of 96 MFMAs).  The loads are unconditional - addresses
     // clamped, out-of-range k zeroed afterwards - so that every wavefront issues exactly 4 per step and the vmcnt arithmetic below holds.
     typedef typename std::conditional<BIO, u32x2, float4>::type XR;  // four consecutive k of a row as loaded
-    constexpr int XD = DB ? LS_XRING : 2;                           // X register sets = steps of X in flight
-    XR xa[XD][RH][2];                                               // [set][row half][k half]
+    XR xa[2][RH][2];                                                // [set][row half][k half]
     float4 ea[PROD ? RH : 1][2];                                    // PROD: the same pieces of the rows' embedding rows - L2 hits, ONE step ahead
     float xmax = 0.f;                                               // NP = 2: the largest |x| this thread split (one v_max3 per two elements)
     auto load_x = [&](int ks, auto set_tag) __attribute__((always_inline)) {
@@ -228,13 +208,13 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
             }
         }
     };
-    auto store_a = [&](int ks, auto set_tag, int off = 0) __attribute__((always_inline)) {     // off: the LDS buffer (double-buffered form)
+    auto store_a = [&](int ks, auto set_tag) __attribute__((always_inline)) {
         constexpr int S = decltype(set_tag)::value;
         const int k = ks * LS_BK + aq * 8;
 #pragma unroll
         for (int h = 0; h < RH; ++h) {
             const int row = arow + 64 * h;
-            const int at = off + row * 4 + (aq ^ dfol_swz(row));
+            const int at = row * 4 + (aq ^ dfol_swz(row));
             if constexpr (BIO) {
                 const u32x2 zz = u32x2{0u, 0u};
                 const u32x2 v0 = k < K ? xa[S][h][0] : zz, v1 = k + 4 < K ? xa[S][h][1] : zz;
@@ -285,43 +265,31 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
 #pragma unroll
         for (int i = 0; i < TILE_PIECES / 256; ++i) wb[i] = wtile[(int64_t)ks * TILE_PIECES + 256 * i + tid];
     };
-    auto store_b = [&](int off = 0) __attribute__((always_inline)) {
+    auto store_b = [&]() __attribute__((always_inline)) {
 #pragma unroll
-        for (int i = 0; i < TILE_PIECES / 256; ++i) Bs[off + 256 * i + tid] = wb[i];
+        for (int i = 0; i < TILE_PIECES / 256; ++i) Bs[256 * i + tid] = wb[i];
     };
 
     const int aoff = (wm * (16 * RT) + r16) * 4 + (kh ^ dfol_swz(r16));
     const int boff = (wn * WN + r16) * 4 + (kh ^ dfol_swz(r16));
 
-    u32x4 bq[1][BG ? NT : 1][BG ? NP : 1];                           // BG: the B fragments of the step (requested at its top, under the split of the X rows)
-    auto load_bq = [&](int ks, auto set_tag) __attribute__((always_inline)) {
-        if constexpr (BG) {
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-#pragma unroll
-                for (int p = 0; p < NP; ++p) bq[0][j][p] = wtile[(int64_t)ks * TILE_PIECES + p * LS_BN * 4 + j * 64 + boff];
-        }
-    };
     constexpr int PA6[6] = {2, 0, 1, 1, 0, 0}, PB6[6] = {0, 2, 1, 0, 1, 0};
     constexpr int X0 = NP == 1 ? 5 : 0;                               // the bf16 mode keeps the last product only (piece 0 x piece 0)
     constexpr int PA3[3] = {1, 0, 0}, PB3[3] = {0, 1, 0};             // NP = 2: xl wh, xh wl, xh wh (smallest first)
     typedef typename std::conditional<NP == 2, f16x8, bf16x8>::type FR;
-    auto multiply = [&](int off, auto bq_tag) __attribute__((always_inline)) {  // the step's MFMAs on the tiles of LDS buffer `off`
+    auto multiply = [&]() __attribute__((always_inline)) {             // the step's MFMAs on the tiles in LDS
 #pragma unroll
         for (int ih = 0; ih < RT; ih += 2) {                // two row tiles at a time (register budget)
             FR a[2][NP];
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int p = 0; p < NP; ++p) a[i][p] = __builtin_bit_cast(FR, As[off + p * BM * 4 + (ih + i) * 64 + aoff]);
+                for (int p = 0; p < NP; ++p) a[i][p] = __builtin_bit_cast(FR, As[p * BM * 4 + (ih + i) * 64 + aoff]);
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 FR b[NP];
 #pragma unroll
-                for (int p = 0; p < NP; ++p) {
-                    if constexpr (BG) b[p] = __builtin_bit_cast(FR, bq[0][j][p]);
-                    else b[p] = __builtin_bit_cast(FR, Bs[off + p * LS_BN * 4 + j * 64 + boff]);
-                }
+                for (int p = 0; p < NP; ++p) b[p] = __builtin_bit_cast(FR, Bs[p * LS_BN * 4 + j * 64 + boff]);
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     if constexpr (NP == 2) {
@@ -342,19 +310,16 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
     auto step = [&](int ks, auto set_tag, auto has_b, auto has_x) __attribute__((always_inline)) {
         constexpr bool HAS_B = decltype(has_b)::value, HAS_X = decltype(has_x)::value;     // is there a B tile ks+1 / an X step ks+2
         LTRACE(4 * ks);
-        if constexpr (BG) load_bq(ks, set_tag);             // (L2 hits: there by the time the X rows are split, stored and the barrier passed)
         store_a(ks, set_tag);
-        if constexpr (!BG) store_b();
+        store_b();
         LTRACE(4 * ks + 1);
         __syncthreads();                                    // A pieces and B tile ks visible
         LTRACE(4 * ks + 2);
-        if constexpr (!BG) {
-            if (HAS_B) load_w(ks + 1);
-        }
+        if (HAS_B) load_w(ks + 1);
         if (HAS_B) load_e(ks + 1);                          // (consumed by this step's store_a already: one register set)
         if (HAS_X) load_x(ks + 2, set_tag);
         __builtin_amdgcn_sched_barrier(0);                  // requests first; and the next step's split must not drift up here
-        multiply(0, set_tag);
+        multiply();
         __builtin_amdgcn_sched_barrier(0);                  // (it would wait for X(ks+1) in the middle of the MFMAs)
         LTRACE(4 * ks + 3);
         __syncthreads();                                    // A and B tile ks fully read
@@ -367,69 +332,15 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
     const std::false_type no;
     LTRACE(60);
     load_x(0, S0);
-    if constexpr (!BG) load_w(0);
+    load_w(0);
     load_e(0);
     load_x(min(1, ksteps - 1), S1);
     int ks = 0;
-    if constexpr (DB) {
-        // Two LDS buffers, ONE barrier per step: step ks multiplies buffer ks & 1 while the tiles of step ks + 1 are split and written
-        // to the other one - by whichever wavefront gets there, under the MFMAs of the others (the single-buffered form below stops
-        // every wavefront twice per step: 3300 cycles per step of 768 cycles of MFMAs at K = 256 .. 300).  All loads are unconditional
-        // (steps past the end re-read the last one: L2 hits, never used), so the compiler's wait counts stay exact; a store past the
-        // end goes to the buffer nobody reads any more.
-        constexpr int BUF = NP * BM * 4 + NP * LS_BN * 4;
-        const int last = ksteps - 1;
-        const std::integral_constant<int, 2 % XD> S2;
-        const std::integral_constant<int, 3 % XD> S3;
-        if constexpr (XD == 4) {                            // (steps 0 and 1 were requested above)
-            load_x(min(2, last), S2);
-            load_x(min(3, last), S3);
-        }
-        store_a(0, S0, 0);
-        store_b(0);
-        load_w(min(1, last));
-        load_e(min(1, last));
-        load_x(min(XD, last), S0);
-        __syncthreads();
-        auto body = [&](int k, auto next_tag) __attribute__((always_inline)) {      // k: the step multiplied; next_tag: the X set of step k + 1
-            const int cur = (k & 1) * BUF, nxt = BUF - cur;
-            LTRACE(4 * k);
-            store_a(k + 1, next_tag, nxt);                  // (k + 1 past the end: all columns >= K, zeros)
-            store_b(nxt);
-            load_w(min(k + 2, last));
-            load_e(min(k + 2, last));
-            load_x(min(k + 1 + XD, last), next_tag);
-            LTRACE(4 * k + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            multiply(cur, std::integral_constant<int, 0>());
-            __builtin_amdgcn_sched_barrier(0);
-            LTRACE(4 * k + 3);
-            __syncthreads();                                // buffer nxt complete, buffer cur fully read
-        };
-        if constexpr (XD == 4) {
-            for (; ks + 3 < ksteps; ks += 4) {
-                body(ks, S1);
-                body(ks + 1, S2);
-                body(ks + 2, S3);
-                body(ks + 3, S0);
-            }
-            if (ks < ksteps) body(ks, S1);                  // (the tags continue where the loop stopped: ks is a multiple of 4)
-            if (ks + 1 < ksteps) body(ks + 1, S2);
-            if (ks + 2 < ksteps) body(ks + 2, S3);
-        } else {
-            for (; ks + 1 < ksteps; ks += 2) {
-                body(ks, S1);
-                body(ks + 1, S0);
-            }
-            if (ks < ksteps) body(ks, S1);
-        }
-        ks = ksteps;
-    }
     for (; ks + 3 < ksteps; ks += 2) {
         step(ks, S0, yes, yes);
         step(ks + 1, S1, yes, yes);
     }
-    const int rem = DB ? 0 : ksteps - ks;
+    const int rem = ksteps - ks;
     if (rem == 0) {
     } else if (rem == 3) {
         step(ks, S0, yes, yes);
@@ -510,63 +421,60 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
         }
         return;
     }
-    if constexpr (!BIO) {
-        // Interior tiles leave through LDS: straight from the accumulator layout a store instruction writes 16 lanes x 4 bytes of four
-        // rows (64 per thread and tile; the stores were a quarter of the tall products' time: 1.96 -> 1.46 ms without them), staged, a
-        // thread stores 16 bytes and 32 consecutive threads one 512-byte row segment.  Two passes of half the block's rows (the loop's
-        // last barrier has freed the operand tiles); rows 132 floats apart: the four row groups of a wavefront land 16 banks apart.
-        const bool interior = NT == 4 && m0 + BM <= M && n0 + LS_BN <= N && ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(Y) & 15) == 0;
-        if (interior) {
-            constexpr int PITCH = LS_BN + 4, IPP = RT / 2;
-            float* stage = reinterpret_cast<float*>(As);
+    // Interior tiles leave through LDS: straight from the accumulator layout a store instruction writes 16 lanes x 4 bytes of four
+    // rows (64 per thread and tile; the stores were a quarter of the tall products' time: 1.96 -> 1.46 ms without them), staged, a
+    // thread stores 16 bytes and 32 consecutive threads one 512-byte row segment.  Two passes of half the block's rows (the loop's
+    // last barrier has freed the operand tiles); rows 132 floats apart: the four row groups of a wavefront land 16 banks apart.
+    const bool interior = NT == 4 && m0 + BM <= M && n0 + LS_BN <= N && ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(Y) & 15) == 0;
+    if (interior) {
+        constexpr int PITCH = LS_BN + 4, IPP = RT / 2;
+        float* stage = reinterpret_cast<float*>(As);
 #pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                if (p) __syncthreads();                               // the first pass's rows have been read
+        for (int p = 0; p < 2; ++p) {
+            if (p) __syncthreads();                               // the first pass's rows have been read
 #pragma unroll
-                for (int ii = 0; ii < IPP; ++ii)
+            for (int ii = 0; ii < IPP; ++ii)
 #pragma unroll
-                    for (int e = 0; e < 4; ++e)
+                for (int e = 0; e < 4; ++e)
 #pragma unroll
-                        for (int j = 0; j < NT; ++j)
-                            stage[(wm * (16 * IPP) + ii * 16 + 4 * kh + e) * PITCH + wn * WN + j * 16 + r16] = dfol_act<ACT>(acc[p * IPP + ii][j][e] + bv[j]);
-                __syncthreads();
+                    for (int j = 0; j < NT; ++j)
+                        stage[(wm * (16 * IPP) + ii * 16 + 4 * kh + e) * PITCH + wn * WN + j * 16 + r16] = dfol_act<ACT>(acc[p * IPP + ii][j][e] + bv[j]);
+            __syncthreads();
 #pragma unroll
-                for (int it = 0; it < 16 * RT * (LS_BN / 4) / 256; ++it) {
-                    const int c = tid + 256 * it, row = c >> 5, c4 = c & 31;
-                    const int half = row / (16 * IPP), within = row - half * (16 * IPP);
-                    float4 v = *reinterpret_cast<const float4*>(stage + row * PITCH + 4 * c4);
-                    float* dst = reinterpret_cast<float*>(Y) + (int64_t)(m0 + half * (16 * RT) + p * (16 * IPP) + within) * ldy + n0 + 4 * c4;
-                    if constexpr (PROD) {
-                        if (prod.accumulate) {
-                            const float4 o = *reinterpret_cast<const float4*>(dst);
-                            v.x += o.x, v.y += o.y, v.z += o.z, v.w += o.w;
-                        }
-                    }
-                    *reinterpret_cast<float4*>(dst) = v;
-                    if constexpr (LOGIT) {                            // 16 consecutive lanes hold the 64 columns of a half block of one row
-                        const int grow = m0 + half * (16 * RT) + p * (16 * IPP) + within;
-                        float4 e = lg_e4;                             // (c4 = tid & 31 in every trip)
-                        bool live = true;
-                        if (!lg_uni) {
-                            const int pr = prod.row_pred[grow];
-                            live = pr >= 0;
-                            e = *reinterpret_cast<const float4*>(prod.E + (int64_t)max(pr, 0) * prod.ld_e + n0 + 4 * c4);
-                        }
-                        float sum = dfol_act<DFOL_ACT_SIGMOID>(v.x) * e.x + dfol_act<DFOL_ACT_SIGMOID>(v.y) * e.y + dfol_act<DFOL_ACT_SIGMOID>(v.z) * e.z +
-                                    dfol_act<DFOL_ACT_SIGMOID>(v.w) * e.w;
-                        sum = live ? sum : 0.f;
-#pragma unroll
-                        for (int sh = 1; sh < 16; sh <<= 1) sum += __shfl_xor(sum, sh, 64);
-                        if ((c4 & 15) == 0) prod.x_part[(int64_t)(2 * nb + (c4 >> 4)) * prod.ld_xp + grow] = sum;
+            for (int it = 0; it < 16 * RT * (LS_BN / 4) / 256; ++it) {
+                const int c = tid + 256 * it, row = c >> 5, c4 = c & 31;
+                const int half = row / (16 * IPP), within = row - half * (16 * IPP);
+                float4 v = *reinterpret_cast<const float4*>(stage + row * PITCH + 4 * c4);
+                float* dst = reinterpret_cast<float*>(Y) + (int64_t)(m0 + half * (16 * RT) + p * (16 * IPP) + within) * ldy + n0 + 4 * c4;
+                if constexpr (PROD) {
+                    if (prod.accumulate) {
+                        const float4 o = *reinterpret_cast<const float4*>(dst);
+                        v.x += o.x, v.y += o.y, v.z += o.z, v.w += o.w;
                     }
                 }
+                *reinterpret_cast<float4*>(dst) = v;
+                if constexpr (LOGIT) {                            // 16 consecutive lanes hold the 64 columns of a half block of one row
+                    const int grow = m0 + half * (16 * RT) + p * (16 * IPP) + within;
+                    float4 e = lg_e4;                             // (c4 = tid & 31 in every trip)
+                    bool live = true;
+                    if (!lg_uni) {
+                        const int pr = prod.row_pred[grow];
+                        live = pr >= 0;
+                        e = *reinterpret_cast<const float4*>(prod.E + (int64_t)max(pr, 0) * prod.ld_e + n0 + 4 * c4);
+                    }
+                    float sum = dfol_act<DFOL_ACT_SIGMOID>(v.x) * e.x + dfol_act<DFOL_ACT_SIGMOID>(v.y) * e.y + dfol_act<DFOL_ACT_SIGMOID>(v.z) * e.z +
+                                dfol_act<DFOL_ACT_SIGMOID>(v.w) * e.w;
+                    sum = live ? sum : 0.f;
+#pragma unroll
+                    for (int sh = 1; sh < 16; sh <<= 1) sum += __shfl_xor(sum, sh, 64);
+                    if ((c4 & 15) == 0) prod.x_part[(int64_t)(2 * nb + (c4 >> 4)) * prod.ld_xp + grow] = sum;
+                }
             }
-            LTRACE(62);
-            return;
         }
+        LTRACE(62);
+        return;
     }
     TX* yp = Y + (int64_t)(m0 + wm * (16 * RT) + 4 * kh) * ldy + n0 + wn * WN + r16;
-    auto out = [](float v) __attribute__((always_inline)) { return v; };
     if constexpr (PROD) {
         if (prod.accumulate) {                                        // (rows / columns past the matrix: clamped reads, never stored)
 #pragma unroll
@@ -585,7 +493,7 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
 #pragma unroll
             for (int e = 0; e < 4; ++e)
 #pragma unroll
-                for (int j = 0; j < NT; ++j) yp[(int64_t)(i * 16 + e) * ldy + j * 16] = out(dfol_act<ACT>(acc[i][j][e] + bv[j]));
+                for (int j = 0; j < NT; ++j) yp[(int64_t)(i * 16 + e) * ldy + j * 16] = dfol_act<ACT>(acc[i][j][e] + bv[j]);
     } else {
 #pragma unroll
         for (int i = 0; i < RT; ++i)
@@ -595,7 +503,7 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
                     const float v = dfol_act<ACT>(acc[i][j][e] + bv[j]);
-                    if (row_ok && n0 + wn * WN + j * 16 + r16 < N) yp[(int64_t)(i * 16 + e) * ldy + j * 16] = out(v);
+                    if (row_ok && n0 + wn * WN + j * 16 + r16 < N) yp[(int64_t)(i * 16 + e) * ldy + j * 16] = v;
                 }
             }
     }
@@ -616,10 +524,7 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
 #pragma unroll
                 for (int sh = 1; sh < 16; sh <<= 1) sum += __shfl_xor(sum, sh, 64);
                 // (a 64-row, two-tile wavefront covers 32 columns: its partial goes to the half block its columns lie in; NT = 2 only in the last block)
-                if (r16 == 0 && grow < M) {
-                    if (NT == 4) prod.x_part[(int64_t)(2 * nb + wn) * prod.ld_xp + grow] = sum;
-                    else prod.x_part[(int64_t)(2 * nb + wn) * prod.ld_xp + grow] = sum;
-                }
+                if (r16 == 0 && grow < M) prod.x_part[(int64_t)(2 * nb + wn) * prod.ld_xp + grow] = sum;
             }
     }
     LTRACE(62);
@@ -640,7 +545,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BIO ? DFOL_
     // the output tile staged for its stores: bf16 storage 34 KB / 17 KB; fp32: half the block's rows, 132 floats apart (33 KB / 16.5 KB)
     constexpr int STAGE_PIECES = BIO ? 32 * RT * (LS_BN + 8) * 2 / 16 : 16 * RT * (LS_BN + 4) * 4 / 16;
     constexpr int R_PIECES = MODE == 1 ? 32 * RT / 4 : 0;                   // PROD: 2^-e_r of the block's rows
-    constexpr int AB_PIECES = (LS_DOUBLE_BUFFER && NP == 2 && !BIO ? 2 : 1) * (A_PIECES + B_PIECES);
+    constexpr int AB_PIECES = A_PIECES + B_PIECES;
     constexpr int T_PIECES = AB_PIECES > STAGE_PIECES ? AB_PIECES : STAGE_PIECES;
     __shared__ __attribute__((aligned(16))) u32x4 Sm[T_PIECES + R_PIECES];
     u32x4* As = Sm;

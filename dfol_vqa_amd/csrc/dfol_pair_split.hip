@@ -15,7 +15,7 @@
 // fragment is conflict-free; SQ_LDS_BANK_CONFLICT = 0).  A chunk is copied to LDS verbatim by LDS-DMA.  Every wavefront owns 32 pair
 // slots and all 19 column tiles (152 accumulator registers).
 // The schedule (ping-pong between the two wavefronts of a SIMD, see pair_ll32s_kernel) came out of clock64 traces
-// (tools/scratch/trace_pair.py, -DDFOL_PAIR_TRACE).
+// (tools/lab/trace_pair.py, -DDFOL_PAIR_TRACE).
 #include "dfol_common.h"
 #include "dfol_split.h"
 
@@ -33,7 +33,7 @@
 #endif
 
 
-// -DDFOL_PAIR_TRACE: clock64 stamps of one wavefront per half in a few workgroups (tools/scratch/trace_pair.py reads them)
+// -DDFOL_PAIR_TRACE: clock64 stamps of one wavefront per half in a few workgroups (tools/lab/trace_pair.py reads them)
 #ifdef DFOL_PAIR_TRACE
 __device__ long long dfol_trace_buf[8 * 8 * 64];
 #define TRACE(slot)                                                                                                  \
@@ -457,7 +457,7 @@ extern "C" int dfol_pair_ll_split_f32(const float* UV, int64_t ld_uv, int32_t HI
     hipStream_t st = (hipStream_t)stream;
     static const int pp = getenv("DFOL_PAIR_SPLIT_PP") ? atoi(getenv("DFOL_PAIR_SPLIT_PP")) : 1;
     // pp = 1 (default): one ping-pong workgroup per 256 slots; 0: two 4-wavefront workgroups per CU.  (The persistent variant with the
-    // epilogue fused into the next task's first multiply tick - measured slower, DESIGN.md 3.3 - is parked in tools/scratch/.)
+    // epilogue fused into the next task's first multiply tick - measured slower, DESIGN.md 3.3 - left the tree in round 4: tools/lab/README.md.)
     const int tpi = dfol_cdiv((int64_t)max_n * (max_n - 1), pp ? 256 : 128);
     DFOL_REQUIRE((int64_t)Q * tpi < ((int64_t)1 << 31), "pair_ll_split: too many tiles");
     const dim3 grid((unsigned)Q * tpi);
