@@ -165,6 +165,8 @@ SIGNATURES = {
     "dfol_pair_wgrad_fused_sums_f32": [_p, _i64, _p, _p, _p, _i32, _p, _i64, _p, _p, _i64, _i64, _i32, _i32, _p, _p, _p, _i64, _p, _p, _p],
     "dfol_pair_wgrad_fused_sums_bf16": [_p, _i64, _p, _p, _p, _i32, _p, _i64, _p, _i64, _i64, _i32, _i32, _p, _p, _p, _i64, _p, _p, _p],
     "dfol_pair_wgrad_fused_f32": [_p, _i64, _p, _p, _p, _p, _i64, _p, _p, _i64, _i64, _i32, _i32, _p, _p, _p],
+    "dfol_pair_wgrad_multi_scale_f32": [_p, _i64, _i32, _p, _p, _i32, _i64, _p, _p],
+    "dfol_pair_wgrad_fused_multi_f32": [_p, _i64, _p, _i64, _i32, _p, _p, _p, _i64, _i32, _p, _p, _i64, _i64, _i32, _i32, _p, _p, _p],
     "dfol_linear_pack_w_bf16x3": [_p, _i64, _i32, _i32, _p, _p],
     "dfol_linear_act_split_f32": [_p, _i64, _p, _p, _p, _i64, _i32, _i32, _i32, _i32, _p],
     "dfol_linear_pack_w_bf16": [_p, _i64, _i32, _i32, _p, _p],
@@ -1368,6 +1370,31 @@ def pair_dz_tall_multi(dx_list, p2, e_rows_list, row_pred, w2, dz_out=None):
              _ptr(emax, F32), _ptr(wp, torch.bfloat16), _dp(dz), dz.stride(0), M, H1, H2, 1 if acc else 0, _ptr(ws), _stream())
         acc = True
     return dz
+
+
+def pair_wgrad_multi(dx_list, p2, z, e_rows_list, pred_off, row_pred):
+    """dW2 [HID2, HID1] = sum_k dpre2_k^T z for SEVERAL readers of one hidden layer in one pass over p2 = pre2 and z (csrc/dfol_dense_wgrad.hip,
+    dfol_pair_wgrad_fused_multi_f32): dpre2_k[r, j] = dx_k[r] E_k[row_pred[r], j] h (1 - h).  The readers share row_pred [M] (int32, non-decreasing),
+    pred_off [P + 1] (int64) and P; up to PAIR_DZ_MULTI_MAX per launch (more: further launches, added in order).  The launch's scale comes from
+    the device (dfol_pair_wgrad_multi_scale_f32: no sync); the readers' own sums are pair_head_sums'."""
+    M, H2 = p2.shape
+    H1 = z.shape[1]
+    dev = p2.device
+    ws = torch.empty(load().dfol_pair_wgrad_fused_workspace(M, H2, H1), dtype=F32, device=dev)
+    dw = None
+    for i in range(0, len(dx_list), PAIR_DZ_MULTI_MAX):
+        dxs, es = dx_list[i:i + PAIR_DZ_MULTI_MAX], e_rows_list[i:i + PAIR_DZ_MULTI_MAX]
+        nr, P = len(dxs), es[0].shape[0]
+        dx = torch.stack([d.reshape(-1) for d in dxs]).contiguous()
+        E = torch.stack([e if e.is_contiguous() else e.contiguous() for e in es]).contiguous()      # [nr, P, HID2]
+        emax = E.abs().amax(2).contiguous()
+        scale = torch.empty(4, dtype=F32, device=dev)
+        call("dfol_pair_wgrad_multi_scale_f32", _ptr(dx, F32), dx.stride(0), nr, _ptr(row_pred, I32), _ptr(emax, F32), P, M, _ptr(scale), _stream())
+        part = torch.empty(H2, H1, dtype=F32, device=dev)
+        call("dfol_pair_wgrad_fused_multi_f32", _dp(p2), p2.stride(0), _ptr(dx, F32), dx.stride(0), nr, _ptr(row_pred, I32), _ptr(pred_off, torch.int64),
+             _ptr(E, F32), E.stride(1), P, _ptr(scale), _dp(z), z.stride(0), M, H2, H1, _ptr(ws), _ptr(part), _stream())
+        dw = part if dw is None else dw + part
+    return dw
 
 
 def pair_head_bwd(dx, p2, z, w2, e_rows, pred_off, row_pred, need_bias=True, dz_out=None, sums=False):

@@ -781,12 +781,23 @@ typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
 // BIO (the bf16 mode): pre2 and Z are rows of bfloat16 (8-byte aligned rows, strides in elements), four columns of dpre2 per thread, ONE
 // bf16 piece per operand and one product on v_mfma_f32_32x32x16_bf16; dpre2 is rounded to bfloat16 exactly as dfol_pair_logit_bwd_bf16
 // stores it (no scaling: bf16 has fp32's exponent range; `scale` is not read).
-template <int CPT, bool SUMS, bool BIO = false>
+// MULTI (several readers of one trunk - relate hops, option slots - in ONE pass): dpre2[r][j] = h (1 - h) sum_k dx_k[r] E_k[p(r)][j], k < nr <= PW_MAXR;
+// reader k's dx at G + k g_stride, its embedding rows at E + k e_stride, one row -> predicate map and one scale for all.  Only the
+// coefficient changes - gs e[t] becomes ((gs_0 e_0[t] + gs_1 e_1[t]) + gs_2 e_2[t]) + gs_3 e_3[t], absent readers entering as exact zeros (one
+// reader: the bits of the kernel without MULTI) - and the schedule stays.  The embedding rows of the step's predicate, all readers, are
+// staged in the LDS the sums of SUMS would occupy, [column][reader], and read where the coefficient is formed (one ds_read_b128 per column:
+// no nr x CPT registers under the MFMAs); two slots: the rows of the NEXT step's predicate are written one step ahead, where the predicate
+// changes, and the step's closing barrier publishes them.  Octets across a predicate boundary or cut by the slab's end look their rows
+// up one by one, once per reader, as before.
+constexpr int PW_MAXR = 4;
+template <int CPT, bool SUMS, bool BIO = false, bool MULTI = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void pair_wgrad_fused_kernel(
     const void* __restrict__ P2v, int64_t ld_p2, const float* __restrict__ G, const int32_t* __restrict__ RP, const int64_t* __restrict__ pred_off,
     const float* __restrict__ E, int64_t ld_e, const float* __restrict__ scale, const void* __restrict__ Zv, int64_t ld_z, int M, int H2, int H1,
-    int rows_per_slab, float* __restrict__ part, float* __restrict__ de_part, float* __restrict__ db_part) {
+    int rows_per_slab, float* __restrict__ part, float* __restrict__ de_part, float* __restrict__ db_part, int nr, int64_t g_stride,
+    int64_t e_stride) {
     static_assert(!BIO || CPT == 4, "bf16 storage: four columns (8 bytes) per thread and row");
+    static_assert(!MULTI || (!SUMS && !BIO), "several readers: fp32 storage, the sums come from the readers' own passes");
     typedef typename std::conditional<BIO, uint16_t, float>::type TIN;
     const TIN* __restrict__ P2 = reinterpret_cast<const TIN*>(P2v);
     const TIN* __restrict__ Z = reinterpret_cast<const TIN*>(Zv);
@@ -886,20 +897,65 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
     };
     bool same = false;
-    float ev[CPT];
+    float ev[MULTI ? 1 : CPT];
     u32x2 gq;                                                       // dx of the row pair that comes next
+    // MULTI: the staged embedding rows [2 slots][320 columns] x {reader 0..3} behind the constant words, `slot` holding the rows of p_cur;
+    // then the readers' dx of two steps, [step parity][32 rows] x {reader 0..3} (absent readers, rows past the slab: zeros), written one step
+    // ahead by 128 threads: eight dx registers per thread prefetched under the MFMAs, as the one reader's two are, do not fit
+    float4* etab = reinterpret_cast<float4*>(pw_lds + 2 * BUFK + 256);
+    float4* dxs = etab + 2 * 32 * PW_TA;
+    int slot = 0;
+    float gnext = 0.f;
+    // (both stagings address through wave-uniform descriptors and the lane number taken where it is needed - v_mbcnt - so that no per-thread
+    // address survives the MFMAs; loads past a descriptor's range return zero)
+    auto lane_now = []() __attribute__((always_inline)) { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); };
+    auto fetch_g = [&](int sn) __attribute__((always_inline)) {        // wavefront q < 4, lane < 32: reader q's dx of row `lane` of step sn
+        if (wave < PW_MAXR) {
+            const int first = m_begin + 32 * sn, left = min(max(m_end - first, 0), 32);
+            const auto dg = w3_descriptor(G + (int64_t)min(wave, nr - 1) * g_stride + first, wave < nr ? (int64_t)left * 4 : 0);
+            gnext = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(dg, 4 * lane_now(), 0, 0));
+        }
+    };
+    auto put_g = [&](int sn) __attribute__((always_inline)) {
+        const int l = lane_now();
+        if (wave < PW_MAXR && l < 32) reinterpret_cast<float*>(dxs)[(sn & 1) * 32 * PW_MAXR + PW_MAXR * l + wave] = gnext;
+    };
+    auto stage = [&](int p, int sl) __attribute__((always_inline)) {   // thread j < H2: column j of predicate p's rows, every reader
+        if (wave < PW_TA / 2) {
+            const int j = 64 * wave + lane_now();
+            float e4[PW_MAXR];
+#pragma unroll
+            for (int q = 0; q < PW_MAXR; ++q) {
+                const auto de = w3_descriptor(E + (int64_t)min(q, nr - 1) * e_stride + (int64_t)p * ld_e, q < nr ? (int64_t)H2 * 4 : 0);
+                e4[q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(de, 4 * j, 0, 0));
+            }
+            etab[sl * (32 * PW_TA) + j] = make_float4(e4[0], e4[1], e4[2], e4[3]);
+        }
+    };
+    auto lookahead = [&](int sn) __attribute__((always_inline)) {      // step sn opens under another predicate than p_cur: its rows -> the other slot
+        if (sn < steps) {
+            int pn = p_cur, en = end_cur;
+            while (m_begin + 32 * sn >= en) {
+                ++pn;
+                en = __builtin_amdgcn_readfirstlane((int)pred_off[pn + 1]);
+            }
+            if (pn != p_cur) stage(pn, slot ^ 1);
+        }
+    };
     auto begin_a = [&](int s, const Desc& d) __attribute__((always_inline)) {          // before the first pair of rows
         if (is_a) {
             const int goff = k_goff(), col0 = k_col0();
             const int first = m_begin + 32 * s + (goff >> 2);         // the octet's first row
             same = first + 7 < m_end && first + 7 < end_cur;          // (all eight rows exist and belong to p_cur)
+            if constexpr (!MULTI) {
 #pragma unroll
-            for (int t = 0; t < CPT; ++t) ev[t] = 0.f;
-            if (same) {
+                for (int t = 0; t < CPT; ++t) ev[t] = 0.f;
+                if (same) {
 #pragma unroll
-                for (int t = 0; t < CPT; ++t) ev[t] = E[(int64_t)p_cur * ld_e + col0 + t];
+                    for (int t = 0; t < CPT; ++t) ev[t] = E[(int64_t)p_cur * ld_e + col0 + t];
+                }
+                gq = __builtin_amdgcn_raw_buffer_load_b64(d.g, goff, 0, 0);
             }
-            gq = __builtin_amdgcn_raw_buffer_load_b64(d.g, goff, 0, 0);
         }
     };
     auto pair_a = [&](int s, int k, const Desc& d, const Desc& next, uint32_t* __restrict__ buf32) __attribute__((always_inline)) {   // rows 2 k, 2 k + 1
@@ -915,13 +971,39 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 const int i = 2 * k + r;
                 float e[CPT];
 #pragma unroll
-                for (int t = 0; t < CPT; ++t) e[t] = ev[t];
-                if (!same) {                                           // (an octet across two predicates, or cut by the slab's end)
+                for (int t = 0; t < CPT; ++t) e[t] = ev[MULTI ? 0 : t];
+                if (!MULTI && !same) {                                 // (an octet across two predicates, or cut by the slab's end)
                     const float* er = E + (int64_t)RP[min(first + i, m_end - 1)] * ld_e + col0;
 #pragma unroll
                     for (int t = 0; t < CPT; ++t) e[t] = er[t];
                 }
-                const float gs = __uint_as_float(gq[r]) * S;          // (rows past the slab were read as zero)
+                const float gs = MULTI ? 0.f : __uint_as_float(gq[r]) * S;      // (rows past the slab were read as zero)
+                float cf[MULTI ? CPT : 1];                             // MULTI: the row's coefficients sum_k gs_k e_k[t], readers in order
+                if constexpr (MULTI) {
+                    if (r == 1) __builtin_amdgcn_sched_barrier(0);     // (a row at a time: both rows' staged operands at once cost a ring row its registers)
+                    const float4 g4 = dxs[(s & 1) * 32 + 8 * o + i];
+                    const float gm[PW_MAXR] = {g4.x * S, g4.y * S, g4.z * S, g4.w * S};
+                    if (same) {
+#pragma unroll
+                        for (int t = 0; t < CPT; ++t) {
+                            // (four columns per thread: a column at a time - the four staged entries read at once cost a ring row its registers)
+                            if (CPT == 4 && t > 0) __builtin_amdgcn_sched_barrier(0);
+                            const float4 e4 = etab[slot * (32 * PW_TA) + col0 + t];
+                            cf[t] = fmaf(gm[3], e4.w, fmaf(gm[2], e4.z, fmaf(gm[1], e4.y, gm[0] * e4.x)));
+                        }
+                    } else {                                           // (an octet across two predicates, or cut by the slab's end)
+                        const float* er = E + (int64_t)RP[min(first + i, m_end - 1)] * ld_e + col0;
+#pragma unroll
+                        for (int t = 0; t < CPT; ++t) cf[t] = gm[0] * er[t];
+#pragma unroll
+                        for (int q = 1; q < PW_MAXR; ++q)
+                            if (q < nr) {
+                                __builtin_amdgcn_sched_barrier(0);     // (a reader at a time: all readers' rows at once cost a ring row its registers)
+#pragma unroll
+                                for (int t = 0; t < CPT; ++t) cf[t] = fmaf(gm[q], er[(int64_t)q * e_stride + t], cf[t]);
+                            }
+                    }
+                }
                 if constexpr (SUMS) {
                     if (!same) {                                       // this thread's first row past the predicate's end: its sums so far belong to p_cur
                         const int rr = first + i;
@@ -939,6 +1021,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     else xv = __uint_as_float(xa[i][t]);
                     const float hh = dfol_sigmoid_hw(xv);
                     if constexpr (BIO) v[r][t] = __uint_as_float(dfol_rne2(gs * e[t] * hh * (1.0f - hh), 0.f) << 16);      // (the value dfol_pair_logit_bwd_bf16 stores)
+                    else if constexpr (MULTI) v[r][t] = cf[t] * (hh * (1.0f - hh));
                     else v[r][t] = (gs * e[t]) * (hh * (1.0f - hh));
                     if constexpr (SUMS) {
                         sde[t] = fmaf(gs, hh, sde[t]);
@@ -950,9 +1033,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
                 for (int t = 0; t < CPT; ++t) sums[512 * t] += sde[t], sums[512 * (CPT + t)] += sdb[t];
             }
-            if (k < 3) gq = __builtin_amdgcn_raw_buffer_load_b64(d.g, goff, 8 * (k + 1), 0);
-            load_a(next, 2 * k);                                       // the same rows of the next step: in flight for a whole step
-            load_a(next, 2 * k + 1);
+            if constexpr (!MULTI) {
+                if (k < 3) gq = __builtin_amdgcn_raw_buffer_load_b64(d.g, goff, 8 * (k + 1), 0);
+            }
+            if constexpr (!MULTI) {
+                load_a(next, 2 * k);                                   // the same rows of the next step: in flight for a whole step
+                load_a(next, 2 * k + 1);
+            }
 #pragma unroll
             for (int t = 0; t < CPT; ++t) {
                 const int at = entry(col0 + t, o, PW_TA) * 4 + k;      // 4-byte piece k of the entry: rows 2 k, 2 k + 1
@@ -964,6 +1051,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     buf32[at] = h;
                     buf32[at + PW_TA * 64 * 4] = l;
                 }
+            }
+            if constexpr (MULTI) {                                     // (after the pair has left: with the pair's values still held, four columns cost a ring row its registers)
+                load_a(next, 2 * k);
+                load_a(next, 2 * k + 1);
             }
         }
     };
@@ -1021,6 +1112,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         for (int i = 0; i < 8; ++i)
             if (is_a) load_a(d0, i);
         if (is_z) load_z(d0);
+        if constexpr (MULTI) {
+            stage(p_cur, 0);
+            lookahead(1);
+            fetch_g(0), put_g(0);
+            fetch_g(1), put_g(1);
+        }
         __syncthreads();                                               // the zeroed buffers
         begin_a(0, d0);
 #pragma unroll
@@ -1042,6 +1139,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             // the predicate ended inside step s: the threads whose octet of step s reached its end have flushed there, the others flush now
             if (p_cur != p_old && is_a && m_begin + 32 * s + 8 * k_oa() + 7 < end_old) flush_de(p_old);
         }
+        if constexpr (MULTI) {
+            if (p_cur != p_old) slot ^= 1;                             // (its rows were staged a step ago; this step's barrier publishes the next)
+            lookahead(s + 2);
+        }
         const Desc d1 = descriptors(s + 1), d2 = descriptors(s + 2);
         if (more) begin_a(s + 1, d1);
         fence();
@@ -1060,6 +1161,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         tile_row(cur, 1, 1); tile_row(cur, 1, 2);
         fence();
         if (more) pair_a(s + 1, 3, d1, d2, nxt32);
+        if constexpr (MULTI) fetch_g(s + 2);                           // (in flight under the last two tile rows only)
         fence();
         tile_row(cur, 1, 3);
         fence();
@@ -1067,6 +1169,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         fence();
         tile_row(cur, 1, 4);
         fence();
+        if constexpr (MULTI) put_g(s + 2);
         __syncthreads();                                               // step s + 1 is complete in LDS; everyone is past the MFMAs of step s
     }
 
@@ -1214,7 +1317,7 @@ static int pw_launch(const void* pre2, int64_t ld_p2, const float* dx, const int
                                                         (int)((size_t)2 * PW_BUF * 16 + (2 + 6) * 512 * 4));                                     \
         DFOL_REQUIRE(ok == hipSuccess, "pair_wgrad_fused: cannot reserve %zu bytes of LDS (%s)", lds, hipGetErrorString(ok));                      \
         hipLaunchKernelGGL((pair_wgrad_fused_kernel<C, S>), dim3(slabs), dim3(512), lds, st, pre2, ld_p2, dx, row_pred, pred_off, E, ld_e, scale, Z, \
-                           ld_z, (int)M, H2, H1, rows_per_slab, workspace, de_part, db_part);                                                   \
+                           ld_z, (int)M, H2, H1, rows_per_slab, workspace, de_part, db_part, 0, (int64_t)0, (int64_t)0);                         \
     }
     if (bio) {
         lds = (size_t)PW_BUF * 16 + (2 + 8) * 512 * 4;                  // (one piece per operand: the two buffers are half the size)
@@ -1222,7 +1325,7 @@ static int pw_launch(const void* pre2, int64_t ld_p2, const float* dx, const int
                                                         (int)((size_t)PW_BUF * 16 + (2 + 8) * 512 * 4));
         DFOL_REQUIRE(ok == hipSuccess && sums, "pair_wgrad_fused (bf16 storage): cannot reserve %zu bytes of LDS (%s)", lds, hipGetErrorString(ok));
         hipLaunchKernelGGL((pair_wgrad_fused_kernel<4, true, true>), dim3(slabs), dim3(512), lds, st, pre2, ld_p2, dx, row_pred, pred_off, E, ld_e, scale, Z,
-                           ld_z, (int)M, H2, H1, rows_per_slab, workspace, de_part, db_part);
+                           ld_z, (int)M, H2, H1, rows_per_slab, workspace, de_part, db_part, 0, (int64_t)0, (int64_t)0);
     } else if (H2 % 3 == 0) {                                          // (4 (H2 / 3) <= 427 threads build dpre2)
         if (sums) DFOL_PW(3, true) else DFOL_PW(3, false)
     } else {
@@ -1238,5 +1341,93 @@ static int pw_launch(const void* pre2, int64_t ld_p2, const float* dx, const int
                            rows_per_slab, dE, ld_de, dbe, db2);
         DFOL_LAUNCH_CHECK("pair_wgrad_fused (sums reduce)");
     }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Several readers of one trunk in ONE weight-gradient pass (pair_wgrad_fused_kernel<.., MULTI>): dW2 = sum_k dpre2_k^T Z with pre2 and Z read
+// once instead of once per reader.  The readers' own sums (dE, dbe, db2) stay with dfol_pair_logit_bwd_sums_f32.
+
+// The launch's scale without a host sync: the largest row bound sum_k |dx_k[r]| emax_k[p(r)] / 4 (formed as tall_row_scale_multi_kernel forms a
+// row's, csrc/dfol_dense_tall.hip) as the bits of a non-negative float - their order is the integers' order and a maximum does not depend
+// on the order of its updates, so the atomic keeps the run repeatable - then {S, 1 / S} of it.
+__global__ __launch_bounds__(256) void pair_wgrad_multi_bound_kernel(const float* __restrict__ dx, int64_t dx_stride, const int32_t* __restrict__ row_pred,
+                                                                     const float* __restrict__ emax, int P, int nr, int M,
+                                                                     uint32_t* __restrict__ bound_max) {
+    __shared__ float wmax[4];
+    float m = 0.f;
+    for (int r = blockIdx.x * 256 + (int)threadIdx.x; r < M; r += gridDim.x * 256) {
+        const int p = row_pred[r];
+        float bound = 0.f;
+#pragma unroll
+        for (int q = 0; q < PW_MAXR; ++q) {
+            const float g = (p >= 0 && q < nr) ? dx[(int64_t)q * dx_stride + r] : 0.f;
+            bound += fabsf(g) * (q < nr ? emax[(int64_t)q * P + max(p, 0)] : 0.f) * 0.25f;
+        }
+        if (bound > 0.f && bound < 3.0e38f) m = fmaxf(m, bound);         // (a non-finite bound leaves the scale alone; the products show the NaN)
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) m = fmaxf(m, __shfl_xor(m, s, 64));
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+        if (m > 0.f) atomicMax(bound_max, __float_as_uint(m));
+    }
+}
+__global__ void pair_wgrad_multi_scale_kernel(const float* __restrict__ bound_max, float* __restrict__ scale) {
+    const int e = dfol_scale_exp(bound_max[0]);
+    scale[0] = ldexpf(1.0f, e);
+    scale[1] = ldexpf(1.0f, -e);
+}
+
+// scale [3] (device): {S, 1 / S}, then the bound itself; dx [nr][dx_stride >= M], emax [nr][P] = max_j |E_k[p][j]|, row_pred [M] (< 0: no gradient)
+extern "C" int dfol_pair_wgrad_multi_scale_f32(const float* dx, int64_t dx_stride, int32_t nr, const int32_t* row_pred, const float* emax, int32_t P,
+                                               int64_t M, float* scale, void* stream) {
+    DFOL_REQUIRE(nr >= 1 && nr <= PW_MAXR && P >= 1 && M > 0 && M < (1ll << 31) - 64 && dx_stride >= M,
+                 "pair_wgrad_multi_scale: %d readers (1..%d), P=%d, M=%lld, dx_stride=%lld", nr, PW_MAXR, P, (long long)M, (long long)dx_stride);
+    DFOL_REQUIRE(dx && row_pred && emax && scale, "pair_wgrad_multi_scale: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    DFOL_REQUIRE(hipMemsetAsync(scale + 2, 0, 4, st) == hipSuccess, "pair_wgrad_multi_scale: hipMemsetAsync failed");
+    hipLaunchKernelGGL(pair_wgrad_multi_bound_kernel, dim3((unsigned)std::min<int64_t>(dfol_cdiv(M, 256), 1024)), dim3(256), 0, st, dx, dx_stride, row_pred, emax, P,
+                       nr, (int)M, reinterpret_cast<uint32_t*>(scale + 2));
+    hipLaunchKernelGGL(pair_wgrad_multi_scale_kernel, dim3(1), dim3(1), 0, st, (const float*)(scale + 2), scale);
+    DFOL_LAUNCH_CHECK("pair_wgrad_multi_scale");
+    return 0;
+}
+
+// dx [nr][dx_stride >= M], E [nr][P][ld_e] (reader k's rows at E + k P ld_e); row_pred, pred_off, scale, workspace and the size rules as
+// dfol_pair_wgrad_fused_f32 (scale from the bound of the SUM: dfol_pair_wgrad_multi_scale_f32); 1 <= nr <= 4, more readers: further launches, added
+extern "C" int dfol_pair_wgrad_fused_multi_f32(const float* pre2, int64_t ld_p2, const float* dx, int64_t dx_stride, int32_t nr, const int32_t* row_pred,
+                                               const int64_t* pred_off, const float* E, int64_t ld_e, int32_t P, const float* scale, const float* Z,
+                                               int64_t ld_z, int64_t M, int32_t H2, int32_t H1, float* workspace, float* dW, void* stream) {
+    DFOL_REQUIRE(nr >= 1 && nr <= PW_MAXR && P >= 1, "pair_wgrad_fused_multi: %d readers (1..%d), P=%d", nr, PW_MAXR, P);
+    DFOL_REQUIRE(M > 0 && M < (1ll << 31) - 64 && H2 >= 4 && H1 >= 4 && H2 % 4 == 0 && H1 % 4 == 0 && H2 <= 32 * PW_TA && H1 <= 32 * PW_TB,
+                 "pair_wgrad_fused_multi: bad sizes M=%lld H2=%d H1=%d (multiples of 4, H2 <= %d, H1 <= %d)", (long long)M, H2, H1, 32 * PW_TA, 32 * PW_TB);
+    DFOL_REQUIRE(dx_stride >= M, "pair_wgrad_fused_multi: dx_stride=%lld < M=%lld", (long long)dx_stride, (long long)M);
+    DFOL_REQUIRE(pre2 && dx && row_pred && pred_off && E && scale && Z && workspace && dW, "pair_wgrad_fused_multi: null pointer");
+    DFOL_REQUIRE(ld_p2 % 4 == 0 && ld_p2 >= H2 && ld_z % 4 == 0 && ld_z >= H1 && ld_e % 4 == 0 && ld_e >= H2 && ((uintptr_t)pre2 % 16 == 0) &&
+                 ((uintptr_t)Z % 16 == 0) && ((uintptr_t)E % 16 == 0), "pair_wgrad_fused_multi: rows of pre2, Z and E must be 16-byte aligned");
+    DFOL_REQUIRE(8 * std::max(ld_p2, ld_z) * 4 * 4 < (1ll << 31), "pair_wgrad_fused_multi: row stride too large (%lld)", (long long)std::max(ld_p2, ld_z));
+    const int slabs = pw_slabs(M);
+    const int rows_per_slab = (dfol_cdiv(M, slabs) + 31) & ~31;
+    const size_t lds = (size_t)2 * PW_BUF * 16 + (2 + 6) * 512 * 4;       // (two slots of 320 x 4 staged floats fit the 12 KB behind the constant words)
+    static_assert(2 * 32 * PW_TA * PW_MAXR * 4 <= 6 * 512 * 4, "the staged embedding rows must fit behind the constant words");
+    const int64_t elems = (int64_t)H2 * H1, e_stride = (int64_t)P * ld_e;
+    float* none = nullptr;
+    hipStream_t st = (hipStream_t)stream;
+#define DFOL_PWM(C)                                                                                                                                         \
+    {                                                                                                                                                      \
+        static const hipError_t ok = hipFuncSetAttribute((const void*)pair_wgrad_fused_kernel<C, false, false, true>,                                       \
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)2 * PW_BUF * 16 + (2 + 6) * 512 * 4));   \
+        DFOL_REQUIRE(ok == hipSuccess, "pair_wgrad_fused_multi: cannot reserve %zu bytes of LDS (%s)", lds, hipGetErrorString(ok));                          \
+        hipLaunchKernelGGL((pair_wgrad_fused_kernel<C, false, false, true>), dim3(slabs), dim3(512), lds, st, (const void*)pre2, ld_p2, dx, row_pred,        \
+                           pred_off, E, ld_e, scale, (const void*)Z, ld_z, (int)M, H2, H1, rows_per_slab, workspace, none, none, (int)nr, dx_stride, e_stride); \
+    }
+    if (H2 % 3 == 0) DFOL_PWM(3) else DFOL_PWM(4)
+#undef DFOL_PWM
+    DFOL_LAUNCH_CHECK("pair_wgrad_fused_multi");
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(dfol_cdiv(dfol_cdiv(elems, 4), 16)), dim3(256), 0, st, workspace, slabs, elems, dW);
+    DFOL_LAUNCH_CHECK("pair_wgrad_fused_multi (reduce)");
     return 0;
 }

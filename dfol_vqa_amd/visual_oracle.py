@@ -410,6 +410,18 @@ class _PairTrunk(torch.autograd.Function):
             else:
                 st["dz"] = L.pair_dz_tall_multi([j[0] for j in jobs], st["pre2"], [j[1] for j in jobs], jobs[0][2], st["w"], dz_out=st["dz"])
                 _lib.note("pair_dz_multi")
+        wjobs = st.get("dw_jobs")
+        if wjobs:                                            # ... and their dW2 shares: one pass over pre2 and Z instead of one per reader
+            for job in wjobs:                                # (held past the readers' backward for kernels queued on THIS stream: the allocator must
+                for t in job:                                # not hand their memory to another stream's node before those have run)
+                    t.record_stream(torch.cuda.current_stream(t.device))
+            if len(wjobs) == 1:
+                dxj, ej, rpj, poj = wjobs[0]
+                _, dwj = L.pair_head_products(dxj, st["pre2"], st["z"], st["w"], ej, poj, rpj, False, True)
+            else:
+                dwj = L.pair_wgrad_multi([j[0] for j in wjobs], st["pre2"], st["z"], [j[1] for j in wjobs], wjobs[0][3], wjobs[0][2])
+                _lib.note("pair_wgrad_multi")
+            st["dw"] = dwj if st["dw"] is None else st["dw"] + dwj
         dz, dw, db = st["dz"], st["dw"], st["db"]
         dev = st["w"].device
         if st["need_dz"] and dz is None:
@@ -461,7 +473,21 @@ class _HeadUse(torch.autograd.Function):
             st["dz_P"] = e_rows.shape[0]
             st.setdefault("dz_jobs", []).append((dx, e_rows, row_pred))
             _lib.note("head_use_dz_deferred")
-        if ctx.sums_ok and st["need_dw"] and pre2.shape[1] % 3 == 0 and mode != "0" and (mode == "1" or pre2.shape[0] >= (1 << 20)):
+        # ... and so are their dW2 shares (DFOL_WGRAD_MULTI=1; dfol_pair_wgrad_fused_multi_f32, which has no row-count floor): the reader keeps the
+        # small pass for its own sums.  DFOL_HEAD_SUMS=1 keeps the per-reader pass that yields the sums as well.
+        defer_dw = (st["need_dw"] and st.get("readers", 1) >= 2 and os.environ.get("DFOL_WGRAD_MULTI", "0") == "1" and mode != "1"
+                    and pre2.dtype == torch.float32 and e_rows.shape[0] == st.get("dw_P", e_rows.shape[0])
+                    and int(pred_off.shape[0]) - 1 == e_rows.shape[0] and row_pred is not None and row_pred.shape[0] == pre2.shape[0]
+                    and row_pred.data_ptr() in st.get("allq", ()))
+        if defer_dw:
+            st["dw_P"] = e_rows.shape[0]
+            st.setdefault("dw_jobs", []).append((dx, e_rows, row_pred, pred_off))
+            _lib.note("head_use_dw_deferred")
+            _lib.note("head_use_backward")
+            de, dbe, db2p = L.pair_head_sums(dx, pre2, e_rows, pred_off, need_bias=need_be)
+            db2 = db2p.sum(0) if st["need_db"] else None
+            dz, dw = L.pair_head_products(dx, pre2, st["z"], st["w"], e_rows, pred_off, row_pred, need_dz_now, False, dz_out=st["dz"])
+        elif ctx.sums_ok and st["need_dw"] and pre2.shape[1] % 3 == 0 and mode != "0" and (mode == "1" or pre2.shape[0] >= (1 << 20)):
             _lib.note("head_use_backward_sums")
             dz, dw, de, dbe, db2 = L.pair_head_products(dx, pre2, st["z"], st["w"], e_rows, pred_off, row_pred, need_dz_now, True, dz_out=st["dz"],
                                                         sums=True, need_bias=need_be)
@@ -472,7 +498,7 @@ class _HeadUse(torch.autograd.Function):
             dz, dw = L.pair_head_products(dx, pre2, st["z"], st["w"], e_rows, pred_off, row_pred, need_dz_now, st["need_dw"], dz_out=st["dz"])
         if need_dz_now:
             st["dz"] = dz                                     # (a later reader adds into it)
-        if st["need_dw"]:
+        if st["need_dw"] and not defer_dw:
             st["dw"] = dw if st["dw"] is None else st["dw"] + dw
         if st["need_db"]:
             st["db"] = db2 if st["db"] is None else st["db"] + db2

@@ -601,6 +601,18 @@ int dfol_pair_dz_tall_f32(const float* pre2, int64_t ld_p2, const float* dx, con
 int dfol_pair_dz_tall_multi_f32(const float* pre2, int64_t ld_p2, const float* dx, int64_t dx_stride, int32_t nr, const int32_t* row_pred, const float* E,
                                 int64_t ld_e, int32_t P, const float* emax, const void* W2t_split, float* dZ, int64_t ld_dz, int32_t M, int32_t HID1,
                                 int32_t HID2, int32_t accumulate, float* workspace, void* stream);
+/* ... and their weight gradient in ONE pass (csrc/dfol_dense_wgrad.hip): dW2 [HID2, HID1] = sum_k dpre2_k^T Z with pre2 and Z read once instead of
+ * once per reader; the readers' own sums (dE, dbe, db2) stay with dfol_pair_logit_bwd_sums_f32.  Operands laid out as for
+ * dfol_pair_dz_tall_multi_f32 (dx [nr][dx_stride >= M], E [nr][P][ld_e], shared row_pred / pred_off as dfol_pair_wgrad_fused_f32 takes them),
+ * 1 <= nr <= 4, sizes, alignment and workspace (dfol_pair_wgrad_fused_workspace) as dfol_pair_wgrad_fused_f32 - no row-count floor.  scale -> {S, 1 / S}
+ * on the device, S a power of two with S max_r sum_k |dx_k[r]| emax_k[row_pred[r]] / 4 <= 2^14: dfol_pair_wgrad_multi_scale_f32 writes it (and the
+ * bound itself) into scale [3] from emax [nr][P] = max_j |E_k[p][j]|, without a host sync.  One reader and the same scale: the bits of
+ * dfol_pair_wgrad_fused_f32. */
+int dfol_pair_wgrad_multi_scale_f32(const float* dx, int64_t dx_stride, int32_t nr, const int32_t* row_pred, const float* emax, int32_t P, int64_t M,
+                                    float* scale, void* stream);
+int dfol_pair_wgrad_fused_multi_f32(const float* pre2, int64_t ld_p2, const float* dx, int64_t dx_stride, int32_t nr, const int32_t* row_pred,
+                                    const int64_t* pred_off, const float* E, int64_t ld_e, int32_t P, const float* scale, const float* Z, int64_t ld_z,
+                                    int64_t M, int32_t HID2, int32_t HID1, float* workspace, float* dW, void* stream);
 /* The bf16 mode's forms of the same (bf16-STORED activations: `void*` rows of bfloat16, strides in elements, multiples of 4; one bf16 piece
  * per operand, fp32 accumulation, bfloat16 results rounded to nearest even): bit for bit dfol_linear_act_bf16_bf16 resp.
  * dfol_pair_logit_bwd_bf16 followed by it; wgrad_fused_sums_bf16 always yields the sums (every predicate >= 64 rows or none), needs no
