@@ -206,6 +206,9 @@ SIGNATURES = {
     "dfol_set_range_status": [_p],
     "dfol_set_feature_rows": [_p, _p],
     "dfol_set_feature_cache": [_p, _i64, _i32, _p, _p],
+    "dfol_pair_features_bwd_f32": [_p, _i64, _i32, _p, _p, _i32, _i32, _p, _i64, _p],
+    "dfol_dropout_advance": [_p, _p],
+    "dfol_dropout_f32": [_p, _i64, _p, _i64, _i64, _i32, _f, _p, ctypes.c_uint32, _p],
 }
 
 
@@ -928,6 +931,137 @@ def pair_features(obj, D, obj_off, pair_off, Q, max_n, pairs):
     call("dfol_pair_features_f32", _dp(obj), obj.stride(0), D, _ptr(obj_off, I32), _ptr(pair_off, I64), Q, max_n,
          _dp(out), out.stride(0), _stream())
     return out
+
+
+def pair_features_bwd(g, D, obj_off, pair_off, Q, max_n, objects):
+    """The gradient of the object matrix [objects, D] from the pair matrix's g [pairs, >= 2 D], without atomics and in one fixed order
+    (csrc/dfol_dropout.hip: pair_features_bwd_kernel)."""
+    if g.dim() != 2 or g.dtype != F32 or g.shape[1] < 2 * D or (g.shape[0] > 1 and g.stride(1) != 1):
+        raise DfolError("pair_features_bwd: g must be fp32 rows of unit column stride and at least 2 D = %d columns" % (2 * D))
+    out = torch.empty(objects, D, dtype=F32, device=g.device)
+    call("dfol_pair_features_bwd_f32", _dp(g), g.stride(0), D, _ptr(obj_off, I32), _ptr(pair_off, I64), Q, max_n, _dp(out), out.stride(0),
+         _stream())
+    return out
+
+
+# ---- dropout: counter-based masks (csrc/dfol_dropout.hip, DESIGN.md 3.5) -----------------------------------------------------------------
+# One 32-byte state per device: {seed u64, step u64, key u32[2], rank u32, pad} as four int64.  A forward that drops advances the step with one
+# tiny launch - on the device, so a replayed graph draws new masks on every replay - and every Dropout of that forward takes the next SITE
+# number: a host counter that starts at zero with the forward, hence the same at capture and at every replay.
+_DROPOUT_STATES = {}                 # device index -> int64 [4] on that device
+_DROPOUT_SEED = None                 # (seed, rank or None) of the last seed_dropout(), for states created after it
+_DROPOUT_FORWARD = threading.local()  # .site: the next site number; .pending: this forward has not advanced the step yet
+DROPOUT_TRACE = None                 # tests: a list that receives (site, shape, p) of every dropout launch of a forward
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 on the host (the kernels' generator, restated with Python integers): -> four 32-bit words."""
+    c0, c1, c2, c3 = (int(v) & 0xFFFFFFFF for v in counter)
+    k0, k1 = (int(v) & 0xFFFFFFFF for v in key)
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & 0xFFFFFFFF, (p0 >> 32) ^ c3 ^ k1, p0 & 0xFFFFFFFF
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return c0, c1, c2, c3
+
+
+def _dropout_record(seed, rank):
+    """The state at step 0 as four signed int64: its key is already the advance rule's for step 0."""
+    seed, rank = int(seed) & 0xFFFFFFFFFFFFFFFF, int(rank) & 0xFFFFFFFF
+    k = philox4x32_10((0, 0, rank, 0), (seed & 0xFFFFFFFF, seed >> 32))
+    signed = lambda v: v - (1 << 64) if v >= (1 << 63) else v
+    return [signed(seed), 0, signed(k[0] | (k[1] << 32)), rank]
+
+
+def _dropout_rank(rank=None):
+    if rank is not None:
+        return int(rank)
+    import torch.distributed as dist
+    return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+
+
+def dropout_state(device=None):
+    """The dropout stream state of `device` (default: the current one), created on first use from torch.initial_seed() and the process-group
+    rank (0 without a group), or from the last seed_dropout()."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise DfolError("the HIP path needs tensors on the GPU (got device %s); there is no CPU fallback" % dev)
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    state = _DROPOUT_STATES.get(index)
+    if state is None:
+        seed, rank = _DROPOUT_SEED if _DROPOUT_SEED is not None else (torch.initial_seed(), None)
+        state = _DROPOUT_STATES[index] = torch.tensor(_dropout_record(seed, _dropout_rank(rank)), dtype=I64, device=torch.device("cuda", index))
+    return state
+
+
+def seed_dropout(seed, rank=None):
+    """Restart the dropout streams of every device at step 0 of (seed, rank); rank=None: the process-group rank, 0 without a group.  States
+    are rewritten in place: a captured graph keeps reading the same record."""
+    global _DROPOUT_SEED
+    _DROPOUT_SEED = (int(seed), rank)
+    record = _dropout_record(seed, _dropout_rank(rank))
+    for state in _DROPOUT_STATES.values():
+        state.copy_(torch.tensor(record, dtype=I64))
+
+
+def dropout_key(device=None):
+    """The 8 bytes of the current key as a view of the state: what dfol_dropout_f32 reads at run time."""
+    return dropout_state(device)[2:3]
+
+
+def dropout_advance(device=None):
+    """step += 1 and the step's key, one tiny launch on the current stream (a node of whatever capture is running)."""
+    state = dropout_state(device)
+    call("dfol_dropout_advance", _ptr(state, I64), _stream())
+
+
+def dropout_forward_begins():
+    """A forward starts (interpreter._forward): its Dropouts count their sites from zero, and the first of them advances the step - a forward
+    without an active Dropout launches nothing."""
+    _DROPOUT_FORWARD.site, _DROPOUT_FORWARD.pending = 0, True
+
+
+def dropout_next_site(device):
+    """-> the site number of the next Dropout of this forward; the forward's first one advances the device's step before it."""
+    if getattr(_DROPOUT_FORWARD, "pending", False):
+        _DROPOUT_FORWARD.pending = False
+        dropout_advance(device)
+    site = getattr(_DROPOUT_FORWARD, "site", 0)
+    _DROPOUT_FORWARD.site = site + 1
+    return site
+
+
+def dropout(x, p, key, site, out=None, count=True):
+    """y = x * mask(key, site) / (1 - p) over a matrix [rows, cols] of unit column stride and any row stride (dfol_dropout_f32); key: int64 [1]
+    on the device - dropout_key() or a copy of it; out= may be x itself.  count=False: a read-out of the mask, not a use (no route counter)."""
+    if x.dim() != 2 or x.dtype != F32 or not x.is_cuda or x.shape[1] < 1 or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise DfolError("dropout: x must be an fp32 device matrix [rows, cols >= 1] of unit column stride (got %s, strides %s, %s on %s)"
+                        % (tuple(x.shape), tuple(x.stride()), x.dtype, x.device))
+    if out is None:
+        out = torch.empty(x.shape, dtype=F32, device=x.device)
+    elif out.shape != x.shape or out.dtype != F32 or out.device != x.device or (x.shape[1] > 1 and out.stride(1) != 1):
+        raise DfolError("dropout: out= must match x in shape, dtype and device, with unit column stride")
+    rows, cols = x.shape
+    if rows > 1 and x.stride(0) < cols:                      # (an expanded tensor - the gradient of a sum - has no rows of its own)
+        x = x.contiguous()
+    if rows > 1 and out.stride(0) < cols:
+        raise DfolError("dropout: out= has overlapping rows (row stride %d < %d columns)" % (out.stride(0), cols))
+    ldx = x.stride(0) if rows > 1 else cols
+    ldy = out.stride(0) if rows > 1 else cols
+    if count:
+        note("dropout")
+        if DROPOUT_TRACE is not None:
+            DROPOUT_TRACE.append((int(site), (rows, cols), float(p)))
+    call("dfol_dropout_f32", _dp(x), ldx, _dp(out), ldy, rows, cols, float(p), _ptr(key, I64), int(site), _stream())
+    return out
+
+
+def dropout_mask(shape, p, site, device=None, key=None):
+    """The keep mask (bool) of (shape, p, site) under the device's current key - or under `key` -, by running the kernel on ones."""
+    rows, cols = shape
+    state = dropout_state(device)
+    y = dropout(torch.ones(int(rows), int(cols), dtype=F32, device=state.device), p, state[2:3] if key is None else key, site, count=False)
+    return y != 0
 
 
 def attr_ll(hidden, emb_w, emb_b, obj_off, pred_q, pred_col, NS, default_ll=-30.0):

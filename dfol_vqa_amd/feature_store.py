@@ -318,6 +318,11 @@ class DeviceFeatureStore(object):
         if torch.cuda.is_current_stream_capturing():
             raise _lib.DfolError("feature store: featurize() builds the cache of featurizer rows and cannot run inside a stream capture; build it "
                                  "(or run one eager forward) before the capture")
+        from .interpreter import active_dropout
+        drop = active_dropout(net)
+        if drop is not None:
+            raise _lib.DfolError("feature store: featurize(): nn.%r of the featurizer network is in training mode: its rows differ from step to "
+                                 "step and cannot be cached; put the featurizer in eval() (or use dropout: 0)" % (drop,))
         self._featurized.need_raw("featurize() for new featurizer weights")
         layers, why = store_layers_of(net, self.F, FEATURIZE_BLOCK_ROWS)
         if layers is None:

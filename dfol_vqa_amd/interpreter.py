@@ -37,6 +37,15 @@ def featurizer_trains(net):
     return torch.is_grad_enabled() and any(p.requires_grad for p in net.parameters())
 
 
+def active_dropout(net):
+    """The first nn.Dropout of a featurizer network (a RegularMLP) that drops under the current mode (training, p > 0), or None."""
+    seq = getattr(net, "_network", None)
+    for m in (() if seq is None else seq):
+        if isinstance(m, nn.Dropout) and m.training and m.p > 0:
+            return m
+    return None
+
+
 def store_layers_of(net, F, M):
     """-> (the featurizer network's layers [(Linear, activation)], None) when its first product can read M rows of a feature store of width F in
     place - the two-piece fp16 arithmetic on a weight of the split kernels' size, the store's width, a shape the wide kernel takes and pays for
@@ -82,9 +91,12 @@ class BatchGQABoxFeaturizer(nn.Module):
     def _cached_objects(self, rows):
         """The object matrix of a `featurized` store's batch from the store's cached featurizer rows (feature_store.DeviceFeatureStore.featurize:
         built on first use, rebuilt once when a weight's version has changed), or None: a store without a cache, a featurizer that trains under
-        the current grad mode (its output is no constant), or a network the cache cannot be built for - the caller goes on as for a direct store."""
+        the current grad mode (its output is no constant), one with an active Dropout (its output differs from step to step), or a network the
+        cache cannot be built for - the caller goes on as for a direct store."""
         net = self._featurizer_network
         if not getattr(rows.store, "featurized", False) or net is None or featurizer_trains(net):
+            return None
+        if active_dropout(net) is not None:                   # (the cached rows were never dropped: a frozen featurizer in train() drops anew)
             return None
         cache = rows.store.cached_for(net, build=True)
         return None if cache is None else rows.objects(cache)
@@ -138,7 +150,7 @@ class BatchGQABoxFeaturizer(nn.Module):
         pair = None
         if geo is not None and geo._pair_num > 0:
             pair = L.pair_features(obj, D, geo._obj_off, geo._pair_off, geo._batch_size, max(geo._n_list), geo._pair_num,
-                                   pair_index=geo.pair_index)                                                                # :252-279
+                                   pair_index=geo.pair_index, ordered=getattr(geo, "_dropout_route", False))                 # :252-279
         return {'attribute_features': obj, 'relation_features': {'features': pair, 'index': None}, 'object_num': object_num}
 
 
@@ -440,6 +452,15 @@ class BatchInterpreterBase(nn.Module):
         geometry = BatchWorld(device, object_features.size(0), None, None, batch_index, meta_data,
                               attention_transfer_state_dim=self._attention_transfer_state_dim, object_nums=object_nums,
                               question_image=question_image)
+        dropping = None if needed or not self._cached else getattr(self._oracle, "active_dropout", lambda: None)()
+        if dropping is not None:
+            # the full-table dataflow because a Dropout drops: every Dropout of the reference is an element-wise kernel on a tensor that exists
+            # there (csrc/dfol_dropout.hip), and the pair matrix's backward takes the ordered kernel instead of atomic index_add_
+            from . import _lib
+            geometry._dropout_route = True
+            _lib.fallback("dropout_full_tables", "nn.%r is in training mode" % (dropping,),
+                          what="takes the full-table dataflow: it stays on this library's dense kernels, with counter-based dropout masks, but "
+                               "not on the fused pair and attribute kernels")
         if needed:
             features = self._featurizer.featurize_scene(device, object_features, batch_index, meta_data, world_geometry=None)
             self._oracle.prepare_scene(geometry, features['attribute_features'], train=oracle_trains)
@@ -480,7 +501,8 @@ class BatchInterpreterBase(nn.Module):
     def _forward(self, program_batch_list, is_training, return_trace, modulator_switch, rerun):
         """rerun: this forward reads its own answers back (no outer queue) and may run the batch again when its range check flags it; a forward
         whose read-backs an owner runs - forward_async, a graph capture - leaves that to the owner."""
-        from . import gqa_ops
+        from . import gqa_ops, _lib
+        _lib.dropout_forward_begins()                          # Dropout sites count from zero; the first one that drops advances the step
         outer = gqa_ops.DEFERRED.queue
         queue = [] if outer is None else outer                 # (a graph capture installs its own queue, see GraphedForward)
         gqa_ops.DEFERRED.queue = queue

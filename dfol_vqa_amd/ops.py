@@ -293,11 +293,75 @@ class _PairFeatures(torch.autograd.Function):
         return g_obj, None, None, None, None, None, None, None, None
 
 
-def pair_features(obj, D, obj_off, pair_off, Q, max_n, pairs, pair_index=None):
+class _PairFeaturesOrdered(torch.autograd.Function):
+    """The same forward with the backward of csrc/dfol_dropout.hip: no atomics, one fixed summation order.  The dropout route's: there the pair
+    matrix is the training route's heaviest backward, and its steps must repeat bit for bit."""
+
+    @staticmethod
+    def forward(ctx, obj, D, obj_off, pair_off, Q, max_n, pairs):
+        ctx.save_for_backward(obj_off, pair_off)
+        ctx.meta = (tuple(obj.shape), D, Q, max_n)
+        return _lib.pair_features(obj, D, obj_off, pair_off, Q, max_n, pairs)
+
+    @staticmethod
+    def backward(ctx, g):
+        obj_off, pair_off = ctx.saved_tensors
+        shape, D, Q, max_n = ctx.meta
+        if g.stride(1) != 1:
+            g = g.contiguous()
+        g_obj = _lib.pair_features_bwd(g, D, obj_off, pair_off, Q, max_n, shape[0])
+        if shape[1] != D:                                   # (an object matrix wider than the D columns the pairs read)
+            wide = torch.zeros(shape, dtype=g.dtype, device=g.device)
+            wide[:, :D] = g_obj
+            g_obj = wide
+        return g_obj, None, None, None, None, None, None
+
+
+def pair_features(obj, D, obj_off, pair_off, Q, max_n, pairs, pair_index=None, ordered=False):
+    """ordered=True: the backward without atomics (dfol_pair_features_bwd_f32) instead of index_add_ - the dropout route asks for it; the
+    dropout-0 full-table route keeps index_add_ and its bits."""
     if _needs_grad(obj):
+        if ordered:
+            _lib.note("pair_features_bwd_ordered")
+            return _PairFeaturesOrdered.apply(obj, D, obj_off, pair_off, Q, max_n, pairs)
         ind_s, ind_o = pair_index()
         return _PairFeatures.apply(obj, D, obj_off, pair_off, Q, max_n, pairs, ind_s, ind_o)
     return _lib.pair_features(obj, D, obj_off, pair_off, Q, max_n, pairs)
+
+
+class _Dropout(torch.autograd.Function):
+    """y = x * mask / (1 - p) by dfol_dropout_f32.  Nothing of the mask is saved but the 8 bytes of the key it was drawn under and the site
+    number: the backward runs the same kernel over the incoming gradient, also after a later forward has advanced the step."""
+
+    @staticmethod
+    def forward(ctx, x, p, key, site):
+        ctx.save_for_backward(key)
+        ctx.meta = (p, site)
+        return _lib.dropout(x, p, key, site)
+
+    @staticmethod
+    def backward(ctx, g):
+        (key,) = ctx.saved_tensors
+        p, site = ctx.meta
+        if g.shape[1] > 1 and g.stride(1) != 1:
+            g = g.contiguous()
+        return _lib.dropout(g, p, key, site), None, None, None
+
+
+def dropout(x, p):
+    """nn.Dropout(p) in training mode on a matrix [rows, cols] (any row stride): the next site of this forward under the device's current key
+    (csrc/dfol_dropout.hip; _lib.dropout_next_site).  p = 0 returns x without a launch."""
+    if p <= 0:
+        return x
+    if not 0 < p < 1:
+        raise DfolError("dropout: p = %r is not in [0, 1)" % (p,))
+    if not x.is_cuda:
+        raise DfolError("the HIP path needs tensors on the GPU (got a %s tensor); there is no CPU fallback" % x.device)
+    site = _lib.dropout_next_site(x.device)
+    key = _lib.dropout_key(x.device)
+    if _needs_grad(x):
+        return _Dropout.apply(x, float(p), key.clone(), site)      # (its own copy of the key: a backward after a later forward keeps its mask)
+    return _lib.dropout(x, float(p), key, site)
 
 
 def _modulate_reference(att, mods, valid):

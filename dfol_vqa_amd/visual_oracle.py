@@ -38,7 +38,7 @@ def _run_layers(seq, x, out=None):
         m = mods[i]
         if isinstance(m, nn.Dropout):
             if m.training and m.p > 0:
-                raise L.DfolError("dropout > 0 in training mode is not built on the HIP path; use dropout: 0")
+                x = L.dropout(x, m.p)                   # csrc/dfol_dropout.hip: the next site of this forward
             i += 1
             continue
         assert isinstance(m, nn.Linear), "unexpected layer %r" % (m,)
@@ -655,7 +655,8 @@ class ClassifierOracle(OracleBase):
     def _relation_embedding(self):
         """Rows of the embedding layer that are relations ([:, relation_index] commutes with the GEMM)."""
         lin = self._embedding_network.linear
-        idx = torch.as_tensor(self._ontology._relation_index, dtype=torch.int64, device=lin.weight.device)
+        # (through the upload cache: a train step on the full-table route is captured into a graph, where a host -> device copy is not allowed)
+        idx = upload(np.asarray(self._ontology._relation_index, np.int64), lin.weight.device)
         live = torch.is_grad_enabled() and lin.weight.requires_grad      # training: the relation rows receive gradient too
         w = (lin.weight if live else lin.weight.detach()).index_select(0, idx).contiguous()
         b = None if lin.bias is None else (lin.bias if live else lin.bias.detach()).index_select(0, idx).contiguous()
@@ -670,9 +671,20 @@ class ClassifierOracle(OracleBase):
             rel_output = pair_object_features
         else:
             h = self._relation_network(pair_object_features)
+            drop = self._embedding_network._network[0]               # the embedding layer's own Dropout, a site of its own for the pair rows
+            if isinstance(drop, nn.Dropout) and drop.training and drop.p > 0:
+                h = L.dropout(h, drop.p)
             w, b = self._relation_embedding()
             rel_output = L.linear_act(h, w, b, L.ACT_LOGSIGMOID)      # only the 333 relation columns are computed
         return attr_output, rel_output
+
+    def active_dropout(self):
+        """The first nn.Dropout of the three networks that drops under the current mode (training, p > 0), or None."""
+        for net in (self._attribute_network, self._relation_network, self._embedding_network):
+            for m in (() if net is None or net._network is None else net._network):
+                if isinstance(m, nn.Dropout) and m.training and m.p > 0:
+                    return m
+        return None
 
     # ---- needed-columns mode ---------------------------------------------------------------------------
     def supports_needed_columns(self):
@@ -689,7 +701,7 @@ class ClassifierOracle(OracleBase):
         acts = [m for m in rel if isinstance(m, (nn.ELU, nn.Sigmoid))]
         if len(lins) != 2 or len(acts) != 2 or not isinstance(acts[0], nn.ELU) or not isinstance(acts[1], nn.Sigmoid):
             return False
-        if any(isinstance(m, nn.Dropout) and m.training and m.p > 0 for m in rel):
+        if self.active_dropout() is not None:                        # a Dropout drops: the full-table dataflow applies it exactly
             return False
         hid1, hid2 = lins[0].out_features, lins[1].out_features
         return hid1 % 4 == 0 and hid1 <= 256 and hid2 <= 320 and (lins[0].in_features - 4) % 2 == 0 and lins[1].bias is not None

@@ -46,7 +46,8 @@ extern "C" {
  * and so were dfol_pair_ll_h1_f32, dfol_pair_pack_w2_f16, dfol_pair_w2_f16_bytes and DFOL_PAIR_F16 (an older library refuses the kind) and
  * dfol_gather_object_rows_f32, and the two size queries dfol_lstm_cell_supported and dfol_calib_walk_supported, and the index form of a store-backed
  * batch: dfol_store_rows_f32, dfol_linear_wide_rows_h2_f32 and dfol_set_feature_rows (no struct and no instruction table changes for it), and
- * its cached form: dfol_store_objects_f32 and dfol_set_feature_cache (likewise);
+ * its cached form: dfol_store_objects_f32 and dfol_set_feature_cache (likewise), and the dropout training route: dfol_dropout_advance,
+ * dfol_dropout_f32 and dfol_pair_features_bwd_f32;
  * a caller that needs them checks for the symbol, and a table that names an opcode an older library lacks is refused by it ("unknown opcode"). */
 #define DFOL_ABI_VERSION 3
 
@@ -343,6 +344,30 @@ int dfol_box_positions_f32(const float* raw, int64_t ld_raw, int32_t raw_cols, i
  */
 int dfol_pair_features_f32(const float* obj, int64_t ld_obj, int32_t D, const int32_t* obj_off, const int64_t* pair_off,
                            int32_t Q, int32_t max_n, float* pair, int64_t ld_pair, void* stream);
+
+/* The backward of dfol_pair_features_f32 without atomics: object t of image q collects columns [0, D) of its n - 1 consecutive pair rows as
+ * subject and columns [D, 2D) of its n - 1 strided rows as object (pair row of (s, o): pair_off[q] + s (n - 1) + (o < s ? o : o - 1)), each in
+ * ascending partner order, then adds the two sums - a fixed order: two runs give the same bits.
+ *   g_pair [pairs, ld_pair], ld_pair >= 2 D: the gradient of the pair matrix (its geometry columns carry no gradient to the objects)
+ *   g_obj  [O, ld_obj], ld_obj >= D: columns [0, D) of every object row are WRITTEN (zero for an image of one object)
+ * Any D >= 1; images of 0, 1 and 2 objects are fine; max_n >= every image's object count. */
+int dfol_pair_features_bwd_f32(const float* g_pair, int64_t ld_pair, int32_t D, const int32_t* obj_off, const int64_t* pair_off, int32_t Q,
+                               int32_t max_n, float* g_obj, int64_t ld_obj, void* stream);
+
+/* ---- dropout: counter-based masks (csrc/dfol_dropout.hip) ----------------------------------------
+ * Philox4x32-10; a mask is a pure function of (seed, rank, step, site, row, column) and is never stored.
+ *   state: a 32-byte device record {seed u64, step u64, key u32[2], rank u32, pad u32}, 8-byte aligned.
+ *   dfol_dropout_advance: one tiny launch: step += 1; key = the first two words of Philox(counter = (step_lo, step_hi, rank, 0),
+ *     key = (seed_lo, seed_hi)).  The step lives on the device: a replayed graph draws new masks on every replay.
+ *   dfol_dropout_f32: y[r][c] = kept(r, c) ? x[r][c] * (1 / (1 - p)) : +0.0f  (by selection: an inf or NaN under a dropped element gives 0).
+ *     The elements (r, 4g .. 4g + 3) use the four words of Philox(counter = (r_lo, r_hi, g, site), key = key[0 .. 1]); element j is kept iff
+ *     (uint64) word[j] >= floor(p 2^32).  1 / (1 - p) is formed once in fp32.
+ *     x [rows, ldx], y [rows, ldy]: any cols >= 1, any row strides >= cols (the access width follows each row's addresses); x == y is allowed.
+ *     key: two uint32 ON THE DEVICE, read at run time - bytes 16 .. 23 of a state, or a copy of them.  0 <= p < 1.
+ *     The backward of a site is the same call over the incoming gradient with the same (key, site). */
+int dfol_dropout_advance(void* state, void* stream);
+int dfol_dropout_f32(const float* x, int64_t ldx, float* y, int64_t ldy, int64_t rows, int32_t cols, float p, const void* key, uint32_t site,
+                     void* stream);
 
 /* Attention calibration: replaces BatchVariableSet.apply_modulations, batch_base_types.py:170-179, for the 4-column
  * modulations the reference's attention_output_network emits (gqa_interpreter_experiments.py:119-132):
