@@ -777,7 +777,8 @@ typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
 // dx h (dE of the current predicate) and of dpre2 (db2) over its rows; the dE sums are flushed where the thread's rows cross into the
 // next predicate - its own first row past the boundary, or, for threads whose rows of the boundary step all lie before it, the step
 // after - into partials indexed by (slab + predicate, row octet), which pair_sums_reduce_kernel adds in a fixed order.  Needs every
-// predicate to own at least 32 rows (or none): a macro step then holds at most one boundary (the launcher's caller checks 64).
+// predicate to own at least 32 rows (or none): a macro step then holds at most one boundary (the launcher's caller checks 64;
+// tests/test_pair_wgrad_sums_shapes_gpu.py holds predicates of exactly 32, 33, 40 and 63 rows to the same bounds as the 64-row ones).
 // BIO (the bf16 mode): pre2 and Z are rows of bfloat16 (8-byte aligned rows, strides in elements), four columns of dpre2 per thread, ONE
 // bf16 piece per operand and one product on v_mfma_f32_32x32x16_bf16; dpre2 is rounded to bfloat16 exactly as dfol_pair_logit_bwd_bf16
 // stores it (no scaling: bf16 has fp32's exponent range; `scale` is not read).
@@ -1182,6 +1183,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 while ((int)pred_off[p_nxt + 1] <= end_cur) ++p_nxt;   // (predicates without rows)
                 flush_de(__builtin_amdgcn_readfirstlane(p_nxt));
             }
+        }
+        // A slab WITHOUT rows (above 65 536 rows the rounding of rows_per_slab to 32 can leave whole slabs past M) writes its zero sums too:
+        // pair_sums_reduce_kernel adds the db2 partial rows of EVERY slab, and the workspace is not cleared.  (Its dE partial rows are not
+        // read: the reduce takes only the slabs that hold rows of the predicate.)
+        if (is_a) {
             float* o = db_part + ((int64_t)blockIdx.x * 4 + k_oa()) * H2 + k_col0();
 #pragma unroll
             for (int t = 0; t < CPT; ++t) o[t] = sums[512 * (CPT + t)] * invS;
@@ -1301,6 +1307,8 @@ static int pw_launch(const void* pre2, int64_t ld_p2, const float* dx, const int
     DFOL_REQUIRE(M > 0 && M < (1ll << 31) - 64 && H2 >= 4 && H1 >= 4 && H2 % 4 == 0 && H1 % 4 == 0 && H2 <= 32 * PW_TA && H1 <= 32 * PW_TB,
                  "pair_wgrad_fused: bad sizes M=%lld H2=%d H1=%d (multiples of 4, H2 <= %d, H1 <= %d)", (long long)M, H2, H1, 32 * PW_TA, 32 * PW_TB);
     DFOL_REQUIRE(pre2 && dx && row_pred && pred_off && E && (scale || bio) && Z && workspace && dW, "pair_wgrad_fused: null pointer");
+    DFOL_REQUIRE(ld_p2 >= H2 && ld_z >= H1 && ld_e >= H2, "pair_wgrad_fused: row strides ld_p2=%lld ld_z=%lld ld_e=%lld must cover H2=%d, H1=%d, H2",
+                 (long long)ld_p2, (long long)ld_z, (long long)ld_e, H2, H1);
     DFOL_REQUIRE(ld_p2 % 4 == 0 && ld_z % 4 == 0 && ld_e % 4 == 0 && ((uintptr_t)pre2 % (bio ? 8 : 16) == 0) && ((uintptr_t)Z % (bio ? 8 : 16) == 0) &&
                  ((uintptr_t)E % 16 == 0), "pair_wgrad_fused: rows of pre2, Z and E must be 16-byte (bf16 storage: 8-byte) aligned");
     DFOL_REQUIRE(8 * std::max(ld_p2, ld_z) * 4 * 4 < (1ll << 31), "pair_wgrad_fused: row stride too large (%lld)", (long long)std::max(ld_p2, ld_z));
