@@ -172,6 +172,9 @@ SIGNATURES = {
     "dfol_linear_pack_w_bf16": [_p, _i64, _i32, _i32, _p, _p],
     "dfol_linear_act_bf16_f32": [_p, _i64, _p, _p, _p, _i64, _i32, _i32, _i32, _i32, _p],
     "dfol_linear_wgrad_bias_bf16": [_p, _i64, _p, _i64, _i64, _i32, _i32, _p, _p, _p, _p],
+    "dfol_linear_wgrad_rows_supported": [_i32, _i32, _i64, _i64],      # returns 0 / 1, not a status: called directly
+    "dfol_linear_wgrad_bias_rows_f32": [_p, _i64, _p, _i64, _p, _i64, _i32, _i32, _p, _p, _p, _p],
+    "dfol_linear_wgrad_bias_rows_bf16": [_p, _i64, _p, _i64, _p, _i64, _i32, _i32, _p, _p, _p, _p],
     "dfol_act_bwd_f32": [_p, _p, _i64, _i32, _p, _p],
     "dfol_linear_act_bf16_bf16": [_p, _i64, _p, _p, _p, _i64, _i32, _i32, _i32, _i32, _p],
     "dfol_linear_wgrad_bias_bf16_bf16": [_p, _i64, _p, _i64, _i64, _i32, _i32, _p, _p, _p, _p],
@@ -786,6 +789,35 @@ def linear_wgrad(dy, x, bias=False):
         return (dw, db) if bias else dw
     call("dfol_linear_wgrad_bias_bf16" if bf16 else "dfol_linear_wgrad_bias_f32", _dp(dy), dy.stride(0),
          _dp(x), x.stride(0), M, N, K, _ptr(ws), _ptr(dw), _ptr(db, F32, True), _stream())
+    return (dw, db) if bias else dw
+
+
+def linear_wgrad_rows_supported(N, K, ld_dy, ld_table):
+    """dfol_linear_wgrad_rows_supported: linear_wgrad_rows exists for the shape (where linear_wgrad runs its bf16-pipe kernel)."""
+    return bool(load().dfol_linear_wgrad_rows_supported(int(N), int(K), int(ld_dy), int(ld_table)))
+
+
+def linear_wgrad_rows(dy, table, src_row, bias=False):
+    """linear_wgrad over indexed rows: dW [N, K] = dy^T table[src_row] for dy [M, N], table [rows, K] fp32 (a feature store's features as a
+    matrix), src_row [M] int32; bias=True: (dW, db).  Bit for bit linear_wgrad(dy, table[src_row]) without the gathered copy
+    (csrc/dfol_dense_wgrad.hip, ROWS); shapes linear_wgrad_rows_supported does not take are refused."""
+    M, N = dy.shape
+    K = table.shape[1]
+    for t in (dy, table):
+        if not t.is_cuda or t.dtype != F32 or t.stride(1) != 1:
+            raise DfolError("linear_wgrad_rows needs fp32 GPU matrices with unit column stride")
+    if src_row.numel() != M:
+        raise DfolError("linear_wgrad_rows: src_row has %d entries for %d rows of dy" % (src_row.numel(), M))
+    if M == 0:                                             # as linear_wgrad: a batch without rows has a zero gradient
+        dw = torch.zeros(N, K, dtype=F32, device=dy.device)
+        return (dw, torch.zeros(N, dtype=F32, device=dy.device)) if bias else dw
+    lib = load()
+    ws = torch.empty(lib.dfol_linear_wgrad_workspace(M, N, K), dtype=F32, device=dy.device)
+    dw = torch.empty(N, K, dtype=F32, device=dy.device)
+    db = torch.empty(N, dtype=F32, device=dy.device) if bias else None
+    bf16 = _dense_math() == "bf16" and N * K >= SPLIT_MIN_WEIGHT      # the mode choice of linear_wgrad
+    call("dfol_linear_wgrad_bias_rows_bf16" if bf16 else "dfol_linear_wgrad_bias_rows_f32", _dp(dy), dy.stride(0), _dp(table), table.stride(0),
+         _ptr(src_row, I32), M, N, K, _ptr(ws), _ptr(dw), _ptr(db, F32, True), _stream())
     return (dw, db) if bias else dw
 
 

@@ -265,13 +265,21 @@ __device__ __forceinline__ u32x4 w3_rne8(const float (&v)[8]) {
     return r;
 }
 
+typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));       // a 16-byte load from a 4-byte aligned address
+
 // AV: floats of dY a lane loads per row = row tiles of the block (4: 128 output rows; 2: a narrow last row block, up to 64 output rows)
 // NP: pieces per operand - 3: fp32 results (six piece products); 1: the bf16 mode (operands rounded to bf16, one product, fp32 accumulation)
-template <int AV, int NP>
+// ROWS: row r of the range is row src_row[r] of the table X (dfol_linear_wgrad_bias_rows_*: a feature store's table, src_row from
+// dfol_store_rows_f32).  Only the address of an X row differs: a table can be larger than a buffer descriptor's 32-bit offsets reach, so the
+// lane forms the 64-bit address itself and loads through it; a row past the range is not loaded at all (neither its index nor the
+// table) and counts as the zero row the descriptor's bounds check gives the matrix form.  A lane reads the index of each of its rows once,
+// a step before the row itself.  The instantiations without ROWS never touch src_row and compile to the code they had before it existed.
+template <int AV, int NP, bool ROWS = false>
 __device__ __forceinline__ void wgrad_tn3_accumulate(const float* __restrict__ dY, int64_t ld_dy, const float* __restrict__ X, int64_t ld_x,
-                                                     int rows, int steps, int N, int K, int n0, int k0, int lane, bool want_bias,
-                                                     f32x16 (&acc)[AV][4], float (&bs)[AV]) {
+                                                     const int32_t* __restrict__ src_row, int rows, int steps, int N, int K, int n0, int k0,
+                                                     int lane, bool want_bias, f32x16 (&acc)[AV][4], float (&bs)[AV]) {
     // dY, X: first row of this wavefront's range (wave-uniform); rows: rows in the range (<= 0: nothing to add)
+    // ROWS: X is the table's first row and src_row the index of the range's first row
     // bs[t] (want_bias, wave-uniform): this lane's part of the bias gradient, the sum of dY[m][n0 + AV col + t] over its rows
     const int col = lane & 31, half = lane >> 5;
     // columns beyond the matrix read a clamped column: they only feed output rows / columns that are never stored
@@ -293,6 +301,14 @@ __device__ __forceinline__ void wgrad_tn3_accumulate(const float* __restrict__ d
 
     float ra[8][AV];                                                               // the step's dY and X rows: dead once the pieces are built,
     u32x4 rb[8];                                                                   // then refilled with the next step's (in flight under the MFMAs)
+    int ix[ROWS ? 8 : 1];                                                          // ROWS: the table rows of the step to load next (-1: past the range)
+    auto index = [&](int s) __attribute__((always_inline)) {
+#pragma unroll
+        for (int r = 0; r < (ROWS ? 8 : 0); ++r) {
+            const int row = 16 * s + 8 * half + r;
+            ix[r] = row < rows ? src_row[row] : -1;
+        }
+    };
     auto load = [&](int s) __attribute__((always_inline)) {
         const int left = rows - 16 * s;                                            // rows of the range from this step on
         const int64_t bytes_a = left > 0 ? ((int64_t)(left - 1) * ld_dy + N) * 4 : 0, bytes_b = left > 0 ? ((int64_t)(left - 1) * ld_x + K) * 4 : 0;
@@ -306,14 +322,21 @@ __device__ __forceinline__ void wgrad_tn3_accumulate(const float* __restrict__ d
                 const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(da, va[r], 0, 0);
                 ra[r][0] = __uint_as_float(v.x), ra[r][1] = __uint_as_float(v.y);
             }
-            rb[r] = __builtin_amdgcn_raw_buffer_load_b128(db, vb[r], 0, 0);
+            if constexpr (ROWS) {
+                rb[r] = u32x4{0u, 0u, 0u, 0u};
+                if (ix[r] >= 0) rb[r] = *reinterpret_cast<const u32x4_a4*>(X + (int64_t)ix[r] * ld_x + cb);
+            } else {
+                rb[r] = __builtin_amdgcn_raw_buffer_load_b128(db, vb[r], 0, 0);
+            }
         }
     };
     constexpr int PA6[6] = {2, 0, 1, 1, 0, 0}, PB6[6] = {0, 2, 1, 0, 1, 0};       // (A piece, B piece): l*h, h*l, m*m, m*h, h*m, h*h
     // One step: all pieces first (a tile at a time: the split's temporaries are 32 registers per tile), then the next step's loads, then
     // 24 AV MFMAs back to back.  (Building the B pieces of column tile u + 1 between the MFMAs of tile u was tried first: with 256
     // accumulators the allocator then parks VGPRs in the accumulator file and cycles every tile through one AGPR tuple.)
+    if constexpr (ROWS) index(0);
     load(0);
+    if constexpr (ROWS) index(1);
     __builtin_amdgcn_sched_barrier(0);
     for (int s = 0; s < steps; ++s) {
         u32x4 ap[AV][NP], bp[4][NP];
@@ -341,6 +364,7 @@ __device__ __forceinline__ void wgrad_tn3_accumulate(const float* __restrict__ d
             __builtin_amdgcn_sched_barrier(0);
         }
         load(s + 1);
+        if constexpr (ROWS) index(s + 2);                                          // (waited for a step later, behind the pieces)
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int u = 0; u < 4; ++u)
@@ -357,11 +381,11 @@ __device__ __forceinline__ void wgrad_tn3_accumulate(const float* __restrict__ d
 // The same with dY and X STORED as bfloat16 (the bf16 mode's per-pair activations: dpre2 [pairs, HID2] and Z [pairs, HID1]): a lane loads
 // AV resp. 4 consecutive bf16 of its eight rows (8- / 4-byte buffer loads), and an operand register pair is two rows' halves of one word
 // (v_perm_b32) - no conversions, no rounding, half the bytes.  The bias sums widen the same registers to fp32.
-template <int AV, int NP>
+template <int AV, int NP, bool ROWS = false>
 __device__ __forceinline__ void wgrad_tn3_accumulate(const uint16_t* __restrict__ dY, int64_t ld_dy, const uint16_t* __restrict__ X, int64_t ld_x,
-                                                     int rows, int steps, int N, int K, int n0, int k0, int lane, bool want_bias,
-                                                     f32x16 (&acc)[AV][4], float (&bs)[AV]) {
-    static_assert(NP == 1, "bf16 storage belongs to the bf16 mode");
+                                                     const int32_t* __restrict__, int rows, int steps, int N, int K, int n0, int k0, int lane,
+                                                     bool want_bias, f32x16 (&acc)[AV][4], float (&bs)[AV]) {
+    static_assert(NP == 1 && !ROWS, "bf16 storage belongs to the bf16 mode, and has no indexed form");
     constexpr int WA = AV / 2;                                                     // 32-bit words of dY per row and lane
     const int col = lane & 31, half = lane >> 5;
     const int ca = min(n0 + AV * col, N - AV), cb = min(k0 + 4 * col, K - 4);
@@ -463,16 +487,16 @@ __device__ __forceinline__ void wgrad_tn3_accumulate(const uint16_t* __restrict_
     }
 }
 
-template <int AV, int NP, typename TIN>
-__device__ __forceinline__ void wgrad_tn3_block(const TIN* __restrict__ dY, int64_t ld_dy, const TIN* __restrict__ X, int64_t ld_x, int rows,
-                                                int steps, int N, int K, int n0, int k0, int lane, int role, float* __restrict__ lds,
-                                                float* __restrict__ out, float* __restrict__ db_out) {
+template <int AV, int NP, typename TIN, bool ROWS>
+__device__ __forceinline__ void wgrad_tn3_block(const TIN* __restrict__ dY, int64_t ld_dy, const TIN* __restrict__ X, int64_t ld_x,
+                                                const int32_t* __restrict__ src_row, int rows, int steps, int N, int K, int n0, int k0, int lane,
+                                                int role, float* __restrict__ lds, float* __restrict__ out, float* __restrict__ db_out) {
     // role 0: accumulate and store; 1: accumulate, add the partner's accumulators from `lds`, store; 2: accumulate into `lds` (the partner)
     // db_out (k0 == 0 wavefronts, or null): this slab's part of the bias gradient
     f32x16 acc[AV][4];
     float bs[AV];
     const bool want_bias = db_out != nullptr && k0 == 0;
-    wgrad_tn3_accumulate<AV, NP>(dY, ld_dy, X, ld_x, rows, steps, N, K, n0, k0, lane, want_bias, acc, bs);
+    wgrad_tn3_accumulate<AV, NP, ROWS>(dY, ld_dy, X, ld_x, src_row, rows, steps, N, K, n0, k0, lane, want_bias, acc, bs);
     if (role == 2) {
 #pragma unroll
         for (int t = 0; t < AV; ++t)
@@ -519,10 +543,11 @@ __device__ __forceinline__ void wgrad_tn3_block(const TIN* __restrict__ dY, int6
 constexpr int W3_LDS_SLOT = 64 * (256 + 4);        // floats a row-half partner hands over: 256 accumulators and 4 bias sums per lane
 
 // grid (row slabs, groups of four blocks); dynamic LDS: two slots when the last group splits its rows (see the launcher), else none
-template <int NP, typename TIN = float>
+// ROWS: X is a table and src_row [M] names the table row of every row of the product (see wgrad_tn3_accumulate); else src_row is not read
+template <int NP, typename TIN = float, bool ROWS = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void wgrad_tn3_kernel(
     const TIN* __restrict__ dY, int64_t ld_dy, const TIN* __restrict__ X, int64_t ld_x, int M, int N, int K, int rows_per_slab, int nb_k,
-    int nb, float* __restrict__ part, float* __restrict__ db_part) {
+    int nb, float* __restrict__ part, float* __restrict__ db_part, const int32_t* __restrict__ src_row) {
     extern __shared__ float w3_lds[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int first = blockIdx.y * 4, in_group = min(4, nb - first);               // blocks of this group
@@ -551,9 +576,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     float* lds = w3_lds + (split ? wave - half_id * in_group : 0) * W3_LDS_SLOT;   // wavefronts w and w + in_group: the same block, one slot
     float* db_out = db_part ? db_part + (int64_t)blockIdx.x * ((N + 3) & ~3) : nullptr;
     const TIN* a = dY + (int64_t)m_first * ld_dy;
-    const TIN* b = X + (int64_t)m_first * ld_x;
-    if (N - n0 > 64) wgrad_tn3_block<4, NP, TIN>(a, ld_dy, b, ld_x, rows, steps, N, K, n0, k0, lane, role, lds, out, db_out);
-    else wgrad_tn3_block<2, NP, TIN>(a, ld_dy, b, ld_x, rows, steps, N, K, n0, k0, lane, role, lds, out, db_out);
+    const TIN* b = ROWS ? X : X + (int64_t)m_first * ld_x;
+    const int32_t* idx = ROWS ? src_row + m_first : nullptr;
+    if (N - n0 > 64) wgrad_tn3_block<4, NP, TIN, ROWS>(a, ld_dy, b, ld_x, idx, rows, steps, N, K, n0, k0, lane, role, lds, out, db_out);
+    else wgrad_tn3_block<2, NP, TIN, ROWS>(a, ld_dy, b, ld_x, idx, rows, steps, N, K, n0, k0, lane, role, lds, out, db_out);
 }
 
 // dW[e] = sum over the slabs in a fixed order: a workgroup takes 16 groups of four elements x 16 slab phases (phase p adds slabs p,
@@ -630,8 +656,15 @@ extern "C" int64_t dfol_linear_wgrad_workspace(int64_t M, int32_t N, int32_t K) 
     return slabs * (((((int64_t)N * K) + 3) & ~(int64_t)3) + ((N + 3) & ~3));
 }
 
-static int wgrad_launch(const float* dY, int64_t ld_dy, const float* X, int64_t ld_x, int64_t M, int32_t N, int32_t K, float* workspace,
-                        float* dW, float* db, void* stream, bool bf16_mode) {
+static bool wgrad_f32_pipe_asked() {
+    const char* math = getenv("DFOL_WGRAD_MATH");                       // "f32": the fp32 matrix pipe (exact products); default: bf16x3
+    return math && !strcmp(math, "f32");
+}
+
+// one launch path for both forms: src_row == nullptr is the plain product over X's own rows; with src_row, X is a table (ld_x its row
+// stride) and the caller has made sure of the bf16-pipe kernel's conditions (dfol_linear_wgrad_bias_rows_*: the other kernels have no indexed form)
+static int wgrad_launch(const float* dY, int64_t ld_dy, const float* X, int64_t ld_x, const int32_t* src_row, int64_t M, int32_t N, int32_t K,
+                        float* workspace, float* dW, float* db, void* stream, bool bf16_mode) {
     DFOL_REQUIRE(M > 0 && M < (1ll << 31) && N > 0 && K > 0, "linear_wgrad: bad sizes M=%lld N=%d K=%d", (long long)M, N, K);
     DFOL_REQUIRE(dY && X && workspace && dW, "linear_wgrad: null pointer");
     float* db_part = db ? workspace + (int64_t)dfol_linear_wgrad_slabs(M, N, K) * ((((int64_t)N * K) + 3) & ~(int64_t)3) : nullptr;
@@ -642,8 +675,7 @@ static int wgrad_launch(const float* dY, int64_t ld_dy, const float* X, int64_t 
     rows_per_slab = (rows_per_slab + 7) & ~7;                           // two rows per MFMA step, four steps per ring turn
     hipStream_t st = (hipStream_t)stream;
     const bool vec4 = N % 4 == 0 && K % 4 == 0 && ld_dy % 4 == 0 && ((uintptr_t)dY % 16 == 0);      // (X rows may be 8-byte aligned only)
-    const char* math = getenv("DFOL_WGRAD_MATH");                       // "f32": the fp32 matrix pipe (exact products); default: bf16x3
-    const bool f32_pipe = !bf16_mode && math && !strcmp(math, "f32");
+    const bool f32_pipe = !bf16_mode && wgrad_f32_pipe_asked();
     bool bias_done = false;
     if (vec4 && !f32_pipe && N >= 4 && K >= 4) {                        // fp32 results from the bf16 matrix pipe (X rows: any 4-byte alignment)
         slabs = wgrad_tn3_slabs(M, nb);
@@ -656,14 +688,28 @@ static int wgrad_launch(const float* dY, int64_t ld_dy, const float* X, int64_t 
         static const hipError_t lds_ok1 = hipFuncSetAttribute((const void*)wgrad_tn3_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                               2 * W3_LDS_SLOT * sizeof(float));
         DFOL_REQUIRE(lds_ok == hipSuccess && lds_ok1 == hipSuccess, "linear_wgrad: cannot reserve 130 KB of LDS (%s)", hipGetErrorString(lds_ok));
-        if (bf16_mode)
+        if (src_row) {
+            static const hipError_t lds_okr = hipFuncSetAttribute((const void*)wgrad_tn3_kernel<3, float, true>,
+                                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 2 * W3_LDS_SLOT * sizeof(float));
+            static const hipError_t lds_okr1 = hipFuncSetAttribute((const void*)wgrad_tn3_kernel<1, float, true>,
+                                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 2 * W3_LDS_SLOT * sizeof(float));
+            DFOL_REQUIRE(lds_okr == hipSuccess && lds_okr1 == hipSuccess, "linear_wgrad_rows: cannot reserve 130 KB of LDS (%s)", hipGetErrorString(lds_okr));
+            if (bf16_mode)
+                hipLaunchKernelGGL((wgrad_tn3_kernel<1, float, true>), dim3(slabs, groups), dim3(256), lds, st, dY, ld_dy, X, ld_x, (int)M, N, K,
+                                   rows_per_slab, nb_k, nb, workspace, db_part, src_row);
+            else
+                hipLaunchKernelGGL((wgrad_tn3_kernel<3, float, true>), dim3(slabs, groups), dim3(256), lds, st, dY, ld_dy, X, ld_x, (int)M, N, K,
+                                   rows_per_slab, nb_k, nb, workspace, db_part, src_row);
+        } else if (bf16_mode)
             hipLaunchKernelGGL(wgrad_tn3_kernel<1>, dim3(slabs, groups), dim3(256), lds, st, dY, ld_dy, X, ld_x, (int)M, N, K, rows_per_slab, nb_k,
-                               nb, workspace, db_part);
+                               nb, workspace, db_part, src_row);
         else
             hipLaunchKernelGGL(wgrad_tn3_kernel<3>, dim3(slabs, groups), dim3(256), lds, st, dY, ld_dy, X, ld_x, (int)M, N, K, rows_per_slab, nb_k,
-                               nb, workspace, db_part);
+                               nb, workspace, db_part, src_row);
         bias_done = true;
-    } else if (vec4)
+    } else if (src_row)
+        DFOL_REQUIRE(false, "linear_wgrad_rows: no indexed form of the fp32-pipe kernels");
+    else if (vec4)
         hipLaunchKernelGGL(wgrad_tn4_kernel, dim3(slabs / 4, nb_n * nb_k), dim3(256), 0, st, dY, ld_dy, X, ld_x, (int)M, N, K, rows_per_slab, nb_n,
                            nb_k, workspace);
     else                                                                // odd widths: one float per lane and load, the four wavefronts of
@@ -686,19 +732,50 @@ static int wgrad_launch(const float* dY, int64_t ld_dy, const float* X, int64_t 
 
 extern "C" int dfol_linear_wgrad_bias_f32(const float* dY, int64_t ld_dy, const float* X, int64_t ld_x, int64_t M, int32_t N, int32_t K,
                                           float* workspace, float* dW, float* db, void* stream) {
-    return wgrad_launch(dY, ld_dy, X, ld_x, M, N, K, workspace, dW, db, stream, false);
+    return wgrad_launch(dY, ld_dy, X, ld_x, nullptr, M, N, K, workspace, dW, db, stream, false);
 }
 
 // bf16 mode (BASELINE configs[3]): both operands rounded to bf16, one product per pair, fp32 accumulation; the bias gradient stays an
 // fp32 sum.  Shapes the bf16x3 kernel does not take (widths that are not multiples of 4) run in fp32 as above.
 extern "C" int dfol_linear_wgrad_bias_bf16(const float* dY, int64_t ld_dy, const float* X, int64_t ld_x, int64_t M, int32_t N, int32_t K,
                                            float* workspace, float* dW, float* db, void* stream) {
-    return wgrad_launch(dY, ld_dy, X, ld_x, M, N, K, workspace, dW, db, stream, true);
+    return wgrad_launch(dY, ld_dy, X, ld_x, nullptr, M, N, K, workspace, dW, db, stream, true);
 }
 
 extern "C" int dfol_linear_wgrad_f32(const float* dY, int64_t ld_dy, const float* X, int64_t ld_x, int64_t M, int32_t N, int32_t K,
                                      float* workspace, float* dW, void* stream) {
-    return wgrad_launch(dY, ld_dy, X, ld_x, M, N, K, workspace, dW, nullptr, stream, false);
+    return wgrad_launch(dY, ld_dy, X, ld_x, nullptr, M, N, K, workspace, dW, nullptr, stream, false);
+}
+
+// The weight gradient over INDEXED rows (a feature store's table read in place): row r of X is row src_row[r] of X_table.  It exists where
+// the matrix form runs the bf16-pipe kernel, and gives that kernel's bits: slabs, workspace layout, reduction and bias partials are the
+// same launch path's, only the address of an X row differs (wgrad_tn3_accumulate, ROWS).
+extern "C" int dfol_linear_wgrad_rows_supported(int32_t N, int32_t K, int64_t ld_dy, int64_t ld_table) {
+    return N >= 4 && K >= 4 && N % 4 == 0 && K % 4 == 0 && ld_dy >= N && ld_dy % 4 == 0 && ld_table >= K &&
+           16 * std::max(ld_dy, ld_table) * 4 < (1ll << 31) && !wgrad_f32_pipe_asked();
+}
+
+static int wgrad_rows_launch(const float* dY, int64_t ld_dy, const float* X_table, int64_t ld_table, const int32_t* src_row, int64_t M, int32_t N,
+                             int32_t K, float* workspace, float* dW, float* db, void* stream, bool bf16_mode) {
+    DFOL_REQUIRE(M > 0 && M < (1ll << 31) && N > 0 && K > 0, "linear_wgrad_rows: bad sizes M=%lld N=%d K=%d", (long long)M, N, K);
+    DFOL_REQUIRE(dY && X_table && src_row && workspace && dW, "linear_wgrad_rows: null pointer");
+    DFOL_REQUIRE(N % 4 == 0 && K % 4 == 0, "linear_wgrad_rows: N=%d and K=%d must be multiples of 4", N, K);
+    DFOL_REQUIRE(ld_dy >= N && ld_dy % 4 == 0 && (uintptr_t)dY % 16 == 0, "linear_wgrad_rows: dY rows must be 16-byte aligned (ld_dy=%lld)", (long long)ld_dy);
+    DFOL_REQUIRE(ld_table >= K, "linear_wgrad_rows: table rows (ld_table=%lld) shorter than K=%d", (long long)ld_table, K);
+    DFOL_REQUIRE((uintptr_t)X_table % 4 == 0 && (uintptr_t)src_row % 4 == 0, "linear_wgrad_rows: table and index must be 4-byte aligned");
+    DFOL_REQUIRE(16 * std::max(ld_dy, ld_table) * 4 < (1ll << 31), "linear_wgrad_rows: row stride too large (%lld)", (long long)std::max(ld_dy, ld_table));
+    DFOL_REQUIRE(!wgrad_f32_pipe_asked(), "linear_wgrad_rows: DFOL_WGRAD_MATH=f32 asks for the fp32 matrix pipe, which has no indexed form");
+    return wgrad_launch(dY, ld_dy, X_table, ld_table, src_row, M, N, K, workspace, dW, db, stream, bf16_mode);
+}
+
+extern "C" int dfol_linear_wgrad_bias_rows_f32(const float* dY, int64_t ld_dy, const float* X_table, int64_t ld_table, const int32_t* src_row,
+                                               int64_t M, int32_t N, int32_t K, float* workspace, float* dW, float* db, void* stream) {
+    return wgrad_rows_launch(dY, ld_dy, X_table, ld_table, src_row, M, N, K, workspace, dW, db, stream, false);
+}
+
+extern "C" int dfol_linear_wgrad_bias_rows_bf16(const float* dY, int64_t ld_dy, const float* X_table, int64_t ld_table, const int32_t* src_row,
+                                                int64_t M, int32_t N, int32_t K, float* workspace, float* dW, float* db, void* stream) {
+    return wgrad_rows_launch(dY, ld_dy, X_table, ld_table, src_row, M, N, K, workspace, dW, db, stream, true);
 }
 
 // bf16 mode with bf16 STORAGE of both operands (the per-pair activations dpre2 [M, N] and Z [M, K] as bfloat16, rows 4-byte / 8-byte
@@ -721,7 +798,7 @@ extern "C" int dfol_linear_wgrad_bias_bf16_bf16(const void* dY_bf16, int64_t ld_
     DFOL_REQUIRE(lds_ok == hipSuccess, "linear_wgrad_bf16_bf16: cannot reserve 130 KB of LDS (%s)", hipGetErrorString(lds_ok));
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL((wgrad_tn3_kernel<1, uint16_t>), dim3(slabs, groups), dim3(256), lds, st, (const uint16_t*)dY_bf16, ld_dy, (const uint16_t*)X_bf16,
-                       ld_x, (int)M, N, K, rows_per_slab, nb_k, nb, workspace, db_part);
+                       ld_x, (int)M, N, K, rows_per_slab, nb_k, nb, workspace, db_part, (const int32_t*)nullptr);
     DFOL_LAUNCH_CHECK("linear_wgrad_bf16_bf16");
     const int64_t elems = (int64_t)N * K;
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(dfol_cdiv(dfol_cdiv(elems, 4), 16)), dim3(256), 0, st, workspace, slabs, elems, dW);

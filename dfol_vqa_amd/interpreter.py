@@ -88,6 +88,20 @@ class BatchGQABoxFeaturizer(nn.Module):
             return None
         return store_layers_of(net, rows.store.F, rows.O)[0]
 
+    def _store_train_layers(self, rows):
+        """The same layers when the featurizer TRAINS and its first layer can run as visual_oracle.StoreRowsLinear: forward as on the inference
+        route (so store_layers_of decides - an active Dropout, another arithmetic, a narrow first layer or a small batch say no), and a weight
+        gradient that reads the table through src_row too (dfol_linear_wgrad_rows_supported; dz is a contiguous [O, N]).  None: the matrix."""
+        from . import _lib
+        net = self._featurizer_network
+        if rows.O == 0 or rows.table is None or net is None or not featurizer_trains(net) or active_dropout(net) is not None:
+            return None
+        layers = store_layers_of(net, rows.store.F, rows.O)[0]
+        if layers is None:
+            return None
+        N, K = layers[0][0].weight.shape
+        return layers if _lib.linear_wgrad_rows_supported(N, K, N, rows.table.stride(0)) else None
+
     def _cached_objects(self, rows):
         """The object matrix of a `featurized` store's batch from the store's cached featurizer rows (feature_store.DeviceFeatureStore.featurize:
         built on first use, rebuilt once when a weight's version has changed), or None: a store without a cache, a featurizer that trains under
@@ -124,7 +138,24 @@ class BatchGQABoxFeaturizer(nn.Module):
                 L.box_positions(rows.box6, obj, D - 4)
                 _lib.note("feature_store_direct")
                 return self._with_pairs(obj, D, rows.O, world_geometry)
-            objects_list = objects_list.materialize()             # training, another arithmetic, a narrow first layer, a small batch: the matrix
+            layers = self._store_train_layers(objects_list)
+            if layers is not None:
+                # a featurizer that trains: the first layer's forward AND weight gradient read the store's rows through src_row (the features
+                # are data: no gradient goes to the table), later layers are ordinary trained dense layers; the bits of the matrix route
+                from .visual_oracle import StoreRowsLinear
+                rows = objects_list
+                lin, act = layers[0]
+                f = StoreRowsLinear.apply(lin.weight, lin.bias, rows.table, rows.src_row, act)
+                for lin, act in layers[1:]:
+                    f = L.linear_act(f, lin.weight, lin.bias, act)
+                D = f.size(1) + 4
+                obj = torch.empty(rows.O, D, dtype=torch.float32, device=device)
+                obj[:, :D - 4] = f
+                L.box_positions(rows.box6, obj, D - 4)
+                _lib.note("feature_store_direct")                 # (a batch whose featurizer read the store in place ...
+                _lib.note("feature_store_direct_train")           # ... and, of those, one whose weight gradient will too)
+                return self._with_pairs(obj, D, rows.O, world_geometry)
+            objects_list = objects_list.materialize()             # a Dropout that drops, another arithmetic, a narrow first layer, a small batch: the matrix
             _lib.note("feature_store_direct_materialized")
         object_num = objects_list.size()[0]
         raw_cols = objects_list.size()[1]

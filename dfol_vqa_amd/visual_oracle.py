@@ -81,6 +81,44 @@ class RegularMLP(nn.Module):
         return [m for m in self._network if isinstance(m, nn.Linear)][-1].out_features
 
 
+class StoreRowsLinear(torch.autograd.Function):
+    """y = act(table[src_row] W^T + b), the featurizer's first layer over a direct feature store's rows (feature_store.StoreRows), when it
+    TRAINS.  Forward: the inference route's product (linear_wide_rows).  Backward: the activation's backward as the trained dense layer does it
+    (torch_ops._linear_backward), then dW, db = linear_wgrad_rows: the weight-gradient kernel forms an X row's address through src_row and is
+    otherwise the matrix kernel, so every result has the bits of the dense layer over the materialised matrix.  The features are data: no
+    gradient for the table.  Saved: y, src_row and the table's handle - never an [O, F] matrix."""
+
+    @staticmethod
+    def forward(ctx, weight, bias, table, src_row, act):
+        w = weight.detach()
+        y = _lib.linear_wide_rows(table, src_row, w, None if bias is None else bias.detach(), act)
+        ctx.save_for_backward(y, src_row, table)
+        ctx.act, ctx.has_bias, ctx.math = act, bias is not None, _lib._dense_math()
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        y, src_row, table = ctx.saved_tensors
+        cur = torch.cuda.current_stream(y.device)
+        for t in (y, src_row):                               # (a backward on another stream than the forward's reads them there)
+            t.record_stream(cur)
+        if ctx.act != _lib.ACT_NONE and g.dtype == torch.float32 and g.shape == y.shape and os.environ.get("DFOL_ACT_BWD", "hip") != "torch":
+            dz = torch.ops.dfol.act_bwd(g, y, ctx.act)
+        elif ctx.act == _lib.ACT_SIGMOID:
+            dz = g * y * (1 - y)
+        elif ctx.act == _lib.ACT_ELU:
+            dz = g * torch.where(y > 0, torch.ones_like(y), y + 1)
+        elif ctx.act == _lib.ACT_LOGSIGMOID:
+            dz = g * (1 - torch.exp(y))
+        else:
+            dz = g
+        gw = gb = None
+        if ctx.needs_input_grad[0] or (ctx.has_bias and ctx.needs_input_grad[1]):
+            with _lib.dense_math(ctx.math):
+                gw, gb = _lib.linear_wgrad_rows(dz.contiguous(), table, src_row, bias=True)
+        return (gw if ctx.needs_input_grad[0] else None), (gb if ctx.has_bias and ctx.needs_input_grad[1] else None), None, None, None
+
+
 class EmbeddingLayer(nn.Module):
     """Dropout + Linear(hidden -> concepts) + LogSigmoid  (gqa_interpreter_experiments.py:60-77)."""
 

@@ -47,7 +47,8 @@ extern "C" {
  * dfol_gather_object_rows_f32, and the two size queries dfol_lstm_cell_supported and dfol_calib_walk_supported, and the index form of a store-backed
  * batch: dfol_store_rows_f32, dfol_linear_wide_rows_h2_f32 and dfol_set_feature_rows (no struct and no instruction table changes for it), and
  * its cached form: dfol_store_objects_f32 and dfol_set_feature_cache (likewise), and the dropout training route: dfol_dropout_advance,
- * dfol_dropout_f32 and dfol_pair_features_bwd_f32;
+ * dfol_dropout_f32 and dfol_pair_features_bwd_f32, and the train step's weight gradient over the store's rows: dfol_linear_wgrad_rows_supported,
+ * dfol_linear_wgrad_bias_rows_f32 and dfol_linear_wgrad_bias_rows_bf16;
  * a caller that needs them checks for the symbol, and a table that names an opcode an older library lacks is refused by it ("unknown opcode"). */
 #define DFOL_ABI_VERSION 3
 
@@ -698,6 +699,19 @@ int dfol_linear_wgrad_bias_f32(const float* dY, int64_t ld_dy, const float* X, i
  * an fp32 sum.  Same workspace. */
 int dfol_linear_wgrad_bias_bf16(const float* dY, int64_t ld_dy, const float* X, int64_t ld_x, int64_t M, int32_t N, int32_t K,
                                 float* workspace, float* dW, float* db, void* stream);
+/* The weight gradient over INDEXED rows: row r of X is row src_row[r] of X_table (a feature store's [S * max_obj, K] table, row stride
+ * ld_table >= K; src_row [M] int32 as dfol_store_rows_f32 writes it, every entry a row of the table - not checked, a device array).  The
+ * bf16-pipe kernel of dfol_linear_wgrad_bias_f32 / _bf16 with the address of an X row formed through the index (read once per row by the
+ * wavefront that loads the row; rows past M read neither the index nor the table): slabs, workspace (dfol_linear_wgrad_workspace),
+ * reduction order and bias partials are the matrix form's, so dW and db are bit for bit those of the matrix form over the gathered
+ * matrix table[src_row], whatever that matrix's row stride.  It exists only where the matrix form runs that kernel - N % 4 == 0,
+ * K % 4 == 0, ld_dy % 4 == 0, 16 * max(ld_dy, ld_table) * 4 < 2^31, not under DFOL_WGRAD_MATH=f32 (either mode): dfol_linear_wgrad_rows_supported
+ * is the predicate (1 / 0) - and dY 16-byte aligned, M < 2^31; everything else is refused.  Table rows need 4-byte alignment only. */
+int dfol_linear_wgrad_rows_supported(int32_t N, int32_t K, int64_t ld_dy, int64_t ld_table);
+int dfol_linear_wgrad_bias_rows_f32(const float* dY, int64_t ld_dy, const float* X_table, int64_t ld_table, const int32_t* src_row, int64_t M,
+                                    int32_t N, int32_t K, float* workspace, float* dW, float* db, void* stream);
+int dfol_linear_wgrad_bias_rows_bf16(const float* dY, int64_t ld_dy, const float* X_table, int64_t ld_table, const int32_t* src_row, int64_t M,
+                                     int32_t N, int32_t K, float* workspace, float* dW, float* db, void* stream);
 /* ... with both operands STORED as bfloat16 (dpre2 [M, N] and Z [M, K] of the bf16 mode; ld in elements, multiples of 4; N, K multiples
  * of 4): no rounding left to do, one product, fp32 accumulation, fp32 dW and db.  Same workspace. */
 int dfol_linear_wgrad_bias_bf16_bf16(const void* dY_bf16, int64_t ld_dy, const void* X_bf16, int64_t ld_x, int64_t M, int32_t N, int32_t K,

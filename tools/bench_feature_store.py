@@ -19,10 +19,19 @@ alone is timed by HIP events beside a device-to-device copy_ of the same byte co
 dfol_linear_wide_h2_f32 against dfol_store_rows_f32 + dfol_linear_wide_rows_h2_f32, alternating; the cached-row kernel likewise beside a copy_
 of its bytes, with the one-off featurize() time and the cache's size.  Prints one JSON line.
 
-usage: python tools/bench_feature_store.py [--images 2048] [--objects 100] [--features 2048] [--batch 256] [--batches 24] [--runs 4] [--workers 5]
+`--leg train` is the train step instead (a featurizer that trains, nothing frozen): replayed GraphedTrainStep steps over one batch of `--batch`
+questions x `--objects` objects at the full model widths, with the store plain (the matrix route: gather, then forward product and weight
+gradient over the [O, F + 6] matrix) against `direct=True` (interpreter.featurize_scene's train route: both read the store's rows through
+src_row), alternating, `--runs` runs each; the peak device memory of each route's batch upload, warm-up and capture above what was allocated before them (model copy and optimizer state included, alike); and
+the weight-gradient kernel alone both ways (dfol_linear_wgrad_bias_f32 over the gathered matrix, dfol_linear_wgrad_bias_rows_f32 over the
+table).  One JSON line.
+
+usage: python tools/bench_feature_store.py [--leg stream|train] [--images 2048] [--objects 100] [--features 2048] [--batch 256] [--batches 24] [--runs 4]
+                                           [--workers 5] [--steps 20]
 """
 import argparse
 import collections
+import copy
 import json
 import os
 import shutil
@@ -106,8 +115,113 @@ def load_wide(_lib, O, N, K):
     return 256 < N <= 512 and K >= 128 and K % 4 == 0 and _lib.linear_wide_supported(O, N, K)
 
 
+def span(xs):
+    return {"min": min(xs), "median": float(np.median(xs)), "max": max(xs)}
+
+
+def apart(a, b):
+    """a against b in ms, by the rule that a difference counts only when the ranges of the runs are apart."""
+    return "faster, ranges apart" if a["max"] < b["min"] else "slower, ranges apart" if a["min"] > b["max"] else "ranges overlap: no difference shown"
+
+
+def train_leg(args):
+    """Replayed train steps over a plain store against a direct store (see the module's docstring) -> the result dictionary."""
+    from dfol_vqa_amd import _lib, training
+    import bench
+    device = torch.device("cuda", 0)
+    tmp = tempfile.mkdtemp(prefix="dfol_store_train_bench_")
+    try:
+        paths, names = syn.write_synthetic_ontology(os.path.join(tmp, "ontology"))
+        cfg = syn.reference_config(paths, box_features_dim=args.features, freeze_featurizer=False, freeze_attribute_network=False,
+                                   freeze_relation_network=False, freeze_embedding_network=False, dropout=0.0)
+        ontology = experiment.build_ontology(cfg)
+        torch.manual_seed(0)
+        model = experiment.build_model(cfg, ontology)
+        bench.init_weights(model)
+        model = model.to(device).train()
+        chunks, info_path, _ = write_corpus(tmp, args.images, args.objects, args.features, args.per_chunk)
+        stores = {"matrix": data.DeviceFeatureStore(tmp, "objs", chunks, info_path, device),
+                  "direct": data.DeviceFeatureStore(tmp, "objs", chunks, info_path, device, direct=True)}
+        with open(paths["attribute_file"]) as f:
+            cats = json.load(f)
+        rng = np.random.RandomState(9)
+        qs = syn.full_size_questions("verify_rel", args.batch, args.objects, args.objects, names, cats, 7100, with_scene=False)
+        for q in qs:
+            q["image_id"] = "img%05d" % rng.randint(args.images)
+        steps, peak, counts = {}, {}, {}
+        for route, store in stores.items():
+            pbs = data.BatchGQABoxFeaturesCollator(tmp, "objs", chunks, info_path, ontology, 1, device_store=store.index).collate([dict(q) for q in qs])
+            for pb in pbs:
+                pb.create_sparse_tensors()
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            base = torch.cuda.memory_allocated()             # (before to_cuda: a plain store's batch IS the gathered [O, F + 6] matrix)
+            torch.cuda.reset_peak_memory_stats()
+            dev = [pb.to_cuda(device) for pb in pbs]
+            net = copy.deepcopy(model)                       # (a graph bakes its parameters' addresses in: each route trains a copy of its own)
+            opt = torch.optim.Adam([p for p in net.parameters() if p.requires_grad], lr=1e-4, capturable=True)
+            before = dict(_lib.PATH_COUNTS)
+            steps[route] = training.GraphedTrainStep(net, opt, dev, 0.65)
+            torch.cuda.synchronize()
+            peak[route] = torch.cuda.max_memory_allocated() - base
+            counts[route] = {k: _lib.PATH_COUNTS.get(k, 0) - before.get(k, 0)
+                             for k in ("feature_store_direct_train", "feature_store_direct_materialized", "python_program")}
+
+        def replay_ms(step):
+            step()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(args.steps):
+                step()
+            b.record()
+            torch.cuda.synchronize()
+            return a.elapsed_time(b) / args.steps
+        ms = {route: [] for route in steps}
+        for _ in range(args.runs):
+            for route in steps:
+                ms[route].append(replay_ms(steps[route]))
+
+        # the weight-gradient kernel alone, both ways, on the batch's own rows (workspace and results allocated by the wrappers, alike)
+        first = [m for m in model._featurizer._featurizer_network._network if isinstance(m, torch.nn.Linear)][0]
+        ids = [q["image_id"] for q in qs]
+        rows, mat = stores["direct"].rows(stores["direct"].index.ref(ids)), stores["matrix"].gather(stores["matrix"].index.ref(ids))
+        dy = torch.randn(rows.O, first.out_features, device=device) * 0.01
+
+        def kernel_ms(fn, n=20):
+            for _ in range(3):
+                fn()
+            evs = []
+            for _ in range(n):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                evs.append((a, b))
+            torch.cuda.synchronize()
+            return float(np.median([a.elapsed_time(b) for a, b in evs]))
+        kernel = {"matrix": [], "rows": []}
+        same = bool(torch.equal(_lib.linear_wgrad(dy, mat[:, :args.features]), _lib.linear_wgrad_rows(dy, rows.table, rows.src_row)))
+        for _ in range(args.runs):
+            kernel["matrix"].append(kernel_ms(lambda: _lib.linear_wgrad(dy, mat[:, :args.features], bias=True)))
+            kernel["rows"].append(kernel_ms(lambda: _lib.linear_wgrad_rows(dy, rows.table, rows.src_row, bias=True)))
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    m, d = span(ms["matrix"]), span(ms["direct"])
+    return {"tool": "bench_feature_store", "leg": "train",
+            "shape": {"images": args.images, "objects": args.objects, "features": args.features, "batch": args.batch, "rows": rows.O,
+                      "runs": args.runs, "replays_per_run": args.steps},
+            "train_step_ms": {"matrix": m, "direct": d, "direct_vs_matrix": apart(d, m)},
+            "peak_bytes_of_upload_warm_up_and_capture": peak, "peak_direct_minus_matrix_bytes": peak["direct"] - peak["matrix"],
+            "matrix_bytes": rows.O * (args.features + 6) * 4,
+            "wgrad_kernel_ms": {"matrix": span(kernel["matrix"]), "rows": span(kernel["rows"]),
+                                "rows_vs_matrix": apart(span(kernel["rows"]), span(kernel["matrix"])), "same_bits": same},
+            "routes": counts}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--leg", choices=("stream", "train"), default="stream", help="the stream of unseen inference batches, or replayed train steps")
+    ap.add_argument("--steps", type=int, default=20, help="--leg train: replays per timed run")
     ap.add_argument("--images", type=int, default=2048)
     ap.add_argument("--objects", type=int, default=100)
     ap.add_argument("--features", type=int, default=2048)
@@ -119,6 +233,9 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_feature_store: needs a GPU (there is no CPU form of this measurement)")
+    if args.leg == "train":
+        print(json.dumps(train_leg(args)))
+        return
     import bench
     from dfol_vqa_amd import _lib, native_exec, training
     device = torch.device("cuda", 0)
@@ -297,12 +414,6 @@ def main():
                 it._shutdown_workers()
         shutil.rmtree(tmp, ignore_errors=True)
 
-    def span(xs):
-        return {"min": min(xs), "median": float(np.median(xs)), "max": max(xs)}
-
-    def apart(a, b):
-        """a against b in ms per batch, by the rule that a difference counts only when the ranges of the runs are apart."""
-        return "faster, ranges apart" if a["max"] < b["min"] else "slower, ranges apart" if a["min"] > b["max"] else "ranges overlap: no difference shown"
     ms = {leg: span(times[leg]) for leg in legs}
     qps = {leg: {"min": args.batch / ms[leg]["max"] * 1e3, "median": args.batch / ms[leg]["median"] * 1e3, "max": args.batch / ms[leg]["min"] * 1e3} for leg in legs}
     g, c = float(np.median(gather_ms)), float(np.median(copy_ms))
