@@ -774,22 +774,23 @@ def linear_wgrad(dy, x, bias=False):
     for t in (dy, x):
         if not t.is_cuda or (t.dtype != F32 and not stored_bf16) or t.stride(1) != 1:
             raise DfolError("linear_wgrad needs fp32 (or, both, bfloat16) GPU matrices with unit column stride")
-    if M == 0:                                             # a shard without rows (no object pairs): the gradient is zero, as dy.t() @ x gives
-        dw = torch.zeros(N, K, dtype=F32, device=dy.device)
-        return (dw, torch.zeros(N, dtype=F32, device=dy.device)) if bias else dw
-    lib = load()
-    ws = torch.empty(lib.dfol_linear_wgrad_workspace(M, N, K), dtype=F32, device=dy.device)
-    dw = torch.empty(N, K, dtype=F32, device=dy.device)
-    db = torch.empty(N, dtype=F32, device=dy.device) if bias else None
+    ws, dw, db, bf16 = _linear_wgrad_buffers(dy.device, M, N, K, bias)
+    if ws is not None:
+        name = "dfol_linear_wgrad_bias_bf16_bf16" if stored_bf16 else ("dfol_linear_wgrad_bias_bf16" if bf16 else "dfol_linear_wgrad_bias_f32")
+        call(name, _dp(dy), dy.stride(0), _dp(x), x.stride(0), M, N, K, _ptr(ws), _ptr(dw), _ptr(db, F32, True), _stream())
+    return (dw, db) if bias else dw
+
+
+def _linear_wgrad_buffers(device, M, N, K, bias):
+    """What linear_wgrad and linear_wgrad_rows share: (workspace, dW, db or None, bf16 mode).  Without rows (a shard without object pairs,
+    a batch without rows) there is nothing to launch: the workspace is None and dW, db are the zero gradient, as dy.t() @ x gives."""
+    new = torch.empty if M else torch.zeros
+    dw = new(N, K, dtype=F32, device=device)
+    db = new(N, dtype=F32, device=device) if bias else None
+    ws = torch.empty(load().dfol_linear_wgrad_workspace(M, N, K), dtype=F32, device=device) if M else None
     # bf16 mode: the same layers whose forward product ran on bf16 operands (linear_act: weights of >= SPLIT_MIN_WEIGHT elements); the small
     # LSTM / attention layers stay fp32 forward AND backward
-    bf16 = _dense_math() == "bf16" and N * K >= SPLIT_MIN_WEIGHT
-    if stored_bf16:
-        call("dfol_linear_wgrad_bias_bf16_bf16", _dp(dy), dy.stride(0), _dp(x), x.stride(0), M, N, K, _ptr(ws), _ptr(dw), _ptr(db, F32, True), _stream())
-        return (dw, db) if bias else dw
-    call("dfol_linear_wgrad_bias_bf16" if bf16 else "dfol_linear_wgrad_bias_f32", _dp(dy), dy.stride(0),
-         _dp(x), x.stride(0), M, N, K, _ptr(ws), _ptr(dw), _ptr(db, F32, True), _stream())
-    return (dw, db) if bias else dw
+    return ws, dw, db, _dense_math() == "bf16" and N * K >= SPLIT_MIN_WEIGHT
 
 
 def linear_wgrad_rows_supported(N, K, ld_dy, ld_table):
@@ -808,16 +809,10 @@ def linear_wgrad_rows(dy, table, src_row, bias=False):
             raise DfolError("linear_wgrad_rows needs fp32 GPU matrices with unit column stride")
     if src_row.numel() != M:
         raise DfolError("linear_wgrad_rows: src_row has %d entries for %d rows of dy" % (src_row.numel(), M))
-    if M == 0:                                             # as linear_wgrad: a batch without rows has a zero gradient
-        dw = torch.zeros(N, K, dtype=F32, device=dy.device)
-        return (dw, torch.zeros(N, dtype=F32, device=dy.device)) if bias else dw
-    lib = load()
-    ws = torch.empty(lib.dfol_linear_wgrad_workspace(M, N, K), dtype=F32, device=dy.device)
-    dw = torch.empty(N, K, dtype=F32, device=dy.device)
-    db = torch.empty(N, dtype=F32, device=dy.device) if bias else None
-    bf16 = _dense_math() == "bf16" and N * K >= SPLIT_MIN_WEIGHT      # the mode choice of linear_wgrad
-    call("dfol_linear_wgrad_bias_rows_bf16" if bf16 else "dfol_linear_wgrad_bias_rows_f32", _dp(dy), dy.stride(0), _dp(table), table.stride(0),
-         _ptr(src_row, I32), M, N, K, _ptr(ws), _ptr(dw), _ptr(db, F32, True), _stream())
+    ws, dw, db, bf16 = _linear_wgrad_buffers(dy.device, M, N, K, bias)
+    if ws is not None:
+        call("dfol_linear_wgrad_bias_rows_bf16" if bf16 else "dfol_linear_wgrad_bias_rows_f32", _dp(dy), dy.stride(0), _dp(table), table.stride(0),
+             _ptr(src_row, I32), M, N, K, _ptr(ws), _ptr(dw), _ptr(db, F32, True), _stream())
     return (dw, db) if bias else dw
 
 
@@ -1377,7 +1372,7 @@ def pair_logit_bwd(dx, p2, e_rows, pred_off, need_bias=True):
 
 
 def pair_head_fused_supported(hid1, hid2):
-    """Widths the fused head backward takes (csrc/dfol_dense_wgrad.hip, pair_wgrad_fused_kernel: all of dW2 in one workgroup's accumulators)."""
+    """Widths the fused head backward takes (csrc/dfol_pair_wgrad.hip, pair_wgrad_fused_kernel: all of dW2 in one workgroup's accumulators)."""
     return hid1 % 4 == 0 and hid2 % 4 == 0 and 16 <= hid2 <= 320 and 4 <= hid1 <= 256
 
 
@@ -1539,7 +1534,7 @@ def pair_dz_tall_multi(dx_list, p2, e_rows_list, row_pred, w2, dz_out=None):
 
 
 def pair_wgrad_multi(dx_list, p2, z, e_rows_list, pred_off, row_pred):
-    """dW2 [HID2, HID1] = sum_k dpre2_k^T z for SEVERAL readers of one hidden layer in one pass over p2 = pre2 and z (csrc/dfol_dense_wgrad.hip,
+    """dW2 [HID2, HID1] = sum_k dpre2_k^T z for SEVERAL readers of one hidden layer in one pass over p2 = pre2 and z (csrc/dfol_pair_wgrad.hip,
     dfol_pair_wgrad_fused_multi_f32): dpre2_k[r, j] = dx_k[r] E_k[row_pred[r], j] h (1 - h).  The readers share row_pred [M] (int32, non-decreasing),
     pred_off [P + 1] (int64) and P; up to PAIR_DZ_MULTI_MAX per launch (more: further launches, added in order).  The launch's scale comes from
     the device (dfol_pair_wgrad_multi_scale_f32: no sync); the readers' own sums are pair_head_sums'."""

@@ -403,7 +403,7 @@ class _PairTrunk(torch.autograd.Function):
     """pre2 = z W2^T + b2 for every pair row, as the ROOT of a deferred backward: the logit layers that read pre2 (`_HeadUse`, one per relation
     operator group) do not send a [pairs, HID2] gradient back through autograd.  Each of them runs, in ITS backward, the two products that
     consume dpre2 (dz (+)= dpre2 W2, dW2 = dpre2^T z) with dpre2 rebuilt on the fly from pre2 (csrc/dfol_dense_tall.hip /
-    dfol_dense_split.hip LsProducer, csrc/dfol_dense_wgrad.hip pair_wgrad_fused_kernel) - the weight-gradient pass also yields the reader's
+    dfol_dense_split.hip LsProducer, csrc/dfol_pair_wgrad.hip pair_wgrad_fused_kernel) - the weight-gradient pass also yields the reader's
     own sums (dE, dbe) - leaves the results in `state`, which it shares with this node, and returns a zero for the one-element `token`
     that ties it to this node.  Autograd runs this backward after all of them: it hands out what they accumulated.  3 GB written and 9 GB
     read less per step at 256 x 100 objects."""

@@ -600,7 +600,7 @@ int dfol_pair_logit_bwd_f32(const float* dx, const float* P2, int64_t ld_p2, int
  *   dz_fused:       dZ [M, HID1] (+)= dpre2 W2, W2t_split = dfol_linear_pack_w_f16x2 of W2^T [HID1, HID2]; row_pred[r] = the row of E
  *                   (or -1: no gradient), emax[p] = max |E[p, :]|; the row's dpre2 is scaled by a power of two from the bound
  *                   |dx[r]| emax / 4 before its fp16 split (csrc/dfol_dense_split.hip, LsProducer)
- *   wgrad_fused:    dW2 [HID2, HID1] = dpre2^T Z in one pass over pre2 and Z (csrc/dfol_dense_wgrad.hip); row_pred non-decreasing and
+ *   wgrad_fused:    dW2 [HID2, HID1] = dpre2^T Z in one pass over pre2 and Z (csrc/dfol_pair_wgrad.hip); row_pred non-decreasing and
  *                   valid, pred_off [P + 1] the predicates' first rows, scale -> {S, 1 / S} on the device, S a power of two with
  *                   S max_r |dx[r]| emax[row_pred[r]] / 4 <= 2^14; HID2 <= 320, HID1 <= 256, multiples of 4
  * HID2 % 4 == 0, rows of pre2, Z and E 16-byte aligned.
@@ -627,7 +627,7 @@ int dfol_pair_dz_tall_f32(const float* pre2, int64_t ld_p2, const float* dx, con
 int dfol_pair_dz_tall_multi_f32(const float* pre2, int64_t ld_p2, const float* dx, int64_t dx_stride, int32_t nr, const int32_t* row_pred, const float* E,
                                 int64_t ld_e, int32_t P, const float* emax, const void* W2t_split, float* dZ, int64_t ld_dz, int32_t M, int32_t HID1,
                                 int32_t HID2, int32_t accumulate, float* workspace, void* stream);
-/* ... and their weight gradient in ONE pass (csrc/dfol_dense_wgrad.hip): dW2 [HID2, HID1] = sum_k dpre2_k^T Z with pre2 and Z read once instead of
+/* ... and their weight gradient in ONE pass (csrc/dfol_pair_wgrad.hip): dW2 [HID2, HID1] = sum_k dpre2_k^T Z with pre2 and Z read once instead of
  * once per reader; the readers' own sums (dE, dbe, db2) stay with dfol_pair_logit_bwd_sums_f32.  Operands laid out as for
  * dfol_pair_dz_tall_multi_f32 (dx [nr][dx_stride >= M], E [nr][P][ld_e], shared row_pred / pred_off as dfol_pair_wgrad_fused_f32 takes them),
  * 1 <= nr <= 4, sizes, alignment and workspace (dfol_pair_wgrad_fused_workspace) as dfol_pair_wgrad_fused_f32 - no row-count floor.  scale -> {S, 1 / S}

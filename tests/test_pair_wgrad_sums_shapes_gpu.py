@@ -1,4 +1,4 @@
-"""The fused pair weight gradient's two SUMS forms (csrc/dfol_dense_wgrad.hip: pair_wgrad_fused_kernel<3, true> behind dfol_pair_wgrad_fused_sums_f32,
+"""The fused pair weight gradient's two SUMS forms (csrc/dfol_pair_wgrad.hip: pair_wgrad_fused_kernel<3, true> behind dfol_pair_wgrad_fused_sums_f32,
 pair_wgrad_fused_kernel<4, true, true> behind dfol_pair_wgrad_fused_sums_bf16, and pair_sums_reduce_kernel) off the shapes they were born at:
 more than 65 536 rows (row slabs WITHOUT rows), narrow and odd widths, a predicate boundary in every position of an octet, of a 32-row step and
 of a slab, predicates without rows, dx = 0, dbe = NULL, a strided dE, and the launcher's guards.
@@ -46,7 +46,7 @@ build's outputs are the same bits in all 48 tensors of a dump of 14 of these cas
 offsets 0, 1 and 7 meet the bounds of the 64-row cases: the kernel's own floor of 32 rows holds, the callers' 64 is margin.  (3) The Python guard
 agrees with the entry points at every width tried.
 
-Two mutants of csrc/dfol_dense_wgrad.hip, each built on a scratch copy and run once against this file (neither reads or writes out of bounds):
+Two mutants of csrc/dfol_pair_wgrad.hip, each built on a scratch copy and run once against this file (neither reads or writes out of bounds):
   * the flush condition of pair_a off by one row (`rr > end_cur` for `rr >= end_cur`): 68 of 88 fail - every sums case with a predicate boundary, or
     the end of the rows, anywhere but on the first row of a 32-row step (NaN left in a dE partial row, or dE beyond its bound).  What passes: the
     layouts whose boundaries all fall on a step's first row (first_64_then_64s, M64, predicates of 32 rows at offset 0), the forms without sums,

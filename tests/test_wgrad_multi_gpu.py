@@ -1,4 +1,4 @@
-"""Several readers' weight gradient in one pass (csrc/dfol_dense_wgrad.hip: pair_wgrad_fused_kernel<CPT, false, false, MULTI> behind
+"""Several readers' weight gradient in one pass (csrc/dfol_pair_wgrad.hip: pair_wgrad_fused_kernel<CPT, false, false, MULTI> behind
 dfol_pair_wgrad_fused_multi_f32, its scale from dfol_pair_wgrad_multi_scale_f32) against float64:  dW2 = sum_k dpre2_k^T Z,
 dpre2_k[r][j] = dx_k[r] E_k[p(r)][j] h (1 - h), h = Sigmoid(pre2[r][j]).
 
