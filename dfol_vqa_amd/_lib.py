@@ -101,6 +101,8 @@ SIGNATURES = {
     "dfol_gate_f32": [_p, _p, _p, _p, _p, _i32, _i32, _p, _p, _p],
     "dfol_gather_rows_f32": [_p, _p, _i32, _i32, _p, _p],
     "dfol_gather_object_rows_f32": [_p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _p],
+    "dfol_store_round_bf16": [_p, _i64, _p, _p],
+    "dfol_gather_object_rows_bf16_f32": [_p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _p],
     "dfol_store_rows_f32": [_p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p],
     "dfol_store_objects_f32": [_p, _i64, _p, _p, _i32, _i32, _p, _i64, _p],
     "dfol_segment_sum_rows_f32": [_p, _p, _i32, _i32, _p, _p],
@@ -175,6 +177,10 @@ SIGNATURES = {
     "dfol_linear_wgrad_rows_supported": [_i32, _i32, _i64, _i64],      # returns 0 / 1, not a status: called directly
     "dfol_linear_wgrad_bias_rows_f32": [_p, _i64, _p, _i64, _p, _i64, _i32, _i32, _p, _p, _p, _p],
     "dfol_linear_wgrad_bias_rows_bf16": [_p, _i64, _p, _i64, _p, _i64, _i32, _i32, _p, _p, _p, _p],
+    "dfol_linear_wgrad_rows_bf16t_supported": [_i32, _i32, _i64, _i64],
+    "dfol_linear_wgrad_bias_rows_bf16t": [_p, _i64, _p, _i64, _p, _i64, _i32, _i32, _p, _p, _p, _p],
+    "dfol_linear_rows_bf16t_supported": [_i32, _i32, _i64],            # returns 0 / 1
+    "dfol_linear_act_rows_bf16t_f32": [_p, _i64, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _i32, _p],
     "dfol_act_bwd_f32": [_p, _p, _i64, _i32, _p, _p],
     "dfol_linear_act_bf16_bf16": [_p, _i64, _p, _p, _p, _i64, _i32, _i32, _i32, _i32, _p],
     "dfol_linear_wgrad_bias_bf16_bf16": [_p, _i64, _p, _i64, _i64, _i32, _i32, _p, _p, _p, _p],
@@ -208,6 +214,7 @@ SIGNATURES = {
     "dfol_run_program": [_p, _p, _p, _i32, _p, _p, _p],
     "dfol_set_range_status": [_p],
     "dfol_set_feature_rows": [_p, _p],
+    "dfol_set_feature_rows_bf16": [_p, _p],
     "dfol_set_feature_cache": [_p, _i64, _i32, _p, _p],
     "dfol_pair_features_bwd_f32": [_p, _i64, _i32, _p, _p, _i32, _i32, _p, _i64, _p],
     "dfol_dropout_advance": [_p, _p],
@@ -581,9 +588,19 @@ def gather_object_rows(features, boxes, sizes, slot, obj_off, out):
         raise DfolError("gather_object_rows: store tensors / index arrays of mismatched shapes")
     if out.dim() != 2 or out.dtype != F32 or not out.is_cuda or (out.shape[0] > 1 and out.stride(1) != 1) or out.shape[1] < F + 6:
         raise DfolError("gather_object_rows: out must be fp32 device rows of at least F + 6 = %d columns" % (F + 6))
-    call("dfol_gather_object_rows_f32", _ptr(features, F32), _ptr(boxes, F32), _ptr(sizes, F32), _ptr(slot, I32), _ptr(obj_off, I32),
+    bf16t = features.dtype == torch.bfloat16                # (a bf16 store's table: the stored values widened exactly, the same matrix)
+    call("dfol_gather_object_rows_bf16_f32" if bf16t else "dfol_gather_object_rows_f32", _ptr(features, torch.bfloat16 if bf16t else F32), _ptr(boxes, F32), _ptr(sizes, F32), _ptr(slot, I32), _ptr(obj_off, I32),
          slot.numel(), max_obj, F, _dp(out), out.stride(0), _stream())
     return out
+
+
+def store_round_bf16(src, dst):
+    """dst = bfloat16(src), round to nearest even by the dense kernels' own dfol_rne2 (csrc/dfol_store.hip): how a bf16 feature store's chunk
+    goes from its fp32 upload buffer into the table.  src fp32, dst bfloat16, contiguous device tensors of the same element count."""
+    if src.numel() != dst.numel():
+        raise DfolError("store_round_bf16: %d source elements for %d destination elements" % (src.numel(), dst.numel()))
+    call("dfol_store_round_bf16", _ptr(src, F32), src.numel(), _ptr(dst, torch.bfloat16), _stream())
+    return dst
 
 
 def store_rows(boxes, sizes, slot, obj_off, src_row, box6):
@@ -765,6 +782,26 @@ def linear_wide_rows(table, src_row, weight, bias, act, out=None):
     return out
 
 
+def linear_rows_bf16t_supported(N, K, ld_table):
+    """dfol_linear_rows_bf16t_supported: linear_rows_bf16t takes a [N, K] weight over a bf16 table of row stride ld_table (elements)."""
+    return bool(load().dfol_linear_rows_bf16t_supported(int(N), int(K), int(ld_table)))
+
+
+def linear_rows_bf16t(table, src_row, weight, bias, act, out=None):
+    """The bf16 mode's product over the indexed rows of a bf16 table: y[r] = act(table[src_row[r]] @ weight.T + bias), table [rows, K] bfloat16
+    (a bf16 feature store's features as a matrix), src_row [M] int32, fp32 y.  Bit for bit linear_act_split(table.float()[src_row]) under
+    dense_math("bf16"), which rounds an fp32 feature to the value the table holds (csrc/dfol_dense_split.hip, MODE 3).  Any M."""
+    M, K = src_row.numel(), table.shape[1]
+    N = weight.shape[0]
+    if weight.shape[1] != K or table.dtype != torch.bfloat16 or table.stride(1) != 1:
+        raise DfolError("linear_rows_bf16t: table [rows, %d] bfloat16 with unit column stride, weight [N, %d]" % (K, K))
+    if out is None:
+        out = torch.empty(M, N, dtype=F32, device=table.device)
+    call("dfol_linear_act_rows_bf16t_f32", _dp(table), table.stride(0), _ptr(src_row, I32), _ptr(linear_pack_w_split(weight, False, 1), torch.bfloat16),
+         _ptr(bias, F32, True), _dp(out), out.stride(0), M, N, K, act, _stream())
+    return out
+
+
 def linear_wgrad(dy, x, bias=False):
     """dW [N, K] = dy^T x for dy [M, N], x [M, K] (fp32, unit column stride); bias=True: (dW, db) with db [N] = dy.sum(0) from the
     same pass.  fp32 results on the matrix cores, deterministic (csrc/dfol_dense_wgrad.hip)."""
@@ -793,25 +830,32 @@ def _linear_wgrad_buffers(device, M, N, K, bias):
     return ws, dw, db, _dense_math() == "bf16" and N * K >= SPLIT_MIN_WEIGHT
 
 
-def linear_wgrad_rows_supported(N, K, ld_dy, ld_table):
-    """dfol_linear_wgrad_rows_supported: linear_wgrad_rows exists for the shape (where linear_wgrad runs its bf16-pipe kernel)."""
-    return bool(load().dfol_linear_wgrad_rows_supported(int(N), int(K), int(ld_dy), int(ld_table)))
+def linear_wgrad_rows_supported(N, K, ld_dy, ld_table, bf16_table=False):
+    """dfol_linear_wgrad_rows_supported: linear_wgrad_rows exists for the shape (where linear_wgrad runs its bf16-pipe kernel).  bf16_table: the
+    question for a bf16 store's table (dfol_linear_wgrad_rows_bf16t_supported; ld_table in elements)."""
+    fn = load().dfol_linear_wgrad_rows_bf16t_supported if bf16_table else load().dfol_linear_wgrad_rows_supported
+    return bool(fn(int(N), int(K), int(ld_dy), int(ld_table)))
 
 
 def linear_wgrad_rows(dy, table, src_row, bias=False):
     """linear_wgrad over indexed rows: dW [N, K] = dy^T table[src_row] for dy [M, N], table [rows, K] fp32 (a feature store's features as a
     matrix), src_row [M] int32; bias=True: (dW, db).  Bit for bit linear_wgrad(dy, table[src_row]) without the gathered copy
-    (csrc/dfol_dense_wgrad.hip, ROWS); shapes linear_wgrad_rows_supported does not take are refused."""
+    (csrc/dfol_dense_wgrad.hip, ROWS); shapes linear_wgrad_rows_supported does not take are refused.  A bfloat16 table (a bf16 feature store's)
+    is taken where the bf16 mode applies to the layer - linear_wgrad(dy, table.float()[src_row])'s bits there - and refused elsewhere."""
     M, N = dy.shape
     K = table.shape[1]
+    bf16t = table.dtype == torch.bfloat16
     for t in (dy, table):
-        if not t.is_cuda or t.dtype != F32 or t.stride(1) != 1:
-            raise DfolError("linear_wgrad_rows needs fp32 GPU matrices with unit column stride")
+        if not t.is_cuda or (t.dtype != F32 and not (bf16t and t is table)) or t.stride(1) != 1:
+            raise DfolError("linear_wgrad_rows needs fp32 GPU matrices (or a bfloat16 table) with unit column stride")
     if src_row.numel() != M:
         raise DfolError("linear_wgrad_rows: src_row has %d entries for %d rows of dy" % (src_row.numel(), M))
     ws, dw, db, bf16 = _linear_wgrad_buffers(dy.device, M, N, K, bias)
+    if bf16t and not bf16:
+        raise DfolError("linear_wgrad_rows: a bfloat16 table needs the bf16 mode on this layer (dense_math('bf16') and a weight of at least %d "
+                        "elements; the arithmetic is %r, the weight [%d, %d]): use the gathered matrix" % (SPLIT_MIN_WEIGHT, _dense_math(), N, K))
     if ws is not None:
-        call("dfol_linear_wgrad_bias_rows_bf16" if bf16 else "dfol_linear_wgrad_bias_rows_f32", _dp(dy), dy.stride(0), _dp(table), table.stride(0),
+        call("dfol_linear_wgrad_bias_rows_bf16t" if bf16t else "dfol_linear_wgrad_bias_rows_bf16" if bf16 else "dfol_linear_wgrad_bias_rows_f32", _dp(dy), dy.stride(0), _dp(table), table.stride(0),
              _ptr(src_row, I32), M, N, K, _ptr(ws), _ptr(dw), _ptr(db, F32, True), _stream())
     return (dw, db) if bias else dw
 

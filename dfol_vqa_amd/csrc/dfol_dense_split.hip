@@ -124,6 +124,10 @@ struct LsProducer {
 // BIO: bf16 storage on both sides (NP = 1 only: the bf16 mode's per-pair activations): X and Y are rows of bfloat16 (8-byte aligned rows,
 // K % 4 == 0); a thread's 8 consecutive k are two 8-byte loads that go to LDS as they are - no conversion - and the epilogue rounds the
 // fp32 accumulators to nearest even.  ldx / ldy count ELEMENTS.
+// MODE 3 (ROWSB; NP = 1, fp32 output): X is a feature store's bf16 TABLE (feature_store.py, feature_dtype="bf16") and row r of the product is
+// its row prod.row_pred[r] (src_row of dfol_store_rows_f32): the X side of BIO - two 8-byte loads per thread and step that go to LDS as
+// they are, the table holding what dfol_rne2 makes of an fp32 feature - and the fp32 epilogue of the plain form.  A row's address is
+// 64-bit (a table is larger than 4 GB); the row is clamped BEFORE its index is read and the K tail inside the row, as in wide_h2_kernel<ROWS>.
 template <int ACT, int XV, int NT, int NP, int RT, bool BIO, int MODE = 0>
 __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restrict__ Bs, const void* __restrict__ Xv, int64_t ldx,
                                         const u32x4* __restrict__ Wp, const float* __restrict__ bias, void* __restrict__ Yv, int64_t ldy, int M, int N,
@@ -132,12 +136,15 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
     // four steps of X in flight, B fragments straight from the packed image) were measured slower at the tall products and are not here:
     // DESIGN_HISTORY.md ("the tiled kernel's step loop, three variants") has the numbers and the commit that holds their code.
     static_assert(!BIO || NP == 1, "bf16 storage belongs to the bf16 mode");
-    constexpr bool PROD = MODE == 1, LOGIT = MODE == 2;
+    constexpr bool PROD = MODE == 1, LOGIT = MODE == 2, ROWSB = MODE == 3;
+    constexpr bool BIN = BIO || ROWSB;                                // X rows are bfloat16
+    static_assert(!ROWSB || (NP == 1 && !BIO && XV == 4), "the bf16 table's rows feed the bf16 mode's fp32-output product");
     static_assert(!LOGIT || (!BIO && ACT == DFOL_ACT_NONE), "the logit partial sums belong to the fp32 pre-activation output");
     static_assert(!PROD || (NP == 2 && !BIO && XV == 4 && ACT == DFOL_ACT_NONE), "the produced operand is two fp16 pieces of fp32 rows");
-    typedef typename std::conditional<BIO, uint16_t, float>::type TX;
+    typedef typename std::conditional<BIN, uint16_t, float>::type TX;
+    typedef typename std::conditional<BIO, uint16_t, float>::type TY;
     const TX* __restrict__ X = reinterpret_cast<const TX*>(Xv);
-    TX* __restrict__ Y = reinterpret_cast<TX*>(Yv);
+    TY* __restrict__ Y = reinterpret_cast<TY*>(Yv);
     constexpr int BM = 32 * RT, RH = RT / 2;                          // rows of the block; 64-row halves staged per thread
     const int m0 = mb * BM, n0 = nb * LS_BN;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), kh = lane >> 4, r16 = lane & 15;
@@ -154,6 +161,10 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
     const int arow = tid >> 2, aq = tid & 3;
     const TX* xp0 = X + (int64_t)min(m0 + arow, M - 1) * ldx + aq * 8;
     const TX* xp1 = X + (int64_t)min(m0 + arow + 64, M - 1) * ldx + aq * 8;      // (RT = 4 only)
+    if constexpr (ROWSB) {
+        xp0 = X + (int64_t)prod.row_pred[min(m0 + arow, M - 1)] * ldx + aq * 8;
+        if constexpr (RT == 4) xp1 = X + (int64_t)prod.row_pred[min(m0 + arow + 64, M - 1)] * ldx + aq * 8;
+    }
     float gs[RT / 2];                                                 // PROD: 2^e_r dx[r] of the thread's rows, and their embedding rows
     const float* ep[RT / 2];
     if constexpr (PROD) {
@@ -173,7 +184,7 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
     }
     // X registers: two steps in flight (HBM latency is longer than one step of 96 MFMAs).  The loads are unconditional - addresses
     // clamped, out-of-range k zeroed afterwards - so that every wavefront issues exactly 4 per step and the vmcnt arithmetic below holds.
-    typedef typename std::conditional<BIO, u32x2, float4>::type XR;  // four consecutive k of a row as loaded
+    typedef typename std::conditional<BIN, u32x2, float4>::type XR;  // four consecutive k of a row as loaded
     XR xa[2][RH][2];                                                // [set][row half][k half]
     float4 ea[PROD ? RH : 1][2];                                    // PROD: the same pieces of the rows' embedding rows - L2 hits, ONE step ahead
     float xmax = 0.f;                                               // NP = 2: the largest |x| this thread split (one v_max3 per two elements)
@@ -182,7 +193,7 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
         const int k = ks * LS_BK + aq * 8;
         const int c0 = min(k, K - 4) - aq * 8, c1 = min(k + 4, K - 4) - aq * 8;      // K % 4 == 0: a group of four is wholly in or out
         auto ld4 = [&](const TX* p) __attribute__((always_inline)) {
-            if constexpr (BIO) {
+            if constexpr (BIN) {
                 return *reinterpret_cast<const u32x2*>(p);
             } else {
                 if (XV == 4) return *reinterpret_cast<const float4*>(p);
@@ -215,7 +226,7 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
         for (int h = 0; h < RH; ++h) {
             const int row = arow + 64 * h;
             const int at = row * 4 + (aq ^ dfol_swz(row));
-            if constexpr (BIO) {
+            if constexpr (BIN) {
                 const u32x2 zz = u32x2{0u, 0u};
                 const u32x2 v0 = k < K ? xa[S][h][0] : zz, v1 = k + 4 < K ? xa[S][h][1] : zz;
                 As[at] = u32x4{v0.x, v0.y, v1.x, v1.y};
@@ -474,7 +485,7 @@ __device__ __forceinline__ void ls_tile(u32x4* __restrict__ As, u32x4* __restric
         LTRACE(62);
         return;
     }
-    TX* yp = Y + (int64_t)(m0 + wm * (16 * RT) + 4 * kh) * ldy + n0 + wn * WN + r16;
+    TY* yp = Y + (int64_t)(m0 + wm * (16 * RT) + 4 * kh) * ldy + n0 + wn * WN + r16;
     if constexpr (PROD) {
         if (prod.accumulate) {                                        // (rows / columns past the matrix: clamped reads, never stored)
 #pragma unroll
@@ -540,7 +551,7 @@ template <int ACT, int XV, int NP, int RT, bool BIO = false, int MODE = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BIO ? DFOL_BIO_WAVES : 2, BIO ? DFOL_BIO_WAVES : (RT == 2 ? 3 : 2)))) void linear_act_split_kernel(
     const void* __restrict__ X, int64_t ldx, const u32x4* __restrict__ Wp, const float* __restrict__ bias, void* __restrict__ Y,
     int64_t ldy, int M, int N, int K, int ksteps, int nbn, int nblocks, LsProducer prod) {
-    constexpr int LP = BIO ? 1 : (NP == 2 ? 2 : 3);                         // (the bf16 mode's fp32-storage kernels keep the 48 KB of NP = 3: same occupancy as before)
+    constexpr int LP = (BIO || MODE == 3) ? 1 : (NP == 2 ? 2 : 3);          // (the bf16 mode's fp32-storage kernels keep the 48 KB of NP = 3: same occupancy as before)
     constexpr int A_PIECES = LP * 32 * RT * 4, B_PIECES = LP * LS_BN * 4;   // [piece][row][k-group] 24 KB (12 KB for 64-row blocks); the B tile of the step 24 KB
     // the output tile staged for its stores: bf16 storage 34 KB / 17 KB; fp32: half the block's rows, 132 floats apart (33 KB / 16.5 KB)
     constexpr int STAGE_PIECES = BIO ? 32 * RT * (LS_BN + 8) * 2 / 16 : 16 * RT * (LS_BN + 4) * 4 / 16;
@@ -689,6 +700,51 @@ extern "C" int dfol_linear_act_bf16_bf16(const void* X_bf16, int64_t ldx, const 
     }
 #undef DFOL_LSB
     DFOL_LAUNCH_CHECK("linear_act_bf16_bf16");
+    return 0;
+}
+
+// The bf16 mode's product over the indexed rows of a bf16 table (ls_tile, MODE 3): Y[r] = act(X_table[src_row[r]] W^T + b), fp32 out.  Bit for
+// bit dfol_linear_act_bf16_f32 over the gathered, widened rows: that kernel rounds an fp32 feature by dfol_rne2 on its way to LDS, the table
+// holds that value already; block heights by the same rule.  Any M; no range word (one piece has none).
+static const char* ls_rows_bf16t_refusal(int32_t N, int32_t K, int64_t ld_table) {
+    if (N <= 0 || K < 4 || K % 4 != 0) return "K must be a positive multiple of 4";
+    if (ld_table < K || ld_table % 4 != 0) return "table rows must be 8-byte aligned (ld_table % 4 == 0) and cover K";
+    return nullptr;
+}
+
+extern "C" int dfol_linear_rows_bf16t_supported(int32_t N, int32_t K, int64_t ld_table) { return ls_rows_bf16t_refusal(N, K, ld_table) == nullptr; }
+
+extern "C" int dfol_linear_act_rows_bf16t_f32(const void* X_table_bf16, int64_t ld_table, const int32_t* src_row, const void* W_bf16, const float* bias,
+                                              float* Y, int64_t ldy, int32_t M, int32_t N, int32_t K, int32_t act, void* stream) {
+    DFOL_REQUIRE(M >= 0 && N > 0 && ldy >= N, "linear_act_rows_bf16t: bad sizes M=%d N=%d K=%d", M, N, K);
+    const char* why = ls_rows_bf16t_refusal(N, K, ld_table);
+    DFOL_REQUIRE(!why, "linear_act_rows_bf16t: %s (N=%d K=%d ld_table=%lld)", why, N, K, (long long)ld_table);
+    if (M == 0) return 0;
+    DFOL_REQUIRE(X_table_bf16 && src_row && W_bf16 && Y, "linear_act_rows_bf16t: null pointer");
+    DFOL_REQUIRE(((uintptr_t)X_table_bf16 % 8 == 0) && ((uintptr_t)W_bf16 % 16 == 0) && ((uintptr_t)src_row % 4 == 0),
+                 "linear_act_rows_bf16t: the table must be 8-byte, W 16-byte and src_row 4-byte aligned");
+    const int ksteps = dfol_cdiv(K, LS_BK), nbn = dfol_cdiv(N, LS_BN);
+    static const int force_bm = getenv("DFOL_DENSE_BM") ? atoi(getenv("DFOL_DENSE_BM")) : 0;
+    const bool small = force_bm ? force_bm == 64 : (int64_t)dfol_cdiv(M, LS_BM) * nbn < 512;      // (ls_launch's rule)
+    const int nbm = dfol_cdiv(M, small ? 64 : LS_BM);
+    DFOL_REQUIRE((int64_t)nbm * nbn < ((int64_t)1 << 31), "linear_act_rows_bf16t: too many tiles");
+    const int nblocks = nbm * nbn;
+    LsProducer rows = LsProducer();
+    rows.row_pred = src_row;
+#define DFOL_LSR(A)                                                                                                                               \
+    if (small) hipLaunchKernelGGL((linear_act_split_kernel<A, 4, 1, 2, false, 3>), dim3(nblocks), dim3(256), 0, (hipStream_t)stream, X_table_bf16, \
+                                  ld_table, (const u32x4*)W_bf16, bias, (void*)Y, ldy, M, N, K, ksteps, nbn, nblocks, rows);                       \
+    else hipLaunchKernelGGL((linear_act_split_kernel<A, 4, 1, 4, false, 3>), dim3(nblocks), dim3(256), 0, (hipStream_t)stream, X_table_bf16,      \
+                            ld_table, (const u32x4*)W_bf16, bias, (void*)Y, ldy, M, N, K, ksteps, nbn, nblocks, rows)
+    switch (act) {
+        case DFOL_ACT_NONE: DFOL_LSR(DFOL_ACT_NONE); break;
+        case DFOL_ACT_SIGMOID: DFOL_LSR(DFOL_ACT_SIGMOID); break;
+        case DFOL_ACT_ELU: DFOL_LSR(DFOL_ACT_ELU); break;
+        case DFOL_ACT_LOGSIGMOID: DFOL_LSR(DFOL_ACT_LOGSIGMOID); break;
+        default: DFOL_REQUIRE(false, "linear_act_rows_bf16t: unknown activation %d", act);
+    }
+#undef DFOL_LSR
+    DFOL_LAUNCH_CHECK("linear_act_rows_bf16t");
     return 0;
 }
 

@@ -370,6 +370,100 @@ __device__ __forceinline__ void wgrad_tn3_accumulate(const float* __restrict__ d
     }
 }
 
+// eight rows' element `odd` of one 32-bit word of bf16 pairs each -> the operand's four registers (row 2j in the low half): v_perm_b32, no conversion
+__device__ __forceinline__ u32x4 w3_gather8(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t w4, uint32_t w5, uint32_t w6, uint32_t w7, bool odd) {
+    return odd ? u32x4{__builtin_amdgcn_perm(w1, w0, 0x07060302u), __builtin_amdgcn_perm(w3, w2, 0x07060302u),
+                       __builtin_amdgcn_perm(w5, w4, 0x07060302u), __builtin_amdgcn_perm(w7, w6, 0x07060302u)}
+               : u32x4{__builtin_amdgcn_perm(w1, w0, 0x05040100u), __builtin_amdgcn_perm(w3, w2, 0x05040100u),
+                       __builtin_amdgcn_perm(w5, w4, 0x05040100u), __builtin_amdgcn_perm(w7, w6, 0x05040100u)};
+}
+
+// The bf16 mode over the indexed rows of a bf16 TABLE (a feature store built with feature_dtype="bf16": dfol_linear_wgrad_bias_rows_bf16t).
+// dY is fp32 as in the first form - rounded by w3_rne8, the bias sums from the fp32 values - and X is four bf16 per row and lane through the
+// ROWS form's 64-bit address, assembled into operand registers as the bf16-storage form below does it: the table holds what w3_rne8 makes of
+// an fp32 feature, so every operand register has the bits the first form builds from the gathered, widened rows.  A row past the range
+// loads neither its index nor the table and counts as zero.
+template <int AV, int NP, bool ROWS = false>
+__device__ __forceinline__ void wgrad_tn3_accumulate(const float* __restrict__ dY, int64_t ld_dy, const uint16_t* __restrict__ X, int64_t ld_x,
+                                                     const int32_t* __restrict__ src_row, int rows, int steps, int N, int K, int n0, int k0,
+                                                     int lane, bool want_bias, f32x16 (&acc)[AV][4], float (&bs)[AV]) {
+    static_assert(NP == 1 && ROWS, "a bf16 table under fp32 gradients is the bf16 mode's indexed form");
+    const int col = lane & 31, half = lane >> 5;
+    const int ca = min(n0 + AV * col, N - AV), cb = min(k0 + 4 * col, K - 4);
+    int va[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) va[r] = (int)(((8 * half + r) * ld_dy + ca) * 4);
+#pragma unroll
+    for (int t = 0; t < AV; ++t)
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[t][u][i] = 0.f;
+#pragma unroll
+    for (int t = 0; t < AV; ++t) bs[t] = 0.f;
+
+    float ra[8][AV];
+    u32x2 rb[8];
+    int ix[8];                                                                     // the table rows of the step to load next (-1: past the range)
+    auto index = [&](int s) __attribute__((always_inline)) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int row = 16 * s + 8 * half + r;
+            ix[r] = row < rows ? src_row[row] : -1;
+        }
+    };
+    auto load = [&](int s) __attribute__((always_inline)) {
+        const int left = rows - 16 * s;
+        const int64_t bytes_a = left > 0 ? ((int64_t)(left - 1) * ld_dy + N) * 4 : 0;
+        const auto da = w3_descriptor(dY + (int64_t)s * 16 * ld_dy, bytes_a);
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            if (AV == 4) {
+                const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(da, va[r], 0, 0);
+                ra[r][0] = __uint_as_float(v.x), ra[r][1] = __uint_as_float(v.y), ra[r][2] = __uint_as_float(v.z), ra[r][3] = __uint_as_float(v.w);
+            } else {
+                const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(da, va[r], 0, 0);
+                ra[r][0] = __uint_as_float(v.x), ra[r][1] = __uint_as_float(v.y);
+            }
+            rb[r] = u32x2{0u, 0u};
+            if (ix[r] >= 0) rb[r] = *reinterpret_cast<const u32x2*>(X + (int64_t)ix[r] * ld_x + cb);      // (8-byte aligned: ld_x % 4 == 0)
+        }
+    };
+    index(0);
+    load(0);
+    index(1);
+    __builtin_amdgcn_sched_barrier(0);
+    for (int s = 0; s < steps; ++s) {
+        u32x4 ap[AV], bp[4];
+        if (want_bias) {
+#pragma unroll
+            for (int t = 0; t < AV; ++t)
+                bs[t] += ((ra[0][t] + ra[1][t]) + (ra[2][t] + ra[3][t])) + ((ra[4][t] + ra[5][t]) + (ra[6][t] + ra[7][t]));
+        }
+#pragma unroll
+        for (int t = 0; t < AV; ++t) {
+            float v[8];
+#pragma unroll
+            for (int r = 0; r < 8; ++r) v[r] = ra[r][t];
+            ap[t] = w3_rne8(v);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            bp[u] = w3_gather8(rb[0][u >> 1], rb[1][u >> 1], rb[2][u >> 1], rb[3][u >> 1], rb[4][u >> 1], rb[5][u >> 1], rb[6][u >> 1], rb[7][u >> 1], u & 1);
+        __builtin_amdgcn_sched_barrier(0);
+        load(s + 1);
+        index(s + 2);                                                              // (waited for a step later, behind the pieces)
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int t = 0; t < AV; ++t)
+                acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ap[t]), __builtin_bit_cast(bf16x8, bp[u]), acc[t][u], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 // The same with dY and X STORED as bfloat16 (the bf16 mode's per-pair activations: dpre2 [pairs, HID2] and Z [pairs, HID1]): a lane loads
 // AV resp. 4 consecutive bf16 of its eight rows (8- / 4-byte buffer loads), and an operand register pair is two rows' halves of one word
 // (v_perm_b32) - no conversions, no rounding, half the bytes.  The bias sums widen the same registers to fp32.
@@ -417,14 +511,6 @@ __device__ __forceinline__ void wgrad_tn3_accumulate(const uint16_t* __restrict_
             rb[S][r] = __builtin_amdgcn_raw_buffer_load_b64(db, vb[r], 0, 0);
         }
     };
-    // eight rows' element `odd` of one word each -> the operand's four registers (row 2j in the low half)
-    auto gather = [](uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t w4, uint32_t w5, uint32_t w6, uint32_t w7, bool odd)
-        __attribute__((always_inline)) {
-        return odd ? u32x4{__builtin_amdgcn_perm(w1, w0, 0x07060302u), __builtin_amdgcn_perm(w3, w2, 0x07060302u),
-                           __builtin_amdgcn_perm(w5, w4, 0x07060302u), __builtin_amdgcn_perm(w7, w6, 0x07060302u)}
-                   : u32x4{__builtin_amdgcn_perm(w1, w0, 0x05040100u), __builtin_amdgcn_perm(w3, w2, 0x05040100u),
-                           __builtin_amdgcn_perm(w5, w4, 0x05040100u), __builtin_amdgcn_perm(w7, w6, 0x05040100u)};
-    };
     auto one_step = [&](int s, auto set_tag) __attribute__((always_inline)) {
         constexpr int S = decltype(set_tag)::value;
         u32x4 ap[AV], bp[4];
@@ -439,11 +525,11 @@ __device__ __forceinline__ void wgrad_tn3_accumulate(const uint16_t* __restrict_
         }
 #pragma unroll
         for (int t = 0; t < AV; ++t)
-            ap[t] = gather(ra[S][0][t >> 1], ra[S][1][t >> 1], ra[S][2][t >> 1], ra[S][3][t >> 1], ra[S][4][t >> 1], ra[S][5][t >> 1], ra[S][6][t >> 1],
+            ap[t] = w3_gather8(ra[S][0][t >> 1], ra[S][1][t >> 1], ra[S][2][t >> 1], ra[S][3][t >> 1], ra[S][4][t >> 1], ra[S][5][t >> 1], ra[S][6][t >> 1],
                            ra[S][7][t >> 1], t & 1);
 #pragma unroll
         for (int u = 0; u < 4; ++u)
-            bp[u] = gather(rb[S][0][u >> 1], rb[S][1][u >> 1], rb[S][2][u >> 1], rb[S][3][u >> 1], rb[S][4][u >> 1], rb[S][5][u >> 1], rb[S][6][u >> 1],
+            bp[u] = w3_gather8(rb[S][0][u >> 1], rb[S][1][u >> 1], rb[S][2][u >> 1], rb[S][3][u >> 1], rb[S][4][u >> 1], rb[S][5][u >> 1], rb[S][6][u >> 1],
                            rb[S][7][u >> 1], u & 1);
         __builtin_amdgcn_sched_barrier(0);
         load(s + D, set_tag);                                                      // (past the range: zero bytes, nothing fetched)
@@ -479,8 +565,8 @@ __device__ __forceinline__ void wgrad_tn3_accumulate(const uint16_t* __restrict_
     }
 }
 
-template <int AV, int NP, typename TIN, bool ROWS>
-__device__ __forceinline__ void wgrad_tn3_block(const TIN* __restrict__ dY, int64_t ld_dy, const TIN* __restrict__ X, int64_t ld_x,
+template <int AV, int NP, typename TIN, bool ROWS, typename TXE = TIN>
+__device__ __forceinline__ void wgrad_tn3_block(const TIN* __restrict__ dY, int64_t ld_dy, const TXE* __restrict__ X, int64_t ld_x,
                                                 const int32_t* __restrict__ src_row, int rows, int steps, int N, int K, int n0, int k0, int lane,
                                                 int role, float* __restrict__ lds, float* __restrict__ out, float* __restrict__ db_out) {
     // role 0: accumulate and store; 1: accumulate, add the partner's accumulators from `lds`, store; 2: accumulate into `lds` (the partner)
@@ -536,9 +622,10 @@ constexpr int W3_LDS_SLOT = 64 * (256 + 4);        // floats a row-half partner 
 
 // grid (row slabs, groups of four blocks); dynamic LDS: two slots when the last group splits its rows (see the launcher), else none
 // ROWS: X is a table and src_row [M] names the table row of every row of the product (see wgrad_tn3_accumulate); else src_row is not read
-template <int NP, typename TIN = float, bool ROWS = false>
+// TXE: X's element type where it is not dY's (uint16_t under fp32 gradients: a bf16 table)
+template <int NP, typename TIN = float, bool ROWS = false, typename TXE = TIN>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void wgrad_tn3_kernel(
-    const TIN* __restrict__ dY, int64_t ld_dy, const TIN* __restrict__ X, int64_t ld_x, int M, int N, int K, int rows_per_slab, int nb_k,
+    const TIN* __restrict__ dY, int64_t ld_dy, const TXE* __restrict__ X, int64_t ld_x, int M, int N, int K, int rows_per_slab, int nb_k,
     int nb, float* __restrict__ part, float* __restrict__ db_part, const int32_t* __restrict__ src_row) {
     extern __shared__ float w3_lds[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -568,10 +655,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     float* lds = w3_lds + (split ? wave - half_id * in_group : 0) * W3_LDS_SLOT;   // wavefronts w and w + in_group: the same block, one slot
     float* db_out = db_part ? db_part + (int64_t)blockIdx.x * ((N + 3) & ~3) : nullptr;
     const TIN* a = dY + (int64_t)m_first * ld_dy;
-    const TIN* b = ROWS ? X : X + (int64_t)m_first * ld_x;
+    const TXE* b = ROWS ? X : X + (int64_t)m_first * ld_x;
     const int32_t* idx = ROWS ? src_row + m_first : nullptr;
-    if (N - n0 > 64) wgrad_tn3_block<4, NP, TIN, ROWS>(a, ld_dy, b, ld_x, idx, rows, steps, N, K, n0, k0, lane, role, lds, out, db_out);
-    else wgrad_tn3_block<2, NP, TIN, ROWS>(a, ld_dy, b, ld_x, idx, rows, steps, N, K, n0, k0, lane, role, lds, out, db_out);
+    if (N - n0 > 64) wgrad_tn3_block<4, NP, TIN, ROWS, TXE>(a, ld_dy, b, ld_x, idx, rows, steps, N, K, n0, k0, lane, role, lds, out, db_out);
+    else wgrad_tn3_block<2, NP, TIN, ROWS, TXE>(a, ld_dy, b, ld_x, idx, rows, steps, N, K, n0, k0, lane, role, lds, out, db_out);
 }
 
 // Bias gradient beside the fp32-pipe kernels (the bf16x3 kernel takes it from the dY rows it loads anyway): column sums of a row slab,
@@ -632,8 +719,8 @@ static float* wgrad_db_part(float* workspace, int64_t M, int32_t N, int32_t K) {
 // The whole path of one instantiation of the bf16-pipe kernel: slabs, launch, both reductions (the bias partials come from the kernel).
 // ROWS: X is a table (ld_x its row stride) and src_row names its rows; else src_row is not read.  `who` names the entry point's family in
 // the messages.  An instantiation reserves its LDS when it is first used.
-template <int NP, typename TIN, bool ROWS>
-static int wgrad_tn3_run(const char* who, const TIN* dY, int64_t ld_dy, const TIN* X, int64_t ld_x, const int32_t* src_row, int64_t M, int32_t N,
+template <int NP, typename TIN, bool ROWS, typename TXE = TIN>
+static int wgrad_tn3_run(const char* who, const TIN* dY, int64_t ld_dy, const TXE* X, int64_t ld_x, const int32_t* src_row, int64_t M, int32_t N,
                          int32_t K, float* workspace, float* dW, float* db, hipStream_t st) {
     DFOL_REQUIRE(16 * std::max(ld_dy, ld_x) * (int64_t)sizeof(TIN) < (1ll << 31), "%s: row stride too large (%lld)", who, (long long)std::max(ld_dy, ld_x));
     const int nb_k = dfol_cdiv(K, 128), nb = dfol_cdiv(N, 128) * nb_k, groups = dfol_cdiv(nb, 4);
@@ -641,10 +728,10 @@ static int wgrad_tn3_run(const char* who, const TIN* dY, int64_t ld_dy, const TI
     const int rows_per_slab = (dfol_cdiv(M, slabs) + 15) & ~15;         // sixteen rows per MFMA step
     constexpr size_t lds_two = 2 * W3_LDS_SLOT * sizeof(float);
     const size_t lds = nb % 4 == 1 || nb % 4 == 2 ? lds_two : 0;        // the last group splits its rows (two slots)
-    static const hipError_t lds_ok = hipFuncSetAttribute((const void*)wgrad_tn3_kernel<NP, TIN, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_two);
+    static const hipError_t lds_ok = hipFuncSetAttribute((const void*)wgrad_tn3_kernel<NP, TIN, ROWS, TXE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_two);
     DFOL_REQUIRE(lds_ok == hipSuccess, "%s: cannot reserve 130 KB of LDS (%s)", who, hipGetErrorString(lds_ok));
     float* db_part = db ? wgrad_db_part(workspace, M, N, K) : nullptr;
-    hipLaunchKernelGGL((wgrad_tn3_kernel<NP, TIN, ROWS>), dim3(slabs, groups), dim3(256), lds, st, dY, ld_dy, X, ld_x, (int)M, N, K, rows_per_slab, nb_k,
+    hipLaunchKernelGGL((wgrad_tn3_kernel<NP, TIN, ROWS, TXE>), dim3(slabs, groups), dim3(256), lds, st, dY, ld_dy, X, ld_x, (int)M, N, K, rows_per_slab, nb_k,
                        nb, workspace, db_part, src_row);
     DFOL_LAUNCH_CHECK(who);
     if (const int rc = wgrad_reduce(who, "reduce", workspace, slabs, (int64_t)N * K, dW, st)) return rc;
@@ -740,6 +827,31 @@ extern "C" int dfol_linear_wgrad_bias_rows_f32(const float* dY, int64_t ld_dy, c
 extern "C" int dfol_linear_wgrad_bias_rows_bf16(const float* dY, int64_t ld_dy, const float* X_table, int64_t ld_table, const int32_t* src_row,
                                                 int64_t M, int32_t N, int32_t K, float* workspace, float* dW, float* db, void* stream) {
     return wgrad_rows_launch(dY, ld_dy, X_table, ld_table, src_row, M, N, K, workspace, dW, db, stream, true);
+}
+
+// The bf16 mode's weight gradient over the indexed rows of a bf16 TABLE (a feature store built with feature_dtype="bf16"): dY fp32, row r of X
+// is row src_row[r] of X_table_bf16 (ld_table in elements, a multiple of 4: 8-byte rows).  Bit for bit dfol_linear_wgrad_bias_bf16 over the
+// gathered rows widened to fp32; slabs, workspace layout and reductions are that launch path's.
+static const char* wgrad_rows_bf16t_refusal(int32_t N, int32_t K, int64_t ld_dy, int64_t ld_table) {
+    if (const char* why = wgrad_rows_refusal(N, K, ld_dy, ld_table, false)) return why;      // (the bf16 mode never asks for the fp32 pipe)
+    if (ld_table % 4 != 0) return "table rows must be 8-byte aligned (ld_table % 4 == 0)";
+    return nullptr;
+}
+
+extern "C" int dfol_linear_wgrad_rows_bf16t_supported(int32_t N, int32_t K, int64_t ld_dy, int64_t ld_table) {
+    return wgrad_rows_bf16t_refusal(N, K, ld_dy, ld_table) == nullptr;
+}
+
+extern "C" int dfol_linear_wgrad_bias_rows_bf16t(const float* dY, int64_t ld_dy, const void* X_table_bf16, int64_t ld_table, const int32_t* src_row,
+                                                 int64_t M, int32_t N, int32_t K, float* workspace, float* dW, float* db, void* stream) {
+    DFOL_REQUIRE(M > 0 && M < (1ll << 31) && N > 0 && K > 0, "linear_wgrad_rows_bf16t: bad sizes M=%lld N=%d K=%d", (long long)M, N, K);
+    DFOL_REQUIRE(dY && X_table_bf16 && src_row && workspace && dW, "linear_wgrad_rows_bf16t: null pointer");
+    const char* why = wgrad_rows_bf16t_refusal(N, K, ld_dy, ld_table);
+    DFOL_REQUIRE(!why, "linear_wgrad_rows_bf16t: %s (N=%d K=%d ld_dy=%lld ld_table=%lld)", why, N, K, (long long)ld_dy, (long long)ld_table);
+    DFOL_REQUIRE((uintptr_t)dY % 16 == 0, "linear_wgrad_rows_bf16t: dY rows must be 16-byte aligned (dY=%p)", (const void*)dY);
+    DFOL_REQUIRE((uintptr_t)X_table_bf16 % 8 == 0 && (uintptr_t)src_row % 4 == 0, "linear_wgrad_rows_bf16t: the table must be 8-byte and the index 4-byte aligned");
+    return wgrad_tn3_run<1, float, true, uint16_t>("linear_wgrad_rows_bf16t", dY, ld_dy, (const uint16_t*)X_table_bf16, ld_table, src_row, M, N, K, workspace,
+                                                   dW, db, (hipStream_t)stream);
 }
 
 // bf16 mode with bf16 STORAGE of both operands (the per-pair activations dpre2 [M, N] and Z [M, K] as bfloat16, rows 4-byte / 8-byte

@@ -126,6 +126,7 @@ static_assert(DFOL_PAIR_PACKED == 1 && DFOL_PAIR_BF16X3 == 2 && DFOL_PAIR_F16X2 
 // dfol_set_feature_rows: the index form of the NEXT dfol_run_program's scene on this thread
 thread_local const int32_t* g_feature_src_row = nullptr;
 thread_local const float* g_feature_box6 = nullptr;
+thread_local bool g_feature_rows_bf16 = false;                       // dfol_set_feature_rows_bf16: scene->features is a bf16 table
 // dfol_set_feature_cache: the cached form of the same (the featurizer's outputs instead of its inputs)
 struct FeatureCache {
     const float* cache;
@@ -149,6 +150,15 @@ extern "C" int dfol_set_feature_rows(const int32_t* src_row, const float* box6) 
     DFOL_REQUIRE((src_row == nullptr) == (box6 == nullptr), "set_feature_rows: src_row and box6 come together");
     g_feature_src_row = src_row;
     g_feature_box6 = box6;
+    g_feature_rows_bf16 = false;
+    return 0;
+}
+
+extern "C" int dfol_set_feature_rows_bf16(const int32_t* src_row, const float* box6) {
+    DFOL_REQUIRE((src_row == nullptr) == (box6 == nullptr), "set_feature_rows_bf16: src_row and box6 come together");
+    g_feature_src_row = src_row;
+    g_feature_box6 = box6;
+    g_feature_rows_bf16 = src_row != nullptr;
     return 0;
 }
 
@@ -158,8 +168,10 @@ extern "C" int dfol_run_program(const DfolProgramModel* model, const DfolProgram
                                 const void* blob, void* workspace, void* stream) {
     const int32_t* src_row = g_feature_src_row;                      // (taken and cleared first: an early return must not leave it to the next batch)
     const float* box6 = g_feature_box6;
+    const bool rows_bf16 = g_feature_rows_bf16;
     g_feature_src_row = nullptr;
     g_feature_box6 = nullptr;
+    g_feature_rows_bf16 = false;
     const FeatureCache cached = g_feature_cache;
     g_feature_cache = FeatureCache{nullptr, 0, 0, nullptr, nullptr};
     DFOL_REQUIRE(model && scene && instr_host && blob && workspace, "run_program: null pointer");
@@ -183,6 +195,16 @@ extern "C" int dfol_run_program(const DfolProgramModel* model, const DfolProgram
                 if (a[9]) layer.act = DFOL_ACT_NONE;
                 if (a[3] == 0 && src_row != nullptr) {              // the scene in index form: the featurizer's first product reads the store's rows
                     const int32_t M = static_cast<int32_t>(a[8]);
+                    if (rows_bf16) {                                // a bf16 table: the bf16 mode's product over its rows, the matrix route's bits
+                        DFOL_REQUIRE(a[4] == 0 && layer.kind == DFOL_DENSE_BF16 && layer.packed != nullptr &&
+                                         dfol_linear_rows_bf16t_supported(layer.N, layer.K, scene->ld_features),
+                                     "run_program[%d]: a scene in bf16 index form (dfol_set_feature_rows_bf16) needs a DFOL_DENSE_BF16 first layer of a shape "
+                                     "dfol_linear_rows_bf16t_supported takes (N %d K %d ld %lld kind %d): hand over the gathered matrix", i, layer.N, layer.K,
+                                     (long long)scene->ld_features, layer.kind);
+                        rc = dfol_linear_act_rows_bf16t_f32(scene->features, scene->ld_features, src_row, layer.packed, layer.bias,
+                                                            static_cast<float*>(at(workspace, a[6])), a[7], M, layer.N, layer.K, layer.act, stream);
+                        break;
+                    }
                     DFOL_REQUIRE(a[4] == 0 && layer.kind == DFOL_DENSE_F16X2 && layer.packed != nullptr && dfol_linear_wide_supported(M, layer.N, layer.K),
                                  "run_program[%d]: a scene in index form (dfol_set_feature_rows) needs a two-piece fp16 product of a shape "
                                  "dfol_linear_wide_supported takes (M %d N %d K %d kind %d): hand over the gathered matrix", i, M, layer.N, layer.K, layer.kind);

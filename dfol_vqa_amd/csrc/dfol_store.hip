@@ -14,7 +14,12 @@
 //
 // The cached form (a `featurized` store): the batch's object matrix [O, W + 4] from the cached OUTPUT of a frozen featurizer for every table
 // row - the indexed rows of the cache beside their box positions, one launch instead of the featurizer's products (store_objects_kernel).
+//
+// The bf16 form (a store built with feature_dtype="bf16"): the table holds every feature rounded to bfloat16 by dfol_rne2 - the rounding the
+// bf16 mode's first product and weight gradient apply to an fp32 feature anyway (round_bf16_kernel, at upload) - and the gather widens the
+// stored values exactly to the same [O, F + 6] fp32 matrix (gather_object_rows_bf16_kernel); boxes and sizes stay fp32.
 #include "dfol_common.h"
+#include "dfol_split.h"
 
 namespace {
 
@@ -84,6 +89,69 @@ __global__ __launch_bounds__(ST_WAVES * 64) void gather_object_rows_kernel(const
                 v = b[lane - 2] - b[lane - 4];
             dst[F + lane] = v;
         }
+    }
+}
+
+// The bf16 table's row: n4 8-byte pieces (four bf16) widened exactly to 16 bytes of fp32 each, four loads in flight per lane as st_copy_row
+template <int SW>
+__device__ __forceinline__ void st_widen_row(const u32x2* __restrict__ src, float* __restrict__ dst, int n4, int lane) {
+    int c = lane;
+    for (; c + 192 < n4; c += 256) {
+        const u32x2 a = src[c], b = src[c + 64], e = src[c + 128], f = src[c + 192];
+        st_store<SW>(dst + 4 * c, dfol_widen(a));
+        st_store<SW>(dst + 4 * (c + 64), dfol_widen(b));
+        st_store<SW>(dst + 4 * (c + 128), dfol_widen(e));
+        st_store<SW>(dst + 4 * (c + 192), dfol_widen(f));
+    }
+    for (; c < n4; c += 64) st_store<SW>(dst + 4 * c, dfol_widen(src[c]));
+}
+
+// gather_object_rows_kernel over a bf16 table (F % 4 == 0, rows 8-byte aligned): same grid, same output rows, same box columns
+__global__ __launch_bounds__(ST_WAVES * 64) void gather_object_rows_bf16_kernel(const uint16_t* __restrict__ feats, const float* __restrict__ boxes,
+                                                                                const float* __restrict__ sizes, const int32_t* __restrict__ slot,
+                                                                                const int32_t* __restrict__ obj_off, int max_obj, int F,
+                                                                                float* __restrict__ out, int64_t ld_out) {
+    const int i = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int first = obj_off[i];
+    const int n = min(obj_off[i + 1] - first, max_obj);
+    const int s = slot[i];
+    const int64_t img = (int64_t)s * max_obj;
+    for (int j = blockIdx.y * ST_WAVES + wave; j < n; j += gridDim.y * ST_WAVES) {
+        const u32x2* src = reinterpret_cast<const u32x2*>(feats + (img + j) * F);
+        float* dst = out + (int64_t)(first + j) * ld_out;
+        const unsigned mis = (unsigned)(reinterpret_cast<uintptr_t>(dst) & 15);
+        if (mis == 0)
+            st_widen_row<4>(src, dst, F >> 2, lane);
+        else if (mis == 8)
+            st_widen_row<2>(src, dst, F >> 2, lane);
+        else
+            st_widen_row<1>(src, dst, F >> 2, lane);
+        if (lane < 6) {                                              // (the fp32 gather's six columns by its own subtractions)
+            const float* b = boxes + (img + j) * 4;
+            float v;
+            if (lane < 2)
+                v = sizes[2 * (int64_t)s + lane];
+            else if (lane < 4)
+                v = b[lane - 2];
+            else
+                v = b[lane - 2] - b[lane - 4];
+            dst[F + lane] = v;
+        }
+    }
+}
+
+// dst[i] = bf16(src[i]), round to nearest even by dfol_rne2 - the dense kernels' own rounding; a thread takes two elements (one 4-byte store),
+// the last thread of an odd count one
+constexpr int RB_THREADS = 256;
+
+__global__ __launch_bounds__(RB_THREADS) void round_bf16_kernel(const float* __restrict__ src, int64_t n, uint16_t* __restrict__ dst) {
+    const int64_t step = (int64_t)gridDim.x * RB_THREADS;
+    for (int64_t p = (int64_t)blockIdx.x * RB_THREADS + threadIdx.x; 2 * p < n; p += step) {
+        const int64_t e = 2 * p;
+        if (e + 1 < n)
+            *reinterpret_cast<uint32_t*>(dst + e) = dfol_rne2(src[e], src[e + 1]);
+        else
+            dst[e] = (uint16_t)dfol_rne2(src[e], 0.f);
     }
 }
 
@@ -186,6 +254,37 @@ extern "C" int dfol_store_rows_f32(const float* store_boxes, const float* store_
     hipLaunchKernelGGL(store_rows_kernel, dim3(I, slices), dim3(SR_THREADS), 0, (hipStream_t)stream, store_boxes, store_sizes, slot, obj_off, max_obj,
                        src_row, box6);
     DFOL_LAUNCH_CHECK("store_rows");
+    return 0;
+}
+
+extern "C" int dfol_store_round_bf16(const float* src, int64_t n, void* dst, void* stream) {
+    DFOL_REQUIRE(n >= 0, "store_round_bf16: bad size n=%lld", (long long)n);
+    if (n == 0) return 0;
+    DFOL_REQUIRE(src && dst, "store_round_bf16: null pointer");
+    DFOL_REQUIRE((uintptr_t)src % 4 == 0 && (uintptr_t)dst % 4 == 0, "store_round_bf16: src and dst must be 4-byte aligned");
+    int64_t blocks = ((n + 1) / 2 + RB_THREADS - 1) / RB_THREADS;
+    blocks = blocks < 8192 ? blocks : 8192;
+    hipLaunchKernelGGL(round_bf16_kernel, dim3((unsigned)blocks), dim3(RB_THREADS), 0, (hipStream_t)stream, src, n, static_cast<uint16_t*>(dst));
+    DFOL_LAUNCH_CHECK("store_round_bf16");
+    return 0;
+}
+
+extern "C" int dfol_gather_object_rows_bf16_f32(const void* store_features_bf16, const float* store_boxes, const float* store_sizes, const int32_t* slot,
+                                                const int32_t* obj_off, int32_t I, int32_t max_obj, int32_t F, float* out, int64_t ld_out,
+                                                void* stream) {
+    DFOL_REQUIRE(I >= 0 && F > 0 && max_obj > 0, "gather_object_rows_bf16: bad sizes I=%d max_obj=%d F=%d", I, max_obj, F);
+    DFOL_REQUIRE(F % 4 == 0, "gather_object_rows_bf16: F=%d must be a multiple of 4 (8-byte rows of bfloat16)", F);
+    DFOL_REQUIRE(ld_out >= (int64_t)F + 6, "gather_object_rows_bf16: ld_out=%lld is less than F + 6 = %d", (long long)ld_out, F + 6);
+    if (I == 0) return 0;
+    DFOL_REQUIRE(store_features_bf16 && store_boxes && store_sizes && slot && obj_off && out, "gather_object_rows_bf16: null pointer");
+    DFOL_REQUIRE((uintptr_t)store_features_bf16 % 8 == 0, "gather_object_rows_bf16: the table must be 8-byte aligned");
+    const int rows = dfol_cdiv(max_obj, ST_WAVES);
+    int slices = dfol_cdiv(ST_TARGET_WAVES / ST_WAVES, I);
+    slices = slices < rows ? slices : rows;
+    slices = slices < 65535 ? slices : 65535;
+    hipLaunchKernelGGL(gather_object_rows_bf16_kernel, dim3(I, slices), dim3(ST_WAVES * 64), 0, (hipStream_t)stream,
+                       static_cast<const uint16_t*>(store_features_bf16), store_boxes, store_sizes, slot, obj_off, max_obj, F, out, ld_out);
+    DFOL_LAUNCH_CHECK("gather_object_rows_bf16");
     return 0;
 }
 

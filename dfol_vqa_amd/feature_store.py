@@ -15,6 +15,12 @@ A store built with `featurized=True` (which implies the index form) also keeps t
 (dfol_store_objects_f32) and no featurizer product runs per batch.  The cache is keyed by the network's weight versions; `release_raw()`
 then frees the raw features (a quarter of the memory is left at 2048 -> 512).
 
+A store built with `feature_dtype="bf16"` (which implies the index form too) holds its features as bfloat16, each rounded to nearest even by the
+dense kernels' own rounding (dfol_store_round_bf16): half the memory.  In the bf16 arithmetic (`mlp_math: bf16`) the featurizer's first product
+and its weight gradient round every feature that way before they multiply, so there they read the table in place (dfol_linear_act_rows_bf16t_f32,
+dfol_linear_wgrad_bias_rows_bf16t) and no result bit changes; every other consumer gets the `[O, F + 6]` fp32 matrix of the ROUNDED features
+(dfol_gather_object_rows_bf16_f32) - reduced precision outside the bf16 arithmetic, never a default.
+
 Three kinds of object, by who may hold them:
   DeviceFeatureStore   main process only: the device tensors, `gather`.  Registers itself by id in this process' table.
   FeatureStoreIndex    `store.index`: host-only and picklable, image id -> (slot or -1, object count).  This is what a collator - and so
@@ -162,7 +168,7 @@ def _array_shape(path, arrays, name):
 class StoreLayout(object):
     """The host half of building a store: the chunk files' shapes (read from their headers, no array is loaded) and the info JSON."""
 
-    def __init__(self, object_h5_path, file_prefix, chunk_num, object_info_json_path):
+    def __init__(self, object_h5_path, file_prefix, chunk_num, object_info_json_path, feature_itemsize=4):
         from .data import _open_arrays
         with open(object_info_json_path, "r") as f:
             self.info = json.load(f)
@@ -176,7 +182,8 @@ class StoreLayout(object):
         self.max_obj, self.F = self.shapes[0][1:]
         if any(s[1:] != (self.max_obj, self.F) for s in self.shapes):
             raise _lib.DfolError("feature store: chunk files of different [max_obj, F]: %s" % sorted(set(s[1:] for s in self.shapes)))
-        self.row_bytes = 4 * (self.max_obj * self.F + self.max_obj * 4 + 2)          # features, boxes and (W, H) of one image
+        self.feature_row_bytes = int(feature_itemsize) * self.max_obj * self.F         # (4: fp32 features; 2: a bf16 store's)
+        self.row_bytes = self.feature_row_bytes + 4 * (self.max_obj * 4 + 2)           # features, boxes and (W, H) of one image
         self.chunk_bytes = [s[0] * self.row_bytes for s in self.shapes]
 
     def index(self, store_id, max_bytes=None):
@@ -218,16 +225,30 @@ class DeviceFeatureStore(object):
 
     featurized=True (opt-in; implies direct=True): the store also caches a frozen featurizer's output for every row of its table - `featurize`,
     `cached_for` - and a batch whose featurizer does not train gets its object matrix from the cache (`StoreRows.objects`); `release_raw()` then
-    frees the raw features."""
+    frees the raw features.
 
-    def __init__(self, object_h5_path, file_prefix, chunk_num, object_info_json_path, device, max_bytes=None, direct=False, featurized=False):
+    feature_dtype="bf16" (opt-in; implies direct=True; "f32" is the default): `features` is bfloat16 - every feature rounded to nearest even on
+    the device, chunk by chunk (one fp32 chunk of extra memory while the store is built) - and `nbytes`, max_bytes and the free-memory check
+    count the bytes actually held.  F must be a multiple of 4 (8-byte rows).  Under `mlp_math: bf16` the featurizer's first layer reads the
+    table in place, forward and weight gradient, with the fp32 store's bits; every other arithmetic and consumer gets the gathered matrix of the
+    rounded features.  Not with featurized=True: a cache over a bf16 table is not built."""
+
+    def __init__(self, object_h5_path, file_prefix, chunk_num, object_info_json_path, device, max_bytes=None, direct=False, featurized=False,
+                 feature_dtype="f32"):
         from .data import _open_arrays
+        if feature_dtype not in ("f32", "bf16"):
+            raise _lib.DfolError("feature store: feature_dtype must be 'f32' or 'bf16', got %r" % (feature_dtype,))
+        bf16 = feature_dtype == "bf16"
+        if bf16 and featurized:
+            raise _lib.DfolError("feature store: feature_dtype='bf16' with featurized=True: a cache of featurizer rows over a bf16 table is not built")
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.DfolError("a feature store lives on a GPU (got device %s)" % (device,))
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
-        lay = StoreLayout(object_h5_path, file_prefix, chunk_num, object_info_json_path)
+        lay = StoreLayout(object_h5_path, file_prefix, chunk_num, object_info_json_path, feature_itemsize=2 if bf16 else 4)
+        if bf16 and lay.F % 4 != 0:
+            raise _lib.DfolError("feature store: feature_dtype='bf16' needs F %% 4 == 0 (8-byte rows of bfloat16), the chunk files have F = %d" % lay.F)
         if max_bytes is None:
             need, free = sum(lay.chunk_bytes), int(torch.cuda.mem_get_info(self.device)[0])
             if need > 0.8 * free:
@@ -236,18 +257,24 @@ class DeviceFeatureStore(object):
         self.id = uuid.uuid4().hex
         self.index, sizes, base = lay.index(self.id, max_bytes)
         S, max_obj, F = int(base[-1]), lay.max_obj, lay.F
-        self.features = torch.empty((S, max_obj, F), dtype=torch.float32, device=self.device)
+        self.features = torch.empty((S, max_obj, F), dtype=torch.bfloat16 if bf16 else torch.float32, device=self.device)
         self.boxes = torch.empty((S, max_obj, 4), dtype=torch.float32, device=self.device)
         for c in range(len(base) - 1):             # one chunk on the host at a time
             arrays = _open_arrays(lay.paths[c])
-            self.features[base[c]:base[c + 1]].copy_(torch.from_numpy(np.ascontiguousarray(arrays["features"][...], np.float32)))
+            chunk = torch.from_numpy(np.ascontiguousarray(arrays["features"][...], np.float32))
+            if bf16:                               # through one fp32 chunk on the device, rounded into the table's slice by the kernels' own rule
+                with torch.cuda.device(self.device):
+                    _lib.store_round_bf16(chunk.to(self.device), self.features[base[c]:base[c + 1]])
+            else:
+                self.features[base[c]:base[c + 1]].copy_(chunk)
             self.boxes[base[c]:base[c + 1]].copy_(torch.from_numpy(np.ascontiguousarray(arrays["bboxes"][...], np.float32)))
             if hasattr(arrays, "close"):
                 arrays.close()
         self.sizes = torch.from_numpy(sizes).to(self.device)
         self.S, self.max_obj, self.F = S, max_obj, F
         self.featurized = bool(featurized)
-        self.direct = bool(direct) or self.featurized
+        self.feature_dtype = feature_dtype
+        self.direct = bool(direct) or self.featurized or bf16
         self._featurized = FeaturizedRows()
         self.cache_nbytes = 0                              # (the cache of featurize(), beside `nbytes` of chunk data)
         if self.direct:
@@ -324,6 +351,8 @@ class DeviceFeatureStore(object):
             raise _lib.DfolError("feature store: featurize(): nn.%r of the featurizer network is in training mode: its rows differ from step to "
                                  "step and cannot be cached; put the featurizer in eval() (or use dropout: 0)" % (drop,))
         self._featurized.need_raw("featurize() for new featurizer weights")
+        if self.features.dtype != torch.float32:
+            raise _lib.DfolError("feature store: featurize(): a cache of featurizer rows over a bf16 table (feature_dtype='bf16') is not built")
         layers, why = store_layers_of(net, self.F, FEATURIZE_BLOCK_ROWS)
         if layers is None:
             raise _lib.DfolError("feature store: featurize(): %s" % why)
@@ -366,7 +395,7 @@ class DeviceFeatureStore(object):
         DfolError naming this call."""
         self._featurized.release_raw()
         if self.features is not None:
-            self.nbytes -= self.features.numel() * 4
+            self.nbytes -= self.features.numel() * self.features.element_size()
             self.features = None
         return self
 
@@ -402,6 +431,7 @@ class StoreRows(object):
     def __init__(self, store, src_row, box6, index, parent=None, picked=None):
         self.store, self.src_row, self.box6 = store, src_row, box6
         self.table = None if store.features is None else store.features.view(store.S * store.max_obj, store.F)      # (None: release_raw())
+        self.bf16_ld = int(self.table.stride(0)) if self.table is not None and self.table.dtype == torch.bfloat16 else None     # a bf16 table's row stride
         self.O = int(src_row.numel())
         self._index = index                                # device [slot (I) | obj_off (I + 1)] of the ref, or None: a selection of `parent`'s rows
         self._parent, self._picked = parent, picked

@@ -46,23 +46,30 @@ def active_dropout(net):
     return None
 
 
-def store_layers_of(net, F, M):
+def store_layers_of(net, F, M, bf16_ld=None):
     """-> (the featurizer network's layers [(Linear, activation)], None) when its first product can read M rows of a feature store of width F in
     place - the two-piece fp16 arithmetic on a weight of the split kernels' size, the store's width, a shape the wide kernel takes and pays for
     (dfol_linear_wide_supported) - else (None, why not).  ONE predicate for the direct route (M = the batch's rows), the executor and the store's
-    cache builder (M = its row block)."""
+    cache builder (M = its row block).  bf16_ld: the store's table is bfloat16 with this row stride (feature_dtype="bf16") - then the question is
+    the bf16 arithmetic's: `mlp_math: bf16`, whose first product rounds a feature to the value the table holds, on a weight of the split
+    kernels' size, any M (dfol_linear_rows_bf16t_supported)."""
     from . import _lib, native_exec
     if net is None or getattr(net, "_network", None) is None or not hasattr(net, "output_width"):
         return None, "the featurizer has no network"
     layers = native_exec._layers(net._network)
     if not layers:
         return None, "the featurizer network is not a chain of Linear layers and activations (or a Dropout is active)"
-    if _lib._dense_math() != "f16x2":
-        return None, "the dense arithmetic is %r, not 'f16x2'" % _lib._dense_math()
+    want = "f16x2" if bf16_ld is None else "bf16"
+    if _lib._dense_math() != want:
+        return None, "the dense arithmetic is %r, not %r" % (_lib._dense_math(), want)
     w = layers[0][0].weight
     N, K = w.shape
     if K != F:
         return None, "the featurizer's first layer takes %d features, the store holds %d" % (K, F)
+    if bf16_ld is not None:
+        if N * K < _lib.SPLIT_MIN_WEIGHT or w.stride(1) != 1 or not _lib.linear_rows_bf16t_supported(N, K, bf16_ld):
+            return None, "the bf16 mode's tiled kernel does not take a %d -> %d product over a bf16 table of row stride %d" % (K, N, bf16_ld)
+        return layers, None
     if N * K < _lib.SPLIT_MIN_WEIGHT or w.stride(1) != 1 or not _lib.linear_wide_supported(M, N, K):
         return None, "the wide kernel does not take a %d -> %d product over %d rows" % (K, N, M)
     return layers, None
@@ -86,7 +93,7 @@ class BatchGQABoxFeaturizer(nn.Module):
         net = self._featurizer_network
         if rows.O == 0 or (net is not None and featurizer_trains(net)):
             return None
-        return store_layers_of(net, rows.store.F, rows.O)[0]
+        return store_layers_of(net, rows.store.F, rows.O, getattr(rows, "bf16_ld", None))[0]
 
     def _store_train_layers(self, rows):
         """The same layers when the featurizer TRAINS and its first layer can run as visual_oracle.StoreRowsLinear: forward as on the inference
@@ -96,11 +103,11 @@ class BatchGQABoxFeaturizer(nn.Module):
         net = self._featurizer_network
         if rows.O == 0 or rows.table is None or net is None or not featurizer_trains(net) or active_dropout(net) is not None:
             return None
-        layers = store_layers_of(net, rows.store.F, rows.O)[0]
+        layers = store_layers_of(net, rows.store.F, rows.O, getattr(rows, "bf16_ld", None))[0]
         if layers is None:
             return None
         N, K = layers[0][0].weight.shape
-        return layers if _lib.linear_wgrad_rows_supported(N, K, N, rows.table.stride(0)) else None
+        return layers if _lib.linear_wgrad_rows_supported(N, K, N, rows.table.stride(0), bf16_table=getattr(rows, "bf16_ld", None) is not None) else None
 
     def _cached_objects(self, rows):
         """The object matrix of a `featurized` store's batch from the store's cached featurizer rows (feature_store.DeviceFeatureStore.featurize:
@@ -131,9 +138,10 @@ class BatchGQABoxFeaturizer(nn.Module):
                 D = net.output_width() + 4
                 obj = torch.empty(rows.O, D, dtype=torch.float32, device=device)
                 x = None
+                first = _lib.linear_wide_rows if getattr(rows, "bf16_ld", None) is None else _lib.linear_rows_bf16t       # (a bf16 table: the bf16 mode's product)
                 for k, (lin, act) in enumerate(layers):
                     out = obj[:, :D - 4] if k == len(layers) - 1 else None
-                    x = _lib.linear_wide_rows(rows.table, rows.src_row, lin.weight, lin.bias, act, out) if k == 0 else \
+                    x = first(rows.table, rows.src_row, lin.weight, lin.bias, act, out) if k == 0 else \
                         L.linear_act(x, lin.weight, lin.bias, act, out)
                 L.box_positions(rows.box6, obj, D - 4)
                 _lib.note("feature_store_direct")

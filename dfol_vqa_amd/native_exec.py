@@ -289,9 +289,19 @@ def run(model, program_batch, plan, queue, give_answer=True):
     elif hasattr(feats, "materialize"):
         # A direct feature store's batch (feature_store.StoreRows).  The plan is lowered as for any batch; where the featurizer's first product
         # is one the wide kernel takes - the question BatchGQABoxFeaturizer._store_layers asks - the executor reads the store's rows in place
-        # (dfol_set_feature_rows), otherwise it gets the gathered matrix.
+        # (dfol_set_feature_rows), otherwise it gets the gathered matrix.  A bf16 store's batch likewise where the model's first featurizer layer
+        # is the bf16 mode's and store_layers_of admits it (dfol_set_feature_rows_bf16).
         first = nm.struct.featurizer[0]
-        if feats.O and first.kind == DENSE_F16X2 and first.K == feats.store.F and _lib.linear_wide_supported(feats.O, first.N, first.K):
+        if getattr(feats, "bf16_ld", None) is not None:
+            from .interpreter import store_layers_of
+            if feats.O and first.kind == DENSE_BF16 and \
+                    store_layers_of(model._featurizer._featurizer_network, feats.store.F, feats.O, feats.bf16_ld)[0] is not None:
+                rows = feats
+                _lib.note("feature_store_direct")
+            else:
+                feats = feats.materialize()
+                _lib.note("feature_store_direct_materialized")
+        elif feats.O and first.kind == DENSE_F16X2 and first.K == feats.store.F and _lib.linear_wide_supported(feats.O, first.N, first.K):
             rows = feats
             _lib.note("feature_store_direct")
         else:
@@ -315,7 +325,8 @@ def run(model, program_batch, plan, queue, give_answer=True):
         _lib.call("dfol_set_feature_cache", cache.data_ptr(), cache.stride(0), cache.shape[1], rows.src_row.data_ptr(), rows.box6.data_ptr())
     elif rows is not None:
         sc.features, sc.ld_features, sc.raw_cols, sc.O = rows.table.data_ptr(), rows.table.stride(0), rows.shape[1], plan.scene["O"]
-        _lib.call("dfol_set_feature_rows", rows.src_row.data_ptr(), rows.box6.data_ptr())        # (picked up, and cleared, by the call below)
+        _lib.call("dfol_set_feature_rows" if getattr(rows, "bf16_ld", None) is None else "dfol_set_feature_rows_bf16", rows.src_row.data_ptr(),
+                  rows.box6.data_ptr())                                                            # (picked up, and cleared, by the call below)
     else:
         sc.features, sc.ld_features, sc.raw_cols, sc.O = feats.data_ptr(), feats.stride(0), feats.shape[1], plan.scene["O"]
     sc.NS, sc.max_n = plan.scene["NS"], plan.scene["max_n"]

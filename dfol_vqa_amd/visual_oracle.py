@@ -83,7 +83,8 @@ class RegularMLP(nn.Module):
 
 class StoreRowsLinear(torch.autograd.Function):
     """y = act(table[src_row] W^T + b), the featurizer's first layer over a direct feature store's rows (feature_store.StoreRows), when it
-    TRAINS.  Forward: the inference route's product (linear_wide_rows).  Backward: the activation's backward as the trained dense layer does it
+    TRAINS.  Forward: the inference route's product (linear_wide_rows; over a bf16 store's table linear_rows_bf16t, and linear_wgrad_rows picks
+    the bf16-table entry point from the table's dtype likewise).  Backward: the activation's backward as the trained dense layer does it
     (torch_ops._linear_backward), then dW, db = linear_wgrad_rows: the weight-gradient kernel forms an X row's address through src_row and is
     otherwise the matrix kernel, so every result has the bits of the dense layer over the materialised matrix.  The features are data: no
     gradient for the table.  Saved: y, src_row and the table's handle - never an [O, F] matrix."""
@@ -91,7 +92,8 @@ class StoreRowsLinear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weight, bias, table, src_row, act):
         w = weight.detach()
-        y = _lib.linear_wide_rows(table, src_row, w, None if bias is None else bias.detach(), act)
+        product = _lib.linear_rows_bf16t if table.dtype == torch.bfloat16 else _lib.linear_wide_rows
+        y = product(table, src_row, w, None if bias is None else bias.detach(), act)
         ctx.save_for_backward(y, src_row, table)
         ctx.act, ctx.has_bias, ctx.math = act, bias is not None, _lib._dense_math()
         return y

@@ -48,7 +48,9 @@ extern "C" {
  * batch: dfol_store_rows_f32, dfol_linear_wide_rows_h2_f32 and dfol_set_feature_rows (no struct and no instruction table changes for it), and
  * its cached form: dfol_store_objects_f32 and dfol_set_feature_cache (likewise), and the dropout training route: dfol_dropout_advance,
  * dfol_dropout_f32 and dfol_pair_features_bwd_f32, and the train step's weight gradient over the store's rows: dfol_linear_wgrad_rows_supported,
- * dfol_linear_wgrad_bias_rows_f32 and dfol_linear_wgrad_bias_rows_bf16;
+ * dfol_linear_wgrad_bias_rows_f32 and dfol_linear_wgrad_bias_rows_bf16, and the bf16 form of the store: dfol_store_round_bf16,
+ * dfol_gather_object_rows_bf16_f32, dfol_linear_rows_bf16t_supported, dfol_linear_act_rows_bf16t_f32, dfol_linear_wgrad_rows_bf16t_supported,
+ * dfol_linear_wgrad_bias_rows_bf16t and dfol_set_feature_rows_bf16;
  * a caller that needs them checks for the symbol, and a table that names an opcode an older library lacks is refused by it ("unknown opcode"). */
 #define DFOL_ABI_VERSION 3
 
@@ -224,6 +226,15 @@ int dfol_gather_rows_f32(const float* src, const int32_t* idx, int32_t P, int32_
 int dfol_gather_object_rows_f32(const float* store_features, const float* store_boxes, const float* store_sizes, const int32_t* slot,
                                 const int32_t* obj_off, int32_t I, int32_t max_obj, int32_t F, float* out, int64_t ld_out, void* stream);
 
+/* The bf16 form of the store (feature_dtype="bf16"): store_features holds every feature rounded to bfloat16, to nearest even - the rounding
+ * dfol_linear_act_bf16_f32 and dfol_linear_wgrad_bias_bf16 apply to an fp32 feature before they multiply, so the bf16 mode loses nothing.
+ *   dfol_store_round_bf16: dst[i] = bf16(src[i]), 0 <= i < n; src fp32, dst bfloat16, both 4-byte aligned device pointers (the upload's step).
+ *   dfol_gather_object_rows_bf16_f32: dfol_gather_object_rows_f32 over such a table - the stored values widened exactly to fp32, the six
+ *   box columns by the same subtractions; F % 4 == 0 and an 8-byte aligned table (refused otherwise). */
+int dfol_store_round_bf16(const float* src, int64_t n, void* dst, void* stream);
+int dfol_gather_object_rows_bf16_f32(const void* store_features_bf16, const float* store_boxes, const float* store_sizes, const int32_t* slot,
+                                     const int32_t* obj_off, int32_t I, int32_t max_obj, int32_t F, float* out, int64_t ld_out, void* stream);
+
 /* The same batch in INDEX form (a store built with direct=True): instead of the matrix, which of the store's rows it is made of, for a consumer
  * that reads the store's [S * max_obj, F] table itself (dfol_linear_wide_rows_h2_f32) - 28 bytes per object instead of 4 (F + 6).
  *   src_row [O] int32  src_row[obj_off[i] + j] = slot[i] * max_obj + j                                0 <= j < obj_off[i + 1] - obj_off[i]
@@ -330,6 +341,14 @@ int dfol_linear_act_bf16_f32(const float* X, int64_t ldx, const void* W_bf16, co
  * (Z -> pre2 and dpre2 -> dZ), which are 14 of the 17 GB an fp32-storage step moves. */
 int dfol_linear_act_bf16_bf16(const void* X_bf16, int64_t ldx, const void* W_bf16, const float* bias, void* Y_bf16, int64_t ldy, int32_t M,
                               int32_t N, int32_t K, int32_t act, void* stream);
+/* The bf16 mode over the INDEXED rows of a bf16 table (a feature store built with feature_dtype="bf16"): Y[r] = act(X_table[src_row[r]] W^T + b),
+ * X_table rows of bfloat16 (ld_table in elements; K % 4 == 0, ld_table % 4 == 0 and >= K, table 8-byte aligned), src_row [M] int32 as
+ * dfol_store_rows_f32 writes it (every entry a row of the table - not checked, a device array), W_bf16 from dfol_linear_pack_w_bf16, fp32 Y.
+ * Bit for bit dfol_linear_act_bf16_f32 over the gathered rows widened to fp32, for a table of dfol_store_round_bf16 values.  The tiled
+ * kernel, any M (M == 0 returns without a launch); dfol_linear_rows_bf16t_supported is the predicate (1 / 0) of the sizes and strides. */
+int dfol_linear_rows_bf16t_supported(int32_t N, int32_t K, int64_t ld_table);
+int dfol_linear_act_rows_bf16t_f32(const void* X_table_bf16, int64_t ld_table, const int32_t* src_row, const void* W_bf16, const float* bias, float* Y,
+                                   int64_t ldy, int32_t M, int32_t N, int32_t K, int32_t act, void* stream);
 
 
 /* Box positional features: replaces batch_gqa_boxfeatures_pipeline.py:208-211.
@@ -712,6 +731,12 @@ int dfol_linear_wgrad_bias_rows_f32(const float* dY, int64_t ld_dy, const float*
                                     int32_t N, int32_t K, float* workspace, float* dW, float* db, void* stream);
 int dfol_linear_wgrad_bias_rows_bf16(const float* dY, int64_t ld_dy, const float* X_table, int64_t ld_table, const int32_t* src_row, int64_t M,
                                      int32_t N, int32_t K, float* workspace, float* dW, float* db, void* stream);
+/* ... over the indexed rows of a bf16 TABLE (feature_dtype="bf16"; ld_table in elements, a multiple of 4, table 8-byte aligned): dY fp32,
+ * rounded as by dfol_linear_wgrad_bias_bf16, the bias sums from the fp32 values; bit for bit that entry point over the gathered rows widened
+ * to fp32.  The other conditions are dfol_linear_wgrad_rows_supported's, but for DFOL_WGRAD_MATH, which the bf16 mode does not read. */
+int dfol_linear_wgrad_rows_bf16t_supported(int32_t N, int32_t K, int64_t ld_dy, int64_t ld_table);
+int dfol_linear_wgrad_bias_rows_bf16t(const float* dY, int64_t ld_dy, const void* X_table_bf16, int64_t ld_table, const int32_t* src_row, int64_t M,
+                                      int32_t N, int32_t K, float* workspace, float* dW, float* db, void* stream);
 /* ... with both operands STORED as bfloat16 (dpre2 [M, N] and Z [M, K] of the bf16 mode; ld in elements, multiples of 4; N, K multiples
  * of 4): no rounding left to do, one product, fp32 accumulation, fp32 dW and db.  Same workspace. */
 int dfol_linear_wgrad_bias_bf16_bf16(const void* dY_bf16, int64_t ld_dy, const void* X_bf16, int64_t ld_x, int64_t M, int32_t N, int32_t K,
@@ -948,6 +973,10 @@ int dfol_calib_walk_supported(int32_t KX, int32_t H); /* 1 / 0: DFOL_OP_CALIB_WA
  * must be a DFOL_DENSE_F16X2 layer of a shape dfol_linear_wide_supported(O, N, K) takes: the caller asks that first and hands over the gathered
  * matrix otherwise; any other source-0 product is refused - and DFOL_OP_BOX_POSITIONS reads box6.  Plans are lowered as ever. */
 int dfol_set_feature_rows(const int32_t* src_row, const float* box6);
+/* The same for a bf16 table (feature_dtype="bf16"): scene->features points at rows of bfloat16 and ld_features counts elements.  The source-0
+ * DFOL_OP_DENSE runs dfol_linear_act_rows_bf16t_f32 - it must be a DFOL_DENSE_BF16 layer that dfol_linear_rows_bf16t_supported takes; any other
+ * layer kind is refused - and DFOL_OP_BOX_POSITIONS reads box6.  Either setting replaces the other. */
+int dfol_set_feature_rows_bf16(const int32_t* src_row, const float* box6);
 /* The same for a scene whose featurizer output is CACHED (a frozen featurizer; dfol_store_objects_f32): the NEXT dfol_run_program of the calling
  * thread runs no featurizer product - every DFOL_OP_DENSE of set 0 is skipped, scene->features is not read and may be NULL - and its
  * DFOL_OP_BOX_POSITIONS writes the whole object matrix: cache rows src_row [O] of cache [rows, ld_cache] (W = the instruction's pos_col columns,

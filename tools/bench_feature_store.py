@@ -26,7 +26,12 @@ src_row), alternating, `--runs` runs each; the peak device memory of each route'
 the weight-gradient kernel alone both ways (dfol_linear_wgrad_bias_f32 over the gathered matrix, dfol_linear_wgrad_bias_rows_f32 over the
 table).  One JSON line.
 
-usage: python tools/bench_feature_store.py [--leg stream|train] [--images 2048] [--objects 100] [--features 2048] [--batch 256] [--batches 24] [--runs 4]
+`--leg bf16` is the same train leg in `mlp_math: bf16` with the store in its bf16 form (`feature_dtype="bf16"`: half the bytes, the first
+layer reads the table in place - dfol_linear_act_rows_bf16t_f32, dfol_linear_wgrad_bias_rows_bf16t) against the fp32 store's matrix route
+(`direct=False`), alternating in one session; beside the replayed step and the weight gradient it times the first product with what runs in
+front of it (dfol_store_rows_f32 + the row kernel against the gather + dfol_linear_act_bf16_f32) and reports both stores' bytes.
+
+usage: python tools/bench_feature_store.py [--leg stream|train|bf16] [--images 2048] [--objects 100] [--features 2048] [--batch 256] [--batches 24] [--runs 4]
                                            [--workers 5] [--steps 20]
 """
 import argparse
@@ -124,8 +129,9 @@ def apart(a, b):
     return "faster, ranges apart" if a["max"] < b["min"] else "slower, ranges apart" if a["min"] > b["max"] else "ranges overlap: no difference shown"
 
 
-def train_leg(args):
-    """Replayed train steps over a plain store against a direct store (see the module's docstring) -> the result dictionary."""
+def train_leg(args, bf16=False):
+    """Replayed train steps over a plain store against a direct store (see the module's docstring) -> the result dictionary.  bf16: the
+    `mlp_math: bf16` arithmetic, and the direct store is the bf16 one."""
     from dfol_vqa_amd import _lib, training
     import bench
     device = torch.device("cuda", 0)
@@ -133,7 +139,7 @@ def train_leg(args):
     try:
         paths, names = syn.write_synthetic_ontology(os.path.join(tmp, "ontology"))
         cfg = syn.reference_config(paths, box_features_dim=args.features, freeze_featurizer=False, freeze_attribute_network=False,
-                                   freeze_relation_network=False, freeze_embedding_network=False, dropout=0.0)
+                                   freeze_relation_network=False, freeze_embedding_network=False, dropout=0.0, **({"mlp_math": "bf16"} if bf16 else {}))
         ontology = experiment.build_ontology(cfg)
         torch.manual_seed(0)
         model = experiment.build_model(cfg, ontology)
@@ -141,7 +147,7 @@ def train_leg(args):
         model = model.to(device).train()
         chunks, info_path, _ = write_corpus(tmp, args.images, args.objects, args.features, args.per_chunk)
         stores = {"matrix": data.DeviceFeatureStore(tmp, "objs", chunks, info_path, device),
-                  "direct": data.DeviceFeatureStore(tmp, "objs", chunks, info_path, device, direct=True)}
+                  "direct": data.DeviceFeatureStore(tmp, "objs", chunks, info_path, device, **({"feature_dtype": "bf16"} if bf16 else {"direct": True}))}
         with open(paths["attribute_file"]) as f:
             cats = json.load(f)
         rng = np.random.RandomState(9)
@@ -199,15 +205,40 @@ def train_leg(args):
                 evs.append((a, b))
             torch.cuda.synchronize()
             return float(np.median([a.elapsed_time(b) for a, b in evs]))
-        kernel = {"matrix": [], "rows": []}
-        same = bool(torch.equal(_lib.linear_wgrad(dy, mat[:, :args.features]), _lib.linear_wgrad_rows(dy, rows.table, rows.src_row)))
-        for _ in range(args.runs):
-            kernel["matrix"].append(kernel_ms(lambda: _lib.linear_wgrad(dy, mat[:, :args.features], bias=True)))
-            kernel["rows"].append(kernel_ms(lambda: _lib.linear_wgrad_rows(dy, rows.table, rows.src_row, bias=True)))
+        kernel, product = {"matrix": [], "rows": []}, {"matrix": [], "rows": []}
+        with _lib.dense_math("bf16" if bf16 else None):
+            same = bool(torch.equal(_lib.linear_wgrad(dy, mat[:, :args.features]), _lib.linear_wgrad_rows(dy, rows.table, rows.src_row)))
+            for _ in range(args.runs):
+                kernel["matrix"].append(kernel_ms(lambda: _lib.linear_wgrad(dy, mat[:, :args.features], bias=True)))
+                kernel["rows"].append(kernel_ms(lambda: _lib.linear_wgrad_rows(dy, rows.table, rows.src_row, bias=True)))
+            if bf16:                                         # the first product with what runs in front of it: gather + matrix kernel, row kernel + rows
+                refs = {k: st.index.ref(ids) for k, st in stores.items()}
+                idx = {k: st.upload_index(refs[k]) for k, st in stores.items()}
+                y, act = torch.empty(rows.O, first.out_features, device=device), _lib.ACT_SIGMOID
+
+                def by_matrix():
+                    stores["matrix"].gather(refs["matrix"], out=mat, index=idx["matrix"])
+                    _lib.linear_act_split(mat[:, :args.features], first.weight, first.bias, act, out=y)
+
+                def by_rows():
+                    stores["direct"].rows(refs["direct"], out=rows, index=idx["direct"])
+                    _lib.linear_rows_bf16t(rows.table, rows.src_row, first.weight, first.bias, act, out=y)
+                by_matrix()
+                y0 = y.clone()
+                by_rows()
+                same = same and bool(torch.equal(y0, y))
+                for _ in range(args.runs):
+                    product["matrix"].append(kernel_ms(by_matrix))
+                    product["rows"].append(kernel_ms(by_rows))
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
     m, d = span(ms["matrix"]), span(ms["direct"])
-    return {"tool": "bench_feature_store", "leg": "train",
+    more = {}
+    if bf16:
+        more = {"first_product_ms": {"gather_and_matrix": span(product["matrix"]), "rows": span(product["rows"]),
+                                     "rows_vs_matrix": apart(span(product["rows"]), span(product["matrix"]))},
+                "store_bytes": {k: st.nbytes for k, st in stores.items()}}
+    return {"tool": "bench_feature_store", "leg": "bf16" if bf16 else "train", **more,
             "shape": {"images": args.images, "objects": args.objects, "features": args.features, "batch": args.batch, "rows": rows.O,
                       "runs": args.runs, "replays_per_run": args.steps},
             "train_step_ms": {"matrix": m, "direct": d, "direct_vs_matrix": apart(d, m)},
@@ -220,7 +251,8 @@ def train_leg(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("stream", "train"), default="stream", help="the stream of unseen inference batches, or replayed train steps")
+    ap.add_argument("--leg", choices=("stream", "train", "bf16"), default="stream",
+                    help="the stream of unseen inference batches, replayed train steps, or the train leg in mlp_math: bf16 over the bf16 store")
     ap.add_argument("--steps", type=int, default=20, help="--leg train: replays per timed run")
     ap.add_argument("--images", type=int, default=2048)
     ap.add_argument("--objects", type=int, default=100)
@@ -233,8 +265,8 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_feature_store: needs a GPU (there is no CPU form of this measurement)")
-    if args.leg == "train":
-        print(json.dumps(train_leg(args)))
+    if args.leg in ("train", "bf16"):
+        print(json.dumps(train_leg(args, bf16=args.leg == "bf16")))
         return
     import bench
     from dfol_vqa_amd import _lib, native_exec, training
