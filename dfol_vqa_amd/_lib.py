@@ -128,6 +128,11 @@ SIGNATURES = {
     "dfol_linear_wgrad_bias_f32": [_p, _i64, _p, _i64, _i64, _i32, _i32, _p, _p, _p, _p],
     "dfol_attr_ll_bwd_f32": [_p, _p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _i64, _p, _i64, _p, _p],
     "dfol_quantify_bwd_f32": [_p, _p, _p, _p, _p, _i32, _i32, _p, _p],
+    "dfol_filter_gate_fwd_f32": [_p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _p, _p, _p],
+    "dfol_relate_gate_fwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p],
+    "dfol_filter_gate_bwd_scratch": [_i32, _i32],           # returns a float count (int64), called directly
+    "dfol_filter_gate_bwd_f32": [_p, _p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _p, _p, _p, _p, _p, _p],
+    "dfol_relate_gate_bwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "dfol_attr_gather_bwd_f32": [_p, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _p],
     "dfol_rel_gather_bwd_f32": [_p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _i64, _p],
     "dfol_option_normalize_bwd_f32": [_p, _p, _p, _i32, _p, _p, _i32, _i32, _p, _p],
@@ -244,6 +249,7 @@ def load():
         fn.argtypes = argtypes
         fn.restype = ctypes.c_int
     lib.dfol_linear_wgrad_workspace.restype = ctypes.c_int64
+    lib.dfol_filter_gate_bwd_scratch.restype = ctypes.c_int64
     lib.dfol_pair_w2_f16x2_bytes.restype = ctypes.c_int64
     lib.dfol_pair_w2_f16_bytes.restype = ctypes.c_int64
     lib.dfol_linear_w_f16x2_bytes.restype = ctypes.c_int64
@@ -519,6 +525,38 @@ def relate_fwd(prior_s, prior_o, tile, pred_q, n_obj, quant_s, quant_o, neg=None
     call("dfol_relate_fwd_f32", _ptr(prior_s, F32), _ptr(prior_o, F32), _ptr(tile, F32), _ptr(pred_q, I32), _ptr(n_obj, I32),
          _ptr(quant_s, F32), _ptr(quant_o, F32), _ptr(neg, U8, True), 0 if neg is None else 1, _ptr(active, U8, True),
          _ptr(want, U8, True), P, NS, orientation, flags, _ptr(post_s, F32, True), _ptr(post_o, F32, True), _stream())
+    return post_s, post_o
+
+
+def gate_params(weight, bias):
+    """The float[18] image of a NeuralLogicGate's nn.Linear(2, 6) the gated kernels read: W row-major, then c (no host read, no sync)."""
+    if tuple(weight.shape) != (6, 2) or tuple(bias.shape) != (6,):
+        raise DfolError("a logic gate holds nn.Linear(2, 6): weight [6, 2] and bias [6], got %s and %s" % (tuple(weight.shape), tuple(bias.shape)))
+    return torch.cat([weight.detach().reshape(12), bias.detach().reshape(6)]).to(F32).contiguous()
+
+
+def filter_gate_fwd(att_in, ll, pred_q, n_obj, gate, neg=None, active=None):
+    """filter_fwd with the trainable gate: gate = gate_params(weight, bias) of axis 0."""
+    P, NS = ll.shape
+    out = torch.empty(P, NS, dtype=F32, device=ll.device)
+    call("dfol_filter_gate_fwd_f32", _ptr(att_in, F32), _ptr(ll, F32), _ptr(pred_q, I32), _ptr(n_obj, I32), _ptr(neg, U8, True),
+         0 if neg is None else 1, _ptr(active, U8, True), P, NS, _ptr(gate, F32), _ptr(out), _stream())
+    return out
+
+
+def relate_gate_fwd(prior_s, prior_o, tile, pred_q, n_obj, quant_s, quant_o, gate_s, gate_o, neg=None, active=None, want=None,
+                    orientation=TILE_SUBJECT_ROWS, lone_forall_identity=False, need_s=True, need_o=True, diag_absent=False):
+    """relate_fwd with the trainable gates: gate_s / gate_o = gate_params of axis 0 / axis 1."""
+    if tile.dtype != F32:
+        raise DfolError("the gated relate kernels read fp32 tiles (got %s): relation_tile_dtype: bf16 and trainable_gate: True do not combine" % tile.dtype)
+    P, NS = tile.shape[0], tile.shape[1]
+    flags = (RELATE_LONE_FORALL_IDENTITY if lone_forall_identity else 0) | (RELATE_DIAG_ABSENT if diag_absent else 0)
+    post_s = torch.empty(P, NS, dtype=F32, device=tile.device) if need_s else None
+    post_o = torch.empty(P, NS, dtype=F32, device=tile.device) if need_o else None
+    call("dfol_relate_gate_fwd_f32", _ptr(prior_s, F32), _ptr(prior_o, F32), _ptr(tile, F32), _ptr(pred_q, I32), _ptr(n_obj, I32),
+         _ptr(quant_s, F32), _ptr(quant_o, F32), _ptr(neg, U8, True), 0 if neg is None else 1, _ptr(active, U8, True),
+         _ptr(want, U8, True), P, NS, orientation, flags, _ptr(gate_s, F32), _ptr(gate_o, F32), _ptr(post_s, F32, True),
+         _ptr(post_o, F32, True), _stream())
     return post_s, post_o
 
 
@@ -1676,6 +1714,41 @@ def relate_bwd(prior_s, prior_o, tile, pred_q, n_obj, quant_s, quant_o, neg, act
     if need_prior:
         return reduce_by_question(pp_s, pred_q, None, Q), reduce_by_question(pp_o, pred_q, None, Q), g_tile
     return None, None, g_tile
+
+
+def filter_gate_bwd(g_out, att_in, ll, pred_q, n_obj, gate, neg, active):
+    """-> (g_prior [Q, NS], g_ll [P, NS], g_gate [18]); the parameter sums are taken in a fixed order (no atomics)."""
+    require_sorted(pred_q, "filter_gate_bwd")
+    P, NS = ll.shape
+    pp = torch.empty(P, NS, dtype=F32, device=ll.device)                                  # per predicate
+    g_ll = torch.empty(P, NS, dtype=F32, device=ll.device)
+    g_gate = torch.empty(18, dtype=F32, device=ll.device)
+    scratch = torch.empty(max(1, load().dfol_filter_gate_bwd_scratch(P, NS)), dtype=F32, device=ll.device)
+    call("dfol_filter_gate_bwd_f32", _ptr(g_out, F32), _ptr(att_in, F32), _ptr(ll, F32), _ptr(pred_q, I32), _ptr(n_obj, I32), _ptr(neg, U8, True),
+         0 if neg is None else 1, _ptr(active, U8, True), P, NS, _ptr(gate, F32), _ptr(scratch), _ptr(pp), _ptr(g_ll), _ptr(g_gate), _stream())
+    return reduce_by_question(pp, pred_q, None, att_in.shape[0]), g_ll, g_gate
+
+
+def relate_gate_bwd(prior_s, prior_o, tile, pred_q, n_obj, quant_s, quant_o, gate_s, gate_o, neg, active, g_post_s, g_post_o, orientation,
+                    lone_forall_identity):
+    """-> (g_prior_s [Q, NS], g_prior_o [Q, NS], g_tile [P, NS, NS], g_gate_s [18], g_gate_o [18])."""
+    require_sorted(pred_q, "relate_gate_bwd")
+    P, NS = tile.shape[0], tile.shape[1]
+    if NS > 1024:
+        raise DfolError("relate_gate_bwd: images of %d object slots; the gated Relate backward keeps its row and column sums in LDS and takes at most 1024" % NS)
+    Q = prior_s.shape[0]
+    dev = tile.device
+    pp_s = torch.empty(P, NS, dtype=F32, device=dev)
+    pp_o = torch.empty(P, NS, dtype=F32, device=dev)
+    g_tile = torch.empty(P, NS, NS, dtype=F32, device=dev)
+    gg_s = torch.empty(18, dtype=F32, device=dev)
+    gg_o = torch.empty(18, dtype=F32, device=dev)
+    scratch = torch.empty(max(1, 36 * P), dtype=F32, device=dev)
+    call("dfol_relate_gate_bwd_f32", _ptr(prior_s, F32), _ptr(prior_o, F32), _ptr(tile, F32), _ptr(pred_q, I32), _ptr(n_obj, I32),
+         _ptr(quant_s, F32), _ptr(quant_o, F32), _ptr(neg, U8, True), 0 if neg is None else 1, _ptr(active, U8, True),
+         _ptr(g_post_s, F32, True), _ptr(g_post_o, F32, True), P, NS, orientation, 1 if lone_forall_identity else 0, _ptr(gate_s, F32),
+         _ptr(gate_o, F32), _ptr(scratch), _ptr(pp_s), _ptr(pp_o), _ptr(g_tile), _ptr(gg_s), _ptr(gg_o), _stream())
+    return reduce_by_question(pp_s, pred_q, None, Q), reduce_by_question(pp_o, pred_q, None, Q), g_tile, gg_s, gg_o
 
 
 def quantify_bwd(g_lp, att, quant, pred_q, n_obj):

@@ -1,0 +1,707 @@
+// The logic cell with the trainable gate (`trainable_gate: True`): gated forms of the Filter and Relate kernels, forward and backward.
+//
+// Reference: NeuralLogicGate, batch_base_ops.py:19-38, used by BatchBayesianLogicCell._forward_core at :99-102 and :135-138: every
+// `x + log_p` of the cell becomes G_k(x, log_p), k the axis whose prior is joined.  With W_k [6, 2], c_k [6] (nn.Linear(2, 6)):
+//     alpha = sigmoid(W_k [a, b] + c_k)
+//     va = alpha0 + alpha3 (1 - 2 alpha0) e^a        vb = alpha1 + alpha4 (1 - 2 alpha1) e^b
+//     G  = log(max(alpha2 + alpha5 (1 - 2 alpha2) max(va, eps) max(vb, eps), eps))
+// (the reference takes e^(log va + log vb) of two clamped logarithms, util.py:46-47: the product is the same value with one logarithm).
+// m = e^G is a probability, so the quantifier transform of an inner term, F(G) = log(max(q + (1 - 2 q) m, eps)), needs no exponential,
+// and an EXISTS aggregation 1 - prod (1 - m) is kept in the complement form q <- q + m - q m (dfol_or, dfol_common.h) with no
+// logarithm per element.  The complement fast path of the ungated kernel (one e^l' for both directions times e^prior) does not apply:
+// the two directions have different inner terms.  What both directions share is l' and e^l'.
+//
+// The gate's 18 parameters per axis are wave-uniform (scalar registers); a column's prior, its exponential and its share W[:,1] b + c of
+// the six pre-activations are computed once per wavefront (forward), a row's once per row.
+//
+// Backward: the formulas as written, clamps included (zero gradient below a floor), recomputed from the inputs.  The parameter
+// gradient is a sum over every element of the launch: per-thread sums -> wavefront (shuffles) -> workgroup (LDS, wavefront order) ->
+// one row of a scratch buffer per workgroup -> a second kernel adds the rows in a fixed order.  No atomics: two runs give the same bits.
+#include "dfol_common.h"
+
+namespace {
+
+struct GateW {
+    float w0[6], w1[6], c[6];
+};
+
+__device__ __forceinline__ GateW gate_load(const float* __restrict__ g) {      // float[18]: W row-major [6][2], then c [6]
+    GateW G;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        G.w0[i] = g[2 * i];
+        G.w1[i] = g[2 * i + 1];
+        G.c[i] = g[12 + i];
+    }
+    return G;
+}
+
+// sigmoid(z) and 1 - sigmoid(z), each accurate relative to itself (e <= 1: no overflow, no cancellation on either side)
+__device__ __forceinline__ void gate_sig(float z, float& al, float& om) {
+    const float e = __builtin_amdgcn_exp2f(-1.44269504088896340736f * fabsf(z));
+    const float r = __builtin_amdgcn_rcpf(1.0f + e), er = e * r;
+    const bool pos = z >= 0.f;
+    al = pos ? r : er;
+    om = pos ? er : r;
+}
+
+__device__ __forceinline__ void gate_zb(const GateW& G, float b, float* zb) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) zb[i] = fmaf(G.w1[i], b, G.c[i]);
+}
+
+// m = e^G(a, b) from a, ea = e^a, zb = W[:,1] b + c, eb = e^b
+__device__ __forceinline__ float gate_m(const GateW& G, float a, float ea, const float* zb, float eb) {
+    float al[6], om[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) gate_sig(fmaf(G.w0[i], a, zb[i]), al[i], om[i]);
+    const float va = fmaxf(fmaf(al[3] * (om[0] - al[0]), ea, al[0]), DFOL_EPS);
+    const float vb = fmaxf(fmaf(al[4] * (om[1] - al[1]), eb, al[1]), DFOL_EPS);
+    return fmaxf(fmaf(al[5] * (om[2] - al[2]), va * vb, al[2]), DFOL_EPS);
+}
+
+__device__ __forceinline__ float gate_log(const GateW& G, float a, float b) {
+    float zb[6];
+    gate_zb(G, b, zb);
+    return dfol_log(gate_m(G, a, dfol_exp(a), zb, dfol_exp(b)));
+}
+
+// Backward of one gate.  g is the gradient of G = log m (from_log) or of m itself; da, db are returned, the parameter gradients are
+// added into acc[18] (the layout of the parameters).
+__device__ __forceinline__ void gate_bwd(const GateW& G, float a, float b, float g, bool from_log, float& da, float& db, float* acc) {
+    float al[6], om[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) gate_sig(fmaf(G.w0[i], a, fmaf(G.w1[i], b, G.c[i])), al[i], om[i]);
+    const float ea = dfol_exp(a), eb = dfol_exp(b);
+    const float k0 = om[0] - al[0], k1 = om[1] - al[1], k2 = om[2] - al[2];
+    const float va_raw = fmaf(al[3] * k0, ea, al[0]), vb_raw = fmaf(al[4] * k1, eb, al[1]);
+    const float va = fmaxf(va_raw, DFOL_EPS), vb = fmaxf(vb_raw, DFOL_EPS), pv = va * vb;
+    const float m_raw = fmaf(al[5] * k2, pv, al[2]);
+    float dm = 0.f;
+    if (m_raw > DFOL_EPS) dm = from_log ? g / m_raw : g;
+    float dal[6];
+    dal[2] = dm * (1.f - 2.f * al[5] * pv);
+    dal[5] = dm * k2 * pv;
+    const float dpv = dm * al[5] * k2;
+    const float dva = va_raw > DFOL_EPS ? dpv * vb : 0.f, dvb = vb_raw > DFOL_EPS ? dpv * va : 0.f;
+    dal[0] = dva * (1.f - 2.f * al[3] * ea);
+    dal[3] = dva * k0 * ea;
+    dal[1] = dvb * (1.f - 2.f * al[4] * eb);
+    dal[4] = dvb * k1 * eb;
+    float xa = dva * al[3] * k0 * ea, xb = dvb * al[4] * k1 * eb;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        const float dz = dal[i] * al[i] * om[i];
+        xa = fmaf(dz, G.w0[i], xa);
+        xb = fmaf(dz, G.w1[i], xb);
+        acc[2 * i] = fmaf(dz, a, acc[2 * i]);
+        acc[2 * i + 1] = fmaf(dz, b, acc[2 * i + 1]);
+        acc[12 + i] += dz;
+    }
+    da = xa;
+    db = xb;
+}
+
+// l' = negation(min(ll, 0)) (batch_base_ops.py:194, :212-213) and its derivative
+__device__ __forceinline__ float gate_prep(float ll, int any_neg, float alpha_n, float cn) {
+    float v = fminf(ll, 0.f);
+    if (any_neg) v = dfol_pnot(v, alpha_n, cn);
+    return v;
+}
+
+__device__ __forceinline__ float gate_dpnot(float x, float alpha, float c) {
+    const float e = dfol_exp(x), d = alpha + c * e;
+    return d > DFOL_EPS ? c * e / d : 0.f;
+}
+
+__device__ __forceinline__ float gate_dprep(float ll, int any_neg, float alpha_n, float cn) {
+    float d = ll < 0.f ? 1.f : 0.f;
+    if (any_neg) d *= gate_dpnot(fminf(ll, 0.f), alpha_n, cn);
+    return d;
+}
+
+// One inner term of an aggregation from m = e^G: EXISTS keeps the probability (complement form), otherwise F(G) = log(max(q + k m, eps))
+// (FOR_ALL: log m = G itself, also in the lone predicate's literal branch, :104-108)
+__device__ __forceinline__ float gate_term(float m, bool ex, float q, float k) { return ex ? m : dfol_slog(fmaf(k, m, q)); }
+__device__ __forceinline__ float gate_join(float acc, float t, bool ex) { return ex ? dfol_or(acc, t) : acc + t; }
+// the aggregate after the outer transform (:129-133): a log-probability
+__device__ __forceinline__ float gate_outer(float agg, bool ex, bool ident, float q, float k) {
+    return ex ? dfol_slog(agg) : (ident ? agg : dfol_pnot(agg, q, k));
+}
+
+// ---------------------------------------------------------------------------------------------------
+// filter (arity 1): post[o] = G_0(l'[o], prior[o])
+// ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void filter_gate_fwd_kernel(const float* __restrict__ att_in, const float* __restrict__ ll,
+                                                              const int32_t* __restrict__ pred_q, const int32_t* __restrict__ n_obj,
+                                                              const uint8_t* __restrict__ neg, int any_neg, const uint8_t* __restrict__ active,
+                                                              int64_t total4, int NS4, const float* __restrict__ gate, float* __restrict__ att_out) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total4) return;
+    const GateW G = gate_load(gate);
+    const int p = (int)(idx / NS4), c0 = (int)(idx - (int64_t)p * NS4) * 4;
+    const int q = pred_q[p], n = n_obj[q];
+    const float4 a4 = *reinterpret_cast<const float4*>(att_in + ((int64_t)q * NS4 * 4 + c0));
+    const float4 l4 = *reinterpret_cast<const float4*>(ll + idx * 4);
+    const float av[4] = {a4.x, a4.y, a4.z, a4.w}, l[4] = {l4.x, l4.y, l4.z, l4.w};
+    float o[4];
+    const bool act = active == nullptr || active[p];
+    const float alpha = (any_neg && neg[p]) ? 1.f : 0.f, cc = 1.f - 2.f * alpha;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        o[j] = av[j];                                                         // no-op token: the prior row (:385)
+        if (act) o[j] = gate_log(G, gate_prep(l[j], any_neg, alpha, cc), av[j]);      // :135-136
+        if (c0 + j >= n) o[j] = 0.f;
+    }
+    *reinterpret_cast<float4*>(att_out + idx * 4) = make_float4(o[0], o[1], o[2], o[3]);
+}
+
+constexpr int FG_THREADS = 256;
+
+// one thread per element; the workgroup's parameter partial goes to scratch[blockIdx.x][18]
+__global__ __launch_bounds__(FG_THREADS) void filter_gate_bwd_kernel(const float* __restrict__ g_out, const float* __restrict__ att_in,
+                                                                     const float* __restrict__ ll, const int32_t* __restrict__ pred_q,
+                                                                     const int32_t* __restrict__ n_obj, const uint8_t* __restrict__ neg, int any_neg,
+                                                                     const uint8_t* __restrict__ active, int64_t total, int NS,
+                                                                     const float* __restrict__ gate, float* __restrict__ scratch,
+                                                                     float* __restrict__ g_prior, float* __restrict__ g_ll) {
+    __shared__ float wpart[FG_THREADS / 64][18];
+    const int64_t i = (int64_t)blockIdx.x * FG_THREADS + threadIdx.x;
+    const GateW G = gate_load(gate);
+    float acc[18];
+#pragma unroll
+    for (int k = 0; k < 18; ++k) acc[k] = 0.f;
+    if (i < total) {
+        const int p = (int)(i / NS), c = (int)(i - (int64_t)p * NS);
+        const int q = pred_q[p], n = n_obj[q];
+        float dp = 0.f, dl = 0.f;
+        if (c < n) {
+            const float g = g_out[i];
+            if (active == nullptr || active[p]) {
+                const float alpha = (any_neg && neg[p]) ? 1.f : 0.f, cc = 1.f - 2.f * alpha;
+                const float raw = ll[i];
+                float da;
+                gate_bwd(G, gate_prep(raw, any_neg, alpha, cc), att_in[(int64_t)q * NS + c], g, true, da, dp, acc);
+                dl = da * gate_dprep(raw, any_neg, alpha, cc);
+            } else {
+                dp = g;                                                       // posterior = prior
+            }
+        }
+        if (g_prior) g_prior[i] = dp;
+        if (g_ll) g_ll[i] = dl;
+    }
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < 18; ++k) {
+        const float s = dfol_wave_sum(acc[k]);
+        if (lane == 0) wpart[w][k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < 18) {
+        float s = wpart[0][threadIdx.x];
+        for (int j = 1; j < FG_THREADS / 64; ++j) s += wpart[j][threadIdx.x];
+        scratch[(int64_t)blockIdx.x * 18 + threadIdx.x] = s;
+    }
+}
+
+// out[k] = sum over the rows of scratch [rows, width], k < width: one wavefront per k, lane l adds rows l, l + 64, ... in order, then the
+// fixed shuffle tree.  out_a gets columns [0, 18), out_b (may be NULL) columns [18, 36).
+__global__ __launch_bounds__(64) void gate_param_reduce_kernel(const float* __restrict__ scratch, int64_t rows, int width, float* __restrict__ out_a,
+                                                               float* __restrict__ out_b) {
+    const int k = blockIdx.x, lane = threadIdx.x;
+    float s = 0.f;
+    for (int64_t r = lane; r < rows; r += 64) s += scratch[r * width + k];
+    s = dfol_wave_sum(s);
+    if (lane == 0) {
+        if (k < 18) {
+            if (out_a) out_a[k] = s;
+        } else if (out_b) {
+            out_b[k - 18] = s;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// relate (arity 2), NS <= 256: one wavefront per predicate tile, the geometry of relate_fwd_kernel (a lane owns four consecutive columns,
+// LPR lanes cover a row, 64 / LPR rows per iteration).  Rows = variable R, columns = variable C:
+//   post_R[r] = G_R( F_C( sum_{c != r} F_C( G_C(l'[r,c], prior_C[c]) ) ), prior_R[r] )        row aggregates (cross-lane)
+//   post_C[c] = G_C( F_R( sum_{r != c} F_R( G_R(l'[r,c], prior_R[r]) ) ), prior_C[c] )        column aggregates (in-register)
+// ---------------------------------------------------------------------------------------------------
+template <int LPR>
+__global__ __launch_bounds__(256) void relate_gate_fwd_kernel(
+    const float* __restrict__ prior_R, const float* __restrict__ prior_C, const float* __restrict__ tile,
+    const int32_t* __restrict__ pred_q, const int32_t* __restrict__ n_obj, const float* __restrict__ quant_R,
+    const float* __restrict__ quant_C, const uint8_t* __restrict__ neg, int any_neg, const uint8_t* __restrict__ active,
+    const uint8_t* __restrict__ want, int want_R_bit, int want_C_bit, int P, int NS, int flags,
+    const float* __restrict__ gate_R, const float* __restrict__ gate_C, float* __restrict__ post_R, float* __restrict__ post_C) {
+    constexpr int RPI = 64 / LPR;
+    __shared__ float row_agg[4][256];
+    const int wave_in_block = threadIdx.x >> 6;
+    const int p = blockIdx.x * 4 + wave_in_block;
+    if (p >= P) return;
+    const int lane = threadIdx.x & 63;
+    const int q = pred_q[p];
+    const int n = min(n_obj[q], NS);
+    const int wbits = want ? want[p] : 3;
+    const bool wantR = (wbits & want_R_bit) && post_R;
+    const bool wantC = (wbits & want_C_bit) && post_C;
+    const float* pR = prior_R + (int64_t)q * NS;
+    const float* pC = prior_C + (int64_t)q * NS;
+    float* oR = post_R ? post_R + (int64_t)p * NS : nullptr;
+    float* oC = post_C ? post_C + (int64_t)p * NS : nullptr;
+
+    if (active && !active[p]) {                         // no-op predicate: posterior = prior (batch_base_ops.py:563-564)
+        for (int c = lane; c < NS; c += 64) {
+            if (oR) oR[c] = (wantR && c < n) ? pR[c] : 0.f;
+            if (oC) oC[c] = (wantC && c < n) ? pC[c] : 0.f;
+        }
+        return;
+    }
+    if (!wantR && oR)
+        for (int c = lane; c < NS; c += 64) oR[c] = 0.f;
+    if (!wantC && oC)
+        for (int c = lane; c < NS; c += 64) oC[c] = 0.f;
+    if (!wantR && !wantC) return;
+
+    const GateW GR = gate_load(gate_R), GC = gate_load(gate_C);
+    const int identity_forall = flags & DFOL_RELATE_LONE_FORALL_IDENTITY;
+    const int cg = lane % LPR, rs = lane / LPR, c0 = cg * 4, cl = min(c0, NS - 4);
+    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
+    const float qR = quant_R[p], qC = quant_C[p], kR = 1.f - 2.f * qR, kC = 1.f - 2.f * qC;
+    const bool exR = qR == 1.f, exC = qC == 1.f;
+    const bool idR = identity_forall && qR == 0.f, idC = identity_forall && qC == 0.f;
+    const float* tp = tile + (int64_t)p * NS * NS;
+
+    // this lane's four columns: prior, its exponential, its share of the six pre-activations (once per wavefront)
+    const float4 pc4 = *reinterpret_cast<const float4*>(pC + cl);
+    const float pc[4] = {pc4.x, pc4.y, pc4.z, pc4.w};
+    float zbC[4][6], ebC[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        gate_zb(GC, pc[j], zbC[j]);
+        ebC[j] = dfol_exp(pc[j]);
+    }
+    float cacc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int r0 = 0; r0 < n; r0 += RPI) {
+        const int r = r0 + rs, rc = min(r, n - 1);
+        const float4 t4 = *reinterpret_cast<const float4*>(tp + (int64_t)rc * NS + cl);
+        const float l[4] = {t4.x, t4.y, t4.z, t4.w};
+        const float pr = pR[rc];
+        float zbR[6];
+        gate_zb(GR, pr, zbR);
+        const float ebR = dfol_exp(pr);
+        float racc = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = c0 + j;
+            const bool keep = r < n && c < n && c != r;       // padding and self-relations contribute nothing (:112)
+            const float v = gate_prep(l[j], any_neg, alpha_n, cn);
+            const float ea = dfol_exp(v);
+            if (wantR) {
+                const float t = gate_term(gate_m(GC, v, ea, zbC[j], ebC[j]), exC, qC, kC);      // :99-100, :108
+                racc = gate_join(racc, keep ? t : 0.f, exC);
+            }
+            if (wantC) {
+                const float t = gate_term(gate_m(GR, v, ea, zbR, ebR), exR, qR, kR);
+                cacc[j] = gate_join(cacc[j], keep ? t : 0.f, exR);
+            }
+        }
+        if (wantR) {
+            racc = exC ? dfol_group_or<LPR>(racc) : dfol_group_sum<LPR>(racc);
+            if (cg == LPR - 1 && r < n) row_agg[wave_in_block][r] = racc;
+        }
+    }
+    if (wantR) {
+        __builtin_amdgcn_wave_barrier();                 // LDS is in order within a wavefront; this only pins the schedule
+        for (int c = lane; c < NS; c += 64) {
+            float o = 0.f;
+            if (c < n) o = gate_log(GR, gate_outer(row_agg[wave_in_block][c], exC, idC, qC, kC), pR[c]);      // :133, :135-136
+            oR[c] = o;
+        }
+    }
+    if (wantC) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+#pragma unroll
+            for (int m = 32; m >= LPR; m >>= 1) cacc[j] = gate_join(cacc[j], __shfl_xor(cacc[j], m, 64), exR);
+        }
+        if (rs == 0 && c0 < NS) {
+            float o[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float a = gate_outer(cacc[j], exR, idR, qR, kR);
+                o[j] = (c0 + j < n) ? dfol_log(gate_m(GC, a, dfol_exp(a), zbC[j], ebC[j])) : 0.f;
+            }
+            *reinterpret_cast<float4*>(oC + c0) = make_float4(o[0], o[1], o[2], o[3]);
+        }
+    }
+}
+
+__device__ __forceinline__ float gate_wave_join(float x, bool ex) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) x = gate_join(x, __shfl_xor(x, m, 64), ex);
+    return x;
+}
+
+// NS > 256: one workgroup per predicate, a thread per column for the column aggregates (rows in order), a workgroup reduction per row
+// for the row aggregates (wavefront partials joined in wavefront order), as relate_big_fwd_kernel.
+__global__ __launch_bounds__(256) void relate_gate_big_fwd_kernel(
+    const float* __restrict__ prior_R, const float* __restrict__ prior_C, const float* __restrict__ tile,
+    const int32_t* __restrict__ pred_q, const int32_t* __restrict__ n_obj, const float* __restrict__ quant_R,
+    const float* __restrict__ quant_C, const uint8_t* __restrict__ neg, int any_neg, const uint8_t* __restrict__ active,
+    const uint8_t* __restrict__ want, int want_R_bit, int want_C_bit, int NS, int flags, const float* __restrict__ gate_R,
+    const float* __restrict__ gate_C, float* __restrict__ post_R, float* __restrict__ post_C) {
+    __shared__ float part[4];
+    const int p = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    const int q = pred_q[p], n = min(n_obj[q], NS);
+    const int wbits = want ? want[p] : 3;
+    const bool wantR = (wbits & want_R_bit) && post_R, wantC = (wbits & want_C_bit) && post_C;
+    const float* pR = prior_R + (int64_t)q * NS;
+    const float* pC = prior_C + (int64_t)q * NS;
+    float* oR = post_R ? post_R + (int64_t)p * NS : nullptr;
+    float* oC = post_C ? post_C + (int64_t)p * NS : nullptr;
+    if (active && !active[p]) {
+        for (int c = tid; c < NS; c += 256) {
+            if (oR) oR[c] = (wantR && c < n) ? pR[c] : 0.f;
+            if (oC) oC[c] = (wantC && c < n) ? pC[c] : 0.f;
+        }
+        return;
+    }
+    if (!wantR && oR)
+        for (int c = tid; c < NS; c += 256) oR[c] = 0.f;
+    if (!wantC && oC)
+        for (int c = tid; c < NS; c += 256) oC[c] = 0.f;
+    const GateW GR = gate_load(gate_R), GC = gate_load(gate_C);
+    const int identity_forall = flags & DFOL_RELATE_LONE_FORALL_IDENTITY;
+    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
+    const float qR = quant_R[p], qC = quant_C[p], kR = 1.f - 2.f * qR, kC = 1.f - 2.f * qC;
+    const bool exR = qR == 1.f, exC = qC == 1.f;
+    const bool idR = identity_forall && qR == 0.f, idC = identity_forall && qC == 0.f;
+    const float* tp = tile + (int64_t)p * NS * NS;
+    if (wantC)
+        for (int c = tid; c < NS; c += 256) {
+            float o = 0.f;
+            if (c < n) {
+                float acc = 0.f;
+                for (int r = 0; r < n; ++r) {
+                    if (r == c) continue;
+                    const float v = gate_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn);
+                    float zb[6];
+                    gate_zb(GR, pR[r], zb);
+                    acc = gate_join(acc, gate_term(gate_m(GR, v, dfol_exp(v), zb, dfol_exp(pR[r])), exR, qR, kR), exR);
+                }
+                o = gate_log(GC, gate_outer(acc, exR, idR, qR, kR), pC[c]);
+            }
+            oC[c] = o;
+        }
+    if (wantR)                                           // (wave-uniform per workgroup: every thread reaches the barriers)
+        for (int r = 0; r < NS; ++r) {
+            float s = 0.f;
+            if (r < n)
+                for (int c = tid; c < n; c += 256) {
+                    if (c == r) continue;
+                    const float v = gate_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn);
+                    float zb[6];
+                    gate_zb(GC, pC[c], zb);
+                    s = gate_join(s, gate_term(gate_m(GC, v, dfol_exp(v), zb, dfol_exp(pC[c])), exC, qC, kC), exC);
+                }
+            s = gate_wave_join(s, exC);
+            if (lane == 0) part[w] = s;
+            __syncthreads();
+            if (tid == 0) {
+                const float tot = gate_join(gate_join(gate_join(part[0], part[1], exC), part[2], exC), part[3], exC);
+                oR[r] = r < n ? gate_log(GR, gate_outer(tot, exC, idC, qC, kC), pR[r]) : 0.f;
+            }
+            __syncthreads();
+        }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// relate backward: one workgroup per predicate, its wavefronts on rows r = w, w + waves, ..., lane = column (the scheme of
+// relate_bwd_kernel): sweep 1 recomputes the aggregates as written (S[r] = sum_c F_C(G_C), T[c] = sum_r F_R(G_R)), the outer gates are
+// differentiated by the thread that owns the row / column, sweep 2 takes the element gradients.  Every thread keeps the 2 x 18 parameter
+// sums of its elements; the workgroup's total goes to scratch[p][36] (R's 18, then C's).
+// ---------------------------------------------------------------------------------------------------
+constexpr int GB_WAVES = 8;
+__global__ __launch_bounds__(64 * GB_WAVES) void relate_gate_bwd_kernel(
+    const float* __restrict__ prior_R, const float* __restrict__ prior_C, const float* __restrict__ tile,
+    const int32_t* __restrict__ pred_q, const int32_t* __restrict__ n_obj, const float* __restrict__ quant_R,
+    const float* __restrict__ quant_C, const uint8_t* __restrict__ neg, int any_neg, const uint8_t* __restrict__ active,
+    const float* __restrict__ g_post_R, const float* __restrict__ g_post_C, int NS, int identity_forall,
+    const float* __restrict__ gate_R, const float* __restrict__ gate_C, float* __restrict__ scratch,
+    float* __restrict__ g_prior_R, float* __restrict__ g_prior_C, float* __restrict__ g_tile) {
+    extern __shared__ float gate_bwd_lds[];              // (5 + waves) NS floats + waves x 36
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, tid = threadIdx.x, nw = (int)blockDim.x >> 6, nt = (int)blockDim.x;
+    float* sS = gate_bwd_lds;                             // row aggregates, later the rows' prior gradients
+    float* sGR = sS + NS;                                 // d loss / d S[r]
+    float* sGC = sGR + NS;                                // d loss / d T[c]
+    float* sDR = sGC + NS;                                // the outer gates' gradients of prior_R / prior_C
+    float* sDC = sDR + NS;
+    float* part_base = sDC + NS;
+    float* wsum = part_base + (size_t)nw * NS;            // [nw][36]
+    auto part = [&](int wave, int c) -> float& { return part_base[wave * NS + c]; };
+    const int p = blockIdx.x;
+    const int q = pred_q[p];
+    const int n = min(n_obj[q], NS);
+    const float* pR = prior_R + (int64_t)q * NS;
+    const float* pC = prior_C + (int64_t)q * NS;
+    const float* tp = tile + (int64_t)p * NS * NS;
+    float* gt = g_tile ? g_tile + (int64_t)p * NS * NS : nullptr;
+    const float* gR = g_post_R ? g_post_R + (int64_t)p * NS : nullptr;
+    const float* gC = g_post_C ? g_post_C + (int64_t)p * NS : nullptr;
+    float* sc = scratch + (int64_t)p * 36;
+
+    if (active && !active[p]) {                            // posterior = prior: the gradient passes straight through, the gates see nothing
+        for (int c = tid; c < NS; c += nt) {
+            if (g_prior_R) g_prior_R[(int64_t)p * NS + c] = (gR && c < n) ? gR[c] : 0.f;
+            if (g_prior_C) g_prior_C[(int64_t)p * NS + c] = (gC && c < n) ? gC[c] : 0.f;
+        }
+        if (gt)
+            for (int e = tid; e < NS * NS; e += nt) gt[e] = 0.f;
+        if (tid < 36) sc[tid] = 0.f;
+        return;
+    }
+    const GateW GR = gate_load(gate_R), GC = gate_load(gate_C);
+    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
+    const float qR = quant_R[p], qC = quant_C[p], kR = 1.f - 2.f * qR, kC = 1.f - 2.f * qC;
+    const bool idR = identity_forall && qR == 0.f, idC = identity_forall && qC == 0.f;
+    float accR[18], accC[18];
+#pragma unroll
+    for (int k = 0; k < 18; ++k) accR[k] = accC[k] = 0.f;
+
+    // sweep 1
+    for (int c0 = 0; c0 < NS; c0 += 64) {
+        const int c = c0 + lane;
+        float t_acc = 0.f;
+        const float pc = c < n ? pC[c] : 0.f;
+        float zbc[6];
+        gate_zb(GC, pc, zbc);
+        const float ebc = dfol_exp(pc);
+        for (int r = w; r < n; r += nw) {
+            float s_part = 0.f;
+            if (c < n && c != r) {
+                const float v = gate_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn), ea = dfol_exp(v);
+                if (gR) s_part = dfol_slog(fmaf(kC, gate_m(GC, v, ea, zbc, ebc), qC));
+                if (gC) {
+                    float zbr[6];
+                    gate_zb(GR, pR[r], zbr);
+                    t_acc += dfol_slog(fmaf(kR, gate_m(GR, v, ea, zbr, dfol_exp(pR[r])), qR));
+                }
+            }
+            s_part = dfol_wave_sum(s_part);
+            if (lane == 0) sS[r] = (c0 == 0 ? 0.f : sS[r]) + s_part;
+        }
+        if (c < NS) part(w, c) = t_acc;
+    }
+    __syncthreads();
+    // the outer gates: G_R(F_C(S[i]), prior_R[i]) and G_C(F_R(T[i]), prior_C[i])
+    for (int i = tid; i < n; i += nt) {
+        float T = part(0, i);
+        for (int j = 1; j < nw; ++j) T += part(j, i);
+        float dS = 0.f, dT = 0.f, dbr = 0.f, dbc = 0.f;
+        if (gR) {
+            const float S = sS[i], a = idC ? S : dfol_pnot(S, qC, kC);
+            float da;
+            gate_bwd(GR, a, pR[i], gR[i], true, da, dbr, accR);
+            dS = da * (idC ? 1.f : gate_dpnot(S, qC, kC));
+        }
+        if (gC) {
+            const float a = idR ? T : dfol_pnot(T, qR, kR);
+            float da;
+            gate_bwd(GC, a, pC[i], gC[i], true, da, dbc, accC);
+            dT = da * (idR ? 1.f : gate_dpnot(T, qR, kR));
+        }
+        sGR[i] = dS;
+        sGC[i] = dT;
+        sDR[i] = dbr;
+        sDC[i] = dbc;
+    }
+    __syncthreads();
+    // sweep 2
+    for (int c0 = 0; c0 < NS; c0 += 64) {
+        const int c = c0 + lane;
+        float dpc = 0.f;
+        const float pc = c < n ? pC[c] : 0.f;
+        const float gcc = c < n ? sGC[c] : 0.f;
+        for (int r = w; r < NS; r += nw) {
+            float dl = 0.f, dpr_part = 0.f;
+            if (r < n && c < n && c != r) {
+                const float raw = tp[(int64_t)r * NS + c];
+                const float v = gate_prep(raw, any_neg, alpha_n, cn), ea = dfol_exp(v);
+                float dv = 0.f;
+                if (gR) {                                      // t = log(max(qC + kC m, eps)), m = e^G_C(v, pc)
+                    float zb[6];
+                    gate_zb(GC, pc, zb);
+                    const float u = fmaf(kC, gate_m(GC, v, ea, zb, dfol_exp(pc)), qC);
+                    const float dm = u > DFOL_EPS ? sGR[r] * kC / u : 0.f;
+                    float da, db;
+                    gate_bwd(GC, v, pc, dm, false, da, db, accC);
+                    dv += da;
+                    dpc += db;
+                }
+                if (gC) {
+                    const float pr = pR[r];
+                    float zb[6];
+                    gate_zb(GR, pr, zb);
+                    const float u = fmaf(kR, gate_m(GR, v, ea, zb, dfol_exp(pr)), qR);
+                    const float dm = u > DFOL_EPS ? gcc * kR / u : 0.f;
+                    float da, db;
+                    gate_bwd(GR, v, pr, dm, false, da, db, accR);
+                    dv += da;
+                    dpr_part = db;
+                }
+                dl = dv * gate_dprep(raw, any_neg, alpha_n, cn);
+            }
+            if (gt && c < NS) gt[(int64_t)r * NS + c] = dl;
+            if (g_prior_R) {                                   // row totals over the column chunks collect in LDS (sS is free by now)
+                dpr_part = dfol_wave_sum(dpr_part);
+                if (lane == 0 && r < n) sS[r] = (c0 == 0 ? sDR[r] : sS[r]) + dpr_part;
+            }
+        }
+        if (c < NS) part(w, c) = dpc;
+    }
+    // the parameter sums of this workgroup: wavefront totals, then the wavefronts in order
+#pragma unroll
+    for (int k = 0; k < 18; ++k) {
+        const float a = dfol_wave_sum(accR[k]), b = dfol_wave_sum(accC[k]);
+        if (lane == 0) {
+            wsum[w * 36 + k] = a;
+            wsum[w * 36 + 18 + k] = b;
+        }
+    }
+    __syncthreads();
+    for (int c = tid; c < NS; c += nt) {
+        if (g_prior_C) {
+            float t = part(0, c);
+            for (int j = 1; j < nw; ++j) t += part(j, c);
+            g_prior_C[(int64_t)p * NS + c] = c < n ? t + sDC[c] : 0.f;
+        }
+        if (g_prior_R) g_prior_R[(int64_t)p * NS + c] = c < n ? sS[c] : 0.f;
+    }
+    if (tid < 36) {
+        float s = wsum[tid];
+        for (int j = 1; j < nw; ++j) s += wsum[j * 36 + tid];
+        sc[tid] = s;
+    }
+}
+
+template <int LPR>
+void launch_relate_gate(hipStream_t st, const float* pR, const float* pC, const float* tile, const int32_t* pred_q, const int32_t* n_obj,
+                        const float* qR, const float* qC, const uint8_t* neg, int any_neg, const uint8_t* active, const uint8_t* want, int bR,
+                        int bC, int P, int NS, int flags, const float* gR, const float* gC, float* oR, float* oC) {
+    hipLaunchKernelGGL(relate_gate_fwd_kernel<LPR>, dim3(dfol_cdiv(P, 4)), dim3(256), 0, st, pR, pC, tile, pred_q, n_obj, qR, qC, neg, any_neg,
+                       active, want, bR, bC, P, NS, flags, gR, gC, oR, oC);
+}
+
+}      // namespace
+
+extern "C" int dfol_filter_gate_fwd_f32(const float* att_in, const float* ll, const int32_t* pred_q, const int32_t* n_obj, const uint8_t* neg,
+                                        int32_t any_neg, const uint8_t* active, int32_t P, int32_t NS, const float* gate, float* att_out,
+                                        void* stream) {
+    DFOL_REQUIRE(P >= 0 && NS > 0 && NS % 4 == 0, "filter_gate_fwd: bad sizes P=%d NS=%d", P, NS);
+    if (P == 0) return 0;
+    DFOL_REQUIRE(att_in && ll && pred_q && n_obj && gate && att_out, "filter_gate_fwd: null pointer");
+    DFOL_REQUIRE(!any_neg || neg, "filter_gate_fwd: any_neg set but neg is NULL");
+    const int64_t total4 = (int64_t)P * (NS / 4);
+    hipLaunchKernelGGL(filter_gate_fwd_kernel, dim3(dfol_cdiv(total4, 256)), dim3(256), 0, (hipStream_t)stream, att_in, ll, pred_q, n_obj, neg,
+                       any_neg, active, total4, NS / 4, gate, att_out);
+    DFOL_LAUNCH_CHECK("filter_gate_fwd");
+    return 0;
+}
+
+extern "C" int64_t dfol_filter_gate_bwd_scratch(int32_t P, int32_t NS) {
+    return P <= 0 || NS <= 0 ? 0 : (int64_t)dfol_cdiv((int64_t)P * NS, FG_THREADS) * 18;
+}
+
+extern "C" int dfol_filter_gate_bwd_f32(const float* g_out, const float* att_in, const float* ll, const int32_t* pred_q, const int32_t* n_obj,
+                                        const uint8_t* neg, int32_t any_neg, const uint8_t* active, int32_t P, int32_t NS, const float* gate,
+                                        float* scratch, float* g_prior, float* g_ll, float* g_gate, void* stream) {
+    DFOL_REQUIRE(P >= 0 && NS > 0 && NS % 4 == 0, "filter_gate_bwd: bad sizes P=%d NS=%d", P, NS);
+    DFOL_REQUIRE(g_gate, "filter_gate_bwd: null pointer (g_gate)");
+    hipStream_t st = (hipStream_t)stream;
+    if (P == 0) {
+        hipLaunchKernelGGL(gate_param_reduce_kernel, dim3(18), dim3(64), 0, st, (const float*)nullptr, (int64_t)0, 18, g_gate, (float*)nullptr);
+        DFOL_LAUNCH_CHECK("filter_gate_bwd (reduce)");
+        return 0;
+    }
+    DFOL_REQUIRE(g_out && att_in && ll && pred_q && n_obj && gate && scratch, "filter_gate_bwd: null pointer");
+    DFOL_REQUIRE(!any_neg || neg, "filter_gate_bwd: any_neg set but neg is NULL");
+    const int64_t total = (int64_t)P * NS;
+    const int blocks = dfol_cdiv(total, FG_THREADS);
+    hipLaunchKernelGGL(filter_gate_bwd_kernel, dim3(blocks), dim3(FG_THREADS), 0, st, g_out, att_in, ll, pred_q, n_obj, neg, any_neg, active, total,
+                       NS, gate, scratch, g_prior, g_ll);
+    DFOL_LAUNCH_CHECK("filter_gate_bwd");
+    hipLaunchKernelGGL(gate_param_reduce_kernel, dim3(18), dim3(64), 0, st, (const float*)scratch, (int64_t)blocks, 18, g_gate, (float*)nullptr);
+    DFOL_LAUNCH_CHECK("filter_gate_bwd (reduce)");
+    return 0;
+}
+
+extern "C" int dfol_relate_gate_fwd_f32(const float* prior_s, const float* prior_o, const float* tile, const int32_t* pred_q,
+                                        const int32_t* n_obj, const float* quant_s, const float* quant_o, const uint8_t* neg, int32_t any_neg,
+                                        const uint8_t* active, const uint8_t* want, int32_t P, int32_t NS, int32_t orientation, int32_t flags,
+                                        const float* gate_s, const float* gate_o, float* post_s, float* post_o, void* stream) {
+    DFOL_REQUIRE(P >= 0 && NS > 0 && NS % 4 == 0, "relate_gate_fwd: bad sizes P=%d NS=%d (NS: a multiple of 4)", P, NS);
+    DFOL_REQUIRE(orientation == 0 || orientation == 1, "relate_gate_fwd: bad orientation %d", orientation);
+    if (P == 0) return 0;
+    DFOL_REQUIRE(prior_s && prior_o && tile && pred_q && n_obj && quant_s && quant_o && gate_s && gate_o, "relate_gate_fwd: null pointer");
+    DFOL_REQUIRE(post_s || post_o, "relate_gate_fwd: no output requested");
+    DFOL_REQUIRE(!any_neg || neg, "relate_gate_fwd: any_neg set but neg is NULL");
+    const bool sr = orientation == DFOL_TILE_SUBJECT_ROWS;
+    const float *pR = sr ? prior_s : prior_o, *pC = sr ? prior_o : prior_s;
+    const float *qR = sr ? quant_s : quant_o, *qC = sr ? quant_o : quant_s;
+    const float *gR = sr ? gate_s : gate_o, *gC = sr ? gate_o : gate_s;
+    float *oR = sr ? post_s : post_o, *oC = sr ? post_o : post_s;
+    const int bR = sr ? DFOL_WANT_SUBJECT : DFOL_WANT_OBJECT, bC = sr ? DFOL_WANT_OBJECT : DFOL_WANT_SUBJECT;
+    hipStream_t st = (hipStream_t)stream;
+    if (NS > 256) {
+        hipLaunchKernelGGL(relate_gate_big_fwd_kernel, dim3(P), dim3(256), 0, st, pR, pC, tile, pred_q, n_obj, qR, qC, neg, any_neg, active, want,
+                           bR, bC, NS, flags, gR, gC, oR, oC);
+        DFOL_LAUNCH_CHECK("relate_gate_fwd (NS > 256)");
+        return 0;
+    }
+    const int groups = NS / 4;
+#define DFOL_GATE_CASE(L) \
+    launch_relate_gate<L>(st, pR, pC, tile, pred_q, n_obj, qR, qC, neg, any_neg, active, want, bR, bC, P, NS, flags, gR, gC, oR, oC)
+    if (groups <= 1) DFOL_GATE_CASE(1);
+    else if (groups <= 2) DFOL_GATE_CASE(2);
+    else if (groups <= 4) DFOL_GATE_CASE(4);
+    else if (groups <= 8) DFOL_GATE_CASE(8);
+    else if (groups <= 16) DFOL_GATE_CASE(16);
+    else if (groups <= 32) DFOL_GATE_CASE(32);
+    else DFOL_GATE_CASE(64);
+#undef DFOL_GATE_CASE
+    DFOL_LAUNCH_CHECK("relate_gate_fwd");
+    return 0;
+}
+
+extern "C" int dfol_relate_gate_bwd_f32(const float* prior_s, const float* prior_o, const float* tile, const int32_t* pred_q,
+                                        const int32_t* n_obj, const float* quant_s, const float* quant_o, const uint8_t* neg, int32_t any_neg,
+                                        const uint8_t* active, const float* g_post_s, const float* g_post_o, int32_t P, int32_t NS,
+                                        int32_t orientation, int32_t lone_forall_identity, const float* gate_s, const float* gate_o,
+                                        float* scratch, float* g_prior_s, float* g_prior_o, float* g_tile, float* g_gate_s, float* g_gate_o,
+                                        void* stream) {
+    DFOL_REQUIRE(P >= 0 && NS > 0 && NS % 4 == 0 && NS <= 1024, "relate_gate_bwd: bad sizes P=%d NS=%d (NS: a multiple of 4, <= 1024)", P, NS);
+    DFOL_REQUIRE(orientation == 0 || orientation == 1, "relate_gate_bwd: bad orientation");
+    DFOL_REQUIRE(g_gate_s && g_gate_o, "relate_gate_bwd: null pointer (g_gate)");
+    const bool sr = orientation == DFOL_TILE_SUBJECT_ROWS;
+    hipStream_t st = (hipStream_t)stream;
+    if (P > 0) {
+        DFOL_REQUIRE(prior_s && prior_o && tile && pred_q && n_obj && quant_s && quant_o && gate_s && gate_o && scratch && (g_post_s || g_post_o),
+                     "relate_gate_bwd: null pointer");
+        DFOL_REQUIRE(!any_neg || neg, "relate_gate_bwd: any_neg set but neg is NULL");
+        // (5 + waves) NS floats of rows / columns and waves x 36 of parameter sums: eight wavefronts while that stays within 48 KB, else four
+        // (NS <= 1024: 37.4 KB)
+        auto lds_bytes = [NS](int waves) { return ((size_t)(5 + waves) * NS + (size_t)waves * 36) * sizeof(float); };
+        const int waves = lds_bytes(GB_WAVES) <= 48 * 1024 ? GB_WAVES : 4;
+        const size_t lds = lds_bytes(waves);
+        hipLaunchKernelGGL(relate_gate_bwd_kernel, dim3(P), dim3(64 * waves), lds, st, sr ? prior_s : prior_o, sr ? prior_o : prior_s, tile, pred_q,
+                           n_obj, sr ? quant_s : quant_o, sr ? quant_o : quant_s, neg, any_neg, active, sr ? g_post_s : g_post_o,
+                           sr ? g_post_o : g_post_s, NS, lone_forall_identity, sr ? gate_s : gate_o, sr ? gate_o : gate_s, scratch,
+                           sr ? g_prior_s : g_prior_o, sr ? g_prior_o : g_prior_s, g_tile);
+        DFOL_LAUNCH_CHECK("relate_gate_bwd");
+    }
+    hipLaunchKernelGGL(gate_param_reduce_kernel, dim3(36), dim3(64), 0, st, (const float*)scratch, (int64_t)P, 36, sr ? g_gate_s : g_gate_o,
+                       sr ? g_gate_o : g_gate_s);
+    DFOL_LAUNCH_CHECK("relate_gate_bwd (reduce)");
+    return 0;
+}

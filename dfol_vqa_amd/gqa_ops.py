@@ -302,6 +302,8 @@ class GQARelateBatch(GQABatchOperatorBase):
         if torch.is_grad_enabled() and (x._log_attention.requires_grad or prev._log_attention.requires_grad):
             return None
         rel = self._relate
+        if rel._blc.gated():                                   # trainable_gate: the generic gate -> relate -> gate route (no gated one-launch form)
+            return None
         calibrated = op_id in rel._subject_modulations
         if calibrated != (op_id in rel._object_modulations):
             return None                                        # one-sided calibration: RelateBatch.forward handles it

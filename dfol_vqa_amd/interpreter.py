@@ -605,7 +605,18 @@ class BatchInterpreterBase(nn.Module):
             return None                                      # gradients reach the oracle or the calibrator: the differentiable Python operators
         if not hasattr(self, "_ontology"):
             return None
+        if self._gated():                                    # trainable_gate: True - the executor has no gated opcode
+            _lib.fallback("trainable_gate", "the native executor has no gated Filter / Relate instruction",
+                          "runs the Python operator loop on the gated HIP kernels instead of the native executor")
+            return None
         return native_exec.model_spec(self, calibrate)
+
+    def _gated(self):
+        """Do the logic cells hold trainable gates (`trainable_gate: True`)?  (The modules do not change after construction: looked up once.)"""
+        gated = self.__dict__.get("_gated_cells")
+        if gated is None:
+            gated = self.__dict__["_gated_cells"] = any(getattr(m, "_trainable_gate", False) for m in self.modules())
+        return gated
 
     def _run_batches(self, program_batch_list, is_training, modulator_switch, return_trace=False):
         from . import _lib
@@ -628,8 +639,9 @@ class BatchInterpreterBase(nn.Module):
             if self._has_modulator and modulator_switch:
                 self._calibration_passes(world, program_batch, device, is_training)
             if world._lazy is not None:
-                # with a training calibrator the attentions carry gradients and the relates run on the generic cell
-                self._oracle.prefetch_relations(world, program_batch, fused=not (self._has_modulator and modulator_switch and torch.is_grad_enabled()))
+                # with a training calibrator the attentions carry gradients and the relates run on the generic cell; a gated model's always do
+                self._oracle.prefetch_relations(world, program_batch, fused=not (self._has_modulator and modulator_switch and torch.is_grad_enabled())
+                                                and not self._gated())
                 if hasattr(self._oracle, "prefetch_attributes"):
                     self._oracle.prefetch_attributes(world, program_batch)
             ops = program_batch._op_batch_list

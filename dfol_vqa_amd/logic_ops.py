@@ -14,6 +14,15 @@ from .fol_types import BatchAttentionState, BatchVariableSet, Quantifier, TokenT
 from .host_util import upload, detect_negations, get_lowered, is_valid_token
 
 
+class NeuralLogicGate(nn.Module):
+    """batch_base_ops.py:19-38: the learned soft conjunction G(a, b) that replaces `a + b` where the cell joins a prior.  It only holds
+    the parameters (the reference's names and shapes); the arithmetic is in csrc/dfol_logic_gate.hip, inside the gated cell kernels."""
+
+    def __init__(self):
+        super(NeuralLogicGate, self).__init__()
+        self._linear = nn.Linear(2, 6)
+
+
 class BatchBayesianLogicCell(nn.Module):
     """batch_base_ops.py:42-237.  Block-layout shapes:
          log_prior      [Q, arity, NS]
@@ -24,12 +33,32 @@ class BatchBayesianLogicCell(nn.Module):
 
     def __init__(self, arity, trainable_module_type=None, feature_dim=1, trainable_gate=False):
         super(BatchBayesianLogicCell, self).__init__()
-        if trainable_module_type is not None or trainable_gate:
-            raise NotImplementedError("trainable_gate / operator_layers_config are off in every shipped config (SURVEY.md §2 row 3)")
+        if trainable_module_type is not None:
+            raise NotImplementedError("operator_layers_config (trainable_module_type) / feature_dim > 1 are off in every shipped config "
+                                      "(SURVEY.md §2 row 3)")
         if arity not in (1, 2):
             raise NotImplementedError("Likelihood for arity > 2 is not implemented.")      # cf. :210
         self._arity = arity
         self._feature_dim = feature_dim
+        self._trainable_gate = bool(trainable_gate)
+        if trainable_gate:
+            self._nlg = nn.ModuleList([NeuralLogicGate() for _ in range(arity)])           # :51-52
+
+    def gated(self):
+        return self._trainable_gate
+
+    def _gate(self, k):
+        lin = self._nlg[k]._linear
+        return lin.weight, lin.bias
+
+    def relate(self, prior_s, prior_o, tile, pred_q, n_obj, quant_s, quant_o, neg, active, want, orientation, **kw):
+        """The arity-2 launch: L.relate_fwd, or its gated form when the cell holds gates."""
+        if self._trainable_gate:
+            if tile.dtype != torch.float32:
+                raise L.DfolError("trainable_gate: True reads fp32 relation tiles; relation_tile_dtype: bf16 does not combine with it")
+            return L.relate_gate_fwd(prior_s, prior_o, tile, pred_q, n_obj, quant_s, quant_o, *self._gate(0), *self._gate(1), neg, active, want,
+                                     orientation, **kw)
+        return L.relate_fwd(prior_s, prior_o, tile, pred_q, n_obj, quant_s, quant_o, neg, active, want, orientation, **kw)
 
     def forward(self, log_prior, log_likelihood, quantifiers, dim_order, batch_object_map=None, predicate_question_map=None,
                 is_negated=None, default_log_likelihood=-30, active=None, want=None, orientation=L.TILE_SUBJECT_ROWS,
@@ -50,11 +79,14 @@ class BatchBayesianLogicCell(nn.Module):
         pred_q = world._ident if predicate_question_map is None else predicate_question_map
         neg = None if is_negated is None else is_negated.to(torch.uint8)
         if self._arity == 1:
-            out = L.filter_fwd(log_prior[:, 0, :].contiguous(), ll.contiguous(), pred_q, world._n_obj, neg, active)
+            if self._trainable_gate:
+                out = L.filter_gate_fwd(log_prior[:, 0, :].contiguous(), ll.contiguous(), pred_q, world._n_obj, *self._gate(0), neg, active)
+            else:
+                out = L.filter_fwd(log_prior[:, 0, :].contiguous(), ll.contiguous(), pred_q, world._n_obj, neg, active)
             return out.unsqueeze(1)
-        ps, po = L.relate_fwd(log_prior[:, 0, :].contiguous(), log_prior[:, 1, :].contiguous(), ll.contiguous(), pred_q, world._n_obj,
-                              quantifiers[:, 0].contiguous(), quantifiers[:, 1].contiguous(), neg, active, want, orientation,
-                              lone_forall_identity=(P == 1), need_s=need[0], need_o=need[1])
+        ps, po = self.relate(log_prior[:, 0, :].contiguous(), log_prior[:, 1, :].contiguous(), ll.contiguous(), pred_q, world._n_obj,
+                             quantifiers[:, 0].contiguous(), quantifiers[:, 1].contiguous(), neg, active, want, orientation,
+                             lone_forall_identity=(P == 1), need_s=need[0], need_o=need[1])
         if ps is None or po is None:
             return ps, po
         return torch.stack([ps, po], 1)
@@ -267,9 +299,9 @@ class RelateBatch(BatchOperatorBase):
         _, neg_dev, valid_dev = low.on(dev)
         tile = self._oracle.block_likelihood(TokenType.RELATION, low, pred_q, range(predicate_num) if identity else host_map,
                                              world, default_log_likelihood, normalized_probability)
-        ps, po = L.relate_fwd(subject_variable_set._log_attention, object_variable_set._log_attention, tile, pred_q, world._n_obj,
-                              q_s, q_o, neg_dev if low.any_neg else None, None if low.all_valid else valid_dev, want,
-                              L.TILE_SUBJECT_ROWS, lone_forall_identity=(predicate_num == 1), diag_absent=True)
+        ps, po = self._blc.relate(subject_variable_set._log_attention, object_variable_set._log_attention, tile, pred_q, world._n_obj,
+                                  q_s, q_o, neg_dev if low.any_neg else None, None if low.all_valid else valid_dev, want,
+                                  L.TILE_SUBJECT_ROWS, lone_forall_identity=(predicate_num == 1), diag_absent=True)
         n_prev = subject_variable_set._prev_variable_sets_num + object_variable_set._prev_variable_sets_num + 1
         pqm = None if identity else pred_q
         new_subject_set = BatchVariableSet(subject_variable_set._name, dev, subject_variable_set.object_num(), predicate_num,

@@ -49,6 +49,66 @@ def relate_fwd(prior_s, prior_o, tile, pred_q, n_obj, quant_s, quant_o, neg=None
                            need_s, need_o, diag_absent)
 
 
+# ---- the cell with the trainable gate (csrc/dfol_logic_gate.hip) -------------------------------------
+def _gate_grads(g_gate, ctx, at):
+    return (g_gate[:12].view(6, 2) if ctx.needs_input_grad[at] else None), (g_gate[12:] if ctx.needs_input_grad[at + 1] else None)
+
+
+class _FilterGate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, att_in, ll, weight, bias, pred_q, n_obj, neg, active):
+        gate = _lib.gate_params(weight, bias)
+        ctx.save_for_backward(att_in, ll, pred_q, n_obj, gate, neg, active)
+        return _lib.filter_gate_fwd(att_in, ll, pred_q, n_obj, gate, neg, active)
+
+    @staticmethod
+    def backward(ctx, g):
+        att_in, ll, pred_q, n_obj, gate, neg, active = ctx.saved_tensors
+        g_prior, g_ll, g_gate = _lib.filter_gate_bwd(g.contiguous(), att_in, ll, pred_q, n_obj, gate, neg, active)
+        return (g_prior if ctx.needs_input_grad[0] else None), (g_ll if ctx.needs_input_grad[1] else None), \
+            *_gate_grads(g_gate, ctx, 2), None, None, None, None
+
+
+def filter_gate_fwd(att_in, ll, pred_q, n_obj, weight, bias, neg=None, active=None):
+    """filter_fwd of a cell with trainable_gate: weight [6, 2] / bias [6] of the gate of axis 0 (NeuralLogicGate._linear)."""
+    if _needs_grad(att_in, ll, weight, bias):
+        return _FilterGate.apply(att_in, ll, weight, bias, pred_q, n_obj, neg, active)
+    return _lib.filter_gate_fwd(att_in, ll, pred_q, n_obj, _lib.gate_params(weight, bias), neg, active)
+
+
+class _RelateGate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, prior_s, prior_o, tile, w_s, b_s, w_o, b_o, pred_q, n_obj, quant_s, quant_o, neg, active, want, orientation, lone, diag_absent):
+        gate_s, gate_o = _lib.gate_params(w_s, b_s), _lib.gate_params(w_o, b_o)
+        ctx.save_for_backward(prior_s, prior_o, tile, pred_q, n_obj, quant_s, quant_o, gate_s, gate_o, neg, active, want)
+        ctx.orientation, ctx.lone = orientation, lone
+        return _lib.relate_gate_fwd(prior_s, prior_o, tile, pred_q, n_obj, quant_s, quant_o, gate_s, gate_o, neg, active, want, orientation, lone,
+                                    diag_absent=diag_absent)
+
+    @staticmethod
+    def backward(ctx, gs, go):
+        prior_s, prior_o, tile, pred_q, n_obj, quant_s, quant_o, gate_s, gate_o, neg, active, want = ctx.saved_tensors
+        gs, go = gs.contiguous(), go.contiguous()
+        if want is not None:                                     # a posterior the forward did not produce carries no gradient
+            gs = gs * ((want & 1) > 0).to(gs.dtype).unsqueeze(1)
+            go = go * ((want & 2) > 0).to(go.dtype).unsqueeze(1)
+        g_ps, g_po, g_tile, gg_s, gg_o = _lib.relate_gate_bwd(prior_s, prior_o, tile, pred_q, n_obj, quant_s, quant_o, gate_s, gate_o, neg, active,
+                                                              gs, go, ctx.orientation, ctx.lone)
+        return (g_ps if ctx.needs_input_grad[0] else None), (g_po if ctx.needs_input_grad[1] else None), \
+            (g_tile if ctx.needs_input_grad[2] else None), *_gate_grads(gg_s, ctx, 3), *_gate_grads(gg_o, ctx, 5), \
+            None, None, None, None, None, None, None, None, None, None
+
+
+def relate_gate_fwd(prior_s, prior_o, tile, pred_q, n_obj, quant_s, quant_o, w_s, b_s, w_o, b_o, neg=None, active=None, want=None,
+                    orientation=_lib.TILE_SUBJECT_ROWS, lone_forall_identity=False, need_s=True, need_o=True, diag_absent=False):
+    """relate_fwd of a cell with trainable_gate: (w_s, b_s) the gate of axis 0 (joins the subject prior), (w_o, b_o) of axis 1."""
+    if _needs_grad(prior_s, prior_o, tile, w_s, b_s, w_o, b_o):
+        return _RelateGate.apply(prior_s, prior_o, tile, w_s, b_s, w_o, b_o, pred_q, n_obj, quant_s, quant_o, neg, active, want, int(orientation),
+                                 bool(lone_forall_identity), bool(diag_absent))
+    return _lib.relate_gate_fwd(prior_s, prior_o, tile, pred_q, n_obj, quant_s, quant_o, _lib.gate_params(w_s, b_s), _lib.gate_params(w_o, b_o),
+                                neg, active, want, orientation, lone_forall_identity, need_s, need_o, diag_absent)
+
+
 # ---- quantify ----------------------------------------------------------------------------------------
 def quantify_fwd(att, quant, pred_q, n_obj):
     if _needs_grad(att):

@@ -50,7 +50,8 @@ extern "C" {
  * dfol_dropout_f32 and dfol_pair_features_bwd_f32, and the train step's weight gradient over the store's rows: dfol_linear_wgrad_rows_supported,
  * dfol_linear_wgrad_bias_rows_f32 and dfol_linear_wgrad_bias_rows_bf16, and the bf16 form of the store: dfol_store_round_bf16,
  * dfol_gather_object_rows_bf16_f32, dfol_linear_rows_bf16t_supported, dfol_linear_act_rows_bf16t_f32, dfol_linear_wgrad_rows_bf16t_supported,
- * dfol_linear_wgrad_bias_rows_bf16t and dfol_set_feature_rows_bf16;
+ * dfol_linear_wgrad_bias_rows_bf16t and dfol_set_feature_rows_bf16, and the logic cell with the trainable gate: dfol_filter_gate_fwd_f32,
+ * dfol_relate_gate_fwd_f32, dfol_filter_gate_bwd_scratch, dfol_filter_gate_bwd_f32 and dfol_relate_gate_bwd_f32;
  * a caller that needs them checks for the symbol, and a table that names an opcode an older library lacks is refused by it ("unknown opcode"). */
 #define DFOL_ABI_VERSION 3
 
@@ -158,6 +159,28 @@ int dfol_relate_fwd_f32(const float* prior_s, const float* prior_o, const float*
                         const int32_t* n_obj, const float* quant_s, const float* quant_o, const uint8_t* neg,
                         int32_t any_neg, const uint8_t* active, const uint8_t* want, int32_t P, int32_t NS,
                         int32_t orientation, int32_t flags, float* post_s, float* post_o, void* stream);
+
+/* ---- the logic cell with the trainable gate (trainable_gate: True) ---------------------------------------
+ * Replaces NeuralLogicGate, batch_base_ops.py:19-38, where BatchBayesianLogicCell._forward_core joins a prior (:99-100 and :135-136):
+ * every `x + log_p` of the cell is G_k(x, log_p), k the axis of the prior.  With the gate's nn.Linear(2, 6) as float[18]
+ * (W [6, 2] row-major, then c [6]) and eps = 1e-20 (util.py:22-25, :46-47):
+ *     alpha = sigmoid(W [a, b] + c),  va = alpha0 + alpha3 (1 - 2 alpha0) e^a,  vb = alpha1 + alpha4 (1 - 2 alpha1) e^b,
+ *     G(a, b) = log(max(alpha2 + alpha5 (1 - 2 alpha2) max(va, eps) max(vb, eps), eps))
+ * Arity 1 (batch_base_ops.py:135-136 for FilterBatch): att_out[p][o] = G_0(l'[p][o], att_in[pred_q[p]][o]).  Every other argument, the
+ * no-op rows and the padding are dfol_filter_fwd_f32's.   gate: device float[18] of axis 0. */
+int dfol_filter_gate_fwd_f32(const float* att_in, const float* ll, const int32_t* pred_q, const int32_t* n_obj, const uint8_t* neg,
+                             int32_t any_neg, const uint8_t* active, int32_t P, int32_t NS, const float* gate, float* att_out, void* stream);
+
+/* Arity 2 (batch_base_ops.py:99-100, :135-136 for RelateBatch), with F and l' of dfol_relate_fwd_f32:
+ *   post_s[s] = G_0( F_o( sum_{o != s} F_o( G_1(l'[s,o], prior_o[o]) ) ), prior_s[s] )
+ *   post_o[o] = G_1( F_s( sum_{s != o} F_s( G_0(l'[s,o], prior_s[s]) ) ), prior_o[o] )
+ * gate_s / gate_o: device float[18] of axis 0 (joins the subject prior) / axis 1 (the object prior).  Every other argument, want,
+ * orientation, flags (DFOL_RELATE_DIAG_ABSENT is accepted and not needed), the no-op rows and the padding are dfol_relate_fwd_f32's.
+ * An EXISTS aggregation is kept in the complement form over the gates' probabilities e^G. */
+int dfol_relate_gate_fwd_f32(const float* prior_s, const float* prior_o, const float* tile, const int32_t* pred_q, const int32_t* n_obj,
+                             const float* quant_s, const float* quant_o, const uint8_t* neg, int32_t any_neg, const uint8_t* active,
+                             const uint8_t* want, int32_t P, int32_t NS, int32_t orientation, int32_t flags, const float* gate_s,
+                             const float* gate_o, float* post_s, float* post_o, void* stream);
 
 /* Relate with ONE posterior: what GQARelateBatch / verify_rel / choose_rel keep (batch_gqa_ops.py:364-371: gate x/prev into
  * subject/object, RelateBatch, gate the wanted posterior back).  Fuses the three gates and the arity-2 cell:
@@ -769,6 +792,21 @@ int dfol_relate_bwd_f32(const float* prior_s, const float* prior_o, const float*
                         const float* quant_s, const float* quant_o, const uint8_t* neg, int32_t any_neg, const uint8_t* active,
                         const float* g_post_s, const float* g_post_o, int32_t P, int32_t NS, int32_t orientation,
                         int32_t lone_forall_identity, float* g_prior_s, float* g_prior_o, float* g_tile, void* stream);
+
+/* Backward of the gated cell (the reference differentiates batch_base_ops.py:19-38 inside :62-151 by autograd): the formulas as written,
+ * clamps included.  g_gate* [18] are WRITTEN: the sum over every element of the launch, taken without atomics (thread -> wavefront ->
+ * workgroup -> one row of `scratch` per workgroup -> a second kernel that adds the rows in a fixed order), bit-identical from run to run.
+ * The priors' gradients are PER PREDICATE ([P, NS], written): reduce them with dfol_reduce_by_question_f32.
+ * scratch: dfol_filter_gate_bwd_scratch(P, NS) floats for the filter, 36 P floats for the relate (NS <= 1024). */
+int64_t dfol_filter_gate_bwd_scratch(int32_t P, int32_t NS);
+int dfol_filter_gate_bwd_f32(const float* g_out, const float* att_in, const float* ll, const int32_t* pred_q, const int32_t* n_obj,
+                             const uint8_t* neg, int32_t any_neg, const uint8_t* active, int32_t P, int32_t NS, const float* gate,
+                             float* scratch, float* g_prior, float* g_ll, float* g_gate, void* stream);
+int dfol_relate_gate_bwd_f32(const float* prior_s, const float* prior_o, const float* tile, const int32_t* pred_q, const int32_t* n_obj,
+                             const float* quant_s, const float* quant_o, const uint8_t* neg, int32_t any_neg, const uint8_t* active,
+                             const float* g_post_s, const float* g_post_o, int32_t P, int32_t NS, int32_t orientation,
+                             int32_t lone_forall_identity, const float* gate_s, const float* gate_o, float* scratch, float* g_prior_s,
+                             float* g_prior_o, float* g_tile, float* g_gate_s, float* g_gate_o, void* stream);
 
 int dfol_quantify_bwd_f32(const float* g_lp, const float* att, const float* quant, const int32_t* pred_q, const int32_t* n_obj,
                           int32_t P, int32_t NS, float* g_att, void* stream);

@@ -3,6 +3,11 @@
 
 usage: python tools/bench_ops.py [--batch 256] [--nmin 10] [--nmax 100] [--steps 5]
 One JSON line per operator kind: questions/s of a batch of `--batch` programs  select -> filter -> relate -> <terminal op>.
+
+       python tools/bench_ops.py --trainable-gate [--batch 256] [--nmax 100] [--rounds 15] [--reps 20] [--out FILE]
+The logic cell's launches with and without the trainable gate (`trainable_gate: True`, csrc/dfol_logic_gate.hip): filter and relate, forward and
+backward, at `--batch` predicates x `--nmax` objects, gated and ungated alternating in one process (every round times each of the eight
+launches over `--reps` back-to-back launches between two events); one JSON line per launch with the median, minimum and maximum over the rounds.
 """
 import argparse
 import json
@@ -47,8 +52,69 @@ def questions(kind, count, nmin, nmax, names, seed):
     return qs
 
 
+def trainable_gate_launches(args):
+    """The eight launches of the logic cell, gated and ungated, alternating."""
+    from dfol_vqa_amd import _lib as L
+    from dfol_vqa_amd import synthetic as syn
+    dev = torch.device("cuda", 0)
+    rng = np.random.RandomState(17)
+    P, n = args.batch, args.nmax
+    NS = (n + 3) // 4 * 4
+    t = lambda a, dt=torch.float32: torch.tensor(np.ascontiguousarray(a), dtype=dt, device=dev)
+    ll, tile = np.full((P, NS), -30, np.float32), np.full((P, NS, NS), -30, np.float32)
+    ll[:, :n] = syn.table_log_likelihood(rng, (P, n), "mix10")
+    tile[:, :n, :n] = syn.table_log_likelihood(rng, (P, n, n), "mix10")
+    tile[:, np.arange(n), np.arange(n)] = -30
+    prior = np.zeros((P, NS), np.float32)
+    prior[:, :n] = -rng.uniform(0.01, 2.0, (P, n))
+    pa, pb, ll, tile = t(prior), t(prior[::-1]), t(ll), t(tile)
+    pq, n_obj = t(np.arange(P), torch.int32), t(np.full(P, n), torch.int32)
+    pq._dfol_sorted = True
+    ones = t(np.ones(P))
+    gs, go = (L.gate_params(t(rng.uniform(-0.7, 0.7, (6, 2))), t(rng.uniform(-0.7, 0.7, 6))) for _ in range(2))
+    g1, g2 = t(rng.normal(size=(P, NS))), t(rng.normal(size=(P, NS)))
+    launches = [
+        ("filter_fwd", lambda: L.filter_fwd(pa, ll, pq, n_obj)),
+        ("filter_gate_fwd", lambda: L.filter_gate_fwd(pa, ll, pq, n_obj, gs)),
+        ("relate_fwd", lambda: L.relate_fwd(pa, pb, tile, pq, n_obj, ones, ones)),
+        ("relate_gate_fwd", lambda: L.relate_gate_fwd(pa, pb, tile, pq, n_obj, ones, ones, gs, go)),
+        ("filter_bwd", lambda: L.filter_bwd(g1, ll, pq, n_obj, None, None, P)),
+        ("filter_gate_bwd", lambda: L.filter_gate_bwd(g1, pa, ll, pq, n_obj, gs, None, None)),
+        ("relate_bwd", lambda: L.relate_bwd(pa, pb, tile, pq, n_obj, ones, ones, None, None, g1, g2, L.TILE_SUBJECT_ROWS, False)),
+        ("relate_gate_bwd", lambda: L.relate_gate_bwd(pa, pb, tile, pq, n_obj, ones, ones, gs, go, None, None, g1, g2, L.TILE_SUBJECT_ROWS, False)),
+    ]
+    for _, fn in launches:                                     # (the first launches of a kernel load its code object)
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name, _ in launches}
+    for _ in range(args.rounds):
+        for name, fn in launches:                              # gated and ungated side by side in every round
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(args.reps):
+                fn()
+            e.record()
+            e.synchronize()
+            times[name].append(s.elapsed_time(e) * 1e3 / args.reps)
+    lines = []
+    for name, _ in launches:
+        v = np.sort(np.asarray(times[name]))
+        lines.append(json.dumps({"launch": name, "predicates": P, "objects": n, "us_median": float(np.median(v)), "us_min": float(v[0]),
+                                 "us_max": float(v[-1]), "rounds": args.rounds, "reps": args.reps,
+                                 "note": "backward entries include their reduce-by-question launches; host-side allocation of the outputs is inside the timed region"}))
+        print(lines[-1], flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--trainable-gate", action="store_true", help="time the gated and ungated logic-cell launches instead of the operator programs")
+    ap.add_argument("--rounds", type=int, default=15)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--out", default=None, help="--trainable-gate: also write the JSON lines to this file")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--nmin", type=int, default=10)
     ap.add_argument("--nmax", type=int, default=100)
@@ -56,6 +122,8 @@ def main():
     ap.add_argument("--kinds", default=",".join(KINDS))
     ap.add_argument("--graph", type=int, default=1, help="1: also time the forward replayed as a captured HIP graph")
     args = ap.parse_args()
+    if args.trainable_gate:
+        return trainable_gate_launches(args)
     device = torch.device("cuda", 0)
     import dfol_vqa_amd as D
     from dfol_vqa_amd import experiment

@@ -1262,6 +1262,190 @@ def g25():
     print("wrote g25_gqa_metadata")
 
 
+# ---------------------------------------------------------------------------------------- g25 (trainable gate)
+def g25_gate():
+    """BatchBayesianLogicCell(arity, trainable_gate=True), batch_base_ops.py:19-38 inside :62-151: output and the gradients of
+    sum(out * cot) with respect to prior, likelihood and each gate's weight and bias, fp32 + fp64, arity 1 and 2, ragged images, P != Q,
+    mixed quantifiers, negation absent / mixed / all set, a lone predicate.  The cotangent is zero on the objects of other images.  Gate weights are drawn here (nn.Linear's default scale, one case
+    at magnitude ~4) and stored.  The state-dict keys of a gated FilterBatch / RelateBatch cell are stored with their shapes.  (The name
+    g25 alone is the metadata family above.)"""
+    arrays, meta = {}, {"source": "batch_base_ops.py:19-38, 62-151, 153-215 (trainable_gate=True)", "cases": []}
+    rng = np.random.RandomState(2525)
+    specs = [
+        # name, n_list, k_list, arity, quantifier mode, negation (None / "mixed" / "all"), gate scale
+        ("a1_lone", [5], [1], 1, "exists", None, 0.7),
+        ("a1_batch", [1, 2, 5, 3], [1, 1, 1, 1], 1, "mixed", None, 0.7),
+        ("a1_expand_neg", [4, 6, 3], [2, 1, 3], 1, "mixed", "mixed", 0.7),
+        ("a1_allneg_w4", [3, 7], [2, 2], 1, "mixed", "all", 4.0),
+        ("a2_lone_exists", [5], [1], 2, "exists", None, 0.7),
+        ("a2_lone_forall", [4], [1], 2, "forall", None, 0.7),
+        ("a2_batch", [1, 2, 5, 4], [1, 1, 1, 1], 2, "mixed", None, 0.7),
+        ("a2_expand_neg", [4, 5, 3], [2, 1, 2], 2, "mixed", "mixed", 0.7),
+        ("a2_allneg", [3, 6, 2], [1, 2, 1], 2, "mixed", "all", 0.7),
+        ("a2_expand_w4", [6, 3, 7], [1, 3, 2], 2, "mixed", None, 4.0),
+    ]
+    for name, n_list, k_list, arity, qmode, neg, scale in specs:
+        pr = flat_problem(rng, n_list, k_list, arity, "mix10")
+        Q, O, P = pr["Q"], pr["O"], pr["P"]
+        if qmode == "exists":
+            quant = np.ones((P, arity), np.float32)
+        elif qmode == "forall":
+            quant = np.zeros((P, arity), np.float32)
+        else:
+            quant = (rng.uniform(size=(Q, arity)) < 0.5).astype(np.float32)[pr["pq"]]
+            quant[0, :] = [1.0, 0.0][:arity]                       # both kinds in every mixed case
+            if P > 1:
+                quant[-1, :] = [0.0, 1.0][:arity]
+        is_neg = None if neg is None else (np.ones(P, np.float32) if neg == "all" else (np.arange(P) % 2 == 0).astype(np.float32))
+        W = rng.uniform(-scale, scale, size=(arity, 6, 2)).astype(np.float32)
+        c = rng.uniform(-scale, scale, size=(arity, 6)).astype(np.float32)
+        # (the flat layout leaves values on the objects of other images, :142-147, for FilterBatch / RelateBatch to drop: no cotangent there)
+        cot = rng.normal(size=(P, arity, O)).astype(np.float32) * (pr["img"][None, :] == pr["pq"][:, None])[:, None, :]
+        for dt, tag in both_dtypes():
+            cell = ref.base_ops.BatchBayesianLogicCell(arity, trainable_gate=True).to(dt)
+            with torch.no_grad():
+                for k in range(arity):
+                    cell._nlg[k]._linear.weight.copy_(torch.tensor(W[k], dtype=dt))
+                    cell._nlg[k]._linear.bias.copy_(torch.tensor(c[k], dtype=dt))
+            bom = sparse_map(pr["img"], np.arange(O), (Q, O), dt)
+            pqm = sparse_map(np.arange(P), pr["pq"], (P, Q), dt) if P != Q else None
+            prior = torch.tensor(pr["prior"], dtype=dt, requires_grad=True)
+            ll = torch.tensor(pr["ll"], dtype=dt, requires_grad=True)
+            out = cell(prior, ll, torch.tensor(quant, dtype=dt), list(range(arity)), bom, pqm,
+                       None if is_neg is None else torch.tensor(is_neg, dtype=dt))
+            (out * torch.tensor(cot, dtype=dt)).sum().backward()
+            arrays["%s_out_%s" % (name, tag)] = out.detach().numpy()
+            arrays["%s_gprior_%s" % (name, tag)] = prior.grad.numpy()
+            arrays["%s_gll_%s" % (name, tag)] = ll.grad.numpy()
+            for k in range(arity):
+                arrays["%s_gW%d_%s" % (name, k, tag)] = cell._nlg[k]._linear.weight.grad.numpy()
+                arrays["%s_gc%d_%s" % (name, k, tag)] = cell._nlg[k]._linear.bias.grad.numpy()
+        for key, v in (("prior", pr["prior"]), ("ll", pr["ll"]), ("quant", quant), ("img", pr["img"]), ("pq", pr["pq"]), ("W", W), ("c", c), ("cot", cot)):
+            arrays["%s_%s" % (name, key)] = v
+        if is_neg is not None:
+            arrays[name + "_neg"] = is_neg
+        meta["cases"].append({"name": name, "n": n_list, "k": k_list, "arity": arity, "neg": neg, "quantifiers": qmode, "gate_scale": scale})
+    meta["state_dict"] = {}
+    for arity, owner in ((1, "filter"), (2, "relate")):
+        cell = ref.base_ops.BatchBayesianLogicCell(arity, trainable_gate=True)
+        meta["state_dict"][owner] = {"_blc." + k: list(v.shape) for k, v in cell.state_dict().items()}
+    save("g25_gate_cell", arrays, meta)
+
+
+def g25_gate_interpreter():
+    """The reference's interpreter with `trainable_gate=True` at g12's reduced dims (gqa_interpreter_experiments.py:107-240 builds it;
+    batch_base_ops.py:19-38 is in every FilterBatch / RelateBatch of its operators): forward results of `exist`, `verify_rel`, `query_attr`
+    and `choose_rel` programs with a filter and a relate hop on ragged scenes, one `_train_batch` per loss type (BINARY, QUERY: loss,
+    log-probabilities, every gate gradient and every oracle gradient in full - they are tiny at these dims), fp32 + fp64, and the model's
+    state-dict key list with shapes."""
+    sys.path.insert(0, ref_harness.REF_SRC)
+    import gqa_interpreter_experiments as gie
+    from nsvqa.train.trainer import VQATrainer
+    fake = types.SimpleNamespace(_device=torch.device("cpu"), _config={})
+    cfg = dict(box_features_dim=32, oracle_input_dim=16, oracle_output_dim=1, word_embedding_dim=mini_ontology.EMBEDDING_DIM,
+               classifier_oracle=True, featurizer_layers_config=[], attribute_network_layers_config=[8],
+               relation_network_layers_config=[8], operator_layers_config=[], normalize_oracle=True, dropout=0.0,
+               freeze_featurizer=False, freeze_attribute_network=False, freeze_relation_network=False,
+               freeze_embedding_network=False, activate_attention_transfer=False, attention_transfer_state_dim=0,
+               freeze_attention_network=False, trainable_gate=True, likelihood_threshold=0, hard_mode=False,
+               verbose=False, model_name="g25", gpu_num=1)
+    exp = gie.GQAObjectBoxExperiment()
+    exp._local_rank = 0
+    torch.manual_seed(25)
+    model = exp.build_model(cfg, ontology, None)
+    rng = np.random.RandomState(250)
+    with torch.no_grad():                                     # gates away from their initial scale, as after some training
+        for k, prm in model.named_parameters():
+            if "._nlg." in k:
+                prm.copy_(torch.tensor(rng.uniform(-1.5, 1.5, tuple(prm.shape)).astype(np.float32)))
+    Q = syn.question
+    D = cfg["box_features_dim"]
+    hop = lambda i, noun="dog", attr="red", rel="on": [op("select", noun), op("filter", attr if i % 3 else "not(%s)" % attr), op("relate", rel, bool(i % 2), "table")]
+    n_fwd = [5, 7, 3, 6, 4]
+    forward = {
+        "exist": [Q(2500 + i, [hop(i)], op("exist"), "yes", syn.feature_scene(2500 + i, n, D)) for i, n in enumerate(n_fwd)],
+        "verify_rel": [Q(2520 + i, [hop(i, "man", "small", "near")], op("verify_rel", "under", bool(i % 2), "cup"), "yes", syn.feature_scene(2520 + i, n, D))
+                       for i, n in enumerate(n_fwd)],
+        "query_attr": [Q(2540 + i, [hop(i, "cup", "blue", "under")], op("query_attr", "color"), "red", syn.feature_scene(2540 + i, n, D))
+                       for i, n in enumerate(n_fwd)],
+        "choose_rel": [Q(2560 + i, [hop(i, "car", "small", "near")], op("choose_rel", ["on", "under"], bool(i % 2), "table"), "on",
+                         syn.feature_scene(2560 + i, n, D)) for i, n in enumerate(n_fwd)],
+    }
+    n_list = [5, 7, 4, 6]
+    train = {
+        "binary": [Q(2600 + i, [hop(i)], op("exist"), "yes" if i % 2 == 0 else "no", syn.feature_scene(2600 + i, n, D)) for i, n in enumerate(n_list)],
+        "query_rel": [Q(2620 + i, [hop(i, "man", "small", "near")], op("choose_rel", ["on", "under"], bool(i % 2), "table"),
+                        "on" if i % 2 == 0 else "under", syn.feature_scene(2620 + i, n, D)) for i, n in enumerate(n_list)],
+    }
+    arrays = {}
+    meta = {"source": "batch_base_ops.py:19-38 in gqa_interpreter_experiments.py:107-240; trainer.py:181-262,429-442", "config": cfg, "forward": {},
+            "train": {}, "state_dict": {k: list(v.shape) for k, v in model.state_dict().items()}}
+    for k, v in model.state_dict().items():
+        if k.startswith("_featurizer.") or k.startswith("_oracle.") or "._nlg." in k:
+            arrays["w:" + k] = v.numpy().copy()
+
+    def batches(qs, dt):
+        pbs = ref_harness.make_collater(ref, 1, "feature").collate(copy.deepcopy(qs))
+        for pb in pbs:
+            pb.create_sparse_tensors()
+            if dt == torch.float64:
+                pb.to(torch.float64)
+                pb._object_batch_index = pb._object_batch_index.long()
+        return pbs
+
+    for name, qs in forward.items():
+        for i, q in enumerate(qs):
+            arrays["fwd:%s:X_%d" % (name, i)] = q["scene"]["X"]
+        fm = {"questions": questions_to_meta(qs)}
+        for dt, tag in both_dtypes():
+            m = (copy.deepcopy(model).double() if dt == torch.float64 else copy.deepcopy(model)).eval()
+            with torch.no_grad():
+                res = m(batches(qs, dt), False, return_trace=False)
+            arrays["fwd:%s:lp_%s" % (name, tag)] = res["log_probability"].numpy()
+            fm["answer_" + tag] = res["answer"]
+            if tag == "f32":
+                fm["options"], fm["type"] = res["options"], int(res["type"])
+        meta["forward"][name] = fm
+    for name, qs in train.items():
+        for i, q in enumerate(qs):
+            arrays["train:%s:X_%d" % (name, i)] = q["scene"]["X"]
+        for dt, tag in both_dtypes():
+            m = copy.deepcopy(model).double() if dt == torch.float64 else copy.deepcopy(model)
+            m.train()
+            pbs = batches(qs, dt)
+            res = m(pbs, True, return_trace=False)
+            lp = res["log_probability"]
+            if dt == torch.float64:           # trainer.py:185-194,207-230 restated in fp64 (its targets are built in fp32), as g12
+                if res["type"] == ref.base_types.QuestionType.BINARY:
+                    target = torch.tensor([a == "yes" for pb in pbs for a in pb._answers], dtype=dt)
+                    loss = torch.nn.functional.binary_cross_entropy(lp.exp(), target, reduction="sum")
+                else:
+                    answers = [a for pb in pbs for a in pb._answers]
+                    target = [[a == o for o in opt] for a, opt in zip(answers, res["options"])]
+                    seg = torch.tensor([i for i, t in enumerate(target) for _ in t])
+                    tflat = torch.tensor([x for t in target for x in t], dtype=dt)
+                    denom = torch.zeros(len(target), dtype=dt).index_add(0, seg, lp.exp())
+                    loss = ref.util.safe_log(denom).sum() - (tflat * lp).sum()
+            else:
+                loss = VQATrainer._compute_loss(fake, pbs, res)
+            loss = loss / sum(pb.batch_size() for pb in pbs)
+            loss.backward()
+            arrays["train:%s:loss_%s" % (name, tag)] = loss.detach().numpy()
+            arrays["train:%s:lp_%s" % (name, tag)] = lp.detach().numpy()
+            seen, live = set(), []
+            for k, prm in m.named_parameters():
+                if id(prm) in seen:
+                    continue
+                seen.add(id(prm))
+                if k.startswith("_featurizer.") or k.startswith("_oracle.") or ("._nlg." in k and prm.grad is not None):
+                    arrays["train:%s:g:%s:%s" % (name, k, tag)] = (torch.zeros_like(prm) if prm.grad is None else prm.grad).detach().numpy()
+                    if "._nlg." in k:
+                        live.append(k)
+            print(name, tag, "loss", float(loss), "gates with a gradient:", len(live))
+        meta["train"][name] = {"questions": questions_to_meta(qs), "gates": live, "type": int(res["type"])}
+    save("g25_gate_interpreter", arrays, meta)
+
+
 # ---------------------------------------------------------------------------------------- g26
 def g26():
     """The reference's config YAMLs (config/sample_config.yaml and config/curriculum_training/cur0..cur7), parsed, keyed by their path under
