@@ -130,6 +130,7 @@ SIGNATURES = {
     "dfol_quantify_bwd_f32": [_p, _p, _p, _p, _p, _i32, _i32, _p, _p],
     "dfol_filter_gate_fwd_f32": [_p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _p, _p, _p],
     "dfol_relate_gate_fwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p],
+    "dfol_relate_one_gate_fwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _p],
     "dfol_filter_gate_bwd_scratch": [_i32, _i32],           # returns a float count (int64), called directly
     "dfol_filter_gate_bwd_f32": [_p, _p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _p, _p, _p, _p, _p, _p],
     "dfol_relate_gate_bwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p],
@@ -220,6 +221,7 @@ SIGNATURES = {
     "dfol_set_range_status": [_p],
     "dfol_set_feature_rows": [_p, _p],
     "dfol_set_feature_rows_bf16": [_p, _p],
+    "dfol_set_program_gates": [_p, _i32],
     "dfol_set_feature_cache": [_p, _i64, _i32, _p, _p],
     "dfol_pair_features_bwd_f32": [_p, _i64, _i32, _p, _p, _i32, _i32, _p, _i64, _p],
     "dfol_dropout_advance": [_p, _p],
@@ -558,6 +560,27 @@ def relate_gate_fwd(prior_s, prior_o, tile, pred_q, n_obj, quant_s, quant_o, gat
          _ptr(want, U8, True), P, NS, orientation, flags, _ptr(gate_s, F32), _ptr(gate_o, F32), _ptr(post_s, F32, True),
          _ptr(post_o, F32, True), _stream())
     return post_s, post_o
+
+
+def gate_native():
+    """DFOL_GATE_NATIVE=1 (opt-in, read when a forward starts): a model with trainable gates takes the fast inference routes - the one-launch
+    gated Relate in the Python loop and the gated opcodes of the native executor.  Unset: the generic gated route and the Python loop, as before."""
+    return os.environ.get("DFOL_GATE_NATIVE", "0") == "1"
+
+
+def relate_one_gate_fwd(x_att, prev_att, tile, pred_q, n_obj, quant_prev, x_is_subject, gate_s, gate_o, neg=None, active=None,
+                        lone_forall_identity=False):
+    """relate_one_fwd with the trainable gates: gate_s / gate_o = gate_params of axis 0 / axis 1, x_is_subject uint8 [P] (which axis x is on)."""
+    if tile.dtype != F32:
+        raise DfolError("the gated relate kernels read fp32 tiles (got %s): relation_tile_dtype: bf16 and trainable_gate: True do not combine" % tile.dtype)
+    P, NS = tile.shape[0], tile.shape[1]
+    if x_is_subject.numel() != P:
+        raise DfolError("relate_one_gate_fwd: %d subject flags for %d predicates" % (x_is_subject.numel(), P))
+    post = torch.empty(P, NS, dtype=F32, device=tile.device)
+    call("dfol_relate_one_gate_fwd_f32", _ptr(x_att, F32), _ptr(prev_att, F32), _ptr(tile, F32), _ptr(pred_q, I32), _ptr(n_obj, I32),
+         _ptr(quant_prev, F32), _ptr(x_is_subject, U8), _ptr(neg, U8, True), 0 if neg is None else 1, _ptr(active, U8, True), P, NS,
+         1 if lone_forall_identity else 0, _ptr(gate_s, F32), _ptr(gate_o, F32), _ptr(post), _stream())
+    return post
 
 
 def relate_one_fwd(x_att, prev_att, tile, pred_q, n_obj, quant_prev, neg=None, active=None, lone_forall_identity=False):

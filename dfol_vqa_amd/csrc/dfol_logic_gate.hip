@@ -1,4 +1,5 @@
-// The logic cell with the trainable gate (`trainable_gate: True`): gated forms of the Filter and Relate kernels, forward and backward.
+// The logic cell with the trainable gate (`trainable_gate: True`): gated forms of the Filter and Relate kernels, forward and backward, and of the
+// one-posterior Relate (forward; inference).
 //
 // Reference: NeuralLogicGate, batch_base_ops.py:19-38, used by BatchBayesianLogicCell._forward_core at :99-102 and :135-138: every
 // `x + log_p` of the cell becomes G_k(x, log_p), k the axis whose prior is joined.  With W_k [6, 2], c_k [6] (nn.Linear(2, 6)):
@@ -585,6 +586,114 @@ __global__ __launch_bounds__(64 * GB_WAVES) void relate_gate_bwd_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// relate, single posterior (the gated form of relate_one_fwd_kernel, dfol_logic.hip): the three gates of GQARelateBatch and the arity-2
+// cell in one launch, only the kept posterior written.  x = the freshly selected variable (columns), prev = the incoming one (rows, summed
+// out); the tile comes with prev's objects along rows.  The two axes hold different gates, so the launch is told which axis x is on:
+// x_is_subject[p] -> x on axis 0 (outer gate = gate_s, inner gate = gate_o), else x on axis 1 (outer = gate_o, inner = gate_s).
+//     post[p][i] = G_out( F( agg_{j < n, j != i} F( G_in(l'[j][i], prev[j]) ) ), x[p][i] ),   F and agg by quant_prev[p]
+// This is the column half of relate_gate_fwd_kernel (R = prev, C = x): a wavefront per predicate, a lane owns four columns, 64 / LPR rows per
+// iteration, the column aggregates stay in registers; a row's prior, its exponential and its share of the six pre-activations are computed
+// once per row, so an element costs six sigmoids and one e^l'.  The outer gate runs once per column, in the lanes of row slot 0.
+// ---------------------------------------------------------------------------------------------------
+template <int LPR>
+__global__ __launch_bounds__(256) void relate_one_gate_fwd_kernel(
+    const float* __restrict__ x_att, const float* __restrict__ prev_att, const float* __restrict__ tile, const int32_t* __restrict__ pred_q,
+    const int32_t* __restrict__ n_obj, const float* __restrict__ quant_prev, const uint8_t* __restrict__ x_is_subject,
+    const uint8_t* __restrict__ neg, int any_neg, const uint8_t* __restrict__ active, int P, int NS, int identity_forall,
+    const float* __restrict__ gate_s, const float* __restrict__ gate_o, float* __restrict__ post) {
+    constexpr int RPI = 64 / LPR;
+    // (the predicate is the same for the whole wavefront: said so, everything derived from it - the gates' 36 parameters among it - is scalar)
+    const int p = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    if (p >= P) return;
+    const int lane = threadIdx.x & 63;
+    const int q = pred_q[p];
+    const int n = min(n_obj[q], NS);
+    const float* pv = prev_att + (int64_t)q * NS;
+    const float* xv = x_att + (int64_t)p * NS;
+    float* out = post + (int64_t)p * NS;
+    if (active && !active[p]) {                         // question without this operator: attention passes through (as relate_one_fwd_kernel)
+        for (int c = lane; c < NS; c += 64) out[c] = c < n ? pv[c] : 0.f;
+        return;
+    }
+    const bool xs = x_is_subject[p] != 0;
+    const GateW GI = gate_load(xs ? gate_o : gate_s), GO = gate_load(xs ? gate_s : gate_o);      // inner: prev's axis, outer: x's
+    const int cg = lane % LPR, rs = lane / LPR, c0 = cg * 4, cl = min(c0, NS - 4);               // (lanes beyond the width read a valid column)
+    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
+    const float qf = quant_prev[p], kf = 1.f - 2.f * qf;
+    const bool ex = qf == 1.f, ident = identity_forall && qf == 0.f;
+    const float* tp = tile + (int64_t)p * NS * NS;
+    float cacc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int r0 = 0; r0 < n; r0 += RPI) {
+        const int r = r0 + rs, rc = min(r, n - 1);
+        const float4 t4 = *reinterpret_cast<const float4*>(tp + (int64_t)rc * NS + cl);
+        const float l[4] = {t4.x, t4.y, t4.z, t4.w};
+        const float pr = pv[rc];
+        float zb[6];
+        gate_zb(GI, pr, zb);
+        const float eb = dfol_exp(pr);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = c0 + j;
+            const bool keep = r < n && c < n && c != r;       // padding and self-relations contribute nothing (:112)
+            const float v = gate_prep(l[j], any_neg, alpha_n, cn);
+            const float t = gate_term(gate_m(GI, v, dfol_exp(v), zb, eb), ex, qf, kf);      // :99-100, :108
+            cacc[j] = gate_join(cacc[j], keep ? t : 0.f, ex);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int m = 32; m >= LPR; m >>= 1) cacc[j] = gate_join(cacc[j], __shfl_xor(cacc[j], m, 64), ex);
+    }
+    if (rs == 0 && c0 < NS) {
+        const float4 x4 = *reinterpret_cast<const float4*>(xv + c0);
+        const float xj[4] = {x4.x, x4.y, x4.z, x4.w};
+        float o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = (c0 + j < n) ? gate_log(GO, gate_outer(cacc[j], ex, ident, qf, kf), xj[j]) : 0.f;      // :133, :135-136
+        *reinterpret_cast<float4*>(out + c0) = make_float4(o[0], o[1], o[2], o[3]);
+    }
+}
+
+// NS > 256: one workgroup per predicate, a thread per column, rows in order (as relate_one_big_kernel)
+__global__ __launch_bounds__(256) void relate_one_gate_big_kernel(
+    const float* __restrict__ x_att, const float* __restrict__ prev_att, const float* __restrict__ tile, const int32_t* __restrict__ pred_q,
+    const int32_t* __restrict__ n_obj, const float* __restrict__ quant_prev, const uint8_t* __restrict__ x_is_subject,
+    const uint8_t* __restrict__ neg, int any_neg, const uint8_t* __restrict__ active, int NS, int identity_forall,
+    const float* __restrict__ gate_s, const float* __restrict__ gate_o, float* __restrict__ post) {
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int q = pred_q[p], n = min(n_obj[q], NS);
+    const float* pv = prev_att + (int64_t)q * NS;
+    const float* xv = x_att + (int64_t)p * NS;
+    float* out = post + (int64_t)p * NS;
+    if (active && !active[p]) {
+        for (int c = tid; c < NS; c += 256) out[c] = c < n ? pv[c] : 0.f;
+        return;
+    }
+    const bool xs = x_is_subject[p] != 0;
+    const GateW GI = gate_load(xs ? gate_o : gate_s), GO = gate_load(xs ? gate_s : gate_o);
+    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
+    const float qf = quant_prev[p], kf = 1.f - 2.f * qf;
+    const bool ex = qf == 1.f, ident = identity_forall && qf == 0.f;
+    const float* tp = tile + (int64_t)p * NS * NS;
+    for (int c = tid; c < NS; c += 256) {
+        float o = 0.f;
+        if (c < n) {
+            float acc = 0.f;
+            for (int r = 0; r < n; ++r) {
+                if (r == c) continue;
+                const float v = gate_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn);
+                float zb[6];
+                gate_zb(GI, pv[r], zb);
+                acc = gate_join(acc, gate_term(gate_m(GI, v, dfol_exp(v), zb, dfol_exp(pv[r])), ex, qf, kf), ex);
+            }
+            o = gate_log(GO, gate_outer(acc, ex, ident, qf, kf), xv[c]);
+        }
+        out[c] = o;
+    }
+}
+
 template <int LPR>
 void launch_relate_gate(hipStream_t st, const float* pR, const float* pC, const float* tile, const int32_t* pred_q, const int32_t* n_obj,
                         const float* qR, const float* qC, const uint8_t* neg, int any_neg, const uint8_t* active, const uint8_t* want, int bR,
@@ -671,6 +780,38 @@ extern "C" int dfol_relate_gate_fwd_f32(const float* prior_s, const float* prior
     else DFOL_GATE_CASE(64);
 #undef DFOL_GATE_CASE
     DFOL_LAUNCH_CHECK("relate_gate_fwd");
+    return 0;
+}
+
+extern "C" int dfol_relate_one_gate_fwd_f32(const float* x_att, const float* prev_att, const float* tile, const int32_t* pred_q,
+                                            const int32_t* n_obj, const float* quant_prev, const uint8_t* x_is_subject, const uint8_t* neg,
+                                            int32_t any_neg, const uint8_t* active, int32_t P, int32_t NS, int32_t lone_forall_identity,
+                                            const float* gate_s, const float* gate_o, float* post, void* stream) {
+    DFOL_REQUIRE(P >= 0 && NS > 0 && NS % 4 == 0, "relate_one_gate_fwd: bad sizes P=%d NS=%d (NS: a multiple of 4)", P, NS);
+    if (P == 0) return 0;
+    DFOL_REQUIRE(x_att && prev_att && tile && pred_q && n_obj && quant_prev && x_is_subject && gate_s && gate_o && post,
+                 "relate_one_gate_fwd: null pointer");
+    DFOL_REQUIRE(!any_neg || neg, "relate_one_gate_fwd: any_neg set but neg is NULL");
+    hipStream_t st = (hipStream_t)stream;
+    if (NS > 256) {
+        hipLaunchKernelGGL(relate_one_gate_big_kernel, dim3(P), dim3(256), 0, st, x_att, prev_att, tile, pred_q, n_obj, quant_prev, x_is_subject, neg,
+                           any_neg, active, NS, lone_forall_identity, gate_s, gate_o, post);
+        DFOL_LAUNCH_CHECK("relate_one_gate_fwd (NS > 256)");
+        return 0;
+    }
+    const int groups = NS / 4;
+#define DFOL_GATE1(L)                                                                                                                          \
+    hipLaunchKernelGGL(relate_one_gate_fwd_kernel<L>, dim3(dfol_cdiv(P, 4)), dim3(256), 0, st, x_att, prev_att, tile, pred_q, n_obj, quant_prev, \
+                       x_is_subject, neg, any_neg, active, P, NS, lone_forall_identity, gate_s, gate_o, post)
+    if (groups <= 1) DFOL_GATE1(1);
+    else if (groups <= 2) DFOL_GATE1(2);
+    else if (groups <= 4) DFOL_GATE1(4);
+    else if (groups <= 8) DFOL_GATE1(8);
+    else if (groups <= 16) DFOL_GATE1(16);
+    else if (groups <= 32) DFOL_GATE1(32);
+    else DFOL_GATE1(64);
+#undef DFOL_GATE1
+    DFOL_LAUNCH_CHECK("relate_one_gate_fwd");
     return 0;
 }
 

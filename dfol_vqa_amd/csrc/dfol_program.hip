@@ -136,6 +136,9 @@ struct FeatureCache {
     const float* box6;
 };
 thread_local FeatureCache g_feature_cache = {nullptr, 0, 0, nullptr, nullptr};
+// dfol_set_program_gates: the gate table of the NEXT dfol_run_program on this thread ([n_gates][18] device floats)
+thread_local const float* g_gate_table = nullptr;
+thread_local int32_t g_gate_count = 0;
 
 }  // namespace
 
@@ -162,6 +165,13 @@ extern "C" int dfol_set_feature_rows_bf16(const int32_t* src_row, const float* b
     return 0;
 }
 
+extern "C" int dfol_set_program_gates(const float* table, int32_t n_gates) {
+    DFOL_REQUIRE(n_gates >= 0 && (table == nullptr) == (n_gates == 0), "set_program_gates: a table of %d gates at %p", n_gates, (const void*)table);
+    g_gate_table = table;
+    g_gate_count = n_gates;
+    return 0;
+}
+
 extern "C" int dfol_calib_walk_supported(int32_t KX, int32_t H) { return lc_walk_fits(KX, H) ? 1 : 0; }
 
 extern "C" int dfol_run_program(const DfolProgramModel* model, const DfolProgramScene* scene, const int64_t* instr_host, int32_t n_instr,
@@ -174,6 +184,16 @@ extern "C" int dfol_run_program(const DfolProgramModel* model, const DfolProgram
     g_feature_rows_bf16 = false;
     const FeatureCache cached = g_feature_cache;
     g_feature_cache = FeatureCache{nullptr, 0, 0, nullptr, nullptr};
+    const float* gates = g_gate_table;
+    const int32_t n_gates = g_gate_count;
+    g_gate_table = nullptr;
+    g_gate_count = 0;
+    // the 18 floats of gate `slot` (+ k: the second axis of an arity-2 cell); the slot was checked by DFOL_GATE_SLOT
+    auto gate_row = [&](int64_t slot, int k) { return gates + (slot + k) * 18; };
+#define DFOL_GATE_SLOT(slot, arity)                                                                                                                   \
+    DFOL_REQUIRE(gates != nullptr && (slot) >= 0 && (slot) + (arity) <= n_gates,                                                                       \
+                 "run_program[%d]: opcode %lld names gate slot %lld (arity %d) of a table of %d gates (dfol_set_program_gates before the call)", i, \
+                 (long long)a[0], (long long)(slot), (arity), gates ? n_gates : 0)
     DFOL_REQUIRE(model && scene && instr_host && blob && workspace, "run_program: null pointer");
     DFOL_REQUIRE(n_instr >= 0 && scene->NS > 0 && scene->NS % 4 == 0, "run_program: bad sizes (n_instr %d, NS %d)", n_instr, scene->NS);
     const int32_t NS = scene->NS;
@@ -306,6 +326,33 @@ extern "C" int dfol_run_program(const DfolProgramModel* model, const DfolProgram
                                          static_cast<int32_t>(a[11]), static_cast<int32_t>(a[12]), static_cast<float*>(at(workspace, a[13])), static_cast<float*>(at(workspace, a[14])),
                                          stream);
                 break;
+            case DFOL_OP_FILTER_GATE:    // DFOL_OP_FILTER's operands, gate slot
+                DFOL_GATE_SLOT(a[8], 1);
+                rc = dfol_filter_gate_fwd_f32(static_cast<const float*>(at(workspace, a[1])), static_cast<const float*>(at(workspace, a[2])),
+                                              static_cast<const int32_t*>(at(blob, a[3])), n_obj, static_cast<const uint8_t*>(at(blob, a[4])), a[4] >= 0 ? 1 : 0,
+                                              static_cast<const uint8_t*>(at(blob, a[5])), static_cast<int32_t>(a[6]), NS, gate_row(a[8], 0),
+                                              static_cast<float*>(at(workspace, a[7])), stream);
+                break;
+            case DFOL_OP_RELATE_ONE_GATE: // DFOL_OP_RELATE_ONE's operands, x_is_subject, the cell's first gate slot
+                DFOL_GATE_SLOT(a[13], 2);
+                DFOL_REQUIRE(a[11] == DFOL_TILE_F32, "run_program[%d]: the gated relate reads fp32 tiles", i);
+                rc = dfol_relate_one_gate_fwd_f32(static_cast<const float*>(at(workspace, a[1])), static_cast<const float*>(at(workspace, a[2])),
+                                                  static_cast<const float*>(at(workspace, a[3])), static_cast<const int32_t*>(at(blob, a[4])), n_obj,
+                                                  static_cast<const float*>(at(blob, a[5])), static_cast<const uint8_t*>(at(blob, a[12])),
+                                                  static_cast<const uint8_t*>(at(blob, a[6])), a[6] >= 0 ? 1 : 0, static_cast<const uint8_t*>(at(blob, a[7])),
+                                                  static_cast<int32_t>(a[8]), NS, static_cast<int32_t>(a[9]), gate_row(a[13], 0), gate_row(a[13], 1),
+                                                  static_cast<float*>(at(workspace, a[10])), stream);
+                break;
+            case DFOL_OP_RELATE_GATE:    // DFOL_OP_RELATE's operands, the cell's first gate slot
+                DFOL_GATE_SLOT(a[15], 2);
+                rc = dfol_relate_gate_fwd_f32(static_cast<const float*>(at(workspace, a[1])), static_cast<const float*>(at(workspace, a[2])),
+                                              static_cast<const float*>(at(workspace, a[3])), static_cast<const int32_t*>(at(blob, a[4])), n_obj,
+                                              static_cast<const float*>(at(blob, a[5])), static_cast<const float*>(at(blob, a[6])),
+                                              static_cast<const uint8_t*>(at(blob, a[7])), a[7] >= 0 ? 1 : 0, static_cast<const uint8_t*>(at(blob, a[8])),
+                                              static_cast<const uint8_t*>(at(blob, a[9])), static_cast<int32_t>(a[10]), NS, static_cast<int32_t>(a[11]),
+                                              static_cast<int32_t>(a[12]), gate_row(a[15], 0), gate_row(a[15], 1), static_cast<float*>(at(workspace, a[13])),
+                                              static_cast<float*>(at(workspace, a[14])), stream);
+                break;
             case DFOL_OP_QUANTIFY:       // att, quant, pred_q, P, lp
                 rc = dfol_quantify_fwd_f32(static_cast<const float*>(at(workspace, a[1])), static_cast<const float*>(at(blob, a[2])),
                                            static_cast<const int32_t*>(at(blob, a[3])), n_obj, static_cast<int32_t>(a[4]), NS, static_cast<float*>(at(workspace, a[5])), stream);
@@ -403,5 +450,6 @@ extern "C" int dfol_run_program(const DfolProgramModel* model, const DfolProgram
             return rc;
         }
     }
+#undef DFOL_GATE_SLOT
     return 0;
 }

@@ -302,8 +302,11 @@ class GQARelateBatch(GQABatchOperatorBase):
         if torch.is_grad_enabled() and (x._log_attention.requires_grad or prev._log_attention.requires_grad):
             return None
         rel = self._relate
-        if rel._blc.gated():                                   # trainable_gate: the generic gate -> relate -> gate route (no gated one-launch form)
+        gated = rel._blc.gated()
+        if gated and not L.gate_native():                      # trainable_gate: the generic gate -> relate -> gate route unless DFOL_GATE_NATIVE=1
             return None
+        if gated and torch.is_grad_enabled() and any(p.requires_grad for p in rel._blc.parameters()):
+            return None                                        # the gates train: the differentiable generic route
         calibrated = op_id in rel._subject_modulations
         if calibrated != (op_id in rel._object_modulations):
             return None                                        # one-sided calibration: RelateBatch.forward handles it
@@ -316,9 +319,17 @@ class GQARelateBatch(GQABatchOperatorBase):
         if tiles is None:
             return None
         _, neg_dev, valid_dev = low.on(world._device)
-        kernel = L.relate_one_fwd_bf16 if tiles.dtype == torch.bfloat16 else L.relate_one_fwd
-        post = kernel(x._log_attention, prev._log_attention, tiles, world._ident, world._n_obj, prev._quantifier,
-                      neg_dev if low.any_neg else None, None if low.all_valid else valid_dev, lone_forall_identity=(x.batch_size() == 1))
+        if gated:                                              # dfol_relate_one_gate_fwd_f32: the cell's two gates, and which axis x is on
+            hf = host_flags if host_flags is not None else [float(f) for f in flag.detach().cpu().tolist()]
+            xs = upload(np.asarray([1 if f > 0 else 0 for f in hf], np.uint8), world._device)
+            post = L.relate_one_gate_fwd(x._log_attention, prev._log_attention, tiles, world._ident, world._n_obj, prev._quantifier, xs,
+                                         L.gate_params(*rel._blc._gate(0)), L.gate_params(*rel._blc._gate(1)),
+                                         neg_dev if low.any_neg else None, None if low.all_valid else valid_dev,
+                                         lone_forall_identity=(x.batch_size() == 1))
+        else:
+            kernel = L.relate_one_fwd_bf16 if tiles.dtype == torch.bfloat16 else L.relate_one_fwd
+            post = kernel(x._log_attention, prev._log_attention, tiles, world._ident, world._n_obj, prev._quantifier,
+                          neg_dev if low.any_neg else None, None if low.all_valid else valid_dev, lone_forall_identity=(x.batch_size() == 1))
         if calibrated:
             # RelateBatch.forward calibrates both posteriors (batch_base_ops.py:588-594) and GQARelateBatch keeps one per question:
             # calibrate the kept one with that side's modulations

@@ -605,7 +605,7 @@ class BatchInterpreterBase(nn.Module):
             return None                                      # gradients reach the oracle or the calibrator: the differentiable Python operators
         if not hasattr(self, "_ontology"):
             return None
-        if self._gated():                                    # trainable_gate: True - the executor has no gated opcode
+        if self._gated() and not _lib.gate_native():         # trainable_gate: True - the gated opcodes are opt-in (DFOL_GATE_NATIVE=1)
             _lib.fallback("trainable_gate", "the native executor has no gated Filter / Relate instruction",
                           "runs the Python operator loop on the gated HIP kernels instead of the native executor")
             return None
@@ -639,9 +639,10 @@ class BatchInterpreterBase(nn.Module):
             if self._has_modulator and modulator_switch:
                 self._calibration_passes(world, program_batch, device, is_training)
             if world._lazy is not None:
-                # with a training calibrator the attentions carry gradients and the relates run on the generic cell; a gated model's always do
+                # with a training calibrator the attentions carry gradients and the relates run on the generic cell; a gated model's do too,
+                # unless its one-launch Relate is switched on (DFOL_GATE_NATIVE=1) and no gradient is recorded
                 self._oracle.prefetch_relations(world, program_batch, fused=not (self._has_modulator and modulator_switch and torch.is_grad_enabled())
-                                                and not self._gated())
+                                                and (not self._gated() or (_lib.gate_native() and not torch.is_grad_enabled())))
                 if hasattr(self._oracle, "prefetch_attributes"):
                     self._oracle.prefetch_attributes(world, program_batch)
             ops = program_batch._op_batch_list

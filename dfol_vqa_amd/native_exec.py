@@ -116,6 +116,26 @@ def attr_head_of(model):
         return model._oracle._attr_head()
 
 
+def gated_cells(model):
+    """[(module path of the FilterBatch / RelateBatch, its BatchBayesianLogicCell)] of a model with trainable gates, in named_modules() order: the
+    order of the executor's gate table (a cell of arity 2 owns two consecutive rows).  The modules do not change after construction: looked up once."""
+    from .logic_ops import BatchBayesianLogicCell
+    hit = model.__dict__.get("_gated_cell_list")
+    if hit is None:
+        hit = model.__dict__["_gated_cell_list"] = [(name.rsplit(".", 1)[0] if "." in name else "", m) for name, m in model.named_modules()
+                                                    if isinstance(m, BatchBayesianLogicCell) and m.gated()]
+    return hit
+
+
+def gate_slots(model):
+    """{cell path: first row of the gate table}, or None for a model without gates."""
+    slots, at = {}, 0
+    for path, cell in gated_cells(model):
+        slots[path] = at
+        at += cell._arity
+    return slots or None
+
+
 def model_spec(model, calibrate=False):
     """native_plan.ModelSpec of an interpreter, or None when its modules are not the shapes the executor drives.  calibrate: the forward runs
     the attention-calibration passes (activate_attention_transfer, modulator_switch on)."""
@@ -138,7 +158,7 @@ def model_spec(model, calibrate=False):
         calib = dict(state_dim=int(nets[0].hidden_size), lstm_in=int(nets[0].input_size), ops_index=dict(model._OPS_INDEX))
     return NP.ModelSpec([l.out_features for l, _ in fl], [l.out_features for l, _ in al], lin1.out_features, fl[-1][0].out_features + 4,
                         oracle._normalize, model._likelihood_threshold, oracle._ontology._relation_index, tile_bf16=tile_bf16, calib=calib,
-                        attr_head=len(al) == 2 and attr_head_on(model))
+                        attr_head=len(al) == 2 and attr_head_on(model), gates=gate_slots(model))
 
 
 class NativeModel(object):
@@ -205,8 +225,25 @@ class NativeModel(object):
             m.att_out_w, m.ld_att_out, m.att_out_n = ow.data_ptr(), ow.stride(0), int(ow.shape[0])
             m.att_out_b = None if nets[2].bias is None else nets[2].bias.detach().data_ptr()
             self._hold += [ow, nets[2].bias]
+        # the gate table of a model with trainable gates: one row of 18 floats per gate, cells in gated_cells' order (dfol_set_program_gates)
+        cells = gated_cells(model)
+        self.gates, self._gate_views = None, None
+        if cells:
+            pairs = [cell._gate(k) for _, cell in cells for k in range(cell._arity)]
+            self.gates = torch.stack([_lib.gate_params(w, b) for w, b in pairs]).contiguous()
+            if all(t.dtype == torch.float32 and t.is_contiguous() for w, b in pairs for t in (w, b)):
+                # views of the parameters in the table's order: run() gathers them again with one launch (refresh_gates)
+                self._gate_views = [v for w, b in pairs for v in (w.detach().view(12), b.detach().view(6))]
+            self._hold += [self.gates, pairs]
         self.struct = m
         self.D = int(D)
+
+    def refresh_gates(self):
+        """The gate table is a copy of 18 floats per gate, and a write through `p.data` does not move the version the model's key is made of:
+        gather the parameters again before every run (one launch over the views taken at construction; their addresses are in the key)."""
+        if self._gate_views is not None:
+            torch.cat(self._gate_views, out=self.gates.view(-1))
+        return self.gates
 
     @staticmethod
     def version_key(model):
@@ -214,6 +251,7 @@ class NativeModel(object):
         nets = calibrator(model)
         if nets is not None:
             params += [p for m in nets for p in m.parameters()]
+        params += [p for _, cell in gated_cells(model) for p in cell.parameters()]      # (the gate table is a copy: an optimiser step must rebuild it)
         return (tuple((p.data_ptr(), p._version) for p in params), _lib._dense_math(), _lib.pair_math(), str(params[0].device) if params else "",
                 attr_head_on(model))
 
@@ -332,6 +370,9 @@ def run(model, program_batch, plan, queue, give_answer=True):
     sc.NS, sc.max_n = plan.scene["NS"], plan.scene["max_n"]
     sc.n_obj, sc.img_n_obj, sc.obj_off = plan.scene["n_obj"], plan.scene["img_n_obj"], plan.scene["obj_off"]
     instrs = plan.instrs
+    if nm.gates is not None:                                 # (picked up, and cleared, by the call below)
+        gates = nm.refresh_gates()
+        _lib.call("dfol_set_program_gates", gates.data_ptr(), gates.shape[0])
     _lib.call("dfol_run_program", ctypes.byref(nm.struct), ctypes.byref(sc), instrs.ctypes.data, instrs.shape[0], blob.data_ptr(), ws.data_ptr(),
               _lib._stream())
     r = plan.result

@@ -24,7 +24,7 @@ from .host_util import flatten_list, get_lowered, lower_tokens, segments_of, unf
 # opcodes of include/dfol_vqa.h
 (OP_DENSE, OP_BOX_POSITIONS, OP_FILL, OP_PAIR_LL, OP_ATTR_LL, OP_OPTION_NORMALIZE, OP_FILTER, OP_RELATE_ONE, OP_RELATE, OP_QUANTIFY, OP_GATE,
  OP_LOGIC, OP_SEGMENT_SUM_ROWS, OP_SEGMENT_OR, OP_IMPLICATION, OP_COMPARE, OP_FIND_MAX_IND, OP_GATHER_TILES, OP_CALIB_FEATURES, OP_LSTM_CELL,
- OP_SELECT_ROWS, OP_ATT_MODULATIONS, OP_MODULATE, OP_CALIB_WALK, OP_ATTR_HEAD) = range(25)
+ OP_SELECT_ROWS, OP_ATT_MODULATIONS, OP_MODULATE, OP_CALIB_WALK, OP_ATTR_HEAD, OP_FILTER_GATE, OP_RELATE_ONE_GATE, OP_RELATE_GATE) = range(28)
 WALK_FILL, WALK_SELECT, WALK_ADD, WALK_LSTM, WALK_ATT_MODULATIONS = range(5)      # steps of an OP_CALIB_WALK table
 INSTR_WIDTH = 16
 LOGIC_AND, LOGIC_OR, LOGIC_NOT = 0, 1, 2
@@ -70,7 +70,7 @@ class ModelSpec(object):
     interpreter's likelihood threshold.  Picklable (collate workers build plans)."""
 
     def __init__(self, featurizer_widths, attribute_widths, hid1, D, normalize, likelihood_threshold, relation_index, tile_bf16=False, calib=None,
-                 attr_head=False):
+                 attr_head=False, gates=None):
         self.featurizer_widths = [int(w) for w in featurizer_widths]      # output width of every featurizer layer (the last = D - 4)
         self.attribute_widths = [int(w) for w in attribute_widths]        # output width of every attribute-network layer
         self.hid1, self.D = int(hid1), int(D)
@@ -83,6 +83,10 @@ class ModelSpec(object):
         # the attribute columns come from the fused head (dfol_attr_head_h2_f32) over the first layer's pre-activations: the network's last
         # layer is not run as a dense product and its hidden table is not allocated (native_exec.attr_head_on: two layers, default arithmetic)
         self.attr_head = bool(attr_head)
+        # a model with trainable gates (trainable_gate: True): {cell = module path of the FilterBatch / RelateBatch: its first row of the executor's
+        # gate table} (native_exec.gate_slots; a cell of arity 2 owns two rows) - the logic instructions are then the gated opcodes, each naming the
+        # cell the Python loop would run for that operator.  None: no gates
+        self.gates = None if gates is None else {str(k): int(v) for k, v in gates.items()}
         # attention calibration (activate_attention_transfer with the modulator switched on): None, or {"state_dim": S, "lstm_in": 18 + token
         # embedding width, "ops_index": operator -> one-hot position (batch_gqa_interpreter.py:67-70)}
         self.calib = None if calib is None else dict(state_dim=int(calib["state_dim"]), lstm_in=int(calib["lstm_in"]), ops_index=dict(calib["ops_index"]))
@@ -90,6 +94,7 @@ class ModelSpec(object):
     def key(self):
         return (tuple(self.featurizer_widths), tuple(self.attribute_widths), self.hid1, self.D, self.normalize, self.likelihood_threshold,
                 self.relation_index.tobytes(), self.tile_bf16, self.attr_head,
+                None if self.gates is None else tuple(sorted(self.gates.items())),
                 None if self.calib is None else (self.calib["state_dim"], self.calib["lstm_in"], tuple(sorted(self.calib["ops_index"].items()))))
 
 
@@ -195,6 +200,15 @@ class _Builder(object):
 
     def block(self, rows, region="t"):
         return self.alloc(rows * self.NS * 4, region)
+
+    def slot(self, cell):
+        """The gate-table row of `cell` (a path below the operator registry, e.g. "relate._gqa_select._filter"), or None for a model without gates."""
+        if self.spec.gates is None:
+            return None
+        hit = self.spec.gates.get("_ops." + cell)
+        if hit is None:
+            raise Unsupported("a gated model without the cell %r" % cell)
+        return hit
 
     def emit(self, *ops):
         assert len(ops) <= INSTR_WIDTH
@@ -362,8 +376,9 @@ class _Builder(object):
         self.emit(OP_MODULATE, att, mods, self.arr(np.asarray(pq_arr, np.int32)), P, out)
         return out
 
-    def filter(self, vs, tokens, key, pq=None, normalized=True, mkey=None):
-        """FilterBatch.forward (logic_ops.py; batch_base_ops.py:311-405).  mkey: the (operator index, role) its modulations were left under."""
+    def filter(self, vs, tokens, key, pq=None, normalized=True, mkey=None, cell=None):
+        """FilterBatch.forward (logic_ops.py; batch_base_ops.py:311-405).  mkey: the (operator index, role) its modulations were left under; cell: the
+        FilterBatch the Python loop runs here (its gates, for a gated model)."""
         low = get_lowered(tokens, self.ont, TokenType.ATTRIBUTE)
         if not low.any_valid:
             return vs
@@ -382,13 +397,15 @@ class _Builder(object):
         ll = self.attr[key]
         self._normalize(ll, low, pq_arr, 1, normalized)
         out = self.block(P)
-        self.emit(OP_FILTER, vs.att, ll, self.arr(pq_arr), self.arr(low.neg) if low.any_neg else -1, -1 if low.all_valid else self.arr(low.valid), P, out)
+        slot = self.slot(cell)
+        self.emit(OP_FILTER if slot is None else OP_FILTER_GATE, vs.att, ll, self.arr(pq_arr), self.arr(low.neg) if low.any_neg else -1,
+                  -1 if low.all_valid else self.arr(low.valid), P, out, 0 if slot is None else slot)
         if mkey is not None:
             out = self.modulate(out, mkey, pq_arr, P)                                  # :401-403
         return _VS(vs.names, out, P, quant, None if pq is None else pq_arr, vs.prev_num + 1)
 
-    def select(self, tokens, key, mkey=None):
-        """GQASelectBatch.forward (batch_gqa_ops.py:168-183)."""
+    def select(self, tokens, key, mkey=None, cell="select._filter"):
+        """GQASelectBatch.forward (batch_gqa_ops.py:168-183).  cell: the select's own filter - an operator that holds a select names its own."""
         Q = self.Q
         if tokens is None:
             names, att = ["entity"] * Q, None
@@ -398,7 +415,7 @@ class _Builder(object):
         x = _VS(names, self.zeros(), Q, np.full(Q, float(Quantifier.EXISTS), np.float32))
         if att is None or all(a is None for a in att):
             return x
-        return self.filter(x, att, key, mkey=mkey)
+        return self.filter(x, att, key, mkey=mkey, cell=cell)
 
     @staticmethod
     def select_tokens(tokens, Q):
@@ -437,17 +454,23 @@ class _Builder(object):
         names = self.gate_names(x.names, prev.names, mask)
         return _VS(names, x.att, x.rows, g * x.quant + (1.0 - g) * prev.quant, x.pq, 0)
 
-    def relate(self, i, prev, relation_list, is_subject, names_tokens, key):
-        """GQARelateBatch.forward on the fused single-posterior kernel (gqa_ops.GQARelateBatch._forward_fused; batch_gqa_ops.py:364-371)."""
-        x = self.select(names_tokens, key, mkey=(i, "sel"))
+    def relate(self, i, prev, relation_list, is_subject, names_tokens, key, cell="relate"):
+        """GQARelateBatch.forward on the fused single-posterior kernel (gqa_ops.GQARelateBatch._forward_fused; batch_gqa_ops.py:364-371).  cell: the
+        GQARelateBatch that runs ("relate", or verify_rel's "verify_rel._gqa_relate"): its select's filter and its RelateBatch hold the gates."""
+        x = self.select(names_tokens, key, mkey=(i, "sel"), cell=cell + "._gqa_select._filter")
         host = [0.0 if f is None else float(f) for f in is_subject]
         hit = self.tiles.get(i)
         if hit is None or x.rows != prev.rows or prev.pq is not None or x.rows != self.Q:
             raise Unsupported("a relate without prefetched tiles")
         tiles, low = hit
         out = self.block(self.Q)
-        self.emit(OP_RELATE_ONE, x.att, prev.att, tiles, self.b_ident, self.arr(prev.quant), self.arr(low.neg) if low.any_neg else -1,
-                  -1 if low.all_valid else self.arr(low.valid), self.Q, 1 if self.Q == 1 else 0, out, self.tile_dtype)
+        slot = self.slot(cell + "._relate")
+        ops = (x.att, prev.att, tiles, self.b_ident, self.arr(prev.quant), self.arr(low.neg) if low.any_neg else -1,
+               -1 if low.all_valid else self.arr(low.valid), self.Q, 1 if self.Q == 1 else 0, out, self.tile_dtype)
+        if slot is None:
+            self.emit(OP_RELATE_ONE, *ops)
+        else:                                                      # which axis x is on picks the outer and the inner gate (dfol_relate_one_gate_fwd_f32)
+            self.emit(OP_RELATE_ONE_GATE, *ops, self.arr(np.asarray([1 if f > 0 else 0 for f in host], np.uint8)), slot)
         if self.calibration is not None and (i, "rel_s") in self.calibration.mods:
             # RelateBatch.forward calibrates both posteriors (batch_base_ops.py:588-594) and GQARelateBatch keeps one per question: the kept one
             # with that side's modulations (gqa_ops.GQARelateBatch._forward_fused)
@@ -913,6 +936,8 @@ def _attribute_requests(b, ops, deps):
 
 
 def _lower(pb, ontology, spec):
+    if spec.gates is not None and spec.tile_bf16:
+        raise Unsupported("trainable gates read fp32 relation tiles")      # (the Python loop raises the DfolError of the combination)
     b = _Builder(pb, ontology, spec)
     ops, deps = getattr(pb._op_batch_list, "host", pb._op_batch_list), pb._dependencies      # (a lazily moved batch: the collated operators)
     if not ops:
@@ -939,7 +964,7 @@ def _lower(pb, ontology, spec):
         if name == "select":
             x = b.select(args[0] if args else None, (i, 0), mkey=(i, "sel"))
         elif name == "filter":
-            x = b.filter(ins[0], args[0], (i, 0), mkey=(i, "flt"))
+            x = b.filter(ins[0], args[0], (i, 0), mkey=(i, "flt"), cell="filter._filter")
             valid = get_lowered(args[0], ontology, TokenType.ATTRIBUTE).valid
         elif name == "relate":
             x, low = b.relate(i, ins[0], args[0], args[1], args[2] if len(args) > 2 else None, (i, 0))
@@ -951,12 +976,12 @@ def _lower(pb, ontology, spec):
             lp = b.quantify(ins[0], region="o")
             result = dict(kind="end", type=QuestionType.STATEMENT, lp=lp, count=ins[0].rows, options=[], num=ins[0].prev_num + 1, names=list(ins[0].names))
         elif name == "verify_rel":
-            x, _ = b.relate(i, ins[0], args[0], args[1], args[2] if len(args) > 2 else None, (i, 0))
+            x, _ = b.relate(i, ins[0], args[0], args[1], args[2] if len(args) > 2 else None, (i, 0), cell="verify_rel._gqa_relate")
             lp = b.quantify(x, region="o")
             result = dict(kind="binary", type=QuestionType.BINARY, lp=lp, count=Q, options=["no", "yes"], num=x.prev_num + 1)
         elif name == "verify_attrs":
             flat, bi = flatten_list(args[0])
-            x = b.filter(ins[0], flat, (i, 0), bi, normalized=False, mkey=(i, "flt"))
+            x = b.filter(ins[0], flat, (i, 0), bi, normalized=False, mkey=(i, "flt"), cell="verify_attrs._filter")
             if x is ins[0]:
                 raise Unsupported("verify_attrs without attributes")
             summed = b.block(Q)
@@ -969,7 +994,8 @@ def _lower(pb, ontology, spec):
                 lists, (flat, bi) = b.category_options(args[0], ins[0].names)
             else:
                 lists, (flat, bi) = args[0], flatten_list(args[0])
-            x = b.filter(ins[0], flat, (i, 0), bi, mkey=(i, "flt"))
+            x = b.filter(ins[0], flat, (i, 0), bi, mkey=(i, "flt"),
+                         cell="query_attr._gqa_choose_attr._filter" if name == "query_attr" else "choose_attr._filter")
             if x is ins[0]:
                 raise Unsupported("an option list without options")
             lp = b.quantify(x, region="o")
@@ -984,7 +1010,8 @@ def _lower(pb, ontology, spec):
             result = dict(kind="binary", type=QuestionType.BINARY, lp=lp, count=Q, options=["no", "yes"], num=ins[0].prev_num + ins[1].prev_num + 2)
         elif name in ("all_same", "all_different"):
             _, (flat, bi) = b.category_options(args[0], ins[0].names)
-            x = b.filter(ins[0], flat, (i, 0), bi, mkey=(i, "flt"))
+            x = b.filter(ins[0], flat, (i, 0), bi, mkey=(i, "flt"),
+                         cell="all_same._filter" if name == "all_same" else "all_different._gqa_all_same._filter")
             if x is ins[0]:
                 raise Unsupported("a category without options")
             post = b.block(x.rows)
@@ -1002,12 +1029,13 @@ def _lower(pb, ontology, spec):
         elif name in ("two_same", "two_different"):
             _, (flat, bi) = b.category_options(args[0], ins[0].names)
             # (the Python operators evaluate and normalise the same blocks twice; once is the same values)
-            x1 = b.filter(ins[0], flat, (i, 0), bi, mkey=(i, "flt:0"))
+            cell = "two_same._filter" if name == "two_same" else "two_different._gqa_two_same._filter"
+            x1 = b.filter(ins[0], flat, (i, 0), bi, mkey=(i, "flt:0"), cell=cell)
             if x1 is ins[0]:
                 raise Unsupported("a category without options")
             spec_norm, b.spec.normalize = b.spec.normalize, False          # already normalised in place by the first filter
             try:
-                x2 = b.filter(ins[1], flat, (i, 0), bi, mkey=(i, "flt:1"))
+                x2 = b.filter(ins[1], flat, (i, 0), bi, mkey=(i, "flt:1"), cell=cell)
             finally:
                 b.spec.normalize = spec_norm
             lp1, lp2 = b.quantify(x1), b.quantify(x2)
@@ -1022,8 +1050,8 @@ def _lower(pb, ontology, spec):
                 lp = lp2_
             result = dict(kind="binary", type=QuestionType.BINARY, lp=lp, count=Q, options=["no", "yes"], num=x1.prev_num + x2.prev_num + 2)
         elif name == "compare":
-            x1 = b.filter(ins[0], args[0], (i, 0), mkey=(i, "flt:0"))
-            x2 = b.filter(ins[1], args[0], (i, 0), mkey=(i, "flt:1"))
+            x1 = b.filter(ins[0], args[0], (i, 0), mkey=(i, "flt:0"), cell="compare._filter")
+            x2 = b.filter(ins[1], args[0], (i, 0), mkey=(i, "flt:1"), cell="compare._filter")
             lp1, lp2 = b.quantify(x1), b.quantify(x2)
             lp = b.alloc(Q * 2 * 4, "o")
             b.emit(OP_COMPARE, lp1, lp2, b.arr(np.asarray([float(bool(v)) for v in args[1]], np.float32)), Q, lp)
@@ -1050,7 +1078,7 @@ def _choose_rel(b, i, prev, args):
     Q = b.Q
     lists = args[0]
     flat, bi = flatten_list(lists)
-    x = b.select(args[2] if len(args) > 2 else None, (i, 0), mkey=(i, "sel"))
+    x = b.select(args[2] if len(args) > 2 else None, (i, 0), mkey=(i, "sel"), cell="choose_rel._gqa_select._filter")
     host = [0.0 if f is None else float(f) for f in args[1]]
     subject_set = b.gate(x, prev, host)
     object_set = b.gate(prev, x, host)
@@ -1066,9 +1094,10 @@ def _choose_rel(b, i, prev, args):
     b._normalize(tiles, low, pq, 2, True)
     ps, po = b.block(P), b.block(P)
     flags = (RELATE_LONE_FORALL_IDENTITY if P == 1 else 0) | RELATE_DIAG_ABSENT
-    b.emit(OP_RELATE, subject_set.att, object_set.att, tiles, b.arr(pq), b.arr(q_s), b.arr(q_o), b.arr(low.neg) if low.any_neg else -1,
-           -1 if low.all_valid else b.arr(low.valid), b.arr(want), P,
-           TILE_SUBJECT_ROWS, flags, ps, po)
+    slot = b.slot("choose_rel._relate")
+    b.emit(OP_RELATE if slot is None else OP_RELATE_GATE, subject_set.att, object_set.att, tiles, b.arr(pq), b.arr(q_s), b.arr(q_o),
+           b.arr(low.neg) if low.any_neg else -1, -1 if low.all_valid else b.arr(low.valid), b.arr(want), P,
+           TILE_SUBJECT_ROWS, flags, ps, po, 0 if slot is None else slot)
     ps = b.modulate(ps, (i, "rel_s"), pq, P)                      # RelateBatch.forward :588-594
     po = b.modulate(po, (i, "rel_o"), pq, P)
     n_prev = subject_set.prev_num + object_set.prev_num + 1

@@ -51,7 +51,9 @@ extern "C" {
  * dfol_linear_wgrad_bias_rows_f32 and dfol_linear_wgrad_bias_rows_bf16, and the bf16 form of the store: dfol_store_round_bf16,
  * dfol_gather_object_rows_bf16_f32, dfol_linear_rows_bf16t_supported, dfol_linear_act_rows_bf16t_f32, dfol_linear_wgrad_rows_bf16t_supported,
  * dfol_linear_wgrad_bias_rows_bf16t and dfol_set_feature_rows_bf16, and the logic cell with the trainable gate: dfol_filter_gate_fwd_f32,
- * dfol_relate_gate_fwd_f32, dfol_filter_gate_bwd_scratch, dfol_filter_gate_bwd_f32 and dfol_relate_gate_bwd_f32;
+ * dfol_relate_gate_fwd_f32, dfol_filter_gate_bwd_scratch, dfol_filter_gate_bwd_f32 and dfol_relate_gate_bwd_f32, and the gated model on the
+ * executor: dfol_relate_one_gate_fwd_f32, dfol_set_program_gates and DFOL_OP_FILTER_GATE / DFOL_OP_RELATE_ONE_GATE / DFOL_OP_RELATE_GATE (no
+ * struct grows: the gate table travels beside the call, as dfol_set_feature_rows' arrays do);
  * a caller that needs them checks for the symbol, and a table that names an opcode an older library lacks is refused by it ("unknown opcode"). */
 #define DFOL_ABI_VERSION 3
 
@@ -181,6 +183,20 @@ int dfol_relate_gate_fwd_f32(const float* prior_s, const float* prior_o, const f
                              const float* quant_s, const float* quant_o, const uint8_t* neg, int32_t any_neg, const uint8_t* active,
                              const uint8_t* want, int32_t P, int32_t NS, int32_t orientation, int32_t flags, const float* gate_s,
                              const float* gate_o, float* post_s, float* post_o, void* stream);
+
+/* The gated cell with ONE posterior: the gated form of dfol_relate_one_fwd_f32 below (batch_gqa_ops.py:364-371 around a RelateBatch whose
+ * cell holds gates, batch_base_ops.py:99-100, :135-136) - the three gates of GQARelateBatch and the arity-2 cell in one launch, only the
+ * kept posterior written.  x_att, prev_att, tile (fp32, the SUMMED-OUT variable - prev's - along rows), pred_q, n_obj, quant_prev, neg,
+ * active, lone_forall_identity, the no-op rows and the padding are dfol_relate_one_fwd_f32's.  The two axes hold different gates, so
+ * x_is_subject [P] (uint8) says which one x is on: set -> the outer gate (joins x) is gate_s and the inner one (joins prev) gate_o; clear ->
+ * the outer gate is gate_o and the inner one gate_s:
+ *     post[p][i] = G_out( F( agg_{j < n, j != i} F( G_in(l'[j][i], prev_att[pred_q[p]][j]) ) ), x_att[p][i] ),  F and agg by quant_prev[p]
+ * i.e. post_s of dfol_relate_gate_fwd_f32 on (x, prev) over the transposed tile where the flag is set, post_o on (prev, x) where it is clear
+ * (the order of the sum differs, so the agreement is to rounding, not to the bit). */
+int dfol_relate_one_gate_fwd_f32(const float* x_att, const float* prev_att, const float* tile, const int32_t* pred_q, const int32_t* n_obj,
+                                 const float* quant_prev, const uint8_t* x_is_subject, const uint8_t* neg, int32_t any_neg,
+                                 const uint8_t* active, int32_t P, int32_t NS, int32_t lone_forall_identity, const float* gate_s,
+                                 const float* gate_o, float* post, void* stream);
 
 /* Relate with ONE posterior: what GQARelateBatch / verify_rel / choose_rel keep (batch_gqa_ops.py:364-371: gate x/prev into
  * subject/object, RelateBatch, gate the wanted posterior back).  Fuses the three gates and the arity-2 cell:
@@ -997,6 +1013,14 @@ typedef struct {            /* the scenes of one ProgramBatch (data_pipeline.py:
                                      * ("too large for the staging buffer") and keeps the separate launches */
 #define DFOL_OP_ATTR_HEAD 24        /* pre1, ld_pre1, pred_img (blob), cols (blob), P, ll, scenes: dfol_attr_head_h2_f32 over the attribute network's last layer
                                      * (a two-layer network whose last layer is DFOL_DENSE_HEAD_F16X2) - replaces that layer's DFOL_OP_DENSE and DFOL_OP_ATTR_LL */
+/* The logic instructions of a model with trainable gates (trainable_gate: True).  The reference builds its FilterBatch / RelateBatch - and so
+ * its gate parameters - per operator class (batch_gqa_ops.py), so every instruction names its cell: `slot` is a row of the table handed over with
+ * dfol_set_program_gates, and a cell of arity 2 owns rows slot (axis 0, the subject's) and slot + 1 (axis 1).  Without a table, or with a slot
+ * beyond it, the program is refused before the instruction launches anything. */
+#define DFOL_OP_FILTER_GATE 25      /* DFOL_OP_FILTER's operands, slot: dfol_filter_gate_fwd_f32 */
+#define DFOL_OP_RELATE_ONE_GATE 26  /* DFOL_OP_RELATE_ONE's operands (tile dtype DFOL_TILE_F32 only), x_is_subject (blob, uint8 [P]), slot:
+                                     * dfol_relate_one_gate_fwd_f32 */
+#define DFOL_OP_RELATE_GATE 27      /* DFOL_OP_RELATE's operands, slot: dfol_relate_gate_fwd_f32 */
 /* steps of a DFOL_OP_CALIB_WALK table; buffers are [planes][rows][width] floats in the workspace (an LSTM state is h then c: two planes) */
 #define DFOL_WALK_FILL 0            /* dst, planes, width, 32-bit pattern */
 #define DFOL_WALK_SELECT 1          /* x, y, flags (blob, uint8 [planes * rows]), planes, width, out: out = flags ? x : y per row */
@@ -1020,6 +1044,10 @@ int dfol_set_feature_rows_bf16(const int32_t* src_row, const float* box6);
  * DFOL_OP_BOX_POSITIONS writes the whole object matrix: cache rows src_row [O] of cache [rows, ld_cache] (W = the instruction's pos_col columns,
  * else refused) and the positions of box6 [O, 6].  Cleared by that call; all NULL / 0 clears it.  It takes precedence over dfol_set_feature_rows. */
 int dfol_set_feature_cache(const float* cache, int64_t ld_cache, int32_t W, const int32_t* src_row, const float* box6);
+/* The gate table of the NEXT dfol_run_program of the calling thread (thread-local, consumed and cleared by that call whether it succeeds or not;
+ * NULL, 0 clears it): table [n_gates][18] device floats, one row per gate in the layout the gated kernels read (W [6, 2] row-major, then c [6]),
+ * what DFOL_OP_FILTER_GATE / DFOL_OP_RELATE_ONE_GATE / DFOL_OP_RELATE_GATE index with their slot. */
+int dfol_set_program_gates(const float* table, int32_t n_gates);
 int dfol_run_program(const DfolProgramModel* model, const DfolProgramScene* scene, const int64_t* instr_host, int32_t n_instr,
                      const void* blob, void* workspace, void* stream);
 

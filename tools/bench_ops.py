@@ -8,6 +8,9 @@ One JSON line per operator kind: questions/s of a batch of `--batch` programs  s
 The logic cell's launches with and without the trainable gate (`trainable_gate: True`, csrc/dfol_logic_gate.hip): filter and relate, forward and
 backward, at `--batch` predicates x `--nmax` objects, gated and ungated alternating in one process (every round times each of the eight
 launches over `--reps` back-to-back launches between two events); one JSON line per launch with the median, minimum and maximum over the rounds.
+Then two legs for the gated model's fast inference path (DFOL_GATE_NATIVE=1): the one-launch gated Relate against the sequence it replaces
+(gate, gate, relate_gate_fwd under `want`, gate), and a stream of unseen gated batches on the native executor against the same stream on the
+Python operator loop (switch unset), each alternating in one process.
 """
 import argparse
 import json
@@ -104,9 +107,124 @@ def trainable_gate_launches(args):
                                  "us_max": float(v[-1]), "rounds": args.rounds, "reps": args.reps,
                                  "note": "backward entries include their reduce-by-question launches; host-side allocation of the outputs is inside the timed region"}))
         print(lines[-1], flush=True)
+    lines += gated_relate_one(args, L, t, rng, pa, pb, tile, pq, n_obj, ones, gs, go)
+    lines += gated_stream(args)
     if args.out:
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")
+
+
+def _summary(what, times, **more):
+    v = np.sort(np.asarray(times))
+    line = json.dumps(dict({"launch": what, "us_median": float(np.median(v)), "us_min": float(v[0]), "us_max": float(v[-1])}, **more))
+    print(line, flush=True)
+    return line
+
+
+def gated_relate_one(args, L, t, rng, x, prev, tile, pq, n_obj, ones, gs, go):
+    """The one-launch gated Relate (dfol_relate_one_gate_fwd_f32, DFOL_GATE_NATIVE=1) against the sequence a gated relate hop runs without it:
+    gate, gate, relate_gate_fwd under `want`, gate - alternating in one process, medians over the rounds.  (The upload of `want` is memoised
+    by content in the interpreter and is left out.)"""
+    P = tile.shape[0]
+    flag = (np.arange(P) % 2).astype(np.float32)                 # subject flags mixed over the batch
+    flag_f, flag_u8 = t(flag), t(flag, torch.uint8)
+    want = t(np.where(flag > 0, L.WANT_SUBJECT, L.WANT_OBJECT), torch.uint8)
+    oriented = torch.where(flag_f.view(-1, 1, 1) > 0, tile.transpose(1, 2), tile).contiguous()      # the summed-out variable (prev) along rows
+
+    def sequence():
+        s, q_s = L.gate(x, prev, ones, ones, flag_f)
+        o, q_o = L.gate(prev, x, ones, ones, flag_f)
+        ps, po = L.relate_gate_fwd(s, o, tile, pq, n_obj, q_s, q_o, gs, go, None, None, want, diag_absent=True)
+        return L.gate(ps, po, q_s, q_s, flag_f)[0]
+
+    def one():
+        return L.relate_one_gate_fwd(x, prev, oriented, pq, n_obj, ones, flag_u8, gs, go)
+
+    a, b = sequence(), one()
+    gap = float((torch.exp(a) - torch.exp(b)).abs().max())
+    assert gap <= 1e-5, gap                                      # the same posterior (another summation order)
+    launches = [("relate_gate_sequence(gate,gate,relate_gate_fwd,gate)", sequence), ("relate_one_gate_fwd", one)]
+    times = {name: [] for name, _ in launches}
+    for _ in range(args.rounds):
+        for name, fn in launches:
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(args.reps):
+                fn()
+            e.record()
+            e.synchronize()
+            times[name].append(s.elapsed_time(e) * 1e3 / args.reps)
+    more = dict(predicates=P, objects=args.nmax, rounds=args.rounds, reps=args.reps, max_abs_probability_gap=gap)
+    lines = [_summary(name, times[name], **more) for name, _ in launches]
+    ratio = float(np.median(times[launches[0][0]]) / np.median(times[launches[1][0]]))
+    lines.append(json.dumps({"ratio": "sequence / one launch (medians)", "value": ratio}))
+    print(lines[-1], flush=True)
+    return lines
+
+
+def gated_stream(args):
+    """A stream of unseen gated batches (every batch collated afresh: no plan, no uploaded side array is reused) with DFOL_GATE_NATIVE=1 (the
+    native executor; the plan is lowered at collate time, where a collate worker does it) against the same stream with the switch unset (the
+    Python operator loop), alternating batch by batch in one process; per-batch wall time from enqueue to the answers on the host."""
+    import dfol_vqa_amd as D
+    from dfol_vqa_amd import _lib, experiment, native_exec
+    from dfol_vqa_amd import synthetic as syn
+    device = torch.device("cuda", 0)
+    paths, names = syn.write_synthetic_ontology(tempfile.mkdtemp(prefix="dfol_gate_"))
+    cfg = syn.reference_config(paths, trainable_gate=True)
+    ontology = experiment.build_ontology(cfg)
+    model = experiment.build_model(cfg, ontology)
+    bench.init_weights(model)
+    model = model.to(device).eval()
+    os.environ["DFOL_GATE_NATIVE"] = "1"
+    spec = native_exec.model_spec(model)
+    assert spec is not None and spec.gates
+
+    class Collater(D.ProgramCollaterBase):
+        def __init__(self, spec):
+            super(Collater, self).__init__("select", "relate", "filter", 1, ontology=ontology, native_spec=spec)
+
+        def collate_object_features(self, qs):
+            feats = torch.cat([torch.from_numpy(q["scene"]["X"]) for q in qs], 0)
+            bi = torch.cat([torch.full((q["scene"]["n"],), i, dtype=torch.int64) for i, q in enumerate(qs)])
+            return feats, bi
+
+        def collate_meta_data(self, qs):
+            return {"index": {}, "embedding": torch.zeros(1, 1)}
+
+    kinds = ["exist", "verify_rel", "choose_rel", "query_attr"]
+    times = {"1": [], "0": []}
+    warm = 2
+    for r in range(warm + args.rounds):
+        kind = kinds[r % len(kinds)]
+        for k, mode in enumerate(("1", "0") if r % 2 == 0 else ("0", "1")):          # (who goes first alternates)
+            qs = questions(kind, args.batch, args.nmin, args.nmax, names, seed=5000 + 2 * r + k)
+            pbs = Collater(spec if mode == "1" else None).collate(qs)
+            for pb in pbs:
+                pb.create_sparse_tensors()
+            pbs = [pb.to_cuda(device) for pb in pbs]
+            del qs
+            if mode == "1":
+                os.environ["DFOL_GATE_NATIVE"] = "1"
+            else:
+                os.environ.pop("DFOL_GATE_NATIVE", None)
+            _lib.PATH_COUNTS.clear()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            with torch.no_grad():
+                model(pbs, False)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            assert _lib.PATH_COUNTS.get("native_program" if mode == "1" else "python_program", 0) == len(pbs), dict(_lib.PATH_COUNTS)
+            if r >= warm:                                          # (the first batches of a route load its kernels' code objects)
+                times[mode].append(dt * 1e6)
+    os.environ.pop("DFOL_GATE_NATIVE", None)
+    more = dict(batch=args.batch, objects=[args.nmin, args.nmax], batches=args.rounds, kinds=kinds)
+    lines = [_summary("unseen gated batch, DFOL_GATE_NATIVE=1 (native executor)", times["1"], **more),
+             _summary("unseen gated batch, switch unset (Python operator loop)", times["0"], **more)]
+    lines.append(json.dumps({"ratio": "Python loop / executor (median per-batch time)", "value": float(np.median(times["0"]) / np.median(times["1"]))}))
+    print(lines[-1], flush=True)
+    return lines
 
 
 def main():
