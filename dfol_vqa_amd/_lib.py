@@ -131,7 +131,9 @@ SIGNATURES = {
     "dfol_filter_gate_fwd_f32": [_p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _p, _p, _p],
     "dfol_relate_gate_fwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p],
     "dfol_relate_one_gate_fwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _p],
-    "dfol_filter_gate_bwd_scratch": [_i32, _i32],           # returns a float count (int64), called directly
+    "dfol_relate_keep_gate_fwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _p],
+    "dfol_relate_keep_gate_bwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    "dfol_filter_gate_bwd_scratch": [_i32, _i32],          # returns a float count (int64), called directly
     "dfol_filter_gate_bwd_f32": [_p, _p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _p, _p, _p, _p, _p, _p],
     "dfol_relate_gate_bwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "dfol_attr_gather_bwd_f32": [_p, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _p],
@@ -578,6 +580,33 @@ def relate_one_gate_fwd(x_att, prev_att, tile, pred_q, n_obj, quant_prev, x_is_s
         raise DfolError("relate_one_gate_fwd: %d subject flags for %d predicates" % (x_is_subject.numel(), P))
     post = torch.empty(P, NS, dtype=F32, device=tile.device)
     call("dfol_relate_one_gate_fwd_f32", _ptr(x_att, F32), _ptr(prev_att, F32), _ptr(tile, F32), _ptr(pred_q, I32), _ptr(n_obj, I32),
+         _ptr(quant_prev, F32), _ptr(x_is_subject, U8), _ptr(neg, U8, True), 0 if neg is None else 1, _ptr(active, U8, True), P, NS,
+         1 if lone_forall_identity else 0, _ptr(gate_s, F32), _ptr(gate_o, F32), _ptr(post), _stream())
+    return post
+
+
+def gate_train():
+    """DFOL_GATE_TRAIN=1 (opt-in, read when a forward starts; independent of DFOL_GATE_NATIVE): a gated relate hop that a gradient reaches runs
+    the one-posterior kernels (relate_keep_gate_fwd / relate_keep_gate_bwd) instead of gate, gate, relate_gate_fwd(want), gate and their autograd
+    backward.  Unset: the generic gated route under autograd, as before."""
+    return os.environ.get("DFOL_GATE_TRAIN", "0") == "1"
+
+
+def _keep_gate_check(what, tile, x_is_subject):
+    if tile.dtype != F32:
+        raise DfolError("the gated relate kernels read fp32 tiles (got %s): relation_tile_dtype: bf16 and trainable_gate: True do not combine" % tile.dtype)
+    P, NS = tile.shape[0], tile.shape[1]
+    if x_is_subject.numel() != P:
+        raise DfolError("%s: %d subject flags for %d predicates" % (what, x_is_subject.numel(), P))
+    return P, NS
+
+
+def relate_keep_gate_fwd(x_att, prev_att, tile, pred_q, n_obj, quant_prev, x_is_subject, gate_s, gate_o, neg=None, active=None,
+                         lone_forall_identity=False):
+    """relate_one_gate_fwd on the train step's tile: SUBJECTS along rows for every predicate, x_is_subject uint8 [P] picks the axis summed out."""
+    P, NS = _keep_gate_check("relate_keep_gate_fwd", tile, x_is_subject)
+    post = torch.empty(P, NS, dtype=F32, device=tile.device)
+    call("dfol_relate_keep_gate_fwd_f32", _ptr(x_att, F32), _ptr(prev_att, F32), _ptr(tile, F32), _ptr(pred_q, I32), _ptr(n_obj, I32),
          _ptr(quant_prev, F32), _ptr(x_is_subject, U8), _ptr(neg, U8, True), 0 if neg is None else 1, _ptr(active, U8, True), P, NS,
          1 if lone_forall_identity else 0, _ptr(gate_s, F32), _ptr(gate_o, F32), _ptr(post), _stream())
     return post
@@ -1772,6 +1801,37 @@ def relate_gate_bwd(prior_s, prior_o, tile, pred_q, n_obj, quant_s, quant_o, gat
          _ptr(g_post_s, F32, True), _ptr(g_post_o, F32, True), P, NS, orientation, 1 if lone_forall_identity else 0, _ptr(gate_s, F32),
          _ptr(gate_o, F32), _ptr(scratch), _ptr(pp_s), _ptr(pp_o), _ptr(g_tile), _ptr(gg_s), _ptr(gg_o), _stream())
     return reduce_by_question(pp_s, pred_q, None, Q), reduce_by_question(pp_o, pred_q, None, Q), g_tile, gg_s, gg_o
+
+
+def is_identity_map(pred_q, Q):
+    """True when pred_q is known, without reading the device, to map predicate p to question p (BatchWorld._ident carries the mark)."""
+    return bool(getattr(pred_q, "_dfol_identity", False)) and pred_q.numel() == Q
+
+
+def relate_keep_gate_bwd(g_post, x_att, prev_att, tile, pred_q, n_obj, quant_prev, x_is_subject, gate_s, gate_o, neg, active,
+                         lone_forall_identity, identity=None):
+    """-> (g_x [P, NS], g_prev [Q, NS], g_tile [P, NS, NS] subjects along rows, g_gate_s [18], g_gate_o [18]).  identity: pred_q maps predicate p
+    to question p, so g_prev needs no reduction (None: is_identity_map)."""
+    P, NS = _keep_gate_check("relate_keep_gate_bwd", tile, x_is_subject)
+    if NS > 1024:
+        raise DfolError("relate_keep_gate_bwd: images of %d object slots; the gated Relate backward keeps its row and column sums in LDS and takes at most 1024" % NS)
+    Q = prev_att.shape[0]
+    if identity is None:
+        identity = is_identity_map(pred_q, Q)
+    if not identity:
+        require_sorted(pred_q, "relate_keep_gate_bwd")
+    dev = tile.device
+    g_x = torch.empty(P, NS, dtype=F32, device=dev)
+    pp = torch.empty(P, NS, dtype=F32, device=dev)                                          # per predicate
+    g_tile = torch.empty(P, NS, NS, dtype=F32, device=dev)
+    gg_s = torch.empty(18, dtype=F32, device=dev)
+    gg_o = torch.empty(18, dtype=F32, device=dev)
+    scratch = torch.empty(max(1, 36 * P), dtype=F32, device=dev)
+    call("dfol_relate_keep_gate_bwd_f32", _ptr(g_post, F32), _ptr(x_att, F32), _ptr(prev_att, F32), _ptr(tile, F32), _ptr(pred_q, I32),
+         _ptr(n_obj, I32), _ptr(quant_prev, F32), _ptr(x_is_subject, U8), _ptr(neg, U8, True), 0 if neg is None else 1, _ptr(active, U8, True),
+         P, NS, 1 if lone_forall_identity else 0, _ptr(gate_s, F32), _ptr(gate_o, F32), _ptr(scratch), _ptr(g_x), _ptr(pp), _ptr(g_tile),
+         _ptr(gg_s), _ptr(gg_o), _stream())
+    return g_x, (pp if identity else reduce_by_question(pp, pred_q, None, Q)), g_tile, gg_s, gg_o
 
 
 def quantify_bwd(g_lp, att, quant, pred_q, n_obj):

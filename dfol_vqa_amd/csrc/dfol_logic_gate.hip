@@ -1,5 +1,5 @@
 // The logic cell with the trainable gate (`trainable_gate: True`): gated forms of the Filter and Relate kernels, forward and backward, and of the
-// one-posterior Relate (forward; inference).
+// one-posterior Relate (forward on prev-row tiles for inference; forward and backward on subject-row tiles for the train step).
 //
 // Reference: NeuralLogicGate, batch_base_ops.py:19-38, used by BatchBayesianLogicCell._forward_core at :99-102 and :135-138: every
 // `x + log_p` of the cell becomes G_k(x, log_p), k the axis whose prior is joined.  With W_k [6, 2], c_k [6] (nn.Linear(2, 6)):
@@ -694,6 +694,350 @@ __global__ __launch_bounds__(256) void relate_one_gate_big_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// relate, single posterior, on the SUBJECT-ROW tile of the train step (oracle.block_likelihood stores subjects along rows for every
+// predicate; the inference prefetch that turns prev's objects onto the rows does not run under autograd).  The predicate's flag picks,
+// wave-uniformly, which axis is summed out:
+//     x_is_subject[p]:  post[p][i] = G_0( F( agg_{j != i} F( G_1(l'[i][j], prev[j]) ) ), x[p][i] )      row aggregate    (inner gate_o, outer gate_s)
+//     otherwise:        post[p][i] = G_1( F( agg_{j != i} F( G_0(l'[j][i], prev[j]) ) ), x[p][i] )      column aggregate (inner gate_s, outer gate_o)
+// The column branch is relate_one_gate_fwd_kernel's loop; the row branch is the row half of relate_gate_fwd_kernel (a column's prev, e^prev
+// and share of the pre-activations once per wavefront, the row aggregate by the group reduction, the outer gate in the lane that owns the
+// row).  Everything else - l', eps, the lone predicate's literal FOR_ALL branch, the no-op rows - is relate_one_gate_fwd_kernel's.
+// ---------------------------------------------------------------------------------------------------
+template <int LPR>
+__global__ __launch_bounds__(256) void relate_keep_gate_fwd_kernel(
+    const float* __restrict__ x_att, const float* __restrict__ prev_att, const float* __restrict__ tile, const int32_t* __restrict__ pred_q,
+    const int32_t* __restrict__ n_obj, const float* __restrict__ quant_prev, const uint8_t* __restrict__ x_is_subject,
+    const uint8_t* __restrict__ neg, int any_neg, const uint8_t* __restrict__ active, int P, int NS, int identity_forall,
+    const float* __restrict__ gate_s, const float* __restrict__ gate_o, float* __restrict__ post) {
+    constexpr int RPI = 64 / LPR;
+    __shared__ float row_agg[4][256];
+    const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int p = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    if (p >= P) return;
+    const int lane = threadIdx.x & 63;
+    const int q = pred_q[p];
+    const int n = min(n_obj[q], NS);
+    const float* pv = prev_att + (int64_t)q * NS;
+    const float* xv = x_att + (int64_t)p * NS;
+    float* out = post + (int64_t)p * NS;
+    if (active && !active[p]) {                         // question without this operator: attention passes through
+        for (int c = lane; c < NS; c += 64) out[c] = c < n ? pv[c] : 0.f;
+        return;
+    }
+    const bool xs = x_is_subject[p] != 0;
+    const GateW GI = gate_load(xs ? gate_o : gate_s), GO = gate_load(xs ? gate_s : gate_o);      // inner: prev's axis, outer: x's
+    const int cg = lane % LPR, rs = lane / LPR, c0 = cg * 4, cl = min(c0, NS - 4);               // (lanes beyond the width read a valid column)
+    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
+    const float qf = quant_prev[p], kf = 1.f - 2.f * qf;
+    const bool ex = qf == 1.f, ident = identity_forall && qf == 0.f;
+    const float* tp = tile + (int64_t)p * NS * NS;
+    if (xs) {                                           // prev along columns: row aggregates
+        const float4 pc4 = *reinterpret_cast<const float4*>(pv + cl);
+        const float pc[4] = {pc4.x, pc4.y, pc4.z, pc4.w};
+        float zbC[4][6], ebC[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            gate_zb(GI, pc[j], zbC[j]);
+            ebC[j] = dfol_exp(pc[j]);
+        }
+        for (int r0 = 0; r0 < n; r0 += RPI) {
+            const int r = r0 + rs, rc = min(r, n - 1);
+            const float4 t4 = *reinterpret_cast<const float4*>(tp + (int64_t)rc * NS + cl);
+            const float l[4] = {t4.x, t4.y, t4.z, t4.w};
+            float racc = 0.f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int c = c0 + j;
+                const bool keep = r < n && c < n && c != r;
+                const float v = gate_prep(l[j], any_neg, alpha_n, cn);
+                const float t = gate_term(gate_m(GI, v, dfol_exp(v), zbC[j], ebC[j]), ex, qf, kf);
+                racc = gate_join(racc, keep ? t : 0.f, ex);
+            }
+            racc = ex ? dfol_group_or<LPR>(racc) : dfol_group_sum<LPR>(racc);
+            if (cg == LPR - 1 && r < n) row_agg[wave_in_block][r] = racc;
+        }
+        __builtin_amdgcn_wave_barrier();                 // LDS is in order within a wavefront; this only pins the schedule
+        for (int c = lane; c < NS; c += 64) {
+            float o = 0.f;
+            if (c < n) o = gate_log(GO, gate_outer(row_agg[wave_in_block][c], ex, ident, qf, kf), xv[c]);
+            out[c] = o;
+        }
+        return;
+    }
+    float cacc[4] = {0.f, 0.f, 0.f, 0.f};               // prev along rows: column aggregates, in registers
+    for (int r0 = 0; r0 < n; r0 += RPI) {
+        const int r = r0 + rs, rc = min(r, n - 1);
+        const float4 t4 = *reinterpret_cast<const float4*>(tp + (int64_t)rc * NS + cl);
+        const float l[4] = {t4.x, t4.y, t4.z, t4.w};
+        const float pr = pv[rc];
+        float zb[6];
+        gate_zb(GI, pr, zb);
+        const float eb = dfol_exp(pr);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = c0 + j;
+            const bool keep = r < n && c < n && c != r;
+            const float v = gate_prep(l[j], any_neg, alpha_n, cn);
+            const float t = gate_term(gate_m(GI, v, dfol_exp(v), zb, eb), ex, qf, kf);
+            cacc[j] = gate_join(cacc[j], keep ? t : 0.f, ex);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int m = 32; m >= LPR; m >>= 1) cacc[j] = gate_join(cacc[j], __shfl_xor(cacc[j], m, 64), ex);
+    }
+    if (rs == 0 && c0 < NS) {
+        const float4 x4 = *reinterpret_cast<const float4*>(xv + c0);
+        const float xj[4] = {x4.x, x4.y, x4.z, x4.w};
+        float o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = (c0 + j < n) ? gate_log(GO, gate_outer(cacc[j], ex, ident, qf, kf), xj[j]) : 0.f;
+        *reinterpret_cast<float4*>(out + c0) = make_float4(o[0], o[1], o[2], o[3]);
+    }
+}
+
+// NS > 256: one workgroup per predicate; a thread per column, rows in order, for the column aggregate, a workgroup reduction per row (wavefront
+// partials joined in wavefront order) for the row aggregate, as relate_gate_big_fwd_kernel.
+__global__ __launch_bounds__(256) void relate_keep_gate_big_kernel(
+    const float* __restrict__ x_att, const float* __restrict__ prev_att, const float* __restrict__ tile, const int32_t* __restrict__ pred_q,
+    const int32_t* __restrict__ n_obj, const float* __restrict__ quant_prev, const uint8_t* __restrict__ x_is_subject,
+    const uint8_t* __restrict__ neg, int any_neg, const uint8_t* __restrict__ active, int NS, int identity_forall,
+    const float* __restrict__ gate_s, const float* __restrict__ gate_o, float* __restrict__ post) {
+    __shared__ float part[4];
+    const int p = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    const int q = pred_q[p], n = min(n_obj[q], NS);
+    const float* pv = prev_att + (int64_t)q * NS;
+    const float* xv = x_att + (int64_t)p * NS;
+    float* out = post + (int64_t)p * NS;
+    if (active && !active[p]) {
+        for (int c = tid; c < NS; c += 256) out[c] = c < n ? pv[c] : 0.f;
+        return;
+    }
+    const bool xs = x_is_subject[p] != 0;
+    const GateW GI = gate_load(xs ? gate_o : gate_s), GO = gate_load(xs ? gate_s : gate_o);
+    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
+    const float qf = quant_prev[p], kf = 1.f - 2.f * qf;
+    const bool ex = qf == 1.f, ident = identity_forall && qf == 0.f;
+    const float* tp = tile + (int64_t)p * NS * NS;
+    if (!xs) {
+        for (int c = tid; c < NS; c += 256) {
+            float o = 0.f;
+            if (c < n) {
+                float acc = 0.f;
+                for (int r = 0; r < n; ++r) {
+                    if (r == c) continue;
+                    const float v = gate_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn);
+                    float zb[6];
+                    gate_zb(GI, pv[r], zb);
+                    acc = gate_join(acc, gate_term(gate_m(GI, v, dfol_exp(v), zb, dfol_exp(pv[r])), ex, qf, kf), ex);
+                }
+                o = gate_log(GO, gate_outer(acc, ex, ident, qf, kf), xv[c]);
+            }
+            out[c] = o;
+        }
+        return;
+    }
+    for (int r = 0; r < NS; ++r) {                       // (xs is the workgroup's: every thread reaches the barriers)
+        float s = 0.f;
+        if (r < n)
+            for (int c = tid; c < n; c += 256) {
+                if (c == r) continue;
+                const float v = gate_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn);
+                float zb[6];
+                gate_zb(GI, pv[c], zb);
+                s = gate_join(s, gate_term(gate_m(GI, v, dfol_exp(v), zb, dfol_exp(pv[c])), ex, qf, kf), ex);
+            }
+        s = gate_wave_join(s, ex);
+        if (lane == 0) part[w] = s;
+        __syncthreads();
+        if (tid == 0) {
+            const float tot = gate_join(gate_join(gate_join(part[0], part[1], ex), part[2], ex), part[3], ex);
+            out[r] = r < n ? gate_log(GO, gate_outer(tot, ex, ident, qf, kf), xv[r]) : 0.f;
+        }
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// backward of the single posterior on the subject-row tile: relate_gate_bwd_kernel's scheme (a workgroup per predicate, its wavefronts on rows
+// r = w, w + waves, ..., lane = column) restricted to the kept direction.  Sweep 1 recomputes the one aggregate as written (sum of logs, EXISTS
+// too), the outer gate is differentiated by the thread that owns the element, sweep 2 takes the element gates.  Every thread keeps the 2 x 18
+// parameter sums of its elements (inner and outer gate); the workgroup's total goes to scratch[p][36] as [axis 0's 18 | axis 1's 18], the halves
+// picked by the predicate's flag, and gate_param_reduce_kernel adds the rows.
+// ---------------------------------------------------------------------------------------------------
+constexpr int KB_WAVES = 8;
+__global__ __launch_bounds__(64 * KB_WAVES) void relate_keep_gate_bwd_kernel(
+    const float* __restrict__ g_post, const float* __restrict__ x_att, const float* __restrict__ prev_att, const float* __restrict__ tile,
+    const int32_t* __restrict__ pred_q, const int32_t* __restrict__ n_obj, const float* __restrict__ quant_prev,
+    const uint8_t* __restrict__ x_is_subject, const uint8_t* __restrict__ neg, int any_neg, const uint8_t* __restrict__ active, int NS,
+    int identity_forall, const float* __restrict__ gate_s, const float* __restrict__ gate_o, float* __restrict__ scratch,
+    float* __restrict__ g_x, float* __restrict__ g_prev, float* __restrict__ g_tile) {
+    extern __shared__ float keep_bwd_lds[];              // (2 + waves) NS floats + waves x 36
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, tid = threadIdx.x, nw = (int)blockDim.x >> 6, nt = (int)blockDim.x;
+    float* sA = keep_bwd_lds;                             // x on rows: the row aggregates; x on columns: the rows' prev gradients (sweep 2)
+    float* sG = sA + NS;                                  // d loss / d aggregate
+    float* part_base = sG + NS;                           // x on columns: the column aggregates' partials; x on rows: the columns' prev gradients
+    float* wsum = part_base + (size_t)nw * NS;            // [nw][36]
+    auto part = [&](int wave, int c) -> float& { return part_base[wave * NS + c]; };
+    const int p = blockIdx.x;
+    const int q = pred_q[p];
+    const int n = min(n_obj[q], NS);
+    const float* pv = prev_att + (int64_t)q * NS;
+    const float* xv = x_att + (int64_t)p * NS;
+    const float* gp = g_post + (int64_t)p * NS;
+    const float* tp = tile + (int64_t)p * NS * NS;
+    float* gt = g_tile + (int64_t)p * NS * NS;
+    float* gx = g_x + (int64_t)p * NS;
+    float* gpv = g_prev + (int64_t)p * NS;
+    float* sc = scratch + (int64_t)p * 36;
+
+    if (active && !active[p]) {                            // posterior = prev: the gradient passes straight through, the gates see nothing
+        for (int c = tid; c < NS; c += nt) {
+            gpv[c] = c < n ? gp[c] : 0.f;
+            gx[c] = 0.f;
+        }
+        for (int e = tid; e < NS * NS; e += nt) gt[e] = 0.f;
+        if (tid < 36) sc[tid] = 0.f;
+        return;
+    }
+    const bool xs = x_is_subject[p] != 0;                  // (the workgroup's: every branch on it is uniform)
+    const GateW GI = gate_load(xs ? gate_o : gate_s), GO = gate_load(xs ? gate_s : gate_o);
+    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
+    const float qf = quant_prev[p], kf = 1.f - 2.f * qf;
+    const bool ident = identity_forall && qf == 0.f;
+    float accI[18], accO[18];
+#pragma unroll
+    for (int k = 0; k < 18; ++k) accI[k] = accO[k] = 0.f;
+
+    // sweep 1: the aggregate over prev's axis
+    for (int c0 = 0; c0 < NS; c0 += 64) {
+        const int c = c0 + lane;
+        if (xs) {                                          // S[r] = sum_c F(G_in(l'[r][c], prev[c]))
+            const float pc = c < n ? pv[c] : 0.f;
+            float zbc[6];
+            gate_zb(GI, pc, zbc);
+            const float ebc = dfol_exp(pc);
+            for (int r = w; r < n; r += nw) {
+                float s_part = 0.f;
+                if (c < n && c != r) {
+                    const float v = gate_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn);
+                    s_part = dfol_slog(fmaf(kf, gate_m(GI, v, dfol_exp(v), zbc, ebc), qf));
+                }
+                s_part = dfol_wave_sum(s_part);
+                if (lane == 0) sA[r] = (c0 == 0 ? 0.f : sA[r]) + s_part;
+            }
+        } else {                                           // T[c] = sum_r F(G_in(l'[r][c], prev[r]))
+            float t_acc = 0.f;
+            for (int r = w; r < n; r += nw) {
+                if (c < n && c != r) {
+                    const float v = gate_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn);
+                    const float pr = pv[r];
+                    float zbr[6];
+                    gate_zb(GI, pr, zbr);
+                    t_acc += dfol_slog(fmaf(kf, gate_m(GI, v, dfol_exp(v), zbr, dfol_exp(pr)), qf));
+                }
+            }
+            if (c < NS) part(w, c) = t_acc;
+        }
+    }
+    __syncthreads();
+    // the outer gate G_out(F(A[i]), x[i]), by the thread that owns element i
+    for (int i = tid; i < NS; i += nt) {
+        float dA = 0.f, dx = 0.f;
+        if (i < n) {
+            float A;
+            if (xs) {
+                A = sA[i];
+            } else {
+                A = part(0, i);
+                for (int j = 1; j < nw; ++j) A += part(j, i);
+            }
+            const float a = ident ? A : dfol_pnot(A, qf, kf);
+            float da;
+            gate_bwd(GO, a, xv[i], gp[i], true, da, dx, accO);
+            dA = da * (ident ? 1.f : gate_dpnot(A, qf, kf));
+        }
+        sG[i] = dA;
+        gx[i] = dx;
+    }
+    __syncthreads();
+    // sweep 2: the element gates
+    for (int c0 = 0; c0 < NS; c0 += 64) {
+        const int c = c0 + lane;
+        if (xs) {
+            const float pc = c < n ? pv[c] : 0.f;
+            float zbc[6];
+            gate_zb(GI, pc, zbc);
+            const float ebc = dfol_exp(pc);
+            float dpc = 0.f;
+            for (int r = w; r < NS; r += nw) {
+                float dl = 0.f;
+                if (r < n && c < n && c != r) {            // t = log(max(q + k m, eps)), m = e^G_in(v, prev[c])
+                    const float raw = tp[(int64_t)r * NS + c];
+                    const float v = gate_prep(raw, any_neg, alpha_n, cn);
+                    const float u = fmaf(kf, gate_m(GI, v, dfol_exp(v), zbc, ebc), qf);
+                    const float dm = u > DFOL_EPS ? sG[r] * kf / u : 0.f;
+                    float da, db;
+                    gate_bwd(GI, v, pc, dm, false, da, db, accI);
+                    dpc += db;
+                    dl = da * gate_dprep(raw, any_neg, alpha_n, cn);
+                }
+                if (c < NS) gt[(int64_t)r * NS + c] = dl;
+            }
+            if (c < NS) part(w, c) = dpc;
+        } else {
+            const float gcc = c < n ? sG[c] : 0.f;
+            for (int r = w; r < NS; r += nw) {
+                float dl = 0.f, dpr = 0.f;
+                if (r < n && c < n && c != r) {
+                    const float raw = tp[(int64_t)r * NS + c];
+                    const float v = gate_prep(raw, any_neg, alpha_n, cn);
+                    const float pr = pv[r];
+                    float zbr[6];
+                    gate_zb(GI, pr, zbr);
+                    const float u = fmaf(kf, gate_m(GI, v, dfol_exp(v), zbr, dfol_exp(pr)), qf);
+                    const float dm = u > DFOL_EPS ? gcc * kf / u : 0.f;
+                    float da;
+                    gate_bwd(GI, v, pr, dm, false, da, dpr, accI);
+                    dl = da * gate_dprep(raw, any_neg, alpha_n, cn);
+                }
+                if (c < NS) gt[(int64_t)r * NS + c] = dl;
+                dpr = dfol_wave_sum(dpr);                  // row totals over the column chunks collect in LDS
+                if (lane == 0 && r < n) sA[r] = (c0 == 0 ? 0.f : sA[r]) + dpr;
+            }
+        }
+    }
+    // the parameter sums of this workgroup: wavefront totals, then the wavefronts in order; axis 0's gate first
+#pragma unroll
+    for (int k = 0; k < 18; ++k) {
+        const float a = dfol_wave_sum(xs ? accO[k] : accI[k]), b = dfol_wave_sum(xs ? accI[k] : accO[k]);
+        if (lane == 0) {
+            wsum[w * 36 + k] = a;
+            wsum[w * 36 + 18 + k] = b;
+        }
+    }
+    __syncthreads();
+    for (int c = tid; c < NS; c += nt) {
+        float t = 0.f;
+        if (c < n) {
+            if (xs) {
+                t = part(0, c);
+                for (int j = 1; j < nw; ++j) t += part(j, c);
+            } else {
+                t = sA[c];
+            }
+        }
+        gpv[c] = t;
+    }
+    if (tid < 36) {
+        float s = wsum[tid];
+        for (int j = 1; j < nw; ++j) s += wsum[j * 36 + tid];
+        sc[tid] = s;
+    }
+}
+
 template <int LPR>
 void launch_relate_gate(hipStream_t st, const float* pR, const float* pC, const float* tile, const int32_t* pred_q, const int32_t* n_obj,
                         const float* qR, const float* qC, const uint8_t* neg, int any_neg, const uint8_t* active, const uint8_t* want, int bR,
@@ -844,5 +1188,61 @@ extern "C" int dfol_relate_gate_bwd_f32(const float* prior_s, const float* prior
     hipLaunchKernelGGL(gate_param_reduce_kernel, dim3(36), dim3(64), 0, st, (const float*)scratch, (int64_t)P, 36, sr ? g_gate_s : g_gate_o,
                        sr ? g_gate_o : g_gate_s);
     DFOL_LAUNCH_CHECK("relate_gate_bwd (reduce)");
+    return 0;
+}
+
+extern "C" int dfol_relate_keep_gate_fwd_f32(const float* x_att, const float* prev_att, const float* tile, const int32_t* pred_q,
+                                             const int32_t* n_obj, const float* quant_prev, const uint8_t* x_is_subject, const uint8_t* neg,
+                                             int32_t any_neg, const uint8_t* active, int32_t P, int32_t NS, int32_t lone_forall_identity,
+                                             const float* gate_s, const float* gate_o, float* post, void* stream) {
+    DFOL_REQUIRE(P >= 0 && NS > 0 && NS % 4 == 0, "relate_keep_gate_fwd: bad sizes P=%d NS=%d (NS: a multiple of 4)", P, NS);
+    if (P == 0) return 0;
+    DFOL_REQUIRE(x_att && prev_att && tile && pred_q && n_obj && quant_prev && x_is_subject && gate_s && gate_o && post,
+                 "relate_keep_gate_fwd: null pointer");
+    DFOL_REQUIRE(!any_neg || neg, "relate_keep_gate_fwd: any_neg set but neg is NULL");
+    hipStream_t st = (hipStream_t)stream;
+    if (NS > 256) {
+        hipLaunchKernelGGL(relate_keep_gate_big_kernel, dim3(P), dim3(256), 0, st, x_att, prev_att, tile, pred_q, n_obj, quant_prev, x_is_subject, neg,
+                           any_neg, active, NS, lone_forall_identity, gate_s, gate_o, post);
+        DFOL_LAUNCH_CHECK("relate_keep_gate_fwd (NS > 256)");
+        return 0;
+    }
+    const int groups = NS / 4;
+#define DFOL_GATEK(L)                                                                                                                           \
+    hipLaunchKernelGGL(relate_keep_gate_fwd_kernel<L>, dim3(dfol_cdiv(P, 4)), dim3(256), 0, st, x_att, prev_att, tile, pred_q, n_obj, quant_prev, \
+                       x_is_subject, neg, any_neg, active, P, NS, lone_forall_identity, gate_s, gate_o, post)
+    if (groups <= 1) DFOL_GATEK(1);
+    else if (groups <= 2) DFOL_GATEK(2);
+    else if (groups <= 4) DFOL_GATEK(4);
+    else if (groups <= 8) DFOL_GATEK(8);
+    else if (groups <= 16) DFOL_GATEK(16);
+    else if (groups <= 32) DFOL_GATEK(32);
+    else DFOL_GATEK(64);
+#undef DFOL_GATEK
+    DFOL_LAUNCH_CHECK("relate_keep_gate_fwd");
+    return 0;
+}
+
+extern "C" int dfol_relate_keep_gate_bwd_f32(const float* g_post, const float* x_att, const float* prev_att, const float* tile,
+                                             const int32_t* pred_q, const int32_t* n_obj, const float* quant_prev, const uint8_t* x_is_subject,
+                                             const uint8_t* neg, int32_t any_neg, const uint8_t* active, int32_t P, int32_t NS,
+                                             int32_t lone_forall_identity, const float* gate_s, const float* gate_o, float* scratch, float* g_x,
+                                             float* g_prev, float* g_tile, float* g_gate_s, float* g_gate_o, void* stream) {
+    DFOL_REQUIRE(P >= 0 && NS > 0 && NS % 4 == 0 && NS <= 1024, "relate_keep_gate_bwd: bad sizes P=%d NS=%d (NS: a multiple of 4, <= 1024)", P, NS);
+    DFOL_REQUIRE(g_gate_s && g_gate_o, "relate_keep_gate_bwd: null pointer (g_gate)");
+    hipStream_t st = (hipStream_t)stream;
+    if (P > 0) {
+        DFOL_REQUIRE(g_post && x_att && prev_att && tile && pred_q && n_obj && quant_prev && x_is_subject && gate_s && gate_o && scratch && g_x &&
+                         g_prev && g_tile,
+                     "relate_keep_gate_bwd: null pointer");
+        DFOL_REQUIRE(!any_neg || neg, "relate_keep_gate_bwd: any_neg set but neg is NULL");
+        // (2 + waves) NS floats of rows / columns and waves x 36 of parameter sums (NS <= 1024: 41.2 KB)
+        const size_t lds = ((size_t)(2 + KB_WAVES) * NS + (size_t)KB_WAVES * 36) * sizeof(float);
+        hipLaunchKernelGGL(relate_keep_gate_bwd_kernel, dim3(P), dim3(64 * KB_WAVES), lds, st, g_post, x_att, prev_att, tile, pred_q, n_obj, quant_prev,
+                           x_is_subject, neg, any_neg, active, NS, lone_forall_identity, gate_s, gate_o, scratch, g_x, g_prev, g_tile);
+        DFOL_LAUNCH_CHECK("relate_keep_gate_bwd");
+    }
+    hipLaunchKernelGGL(gate_param_reduce_kernel, dim3(36), dim3(64), 0, st, (const float*)scratch, (int64_t)P, 36, g_gate_s, g_gate_o);
+    DFOL_LAUNCH_CHECK("relate_keep_gate_bwd (reduce)");
     return 0;
 }

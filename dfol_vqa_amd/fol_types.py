@@ -57,6 +57,7 @@ def _geometry_on_device(device, n_list):
                torch.as_tensor(np.concatenate([[0], np.cumsum(n * (n - 1))]).astype(np.int64)).to(device),
                torch.arange(len(n_list), dtype=torch.int32, device=device))
         hit[3]._dfol_sorted = True                               # the identity map (see _lib.require_sorted)
+        hit[3]._dfol_identity = True                             # (and _lib.is_identity_map: a per-predicate gradient is per question already)
         _geometry_cache[key] = hit
     return L.keep_alive(hit)
 

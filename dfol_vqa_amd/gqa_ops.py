@@ -15,7 +15,7 @@ import torch
 
 from . import ops as L
 from .fol_types import BatchVariableSet, Quantifier, QuestionType, TokenType
-from .host_util import TokenList, find_max_ind, flatten_list, unflatten_list, upload
+from .host_util import TokenList, find_max_ind, flatten_list, get_lowered, unflatten_list, upload
 from .logic_ops import BatchOperatorBase, FilterBatch, RelateBatch
 
 UNKNOWN = 'UNKNOWN'
@@ -289,6 +289,9 @@ class GQARelateBatch(GQABatchOperatorBase):
         fused = self._forward_fused(op_id, world, x, variable_set, relation_list, flag, host)
         if fused is not None:
             return fused
+        trained = self._forward_train_one(op_id, world, x, variable_set, relation_list, flag, host)
+        if trained is not None:
+            return trained
         subject_set = x.gate(variable_set, flag)
         object_set = variable_set.gate(x, flag)
         want = upload(np.asarray([L.WANT_SUBJECT if f > 0 else L.WANT_OBJECT for f in host], np.uint8), world._device)
@@ -335,6 +338,10 @@ class GQARelateBatch(GQABatchOperatorBase):
             # calibrate the kept one with that side's modulations
             mods = torch.where(flag.unsqueeze(1) > 0, rel._subject_modulations.pop(op_id), rel._object_modulations.pop(op_id))
             post = L.modulate(post, mods, world._ident, world._n_obj)
+        return self._kept_set(world, x, prev, post, flag, host_flags)
+
+    def _kept_set(self, world, x, prev, post, flag, host_flags):
+        """The variable set a relate hop hands on from its one kept posterior."""
         # both posteriors carry the subject's quantifier (:571-586); the flags are host data, so the selection costs at most one launch
         if host_flags is not None and all(f > 0 for f in host_flags):
             quant = x._quantifier
@@ -348,6 +355,44 @@ class GQARelateBatch(GQABatchOperatorBase):
             quant = torch.where(flag > 0, x._quantifier, prev._quantifier)
         return BatchVariableSet(x._name, world._device, x.object_num(), x.batch_size(), quantifiers=quant, log_attention=post, world=world,
                                 prev_variable_sets_num=x._prev_variable_sets_num + prev._prev_variable_sets_num + 1)
+
+    def _forward_train_one(self, op_id, world, x, prev, relation_list, flag, host_flags):
+        """Train-side fast path of a gated cell (DFOL_GATE_TRAIN=1): the three gates and the arity-2 cell in ONE launch forward
+        (dfol_relate_keep_gate_fwd_f32) and ONE backward (dfol_relate_keep_gate_bwd_f32, the kept direction only), on the subject-row tile
+        RelateBatch.forward asks the oracle for.  Same value as the generic route below it to rounding (another summation order)."""
+        rel = self._relate
+        if not (rel._blc.gated() and L.gate_train() and torch.is_grad_enabled()):
+            return None
+        gates = (*rel._blc._gate(0), *rel._blc._gate(1))
+        if not (x._log_attention.requires_grad or prev._log_attention.requires_grad or any(g.requires_grad for g in gates)):
+            return None
+        calibrated = op_id in rel._subject_modulations
+        if calibrated != (op_id in rel._object_modulations):
+            return None                                        # one-sided calibration: RelateBatch.forward handles it
+        if calibrated and (rel._subject_modulations[op_id] is None or rel._object_modulations[op_id] is None):
+            return None
+        if x.batch_size() != prev.batch_size() or prev._predicate_question_map is not None:
+            return None
+        if not isinstance(relation_list, list):
+            relation_list = [relation_list]
+        predicate_num = len(relation_list)
+        if predicate_num != world.batch_size() or predicate_num != x.batch_size():
+            return None
+        low = get_lowered(relation_list, self._oracle._ontology, TokenType.RELATION)
+        if not low.any_valid:                                  # nothing to relate: the generic route hands the incoming sets on
+            return None
+        _, neg_dev, valid_dev = low.on(world._device)
+        # the request RelateBatch.forward makes, argument for argument: the train-side pair branch and its readers see the same one
+        tile = self._oracle.block_likelihood(TokenType.RELATION, low, world._ident, range(predicate_num), world, -30, True)
+        xs = upload(np.asarray([1 if f > 0 else 0 for f in host_flags], np.uint8), world._device)
+        post = L.relate_keep_gate(x._log_attention, prev._log_attention, tile, world._ident, world._n_obj, prev._quantifier, xs, *gates,
+                                  neg_dev if low.any_neg else None, None if low.all_valid else valid_dev,
+                                  lone_forall_identity=(predicate_num == 1))
+        L.note("relate_gate_train_one")
+        if calibrated:                                         # the kept side's modulations, as _forward_fused; L.modulate carries their gradient
+            mods = torch.where(flag.unsqueeze(1) > 0, rel._subject_modulations.pop(op_id), rel._object_modulations.pop(op_id))
+            post = L.modulate(post, mods, world._ident, world._n_obj)
+        return self._kept_set(world, x, prev, post, flag, host_flags)
 
 
 class GQAExistBatch(GQABatchOperatorBase):

@@ -109,6 +109,37 @@ def relate_gate_fwd(prior_s, prior_o, tile, pred_q, n_obj, quant_s, quant_o, w_s
                                 neg, active, want, orientation, lone_forall_identity, need_s, need_o, diag_absent)
 
 
+class _RelateKeepGate(torch.autograd.Function):
+    """The one posterior a relate hop keeps, forward and backward in one launch each (DFOL_GATE_TRAIN=1): the inputs and the packed gates are
+    saved, the aggregate is recomputed by the backward."""
+
+    @staticmethod
+    def forward(ctx, x, prev, tile, w_s, b_s, w_o, b_o, pred_q, n_obj, quant_prev, x_is_subject, neg, active, lone):
+        gate_s, gate_o = _lib.gate_params(w_s, b_s), _lib.gate_params(w_o, b_o)
+        ctx.save_for_backward(x, prev, tile, pred_q, n_obj, quant_prev, x_is_subject, gate_s, gate_o, neg, active)
+        ctx.lone, ctx.identity = lone, _lib.is_identity_map(pred_q, prev.shape[0])
+        return _lib.relate_keep_gate_fwd(x, prev, tile, pred_q, n_obj, quant_prev, x_is_subject, gate_s, gate_o, neg, active, lone)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, prev, tile, pred_q, n_obj, quant_prev, x_is_subject, gate_s, gate_o, neg, active = ctx.saved_tensors
+        g_x, g_prev, g_tile, gg_s, gg_o = _lib.relate_keep_gate_bwd(g.contiguous(), x, prev, tile, pred_q, n_obj, quant_prev, x_is_subject, gate_s,
+                                                                    gate_o, neg, active, ctx.lone, identity=ctx.identity)
+        return (g_x if ctx.needs_input_grad[0] else None), (g_prev if ctx.needs_input_grad[1] else None), \
+            (g_tile if ctx.needs_input_grad[2] else None), *_gate_grads(gg_s, ctx, 3), *_gate_grads(gg_o, ctx, 5), \
+            None, None, None, None, None, None, None
+
+
+def relate_keep_gate(x, prev, tile, pred_q, n_obj, quant_prev, x_is_subject, w_s, b_s, w_o, b_o, neg=None, active=None, lone_forall_identity=False):
+    """The posterior GQARelateBatch keeps, from a cell with trainable_gate, on the train step's subject-row tile: x [P, NS] the selected
+    variable, prev [Q, NS] the incoming one, x_is_subject uint8 [P]; (w_s, b_s) the gate of axis 0, (w_o, b_o) of axis 1."""
+    if _needs_grad(x, prev, tile, w_s, b_s, w_o, b_o):
+        return _RelateKeepGate.apply(x, prev, tile, w_s, b_s, w_o, b_o, pred_q, n_obj, quant_prev, x_is_subject, neg, active,
+                                     bool(lone_forall_identity))
+    return _lib.relate_keep_gate_fwd(x, prev, tile, pred_q, n_obj, quant_prev, x_is_subject, _lib.gate_params(w_s, b_s), _lib.gate_params(w_o, b_o),
+                                     neg, active, lone_forall_identity)
+
+
 # ---- quantify ----------------------------------------------------------------------------------------
 def quantify_fwd(att, quant, pred_q, n_obj):
     if _needs_grad(att):

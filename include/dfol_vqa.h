@@ -53,7 +53,8 @@ extern "C" {
  * dfol_linear_wgrad_bias_rows_bf16t and dfol_set_feature_rows_bf16, and the logic cell with the trainable gate: dfol_filter_gate_fwd_f32,
  * dfol_relate_gate_fwd_f32, dfol_filter_gate_bwd_scratch, dfol_filter_gate_bwd_f32 and dfol_relate_gate_bwd_f32, and the gated model on the
  * executor: dfol_relate_one_gate_fwd_f32, dfol_set_program_gates and DFOL_OP_FILTER_GATE / DFOL_OP_RELATE_ONE_GATE / DFOL_OP_RELATE_GATE (no
- * struct grows: the gate table travels beside the call, as dfol_set_feature_rows' arrays do);
+ * struct grows: the gate table travels beside the call, as dfol_set_feature_rows' arrays do), and the one-posterior gated Relate of the train
+ * step: dfol_relate_keep_gate_fwd_f32 and dfol_relate_keep_gate_bwd_f32;
  * a caller that needs them checks for the symbol, and a table that names an opcode an older library lacks is refused by it ("unknown opcode"). */
 #define DFOL_ABI_VERSION 3
 
@@ -197,6 +198,18 @@ int dfol_relate_one_gate_fwd_f32(const float* x_att, const float* prev_att, cons
                                  const float* quant_prev, const uint8_t* x_is_subject, const uint8_t* neg, int32_t any_neg,
                                  const uint8_t* active, int32_t P, int32_t NS, int32_t lone_forall_identity, const float* gate_s,
                                  const float* gate_o, float* post, void* stream);
+
+/* The same one posterior on the tile of the TRAIN step (DFOL_GATE_TRAIN=1): batch_gqa_ops.py:364-371 around batch_base_ops.py:99-100,
+ * :135-136, i.e. the sequence gate, gate, dfol_relate_gate_fwd_f32(want), gate.  The arguments are dfol_relate_one_gate_fwd_f32's, but tile
+ * holds SUBJECTS along rows for every predicate (DFOL_TILE_SUBJECT_ROWS, what the oracle writes under autograd), and the flag picks the axis
+ * that is summed out:
+ *     x_is_subject[p] = 1:  post[p][i] = G_0( F( agg_{j < n, j != i} F( G_1(l'[i][j], prev[j]) ) ), x_att[p][i] )     (row aggregate)
+ *     x_is_subject[p] = 0:  post[p][i] = G_1( F( agg_{j < n, j != i} F( G_0(l'[j][i], prev[j]) ) ), x_att[p][i] )     (column aggregate)
+ * prev = prev_att[pred_q[p]], F and agg by quant_prev[p]; a no-op row is prev's row.  No atomics: two launches give the same bits. */
+int dfol_relate_keep_gate_fwd_f32(const float* x_att, const float* prev_att, const float* tile, const int32_t* pred_q, const int32_t* n_obj,
+                                  const float* quant_prev, const uint8_t* x_is_subject, const uint8_t* neg, int32_t any_neg,
+                                  const uint8_t* active, int32_t P, int32_t NS, int32_t lone_forall_identity, const float* gate_s,
+                                  const float* gate_o, float* post, void* stream);
 
 /* Relate with ONE posterior: what GQARelateBatch / verify_rel / choose_rel keep (batch_gqa_ops.py:364-371: gate x/prev into
  * subject/object, RelateBatch, gate the wanted posterior back).  Fuses the three gates and the arity-2 cell:
@@ -823,6 +836,18 @@ int dfol_relate_gate_bwd_f32(const float* prior_s, const float* prior_o, const f
                              const float* g_post_s, const float* g_post_o, int32_t P, int32_t NS, int32_t orientation,
                              int32_t lone_forall_identity, const float* gate_s, const float* gate_o, float* scratch, float* g_prior_s,
                              float* g_prior_o, float* g_tile, float* g_gate_s, float* g_gate_o, void* stream);
+
+/* Backward of dfol_relate_keep_gate_fwd_f32 (the reference differentiates batch_gqa_ops.py:364-371 and batch_base_ops.py:19-38, :99-100,
+ * :135-136 by autograd): only the kept direction of each predicate is computed - the other direction's cotangent is exactly zero.
+ * g_post [P, NS] is the posterior's cotangent.  WRITTEN: g_x [P, NS]; g_prev [P, NS] PER PREDICATE (reduce it with
+ * dfol_reduce_by_question_f32 when pred_q is not the identity); g_tile [P, NS, NS] with subjects along rows; g_gate_s / g_gate_o [18], summed
+ * without atomics as dfol_relate_gate_bwd_f32 does.  A no-op predicate hands g_post to g_prev and writes zeros elsewhere; padding, the
+ * diagonal and a no-op predicate's tile are +0.  scratch: 36 P floats.  NS <= 1024. */
+int dfol_relate_keep_gate_bwd_f32(const float* g_post, const float* x_att, const float* prev_att, const float* tile, const int32_t* pred_q,
+                                  const int32_t* n_obj, const float* quant_prev, const uint8_t* x_is_subject, const uint8_t* neg,
+                                  int32_t any_neg, const uint8_t* active, int32_t P, int32_t NS, int32_t lone_forall_identity,
+                                  const float* gate_s, const float* gate_o, float* scratch, float* g_x, float* g_prev, float* g_tile,
+                                  float* g_gate_s, float* g_gate_o, void* stream);
 
 int dfol_quantify_bwd_f32(const float* g_lp, const float* att, const float* quant, const int32_t* pred_q, const int32_t* n_obj,
                           int32_t P, int32_t NS, float* g_att, void* stream);

@@ -11,6 +11,9 @@ launches over `--reps` back-to-back launches between two events); one JSON line 
 Then two legs for the gated model's fast inference path (DFOL_GATE_NATIVE=1): the one-launch gated Relate against the sequence it replaces
 (gate, gate, relate_gate_fwd under `want`, gate), and a stream of unseen gated batches on the native executor against the same stream on the
 Python operator loop (switch unset), each alternating in one process.
+Then two legs for the gated train step (DFOL_GATE_TRAIN=1; `--gate-train-only` runs these alone): the one-posterior forward and backward
+launches against the sequence and the autograd backward they replace, and a whole gated train step, eager and replayed, with the switch unset
+and set, on the one-hop program and on ragged 1..3-hop programs.
 """
 import argparse
 import json
@@ -86,6 +89,13 @@ def trainable_gate_launches(args):
         ("relate_bwd", lambda: L.relate_bwd(pa, pb, tile, pq, n_obj, ones, ones, None, None, g1, g2, L.TILE_SUBJECT_ROWS, False)),
         ("relate_gate_bwd", lambda: L.relate_gate_bwd(pa, pb, tile, pq, n_obj, ones, ones, gs, go, None, None, g1, g2, L.TILE_SUBJECT_ROWS, False)),
     ]
+    if args.gate_train_only:                                   # the two legs of the gated train step alone
+        lines = gated_train_launches(args, L, t, rng, pa, pb, tile, pq, n_obj, ones, gs, go)
+        lines += gated_train_step(args) + gated_train_step(args, hops="ragged")
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     for _, fn in launches:                                     # (the first launches of a kernel load its code object)
         for _ in range(3):
             fn()
@@ -109,6 +119,8 @@ def trainable_gate_launches(args):
         print(lines[-1], flush=True)
     lines += gated_relate_one(args, L, t, rng, pa, pb, tile, pq, n_obj, ones, gs, go)
     lines += gated_stream(args)
+    lines += gated_train_launches(args, L, t, rng, pa, pb, tile, pq, n_obj, ones, gs, go)
+    lines += gated_train_step(args) + gated_train_step(args, hops="ragged")
     if args.out:
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")
@@ -159,6 +171,142 @@ def gated_relate_one(args, L, t, rng, x, prev, tile, pq, n_obj, ones, gs, go):
     ratio = float(np.median(times[launches[0][0]]) / np.median(times[launches[1][0]]))
     lines.append(json.dumps({"ratio": "sequence / one launch (medians)", "value": ratio}))
     print(lines[-1], flush=True)
+    return lines
+
+
+def gated_train_launches(args, L, t, rng, x, prev, tile, pq, n_obj, ones, gs, go):
+    """The one-posterior gated Relate under autograd (dfol_relate_keep_gate_fwd_f32 / _bwd_f32, DFOL_GATE_TRAIN=1) against the sequence a gated
+    relate hop runs without it - forward: gate, gate, relate_gate_fwd under `want`, gate; backward: that sequence's autograd backward - on the
+    subject-row tile with mixed subject flags, through the Python wrappers, alternating in one process.  A backward is timed as
+    torch.autograd.grad over a retained graph, so the forward is not inside it."""
+    from dfol_vqa_amd import ops
+    P = tile.shape[0]
+    flag = (np.arange(P) % 2).astype(np.float32)
+    flag_f, flag_u8 = t(flag), t(flag, torch.uint8)
+    want = t(np.where(flag > 0, L.WANT_SUBJECT, L.WANT_OBJECT), torch.uint8)
+    pq._dfol_identity = True                                     # (what BatchWorld marks its identity map with: no reduction by question)
+    leaf = lambda a: a.detach().clone().requires_grad_(True)
+    xg, pg, tg = leaf(x), leaf(prev), leaf(tile)
+    w = [leaf(gs[:12].view(6, 2)), leaf(gs[12:]), leaf(go[:12].view(6, 2)), leaf(go[12:])]
+    leaves = [xg, pg, tg] + w
+    cot = t(rng.normal(size=tuple(x.shape)))
+
+    def sequence(a=x, b=prev, c=tile, gates=(gs[:12].view(6, 2), gs[12:], go[:12].view(6, 2), go[12:])):
+        s, q_s = ops.gate(a, b, ones, ones, flag_f)
+        o, q_o = ops.gate(b, a, ones, ones, flag_f)
+        ps, po = ops.relate_gate_fwd(s, o, c, pq, n_obj, q_s, q_o, *gates, None, None, want, diag_absent=True)
+        return ops.gate(ps, po, q_s, q_s, flag_f)[0]
+
+    def one(a=x, b=prev, c=tile, gates=(gs[:12].view(6, 2), gs[12:], go[:12].view(6, 2), go[12:])):
+        return ops.relate_keep_gate(a, b, c, pq, n_obj, ones, flag_u8, *gates)
+
+    with torch.no_grad():
+        gap = float((torch.exp(sequence()) - torch.exp(one())).abs().max())
+    assert gap <= 1e-5, gap
+    out_seq, out_one = sequence(xg, pg, tg, w), one(xg, pg, tg, w)
+    g_seq = torch.autograd.grad(out_seq, leaves, cot, retain_graph=True)
+    g_one = torch.autograd.grad(out_one, leaves, cot, retain_graph=True)
+    grad_gap = max(float((a - b).abs().max() / max(1e-30, float(a.abs().max()))) for a, b in zip(g_seq, g_one))
+    assert grad_gap <= 2e-3, grad_gap                            # the same gradients (another summation order), relative to each tensor's scale
+
+    def fwd_seq():
+        with torch.no_grad():
+            sequence()
+
+    def fwd_one():
+        with torch.no_grad():
+            one()
+
+    launches = [("train forward, sequence(gate,gate,relate_gate_fwd,gate)", fwd_seq),
+                ("train forward, relate_keep_gate_fwd", fwd_one),
+                ("train backward, autograd of the sequence", lambda: torch.autograd.grad(out_seq, leaves, cot, retain_graph=True)),
+                ("train backward, relate_keep_gate_bwd", lambda: torch.autograd.grad(out_one, leaves, cot, retain_graph=True))]
+    for _, fn in launches:
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name, _ in launches}
+    for _ in range(args.rounds):
+        for name, fn in launches:
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(args.reps):
+                fn()
+            e.record()
+            e.synchronize()
+            times[name].append(s.elapsed_time(e) * 1e3 / args.reps)
+    more = dict(predicates=P, objects=args.nmax, rounds=args.rounds, reps=args.reps, max_abs_probability_gap=gap, max_rel_gradient_gap=grad_gap,
+                note="event time over back-to-back calls of the Python wrappers: host-side allocation and autograd bookkeeping are inside")
+    lines = [_summary(name, times[name], **more) for name, _ in launches]
+    for a, b, what in ((0, 1, "forward"), (2, 3, "backward")):
+        ta, tb = np.asarray(times[launches[a][0]]), np.asarray(times[launches[b][0]])
+        lines.append(json.dumps({"ratio": "train %s: sequence / one launch (medians)" % what, "value": float(np.median(ta) / np.median(tb)),
+                                 "ranges_apart": bool(ta.min() > tb.max() or tb.min() > ta.max())}))
+        print(lines[-1], flush=True)
+    return lines
+
+
+def gated_train_step(args, hops="aligned"):
+    """A gated train step (zero grads -> forward -> loss -> backward -> clip -> Adam; every parameter trains) on bench.py's one-hop program
+    (select -> filter -> relate -> exist) or its ragged 1..3-hop programs, eager and replayed (GraphedTrainStep), with DFOL_GATE_TRAIN unset and
+    set: four variants alternating in one process, each on its own copy of the model, wall time per step with a device synchronisation."""
+    import copy
+    from dfol_vqa_amd import _lib, experiment, parallel, training
+    from dfol_vqa_amd import synthetic as syn
+    device = torch.device("cuda", 0)
+    paths, names = syn.write_synthetic_ontology(tempfile.mkdtemp(prefix="dfol_gate_train_"))
+    cfg = syn.reference_config(paths, trainable_gate=True, dropout=0.0, freeze_featurizer=False, freeze_attribute_network=False,
+                               freeze_relation_network=False, freeze_embedding_network=False)      # bench.py --mode train's oracle-training phases
+    ontology = experiment.build_ontology(cfg)
+    torch.manual_seed(0)
+    base = experiment.build_model(cfg, ontology)
+    bench.init_weights(base)
+    base = base.to(device).train()
+    shape = argparse.Namespace(batch=args.batch, objects=args.nmax, ragged=0, hops=hops, workload="north_star", questions_per_image=1, share_scenes=1)
+    _, pbs = bench.build_batch(shape, 0, ontology, names, device)
+    variants, counts = {}, {}
+    for switch in ("0", "1"):
+        os.environ["DFOL_GATE_TRAIN"] = switch
+        for graphed in (False, True):
+            model = copy.deepcopy(base)
+            params = [p for p in model.parameters() if p.requires_grad]
+            opt = torch.optim.Adam(params, lr=1e-4, capturable=True)
+            bucket = parallel.GradBucket(params)
+            _lib.PATH_COUNTS.clear()
+            if graphed:
+                step = training.GraphedTrainStep(model, opt, pbs, 0.65, bucket=bucket, warmup=2)
+            else:
+                step = (lambda m, o, b: (lambda: training.train_batch(m, o, pbs, 0.65, bucket=b, sync_loss=False)))(model, opt, bucket)
+                step()
+                step()
+            torch.cuda.synchronize()
+            took = _lib.PATH_COUNTS.get("relate_gate_train_one", 0)
+            assert (took > 0) == (switch == "1"), (switch, graphed, took)
+            variants[switch, graphed] = step
+            counts[switch, graphed] = took
+    order = [("0", False), ("1", False), ("0", True), ("1", True)]
+    times = {k: [] for k in order}
+    rounds, n = max(4, args.rounds // 2), 4
+    for r in range(rounds):
+        for k in (order if r % 2 == 0 else order[::-1]):           # (who goes first alternates)
+            os.environ["DFOL_GATE_TRAIN"] = k[0]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                variants[k]()
+            torch.cuda.synchronize()
+            times[k].append((time.perf_counter() - t0) / n * 1e6)
+    os.environ.pop("DFOL_GATE_TRAIN", None)
+    lines = []
+    for k in order:
+        lines.append(_summary("gated train step, %s hops, %s, DFOL_GATE_TRAIN %s" % (hops, "replayed" if k[1] else "eager", "set" if k[0] == "1" else "unset"),
+                              times[k], questions=args.batch, objects=args.nmax, rounds=rounds, steps_per_round=n,
+                              relate_gate_train_one_hops_in_setup=counts[k]))
+    for graphed in (False, True):
+        a, b = np.asarray(times["0", graphed]), np.asarray(times["1", graphed])
+        lines.append(json.dumps({"ratio": "gated train step, %s hops, %s: unset / set (medians)" % (hops, "replayed" if graphed else "eager"),
+                                 "value": float(np.median(a) / np.median(b)), "ranges_apart": bool(a.min() > b.max() or b.min() > a.max())}))
+        print(lines[-1], flush=True)
     return lines
 
 
@@ -233,6 +381,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None, help="--trainable-gate: also write the JSON lines to this file")
+    ap.add_argument("--gate-train-only", action="store_true", help="--trainable-gate: only the two legs of the gated train step (DFOL_GATE_TRAIN)")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--nmin", type=int, default=10)
     ap.add_argument("--nmax", type=int, default=100)
