@@ -131,6 +131,7 @@ SIGNATURES = {
     "dfol_filter_gate_fwd_f32": [_p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _p, _p, _p],
     "dfol_relate_gate_fwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p],
     "dfol_relate_one_gate_fwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _p],
+    "dfol_relate_one_gate_fwd_bf16": [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _p],
     "dfol_relate_keep_gate_fwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _p],
     "dfol_relate_keep_gate_bwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "dfol_filter_gate_bwd_scratch": [_i32, _i32],          # returns a float count (int64), called directly
@@ -580,6 +581,31 @@ def relate_one_gate_fwd(x_att, prev_att, tile, pred_q, n_obj, quant_prev, x_is_s
         raise DfolError("relate_one_gate_fwd: %d subject flags for %d predicates" % (x_is_subject.numel(), P))
     post = torch.empty(P, NS, dtype=F32, device=tile.device)
     call("dfol_relate_one_gate_fwd_f32", _ptr(x_att, F32), _ptr(prev_att, F32), _ptr(tile, F32), _ptr(pred_q, I32), _ptr(n_obj, I32),
+         _ptr(quant_prev, F32), _ptr(x_is_subject, U8), _ptr(neg, U8, True), 0 if neg is None else 1, _ptr(active, U8, True), P, NS,
+         1 if lone_forall_identity else 0, _ptr(gate_s, F32), _ptr(gate_o, F32), _ptr(post), _stream())
+    return post
+
+
+def gate_bf16():
+    """DFOL_GATE_BF16=1 together with DFOL_GATE_NATIVE=1 (opt-in, read when a forward starts): a gated model with `relation_tile_dtype: bf16` keeps
+    bf16 relation tiles where the one-launch gated Relate reads them (relate_one_gate_fwd_bf16: inference, no gradient recorded, NS % 8 == 0, no
+    choose_rel in the batch); without DFOL_GATE_NATIVE it has no effect, only the one-launch route has a bf16 form.  Unset: the combination of the
+    two config keys is refused, as before."""
+    return gate_native() and os.environ.get("DFOL_GATE_BF16", "0") == "1"
+
+
+def relate_one_gate_fwd_bf16(x_att, prev_att, tile, pred_q, n_obj, quant_prev, x_is_subject, gate_s, gate_o, neg=None, active=None,
+                             lone_forall_identity=False):
+    """relate_one_gate_fwd on bfloat16 tiles (NS % 8 == 0, NS <= 256)."""
+    if tile.dtype != torch.bfloat16:
+        raise DfolError("relate_one_gate_fwd_bf16 reads bfloat16 tiles (got %s): fp32 tiles go to relate_one_gate_fwd" % tile.dtype)
+    P, NS = tile.shape[0], tile.shape[1]
+    if NS % 8 != 0 or NS > 256:
+        raise DfolError("relate_one_gate_fwd_bf16: NS=%d (a multiple of 8, at most 256)" % NS)
+    if x_is_subject.numel() != P:
+        raise DfolError("relate_one_gate_fwd_bf16: %d subject flags for %d predicates" % (x_is_subject.numel(), P))
+    post = torch.empty(P, NS, dtype=F32, device=tile.device)
+    call("dfol_relate_one_gate_fwd_bf16", _ptr(x_att, F32), _ptr(prev_att, F32), _ptr(tile, torch.bfloat16), _ptr(pred_q, I32), _ptr(n_obj, I32),
          _ptr(quant_prev, F32), _ptr(x_is_subject, U8), _ptr(neg, U8, True), 0 if neg is None else 1, _ptr(active, U8, True), P, NS,
          1 if lone_forall_identity else 0, _ptr(gate_s, F32), _ptr(gate_o, F32), _ptr(post), _stream())
     return post

@@ -168,4 +168,14 @@ __device__ __forceinline__ float dfol_group_or(float q) {
     return q;
 }
 
+// Eight bf16 bit patterns (one 16-byte load of a bf16 relation tile) widened to fp32: exact, a bf16 is the upper half of an fp32.
+__device__ __forceinline__ void bf16x8_to_f32(const uint4 w, float (&l)[8]) {
+    const uint32_t v[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        l[2 * i] = __uint_as_float(v[i] << 16);
+        l[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u);
+    }
+}
+
 static inline int dfol_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

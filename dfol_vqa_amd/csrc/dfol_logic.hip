@@ -1006,16 +1006,8 @@ extern "C" int dfol_relate_one_fwd_f32(const float* x_att, const float* prev_att
 // Relate, single posterior, bf16 tiles (BASELINE configs[4]: 256-object scenes, tiles stored in bf16 to halve the HBM bytes)
 // =====================================================================================================
 // Same contract as relate_one_fwd_kernel; a lane owns EIGHT consecutive columns (one 16-byte load = 8 bf16 per row), so LPR =
-// NS / 8 lanes cover a row (NS a multiple of 8, <= 256).  Arithmetic is fp32; only the stored likelihoods are rounded.
-__device__ __forceinline__ void bf16x8_to_f32(const uint4 w, float (&l)[8]) {
-    const uint32_t v[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        l[2 * i] = __uint_as_float(v[i] << 16);
-        l[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u);
-    }
-}
-
+// NS / 8 lanes cover a row (NS a multiple of 8, <= 256).  Arithmetic is fp32; only the stored likelihoods are rounded (widened by
+// bf16x8_to_f32, dfol_common.h).
 template <int LPR>
 __global__ __launch_bounds__(256) void relate_one_bf16_kernel(
     const float* __restrict__ x_att, const float* __restrict__ prev_att, const uint16_t* __restrict__ tile,

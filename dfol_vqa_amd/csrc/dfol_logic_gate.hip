@@ -694,6 +694,75 @@ __global__ __launch_bounds__(256) void relate_one_gate_big_kernel(
     }
 }
 
+// The same one posterior on bf16 tiles (relation_tile_dtype: bf16 with trainable_gate: True, DFOL_GATE_BF16=1; NS a multiple of 8, <= 256): the
+// geometry of relate_one_bf16_kernel (dfol_logic.hip) - a lane owns EIGHT consecutive columns, one 16-byte load = 8 bf16 per row widened
+// exactly, LPR = NS / 8 lanes cover a row, 64 / LPR rows per iteration - around the arithmetic of relate_one_gate_fwd_kernel, term for term.
+// Only the stored likelihoods are rounded; which rows share a lane differs from the fp32 kernel, so the two agree to rounding, not to the bit.
+template <int LPR>
+__global__ __launch_bounds__(256) void relate_one_gate_bf16_kernel(
+    const float* __restrict__ x_att, const float* __restrict__ prev_att, const uint16_t* __restrict__ tile, const int32_t* __restrict__ pred_q,
+    const int32_t* __restrict__ n_obj, const float* __restrict__ quant_prev, const uint8_t* __restrict__ x_is_subject,
+    const uint8_t* __restrict__ neg, int any_neg, const uint8_t* __restrict__ active, int P, int NS, int identity_forall,
+    const float* __restrict__ gate_s, const float* __restrict__ gate_o, float* __restrict__ post) {
+    constexpr int RPI = 64 / LPR;
+    const int p = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));      // (wave-uniform: the gates' 36 parameters stay scalar)
+    if (p >= P) return;
+    const int lane = threadIdx.x & 63;
+    const int q = pred_q[p];
+    const int n = min(n_obj[q], NS);
+    const float* pv = prev_att + (int64_t)q * NS;
+    const float* xv = x_att + (int64_t)p * NS;
+    float* out = post + (int64_t)p * NS;
+    if (active && !active[p]) {                         // question without this operator: attention passes through
+        for (int c = lane; c < NS; c += 64) out[c] = c < n ? pv[c] : 0.f;
+        return;
+    }
+    const bool xs = x_is_subject[p] != 0;
+    const GateW GI = gate_load(xs ? gate_o : gate_s), GO = gate_load(xs ? gate_s : gate_o);      // inner: prev's axis, outer: x's
+    const int cg = lane % LPR, rs = lane / LPR, c0 = cg * 8;
+    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
+    const float qf = quant_prev[p], kf = 1.f - 2.f * qf;
+    const bool ex = qf == 1.f, ident = identity_forall && qf == 0.f;
+    const uint16_t* tp = tile + (int64_t)p * NS * NS + min(c0, NS - 8);      // lanes beyond the tile width read valid columns and are discarded
+    float cacc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) cacc[j] = 0.f;
+    for (int r0 = 0; r0 < n; r0 += RPI) {
+        const int r = r0 + rs, rc = min(r, n - 1);      // rows beyond n read row n - 1 and are masked
+        float l[8];
+        bf16x8_to_f32(*reinterpret_cast<const uint4*>(tp + (int64_t)rc * NS), l);
+        const float pr = pv[rc];
+        float zb[6];
+        gate_zb(GI, pr, zb);
+        const float eb = dfol_exp(pr);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int c = c0 + j;
+            const bool keep = r < n && c < n && c != r;       // padding and self-relations contribute nothing (:112)
+            const float v = gate_prep(l[j], any_neg, alpha_n, cn);
+            const float t = gate_term(gate_m(GI, v, dfol_exp(v), zb, eb), ex, qf, kf);      // :99-100, :108
+            cacc[j] = gate_join(cacc[j], keep ? t : 0.f, ex);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+#pragma unroll
+        for (int m = 32; m >= LPR; m >>= 1) cacc[j] = gate_join(cacc[j], __shfl_xor(cacc[j], m, 64), ex);
+    }
+    if (rs == 0 && c0 < NS) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const float4 x4 = *reinterpret_cast<const float4*>(xv + c0 + 4 * h);
+            const float xj[4] = {x4.x, x4.y, x4.z, x4.w};
+            float o[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                o[j] = (c0 + 4 * h + j < n) ? gate_log(GO, gate_outer(cacc[4 * h + j], ex, ident, qf, kf), xj[j]) : 0.f;      // :133, :135-136
+            *reinterpret_cast<float4*>(out + c0 + 4 * h) = make_float4(o[0], o[1], o[2], o[3]);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // relate, single posterior, on the SUBJECT-ROW tile of the train step (oracle.block_likelihood stores subjects along rows for every
 // predicate; the inference prefetch that turns prev's objects onto the rows does not run under autograd).  The predicate's flag picks,
@@ -1156,6 +1225,31 @@ extern "C" int dfol_relate_one_gate_fwd_f32(const float* x_att, const float* pre
     else DFOL_GATE1(64);
 #undef DFOL_GATE1
     DFOL_LAUNCH_CHECK("relate_one_gate_fwd");
+    return 0;
+}
+
+extern "C" int dfol_relate_one_gate_fwd_bf16(const float* x_att, const float* prev_att, const uint16_t* tile, const int32_t* pred_q,
+                                             const int32_t* n_obj, const float* quant_prev, const uint8_t* x_is_subject, const uint8_t* neg,
+                                             int32_t any_neg, const uint8_t* active, int32_t P, int32_t NS, int32_t lone_forall_identity,
+                                             const float* gate_s, const float* gate_o, float* post, void* stream) {
+    DFOL_REQUIRE(P >= 0 && NS > 0 && NS % 8 == 0 && NS <= 256, "relate_one_gate_fwd_bf16: bad sizes P=%d NS=%d (NS: multiple of 8, <= 256)", P, NS);
+    if (P == 0) return 0;
+    DFOL_REQUIRE(x_att && prev_att && tile && pred_q && n_obj && quant_prev && x_is_subject && gate_s && gate_o && post,
+                 "relate_one_gate_fwd_bf16: null pointer");
+    DFOL_REQUIRE(!any_neg || neg, "relate_one_gate_fwd_bf16: any_neg set but neg is NULL");
+    hipStream_t st = (hipStream_t)stream;
+    const int groups = NS / 8;
+#define DFOL_GATE1B(L)                                                                                                                          \
+    hipLaunchKernelGGL(relate_one_gate_bf16_kernel<L>, dim3(dfol_cdiv(P, 4)), dim3(256), 0, st, x_att, prev_att, tile, pred_q, n_obj, quant_prev, \
+                       x_is_subject, neg, any_neg, active, P, NS, lone_forall_identity, gate_s, gate_o, post)
+    if (groups <= 1) DFOL_GATE1B(1);
+    else if (groups <= 2) DFOL_GATE1B(2);
+    else if (groups <= 4) DFOL_GATE1B(4);
+    else if (groups <= 8) DFOL_GATE1B(8);
+    else if (groups <= 16) DFOL_GATE1B(16);
+    else DFOL_GATE1B(32);
+#undef DFOL_GATE1B
+    DFOL_LAUNCH_CHECK("relate_one_gate_fwd_bf16");
     return 0;
 }
 

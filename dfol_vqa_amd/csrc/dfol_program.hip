@@ -335,7 +335,18 @@ extern "C" int dfol_run_program(const DfolProgramModel* model, const DfolProgram
                 break;
             case DFOL_OP_RELATE_ONE_GATE: // DFOL_OP_RELATE_ONE's operands, x_is_subject, the cell's first gate slot
                 DFOL_GATE_SLOT(a[13], 2);
-                DFOL_REQUIRE(a[11] == DFOL_TILE_F32, "run_program[%d]: the gated relate reads fp32 tiles", i);
+                DFOL_REQUIRE(a[11] == DFOL_TILE_F32 || a[11] == DFOL_TILE_BF16, "run_program[%d]: the gated relate reads fp32 or bf16 tiles", i);
+                if (a[11] == DFOL_TILE_BF16) {
+                    DFOL_REQUIRE(model->pair_kind != DFOL_PAIR_PLAIN, "run_program[%d]: bf16 tiles need a packed second layer", i);
+                    DFOL_REQUIRE(NS % 8 == 0, "run_program[%d]: the gated relate on bf16 tiles needs NS %% 8 == 0 (NS=%d)", i, NS);
+                    rc = dfol_relate_one_gate_fwd_bf16(static_cast<const float*>(at(workspace, a[1])), static_cast<const float*>(at(workspace, a[2])),
+                                                       static_cast<const uint16_t*>(at(workspace, a[3])), static_cast<const int32_t*>(at(blob, a[4])), n_obj,
+                                                       static_cast<const float*>(at(blob, a[5])), static_cast<const uint8_t*>(at(blob, a[12])),
+                                                       static_cast<const uint8_t*>(at(blob, a[6])), a[6] >= 0 ? 1 : 0, static_cast<const uint8_t*>(at(blob, a[7])),
+                                                       static_cast<int32_t>(a[8]), NS, static_cast<int32_t>(a[9]), gate_row(a[13], 0), gate_row(a[13], 1),
+                                                       static_cast<float*>(at(workspace, a[10])), stream);
+                    break;
+                }
                 rc = dfol_relate_one_gate_fwd_f32(static_cast<const float*>(at(workspace, a[1])), static_cast<const float*>(at(workspace, a[2])),
                                                   static_cast<const float*>(at(workspace, a[3])), static_cast<const int32_t*>(at(blob, a[4])), n_obj,
                                                   static_cast<const float*>(at(blob, a[5])), static_cast<const uint8_t*>(at(blob, a[12])),

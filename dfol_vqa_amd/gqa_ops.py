@@ -325,10 +325,14 @@ class GQARelateBatch(GQABatchOperatorBase):
         if gated:                                              # dfol_relate_one_gate_fwd_f32: the cell's two gates, and which axis x is on
             hf = host_flags if host_flags is not None else [float(f) for f in flag.detach().cpu().tolist()]
             xs = upload(np.asarray([1 if f > 0 else 0 for f in hf], np.uint8), world._device)
-            post = L.relate_one_gate_fwd(x._log_attention, prev._log_attention, tiles, world._ident, world._n_obj, prev._quantifier, xs,
-                                         L.gate_params(*rel._blc._gate(0)), L.gate_params(*rel._blc._gate(1)),
-                                         neg_dev if low.any_neg else None, None if low.all_valid else valid_dev,
-                                         lone_forall_identity=(x.batch_size() == 1))
+            kernel = L.relate_one_gate_fwd
+            if tiles.dtype == torch.bfloat16 and L.gate_bf16():   # (switch off: relate_one_gate_fwd refuses the bf16 tile, as before)
+                kernel = L.relate_one_gate_fwd_bf16
+                L.note("relate_one_gate_bf16")
+            post = kernel(x._log_attention, prev._log_attention, tiles, world._ident, world._n_obj, prev._quantifier, xs,
+                          L.gate_params(*rel._blc._gate(0)), L.gate_params(*rel._blc._gate(1)),
+                          neg_dev if low.any_neg else None, None if low.all_valid else valid_dev,
+                          lone_forall_identity=(x.batch_size() == 1))
         else:
             kernel = L.relate_one_fwd_bf16 if tiles.dtype == torch.bfloat16 else L.relate_one_fwd
             post = kernel(x._log_attention, prev._log_attention, tiles, world._ident, world._n_obj, prev._quantifier,

@@ -642,7 +642,7 @@ class BatchInterpreterBase(nn.Module):
                 # with a training calibrator the attentions carry gradients and the relates run on the generic cell; a gated model's do too,
                 # unless its one-launch Relate is switched on (DFOL_GATE_NATIVE=1) and no gradient is recorded
                 self._oracle.prefetch_relations(world, program_batch, fused=not (self._has_modulator and modulator_switch and torch.is_grad_enabled())
-                                                and (not self._gated() or (_lib.gate_native() and not torch.is_grad_enabled())))
+                                                and (not self._gated() or (_lib.gate_native() and not torch.is_grad_enabled())), gated=self._gated())
                 if hasattr(self._oracle, "prefetch_attributes"):
                     self._oracle.prefetch_attributes(world, program_batch)
             ops = program_batch._op_batch_list

@@ -158,7 +158,7 @@ def model_spec(model, calibrate=False):
         calib = dict(state_dim=int(nets[0].hidden_size), lstm_in=int(nets[0].input_size), ops_index=dict(model._OPS_INDEX))
     return NP.ModelSpec([l.out_features for l, _ in fl], [l.out_features for l, _ in al], lin1.out_features, fl[-1][0].out_features + 4,
                         oracle._normalize, model._likelihood_threshold, oracle._ontology._relation_index, tile_bf16=tile_bf16, calib=calib,
-                        attr_head=len(al) == 2 and attr_head_on(model), gates=gate_slots(model))
+                        attr_head=len(al) == 2 and attr_head_on(model), gates=gate_slots(model), gate_bf16=_lib.gate_bf16())
 
 
 class NativeModel(object):

@@ -70,7 +70,7 @@ class ModelSpec(object):
     interpreter's likelihood threshold.  Picklable (collate workers build plans)."""
 
     def __init__(self, featurizer_widths, attribute_widths, hid1, D, normalize, likelihood_threshold, relation_index, tile_bf16=False, calib=None,
-                 attr_head=False, gates=None):
+                 attr_head=False, gates=None, gate_bf16=False):
         self.featurizer_widths = [int(w) for w in featurizer_widths]      # output width of every featurizer layer (the last = D - 4)
         self.attribute_widths = [int(w) for w in attribute_widths]        # output width of every attribute-network layer
         self.hid1, self.D = int(hid1), int(D)
@@ -87,6 +87,9 @@ class ModelSpec(object):
         # gate table} (native_exec.gate_slots; a cell of arity 2 owns two rows) - the logic instructions are then the gated opcodes, each naming the
         # cell the Python loop would run for that operator.  None: no gates
         self.gates = None if gates is None else {str(k): int(v) for k, v in gates.items()}
+        # DFOL_GATE_BF16=1 (_lib.gate_bf16): a gated model's relate hops read bf16 tiles where tile_bf16 stores them (dfol_relate_one_gate_fwd_bf16);
+        # off, gates and tile_bf16 together yield no plan
+        self.gate_bf16 = bool(gate_bf16)
         # attention calibration (activate_attention_transfer with the modulator switched on): None, or {"state_dim": S, "lstm_in": 18 + token
         # embedding width, "ops_index": operator -> one-hot position (batch_gqa_interpreter.py:67-70)}
         self.calib = None if calib is None else dict(state_dim=int(calib["state_dim"]), lstm_in=int(calib["lstm_in"]), ops_index=dict(calib["ops_index"]))
@@ -94,7 +97,7 @@ class ModelSpec(object):
     def key(self):
         return (tuple(self.featurizer_widths), tuple(self.attribute_widths), self.hid1, self.D, self.normalize, self.likelihood_threshold,
                 self.relation_index.tobytes(), self.tile_bf16, self.attr_head,
-                None if self.gates is None else tuple(sorted(self.gates.items())),
+                None if self.gates is None else tuple(sorted(self.gates.items())), self.gate_bf16,
                 None if self.calib is None else (self.calib["state_dim"], self.calib["lstm_in"], tuple(sorted(self.calib["ops_index"].items()))))
 
 
@@ -469,7 +472,7 @@ class _Builder(object):
                -1 if low.all_valid else self.arr(low.valid), self.Q, 1 if self.Q == 1 else 0, out, self.tile_dtype)
         if slot is None:
             self.emit(OP_RELATE_ONE, *ops)
-        else:                                                      # which axis x is on picks the outer and the inner gate (dfol_relate_one_gate_fwd_f32)
+        else:                                                      # which axis x is on picks the outer and the inner gate (dfol_relate_one_gate_fwd_f32 / _bf16)
             self.emit(OP_RELATE_ONE_GATE, *ops, self.arr(np.asarray([1 if f > 0 else 0 for f in host], np.uint8)), slot)
         if self.calibration is not None and (i, "rel_s") in self.calibration.mods:
             # RelateBatch.forward calibrates both posteriors (batch_base_ops.py:588-594) and GQARelateBatch keeps one per question: the kept one
@@ -936,7 +939,7 @@ def _attribute_requests(b, ops, deps):
 
 
 def _lower(pb, ontology, spec):
-    if spec.gates is not None and spec.tile_bf16:
+    if spec.gates is not None and spec.tile_bf16 and not getattr(spec, "gate_bf16", False):
         raise Unsupported("trainable gates read fp32 relation tiles")      # (the Python loop raises the DfolError of the combination)
     b = _Builder(pb, ontology, spec)
     ops, deps = getattr(pb._op_batch_list, "host", pb._op_batch_list), pb._dependencies      # (a lazily moved batch: the collated operators)
@@ -1086,6 +1089,8 @@ def _choose_rel(b, i, prev, args):
     if hit is None or prev.pq is not None or prev.rows != Q:
         raise Unsupported("choose_rel without prefetched tiles")
     tiles, low = hit
+    if b.tile_dtype != TILE_F32:                                   # (relation_stage keeps fp32 tiles for a batch with a choose_rel: never reached)
+        raise Unsupported("the two-posterior cell reads fp32 tiles")
     P = len(flat)
     pq = np.asarray(bi, np.int32)
     q_s, q_o = subject_set.quant[pq], object_set.quant[pq]

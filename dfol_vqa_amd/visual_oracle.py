@@ -1261,9 +1261,11 @@ class ClassifierOracle(OracleBase):
                 if not any(np.array_equal(full, c) for c in world._train_rel_readers) and len(world._train_rel_readers) < 8:
                     world._train_rel_readers.append(full.astype(np.int64))
 
-    def prefetch_relations(self, world, program_batch, fused=True):
+    def prefetch_relations(self, world, program_batch, fused=True, gated=False):
         """One fused pair-kernel launch for every relation operator of the program batch (relate / verify_rel /
-        choose_rel): the pair MLP's hidden layer is then evaluated once per object pair, whatever the number of hops."""
+        choose_rel): the pair MLP's hidden layer is then evaluated once per object pair, whatever the number of hops.
+        gated: the model's cells hold trainable gates - with DFOL_GATE_BF16=1 its bf16 tiles exist only where the one-launch gated Relate reads
+        them (`fused`); switched off the rule is the ungated one and the gated kernels refuse the bf16 tile, as before."""
         if world._lazy is not None and getattr(world, "_train", False):
             self._collect_relation_readers(world, program_batch)
         if world._lazy is None or getattr(world, "_train", False):
@@ -1296,6 +1298,8 @@ class ClassifierOracle(OracleBase):
         total = sum(len(e[0].cols) for e in entries)
         # bf16 storage only when every consumer is the fused single-posterior kernel (relate / verify_rel), which reads it directly
         bf16 = self._tile_dtype == torch.bfloat16 and world._NS % 8 == 0 and all(ob._op_name != "choose_rel" for ob in program_batch._op_batch_list)
+        if bf16 and gated and L.gate_bf16():
+            bf16 = bool(fused)                          # the generic gated cell (a recorded gradient, a training calibrator) reads fp32 tiles
         if bf16:
             img = self._pair_image()
             bf16 = L.pair_tiles_bf16_ok(img.w2_padded.shape[1], img.hid2)

@@ -54,7 +54,8 @@ extern "C" {
  * dfol_relate_gate_fwd_f32, dfol_filter_gate_bwd_scratch, dfol_filter_gate_bwd_f32 and dfol_relate_gate_bwd_f32, and the gated model on the
  * executor: dfol_relate_one_gate_fwd_f32, dfol_set_program_gates and DFOL_OP_FILTER_GATE / DFOL_OP_RELATE_ONE_GATE / DFOL_OP_RELATE_GATE (no
  * struct grows: the gate table travels beside the call, as dfol_set_feature_rows' arrays do), and the one-posterior gated Relate of the train
- * step: dfol_relate_keep_gate_fwd_f32 and dfol_relate_keep_gate_bwd_f32;
+ * step: dfol_relate_keep_gate_fwd_f32 and dfol_relate_keep_gate_bwd_f32, and the one-posterior gated Relate on bf16 tiles:
+ * dfol_relate_one_gate_fwd_bf16 and DFOL_TILE_BF16 as DFOL_OP_RELATE_ONE_GATE's tile dtype (an older library refuses that operand);
  * a caller that needs them checks for the symbol, and a table that names an opcode an older library lacks is refused by it ("unknown opcode"). */
 #define DFOL_ABI_VERSION 3
 
@@ -198,6 +199,16 @@ int dfol_relate_one_gate_fwd_f32(const float* x_att, const float* prev_att, cons
                                  const float* quant_prev, const uint8_t* x_is_subject, const uint8_t* neg, int32_t any_neg,
                                  const uint8_t* active, int32_t P, int32_t NS, int32_t lone_forall_identity, const float* gate_s,
                                  const float* gate_o, float* post, void* stream);
+
+/* dfol_relate_one_gate_fwd_f32 on bf16 tiles (relation_tile_dtype: bf16 with trainable_gate: True, opt-in DFOL_GATE_BF16=1; replaces the same
+ * lines, batch_gqa_ops.py:364-371 around batch_base_ops.py:99-100, :135-136): tile [P, NS, NS] of bf16 bit patterns as dfol_relate_one_fwd_bf16
+ * reads them (written by dfol_pair_ll_packed_f32 with tile_dtype = DFOL_TILE_BF16), widened exactly; every other argument and the arithmetic
+ * (fp32) are dfol_relate_one_gate_fwd_f32's.  Results differ from the fp32 entry point by the rounding of the stored likelihoods and by the
+ * order of the sum over rows.  LIMIT: NS a multiple of 8 and <= 256, anything else is refused with an error (no NS > 256 form). */
+int dfol_relate_one_gate_fwd_bf16(const float* x_att, const float* prev_att, const uint16_t* tile, const int32_t* pred_q, const int32_t* n_obj,
+                                  const float* quant_prev, const uint8_t* x_is_subject, const uint8_t* neg, int32_t any_neg,
+                                  const uint8_t* active, int32_t P, int32_t NS, int32_t lone_forall_identity, const float* gate_s,
+                                  const float* gate_o, float* post, void* stream);
 
 /* The same one posterior on the tile of the TRAIN step (DFOL_GATE_TRAIN=1): batch_gqa_ops.py:364-371 around batch_base_ops.py:99-100,
  * :135-136, i.e. the sequence gate, gate, dfol_relate_gate_fwd_f32(want), gate.  The arguments are dfol_relate_one_gate_fwd_f32's, but tile
@@ -1043,8 +1054,8 @@ typedef struct {            /* the scenes of one ProgramBatch (data_pipeline.py:
  * dfol_set_program_gates, and a cell of arity 2 owns rows slot (axis 0, the subject's) and slot + 1 (axis 1).  Without a table, or with a slot
  * beyond it, the program is refused before the instruction launches anything. */
 #define DFOL_OP_FILTER_GATE 25      /* DFOL_OP_FILTER's operands, slot: dfol_filter_gate_fwd_f32 */
-#define DFOL_OP_RELATE_ONE_GATE 26  /* DFOL_OP_RELATE_ONE's operands (tile dtype DFOL_TILE_F32 only), x_is_subject (blob, uint8 [P]), slot:
-                                     * dfol_relate_one_gate_fwd_f32 */
+#define DFOL_OP_RELATE_ONE_GATE 26  /* DFOL_OP_RELATE_ONE's operands, x_is_subject (blob, uint8 [P]), slot: dfol_relate_one_gate_fwd_f32, or
+                                     * dfol_relate_one_gate_fwd_bf16 for tile dtype DFOL_TILE_BF16 (NS % 8 == 0, a packed second layer) */
 #define DFOL_OP_RELATE_GATE 27      /* DFOL_OP_RELATE's operands, slot: dfol_relate_gate_fwd_f32 */
 /* steps of a DFOL_OP_CALIB_WALK table; buffers are [planes][rows][width] floats in the workspace (an LSTM state is h then c: two planes) */
 #define DFOL_WALK_FILL 0            /* dst, planes, width, 32-bit pattern */

@@ -14,6 +14,9 @@ Python operator loop (switch unset), each alternating in one process.
 Then two legs for the gated train step (DFOL_GATE_TRAIN=1; `--gate-train-only` runs these alone): the one-posterior forward and backward
 launches against the sequence and the autograd backward they replace, and a whole gated train step, eager and replayed, with the switch unset
 and set, on the one-hop program and on ragged 1..3-hop programs.
+Then one leg for the gated model over bf16 relation tiles (DFOL_GATE_BF16=1; `--gate-bf16-only` runs it alone): the one-launch gated Relate on
+bf16 tiles against the same launch on fp32 tiles, at `--batch` predicates x `--nmax` objects and x 256 objects (BASELINE configs[4]'s size), with
+the tile bytes of both.
 """
 import argparse
 import json
@@ -89,6 +92,12 @@ def trainable_gate_launches(args):
         ("relate_bwd", lambda: L.relate_bwd(pa, pb, tile, pq, n_obj, ones, ones, None, None, g1, g2, L.TILE_SUBJECT_ROWS, False)),
         ("relate_gate_bwd", lambda: L.relate_gate_bwd(pa, pb, tile, pq, n_obj, ones, ones, gs, go, None, None, g1, g2, L.TILE_SUBJECT_ROWS, False)),
     ]
+    if args.gate_bf16_only:                                    # the bf16-tile leg alone
+        lines = gated_relate_one_bf16(args)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     if args.gate_train_only:                                   # the two legs of the gated train step alone
         lines = gated_train_launches(args, L, t, rng, pa, pb, tile, pq, n_obj, ones, gs, go)
         lines += gated_train_step(args) + gated_train_step(args, hops="ragged")
@@ -121,6 +130,7 @@ def trainable_gate_launches(args):
     lines += gated_stream(args)
     lines += gated_train_launches(args, L, t, rng, pa, pb, tile, pq, n_obj, ones, gs, go)
     lines += gated_train_step(args) + gated_train_step(args, hops="ragged")
+    lines += gated_relate_one_bf16(args)
     if args.out:
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")
@@ -171,6 +181,59 @@ def gated_relate_one(args, L, t, rng, x, prev, tile, pq, n_obj, ones, gs, go):
     ratio = float(np.median(times[launches[0][0]]) / np.median(times[launches[1][0]]))
     lines.append(json.dumps({"ratio": "sequence / one launch (medians)", "value": ratio}))
     print(lines[-1], flush=True)
+    return lines
+
+
+def gated_relate_one_bf16(args):
+    """The one-launch gated Relate on bf16 tiles (dfol_relate_one_gate_fwd_bf16, DFOL_GATE_BF16=1) against the same launch on fp32 tiles
+    (dfol_relate_one_gate_fwd_f32 over the widened values, so both compute the same posterior), alternating in one process: `--batch` predicates
+    at `--nmax` objects and at 256 objects.  The gated cell is bound by its sigmoids, not by the tile stream: what bf16 storage buys is the tile
+    bytes, reported beside the times.  `ranges_apart` false: no separated difference between the two launches."""
+    from dfol_vqa_amd import _lib as L
+    from dfol_vqa_amd import synthetic as syn
+    dev = torch.device("cuda", 0)
+    t = lambda a, dt=torch.float32: torch.tensor(np.ascontiguousarray(a), dtype=dt, device=dev)
+    lines = []
+    for n in (args.nmax, 256):
+        rng = np.random.RandomState(1000 + n)
+        P, NS = args.batch, (n + 7) // 8 * 8
+        tile = np.full((P, NS, NS), -30, np.float32)
+        tile[:, :n, :n] = syn.table_log_likelihood(rng, (P, n, n), "mix10")
+        tile[:, np.arange(n), np.arange(n)] = -30
+        prior = np.zeros((P, NS), np.float32)
+        prior[:, :n] = -rng.uniform(0.01, 2.0, (P, n))
+        x, prev = t(prior), t(prior[::-1])
+        t16 = t(tile).to(torch.bfloat16)
+        t32 = t16.to(torch.float32)                              # the widened values: the fp32 launch reads what the bf16 launch reads
+        pq, n_obj, ones = t(np.arange(P), torch.int32), t(np.full(P, n), torch.int32), t(np.ones(P))
+        flag = t(np.arange(P) % 2, torch.uint8)                  # subject flags mixed over the batch
+        gs, go = (L.gate_params(t(rng.uniform(-0.7, 0.7, (6, 2))), t(rng.uniform(-0.7, 0.7, 6))) for _ in range(2))
+        launches = [("relate_one_gate_fwd (fp32 tiles)", lambda: L.relate_one_gate_fwd(x, prev, t32, pq, n_obj, ones, flag, gs, go)),
+                    ("relate_one_gate_fwd_bf16 (bf16 tiles)", lambda: L.relate_one_gate_fwd_bf16(x, prev, t16, pq, n_obj, ones, flag, gs, go))]
+        gap = float((torch.exp(launches[0][1]()) - torch.exp(launches[1][1]())).abs().max())
+        assert gap <= 1e-5, gap                                  # the same posterior (another summation order)
+        for _, fn in launches:
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        times = {name: [] for name, _ in launches}
+        for r in range(args.rounds):
+            for name, fn in (launches if r % 2 == 0 else launches[::-1]):      # (who goes first alternates)
+                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.record()
+                for _ in range(args.reps):
+                    fn()
+                e.record()
+                e.synchronize()
+                times[name].append(s.elapsed_time(e) * 1e3 / args.reps)
+        for (name, _), tl in zip(launches, (t32, t16)):
+            lines.append(_summary(name, times[name], predicates=P, objects=n, NS=NS, tile_bytes=int(tl.numel() * tl.element_size()), rounds=args.rounds,
+                                  reps=args.reps, max_abs_probability_gap=gap,
+                                  note="event time over back-to-back calls of the Python wrappers: host-side allocation of the output is inside"))
+        a, b = np.asarray(times[launches[0][0]]), np.asarray(times[launches[1][0]])
+        lines.append(json.dumps({"ratio": "fp32 tiles / bf16 tiles (medians), %d x %d" % (P, n), "value": float(np.median(a) / np.median(b)),
+                                 "ranges_apart": bool(a.min() > b.max() or b.min() > a.max())}))
+        print(lines[-1], flush=True)
     return lines
 
 
@@ -382,6 +445,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None, help="--trainable-gate: also write the JSON lines to this file")
     ap.add_argument("--gate-train-only", action="store_true", help="--trainable-gate: only the two legs of the gated train step (DFOL_GATE_TRAIN)")
+    ap.add_argument("--gate-bf16-only", action="store_true", help="--trainable-gate: only the leg of the one-launch gated Relate on bf16 tiles (DFOL_GATE_BF16)")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--nmin", type=int, default=10)
     ap.add_argument("--nmax", type=int, default=100)
