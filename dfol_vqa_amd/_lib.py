@@ -134,7 +134,9 @@ SIGNATURES = {
     "dfol_relate_one_gate_fwd_bf16": [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _p],
     "dfol_relate_keep_gate_fwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _p],
     "dfol_relate_keep_gate_bwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p],
-    "dfol_filter_gate_bwd_scratch": [_i32, _i32],          # returns a float count (int64), called directly
+    "dfol_relate_keep_fwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _p],
+    "dfol_relate_keep_bwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _p],
+    "dfol_filter_gate_bwd_scratch": [_i32, _i32],         # returns a float count (int64), called directly
     "dfol_filter_gate_bwd_f32": [_p, _p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _p, _p, _p, _p, _p, _p],
     "dfol_relate_gate_bwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "dfol_attr_gather_bwd_f32": [_p, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _p],
@@ -635,6 +637,39 @@ def relate_keep_gate_fwd(x_att, prev_att, tile, pred_q, n_obj, quant_prev, x_is_
     call("dfol_relate_keep_gate_fwd_f32", _ptr(x_att, F32), _ptr(prev_att, F32), _ptr(tile, F32), _ptr(pred_q, I32), _ptr(n_obj, I32),
          _ptr(quant_prev, F32), _ptr(x_is_subject, U8), _ptr(neg, U8, True), 0 if neg is None else 1, _ptr(active, U8, True), P, NS,
          1 if lone_forall_identity else 0, _ptr(gate_s, F32), _ptr(gate_o, F32), _ptr(post), _stream())
+    return post
+
+
+def relate_train():
+    """DFOL_RELATE_TRAIN=1 (opt-in, read when a forward starts): an ungated relate hop that a gradient reaches runs the one-posterior kernels
+    (relate_keep_fwd / relate_keep_bwd) instead of gate, gate, relate_fwd(want), gate and their autograd backward over both directions.
+    Unset: the generic route under autograd, as before."""
+    return os.environ.get("DFOL_RELATE_TRAIN", "0") == "1"
+
+
+RELATE_KEEP_BWD_MAX_NS = 2048      # the backward's (2 + 4) NS floats of LDS = 48 KB
+
+
+def _keep_check(what, x_att, prev_att, tile, x_is_subject):
+    if tile.dtype != F32:
+        raise DfolError("%s reads fp32 tiles (got %s): the train step never stores bf16 relation tiles" % (what, tile.dtype))
+    if tile.dim() != 3 or tile.shape[1] != tile.shape[2]:
+        raise DfolError("%s: tile of shape %s (expected [P, NS, NS])" % (what, tuple(tile.shape)))
+    P, NS = tile.shape[0], tile.shape[1]
+    if tuple(x_att.shape) != (P, NS) or prev_att.dim() != 2 or prev_att.shape[1] != NS:
+        raise DfolError("%s: x %s / prev %s do not match the tile's [%d, %d, %d]" % (what, tuple(x_att.shape), tuple(prev_att.shape), P, NS, NS))
+    if x_is_subject.numel() != P:
+        raise DfolError("%s: %d subject flags for %d predicates" % (what, x_is_subject.numel(), P))
+    return P, NS
+
+
+def relate_keep_fwd(x_att, prev_att, tile, pred_q, n_obj, quant_prev, x_is_subject, neg=None, active=None, lone_forall_identity=False):
+    """relate_one_fwd on the train step's tile: fp32, SUBJECTS along rows for every predicate; x_is_subject uint8 [P] picks the axis summed out."""
+    P, NS = _keep_check("relate_keep_fwd", x_att, prev_att, tile, x_is_subject)
+    args = (_ptr(x_att, F32), _ptr(prev_att, F32), _ptr(tile, F32), _ptr(pred_q, I32), _ptr(n_obj, I32), _ptr(quant_prev, F32),
+            _ptr(x_is_subject, U8), _ptr(neg, U8, True), 0 if neg is None else 1, _ptr(active, U8, True), P, NS, 1 if lone_forall_identity else 0)
+    post = torch.empty(P, NS, dtype=F32, device=tile.device)
+    call("dfol_relate_keep_fwd_f32", *args, _ptr(post), _stream())
     return post
 
 
@@ -1858,6 +1893,30 @@ def relate_keep_gate_bwd(g_post, x_att, prev_att, tile, pred_q, n_obj, quant_pre
          P, NS, 1 if lone_forall_identity else 0, _ptr(gate_s, F32), _ptr(gate_o, F32), _ptr(scratch), _ptr(g_x), _ptr(pp), _ptr(g_tile),
          _ptr(gg_s), _ptr(gg_o), _stream())
     return g_x, (pp if identity else reduce_by_question(pp, pred_q, None, Q)), g_tile, gg_s, gg_o
+
+
+def relate_keep_bwd(g_post, x_att, prev_att, tile, pred_q, n_obj, quant_prev, x_is_subject, neg, active, lone_forall_identity, identity=None):
+    """-> (g_x [P, NS], g_prev [Q, NS], g_tile [P, NS, NS] subjects along rows).  identity: pred_q maps predicate p to question p, so g_prev
+    needs no reduction (None: is_identity_map)."""
+    P, NS = _keep_check("relate_keep_bwd", x_att, prev_att, tile, x_is_subject)
+    if NS > RELATE_KEEP_BWD_MAX_NS:
+        raise DfolError("relate_keep_bwd: images of %d object slots; the one-posterior Relate backward keeps its row and column sums in LDS and "
+                        "takes at most %d" % (NS, RELATE_KEEP_BWD_MAX_NS))
+    if tuple(g_post.shape) != (P, NS):
+        raise DfolError("relate_keep_bwd: cotangent of shape %s for a posterior of [%d, %d]" % (tuple(g_post.shape), P, NS))
+    Q = prev_att.shape[0]
+    if identity is None:
+        identity = is_identity_map(pred_q, Q)
+    if not identity:
+        require_sorted(pred_q, "relate_keep_bwd")
+    args = (_ptr(g_post, F32), _ptr(x_att, F32), _ptr(prev_att, F32), _ptr(tile, F32), _ptr(pred_q, I32), _ptr(n_obj, I32), _ptr(quant_prev, F32),
+            _ptr(x_is_subject, U8), _ptr(neg, U8, True), 0 if neg is None else 1, _ptr(active, U8, True), P, NS, 1 if lone_forall_identity else 0)
+    dev = tile.device
+    g_x = torch.empty(P, NS, dtype=F32, device=dev)
+    pp = torch.empty(P, NS, dtype=F32, device=dev)                                          # per predicate
+    g_tile = torch.empty(P, NS, NS, dtype=F32, device=dev)
+    call("dfol_relate_keep_bwd_f32", *args, _ptr(g_x), _ptr(pp), _ptr(g_tile), _stream())
+    return g_x, (pp if identity else reduce_by_question(pp, pred_q, None, Q)), g_tile
 
 
 def quantify_bwd(g_lp, att, quant, pred_q, n_obj):

@@ -1003,6 +1003,337 @@ extern "C" int dfol_relate_one_fwd_f32(const float* x_att, const float* prev_att
 }
 
 // =====================================================================================================
+// Relate, single posterior, on the SUBJECT-ROW tile of the train step (DFOL_RELATE_TRAIN=1)
+// =====================================================================================================
+// oracle.block_likelihood stores subjects along rows for every predicate (the inference prefetch that turns prev's objects onto the rows
+// does not run under autograd), so the predicate's flag picks, wave-uniformly, the axis that is summed out:
+//     x_is_subject[p]:  post[p][i] = x[p][i] + F( agg_{j != i} F( l'[i][j] + prev[j] ) )      row aggregate    (x = R, prev = C of relate_fwd_kernel)
+//     otherwise:        post[p][i] = x[p][i] + F( agg_{j != i} F( l'[j][i] + prev[j] ) )      column aggregate (prev = R, x = C)
+// This is relate_fwd_kernel with one quantifier (prev's) and exactly one wanted side: the same EXISTS complement form (relate_exists_fast,
+// row partials by the DPP group OR), the same transcendental-free FOR_ALL forms with their fall-back to the clamping loop, the same
+// diagonal and padding selects.  Column aggregates stay in registers and the row slots are joined by __shfl_xor; row aggregates go through
+// the DPP group reduction into the wavefront's LDS row.  A no-op row is prev's row.  No atomics: two launches give the same bits.
+template <int LPR>
+__global__ __launch_bounds__(256) void relate_keep_fwd_kernel(
+    const float* __restrict__ x_att, const float* __restrict__ prev_att, const float* __restrict__ tile,
+    const int32_t* __restrict__ pred_q, const int32_t* __restrict__ n_obj, const float* __restrict__ quant_prev,
+    const uint8_t* __restrict__ x_is_subject, const uint8_t* __restrict__ neg, int any_neg, const uint8_t* __restrict__ active, int P, int NS,
+    int identity_forall, float* __restrict__ post) {
+    constexpr int RPI = 64 / LPR;
+    __shared__ float row_sum[4][256];
+    const int wave_in_block = threadIdx.x >> 6;
+    const int p = blockIdx.x * 4 + wave_in_block;
+    if (p >= P) return;
+    const int lane = threadIdx.x & 63;
+    const int q = pred_q[p];
+    const int n = min(n_obj[q], NS);
+    const float* pv = prev_att + (int64_t)q * NS;
+    const float* xv = x_att + (int64_t)p * NS;
+    float* out = post + (int64_t)p * NS;
+    if (active && !active[p]) {                         // question without this operator: attention passes through
+        for (int c = lane; c < NS; c += 64) out[c] = c < n ? pv[c] : 0.f;
+        return;
+    }
+    const bool wantR = x_is_subject[p] != 0, wantC = !wantR;      // x on the rows: its posterior is the row side's
+    const float* pR = wantR ? xv : pv;
+    const float* pC = wantR ? pv : xv;
+    const int cg = lane % LPR, rs = lane / LPR, c0 = cg * 4, cl = min(c0, NS - 4);
+    const bool col_live = c0 < n;
+    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
+    const float qf = quant_prev[p], kf = 1.f - 2.f * qf;
+    const bool ident = identity_forall && qf == 0.f;
+    const float* tp = tile + (int64_t)p * NS * NS;
+    float* rsum = row_sum[wave_in_block];
+
+    if (qf == 1.f) {                                     // EXISTS: the complement form (see relate_exists_fast); false: a prior above log 1
+        const bool ok = wantR ? relate_exists_fast<LPR, true, false>(tp, pR, pC, NS, n, lane, rsum, out, nullptr, alpha_n)
+                              : relate_exists_fast<LPR, false, true>(tp, pR, pC, NS, n, lane, rsum, nullptr, out, alpha_n);
+        if (ok) return;
+        __builtin_amdgcn_wave_barrier();
+    }
+
+    const float4 pc4 = *reinterpret_cast<const float4*>(pC + cl);
+    const float pc[4] = {pc4.x, pc4.y, pc4.z, pc4.w};
+    float col_acc[4] = {0.f, 0.f, 0.f, 0.f};
+
+    // FOR_ALL, un-negated: both F are the identity unless a term is below log eps, so the aggregate is a plain sum of l' + prev with NO
+    // transcendental; the smallest term is tracked and a predicate at the clamp goes through the general loop (relate_fwd_kernel).
+    bool sums_done = false;
+    if (alpha_n == 0.f && qf == 0.f) {
+        float chk = 0.f, pmax = -1.f;
+        constexpr int UNRF = 4;
+        for (int r0 = 0; r0 < n; r0 += RPI * UNRF) {
+            float4 tq[UNRF];
+            float prq[UNRF];
+#pragma unroll
+            for (int u = 0; u < UNRF; ++u) {                             // all loads of the step first (clamped, unconditional)
+                const int rc = min(r0 + u * RPI + rs, n - 1);
+                tq[u] = *reinterpret_cast<const float4*>(tp + (int64_t)rc * NS + cl);
+                prq[u] = pR[rc];
+            }
+#pragma unroll
+            for (int u = 0; u < UNRF; ++u) {
+                const int r = r0 + u * RPI + rs;
+                const bool live = r < n && col_live;
+                const float l[4] = {tq[u].x, tq[u].y, tq[u].z, tq[u].w};
+                const float pr = prq[u];
+                if (wantC) pmax = fmaxf(pmax, r < n ? pr : -1.f);
+                float row_part = 0.f;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int c = c0 + j;
+                    const bool keep = live && c < n && c != r;
+                    const float uu = fminf(l[j], 0.f) + (wantR ? pc[j] : pr);
+                    chk = fminf(chk, keep ? uu : 0.f);
+                    if (wantR) {
+                        row_part += keep ? uu : 0.f;
+                        if (c < n) pmax = fmaxf(pmax, pc[j]);
+                    } else {
+                        col_acc[j] += keep ? uu : 0.f;
+                    }
+                }
+                if (wantR) {
+                    row_part = dfol_group_sum<LPR>(row_part);
+                    if (cg == LPR - 1 && r < n) rsum[r] = row_part;
+                }
+            }
+        }
+        sums_done = !__any(chk < -46.0f || pmax > 0.f);                 // log(1e-20) = -46.05
+        if (!sums_done) {
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int j = 0; j < 4; ++j) col_acc[j] = 0.f;
+        }
+    }
+
+    // FOR_ALL, NEGATED: l' = log(1 - E), so the aggregate is the log of a product of (1 - E) factors plus the sum of prev's entries; the
+    // smallest (1 - E) e^prev is tracked against eps (the outer clamp), a zero factor (the inner one) shows as -inf (relate_fwd_kernel).
+    if (!sums_done && alpha_n == 1.f && qf == 0.f) {
+        constexpr float L2E = 1.44269504088896340736f, LN2 = 0.69314718055994530942f;
+        constexpr int UNR = 4;
+        float Pc[4], pcsum = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool cv = c0 + j < n;
+            Pc[j] = cv ? __builtin_amdgcn_exp2f(pc[j] * L2E) : 1.f;
+            pcsum += cv ? pc[j] : 0.f;                                    // (a lane beyond the width has c0 >= NS >= n: nothing twice)
+        }
+        pcsum = dfol_group_sum<LPR>(pcsum);                               // sum of the column entries (valid in the group's last lane)
+        pcsum = __shfl(pcsum, (lane / LPR) * LPR + LPR - 1, 64);
+        float chk = 1.f, pmax = -1.f, prsum = 0.f;
+        for (int r0 = 0; r0 < n; r0 += RPI * UNR) {
+            float cprod[4] = {1.f, 1.f, 1.f, 1.f};
+            float4 tq[UNR];
+            float prq[UNR];
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) {                              // all loads of the step first
+                const int rc = min(r0 + u * RPI + rs, n - 1);
+                tq[u] = *reinterpret_cast<const float4*>(tp + (int64_t)rc * NS + cl);
+                prq[u] = pR[rc];
+            }
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) {
+                const int r = r0 + u * RPI + rs;
+                const bool rlive = r < n, live = rlive && col_live;
+                const float l[4] = {tq[u].x, tq[u].y, tq[u].z, tq[u].w};
+                const float pr = prq[u];
+                const float Pr = __builtin_amdgcn_exp2f(pr * L2E);
+                if (wantC) pmax = fmaxf(pmax, rlive ? pr : -1.f);
+                if (cg == 0) prsum += rlive ? pr : 0.f;                   // each row's entry once per wavefront
+                float rprod = 1.f;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int c = c0 + j;
+                    const bool keep = live && c < n && c != r;
+                    const float a = keep ? 1.f - __builtin_amdgcn_exp2f(fminf(l[j] * L2E, 0.f)) : 1.f;       // e^{l'} (:194, :212-213)
+                    if (wantR) {
+                        chk = fminf(chk, keep ? a * Pc[j] : 1.f);
+                        rprod *= a;
+                        if (c < n) pmax = fmaxf(pmax, pc[j]);
+                    } else {
+                        chk = fminf(chk, keep ? a * Pr : 1.f);
+                        cprod[j] *= a;
+                    }
+                }
+                if (wantR) {
+                    const float part = dfol_group_sum<LPR>(__builtin_amdgcn_logf(rprod));
+                    // sum_{c != r} (l' + pC[c]) = ln2 * log2(prod) + (sum of the column entries - pC[r])
+                    if (cg == LPR - 1 && rlive) rsum[r] = part * LN2 + pcsum - pC[r];
+                }
+            }
+            if (wantC) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) col_acc[j] += __builtin_amdgcn_logf(cprod[j]);
+            }
+        }
+        bool bad = chk < 1.2e-20f || pmax > 0.f;
+        if (wantC) {
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) prsum += __shfl_xor(prsum, m, 64);          // every row's entry
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float v = col_acc[j];
+#pragma unroll
+                for (int m = 32; m >= LPR; m >>= 1) v += __shfl_xor(v, m, 64);
+                bad |= (c0 + j < n) && !(v >= -3.0e38f);
+                // reduced here already: the common epilogue below adds the row slots again, so leave the total in slot 0 only
+                col_acc[j] = (rs == 0 && c0 + j < n) ? v * LN2 + prsum - pR[c0 + j] : 0.f;      // sum_{r != c} pR[r] = all of them - pR[c]
+            }
+        } else {
+            __builtin_amdgcn_wave_barrier();
+            for (int c = lane; c < n; c += 64) bad |= !(rsum[c] >= -3.0e38f);
+        }
+        sums_done = !__any(bad);
+        if (!sums_done) {
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int j = 0; j < 4; ++j) col_acc[j] = 0.f;
+        }
+    }
+
+    for (int r0 = sums_done ? n : 0; r0 < n; r0 += RPI) {                // the general, clamping loop of relate_fwd_kernel
+        const int r = r0 + rs;
+        const bool live = r < n && col_live;
+        float l[4] = {0.f, 0.f, 0.f, 0.f};
+        float pr = 0.f;
+        if (live) {
+            const float4 t = *reinterpret_cast<const float4*>(tp + (int64_t)r * NS + c0);
+            l[0] = t.x; l[1] = t.y; l[2] = t.z; l[3] = t.w;
+            pr = pR[r];
+        }
+        float row_part = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = c0 + j;
+            const bool keep = live && c < n && c != r;        // padding and self-relations contribute 0 (:112)
+            float v = fminf(l[j], 0.f);                       // :194
+            if (any_neg) v = dfol_pnot(v, alpha_n, cn);       // :212-213
+            const float u = v + (wantR ? pc[j] : pr);         // :102
+            const float t = ident ? u : dfol_pnot(u, qf, kf); // :108
+            if (wantR) row_part += keep ? t : 0.f;
+            else col_acc[j] += keep ? t : 0.f;
+        }
+        if (wantR) {
+            row_part = dfol_group_sum<LPR>(row_part);
+            if (cg == LPR - 1 && r < n) rsum[r] = row_part;
+        }
+    }
+    if (wantR) {
+        __builtin_amdgcn_wave_barrier();                 // LDS is in-order within a wave; this only pins the schedule
+        for (int c = lane; c < NS; c += 64) {
+            float o = 0.f;
+            if (c < n) {
+                const float s = rsum[c];
+                o = pR[c] + (ident ? s : dfol_pnot(s, qf, kf));          // :133, :138
+            }
+            out[c] = o;
+        }
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int m = 32; m >= LPR; m >>= 1) col_acc[j] += __shfl_xor(col_acc[j], m, 64);
+    }
+    if (rs == 0 && c0 < NS) {
+        float o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float s = col_acc[j];
+            o[j] = (c0 + j < n) ? pc[j] + (ident ? s : dfol_pnot(s, qf, kf)) : 0.f;
+        }
+        *reinterpret_cast<float4*>(out + c0) = make_float4(o[0], o[1], o[2], o[3]);
+    }
+}
+
+// NS > 256: one workgroup per predicate; a thread per column, rows in order, for the column aggregate, a workgroup reduction per row (wavefront
+// partials added in wavefront order) for the row aggregate, as relate_big_fwd_kernel.
+__global__ __launch_bounds__(256) void relate_keep_big_kernel(
+    const float* __restrict__ x_att, const float* __restrict__ prev_att, const float* __restrict__ tile,
+    const int32_t* __restrict__ pred_q, const int32_t* __restrict__ n_obj, const float* __restrict__ quant_prev,
+    const uint8_t* __restrict__ x_is_subject, const uint8_t* __restrict__ neg, int any_neg, const uint8_t* __restrict__ active, int NS,
+    int identity_forall, float* __restrict__ post) {
+    __shared__ float part[4];
+    const int p = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    const int q = pred_q[p], n = min(n_obj[q], NS);
+    const float* pv = prev_att + (int64_t)q * NS;
+    const float* xv = x_att + (int64_t)p * NS;
+    float* out = post + (int64_t)p * NS;
+    if (active && !active[p]) {
+        for (int c = tid; c < NS; c += 256) out[c] = c < n ? pv[c] : 0.f;
+        return;
+    }
+    const bool xs = x_is_subject[p] != 0;                // (the workgroup's: every thread reaches the barriers below)
+    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
+    const float qf = quant_prev[p], kf = 1.f - 2.f * qf;
+    const bool ident = identity_forall && qf == 0.f;
+    const float* tp = tile + (int64_t)p * NS * NS;
+    if (!xs) {
+        for (int c = tid; c < NS; c += 256) {
+            float acc = 0.f;
+            if (c < n) {
+                for (int r = 0; r < n; ++r) {
+                    if (r == c) continue;                                 // self-relations contribute 0 (:112)
+                    const float u = relate_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn) + pv[r];
+                    acc += ident ? u : dfol_pnot(u, qf, kf);
+                }
+                acc = xv[c] + (ident ? acc : dfol_pnot(acc, qf, kf));
+            }
+            out[c] = acc;
+        }
+        return;
+    }
+    for (int r = 0; r < NS; ++r) {
+        float s = 0.f;
+        if (r < n)
+            for (int c = tid; c < n; c += 256) {
+                if (c == r) continue;
+                const float u = relate_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn) + pv[c];     // :102
+                s += ident ? u : dfol_pnot(u, qf, kf);                                               // :108
+            }
+        s = dfol_wave_sum(s);
+        if (lane == 0) part[w] = s;
+        __syncthreads();
+        if (tid == 0) {
+            const float tot = ((part[0] + part[1]) + part[2]) + part[3];
+            out[r] = r < n ? xv[r] + (ident ? tot : dfol_pnot(tot, qf, kf)) : 0.f;                    // :133, :138
+        }
+        __syncthreads();
+    }
+}
+
+extern "C" int dfol_relate_keep_fwd_f32(const float* x_att, const float* prev_att, const float* tile, const int32_t* pred_q,
+                                        const int32_t* n_obj, const float* quant_prev, const uint8_t* x_is_subject, const uint8_t* neg,
+                                        int32_t any_neg, const uint8_t* active, int32_t P, int32_t NS, int32_t lone_forall_identity,
+                                        float* post, void* stream) {
+    DFOL_REQUIRE(P >= 0 && NS > 0 && NS % 4 == 0, "relate_keep_fwd: bad sizes P=%d NS=%d (NS: a multiple of 4)", P, NS);
+    if (P == 0) return 0;
+    DFOL_REQUIRE(x_att && prev_att && tile && pred_q && n_obj && quant_prev && x_is_subject && post, "relate_keep_fwd: null pointer");
+    DFOL_REQUIRE(!any_neg || neg, "relate_keep_fwd: any_neg set but neg is NULL");
+    hipStream_t st = (hipStream_t)stream;
+    if (NS > 256) {
+        hipLaunchKernelGGL(relate_keep_big_kernel, dim3(P), dim3(256), 0, st, x_att, prev_att, tile, pred_q, n_obj, quant_prev, x_is_subject, neg,
+                           any_neg, active, NS, lone_forall_identity, post);
+        DFOL_LAUNCH_CHECK("relate_keep_fwd (NS > 256)");
+        return 0;
+    }
+    const int groups = NS / 4;
+#define DFOL_RELK(L)                                                                                                                  \
+    hipLaunchKernelGGL(relate_keep_fwd_kernel<L>, dim3(dfol_cdiv(P, 4)), dim3(256), 0, st, x_att, prev_att, tile, pred_q, n_obj, quant_prev, \
+                       x_is_subject, neg, any_neg, active, P, NS, lone_forall_identity, post)
+    if (groups <= 1) DFOL_RELK(1);
+    else if (groups <= 2) DFOL_RELK(2);
+    else if (groups <= 4) DFOL_RELK(4);
+    else if (groups <= 8) DFOL_RELK(8);
+    else if (groups <= 16) DFOL_RELK(16);
+    else if (groups <= 32) DFOL_RELK(32);
+    else DFOL_RELK(64);
+#undef DFOL_RELK
+    DFOL_LAUNCH_CHECK("relate_keep_fwd");
+    return 0;
+}
+
+// =====================================================================================================
 // Relate, single posterior, bf16 tiles (BASELINE configs[4]: 256-object scenes, tiles stored in bf16 to halve the HBM bytes)
 // =====================================================================================================
 // Same contract as relate_one_fwd_kernel; a lane owns EIGHT consecutive columns (one 16-byte load = 8 bf16 per row), so LPR =

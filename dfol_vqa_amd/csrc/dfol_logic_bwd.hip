@@ -238,6 +238,160 @@ extern "C" int dfol_relate_bwd_f32(const float* prior_s, const float* prior_o, c
 }
 
 // ---------------------------------------------------------------------------------------------------
+// relate, single posterior on the subject-row tile (dfol_relate_keep_fwd_f32): relate_bwd_kernel's two sweeps restricted to the kept
+// direction - the other direction's cotangent is exactly zero, so its F', its sums and its reductions are not computed.  With g the
+// posterior's cotangent and A the aggregate over prev's axis (recomputed by sweep 1 as written: a sum of logs, EXISTS too):
+//   x on rows    (flag set):   D[r] = g[r] F'(A[r]);  d l'[r][c] = D[r] F'(l' + prev[c]);  d prev[c] = sum_r of it
+//   x on columns (flag clear): D[c] = g[c] F'(A[c]);  d l'[r][c] = D[c] F'(l' + prev[r]);  d prev[r] = sum_c of it
+//   d x = g (the posterior adds x);  d tile = d l' * dprep.
+// The flag is the workgroup's, so every branch on it is uniform.  LDS: (2 + waves) NS floats (A or the rows' prev sums, D, the wavefronts'
+// column partials): 16 wavefronts while that stays within 48 KB (NS <= 680), four beyond, NS <= 2048 (48 KB).
+// ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64 * RB_WAVES) void relate_keep_bwd_kernel(
+    const float* __restrict__ g_post, const float* __restrict__ x_att, const float* __restrict__ prev_att, const float* __restrict__ tile,
+    const int32_t* __restrict__ pred_q, const int32_t* __restrict__ n_obj, const float* __restrict__ quant_prev,
+    const uint8_t* __restrict__ x_is_subject, const uint8_t* __restrict__ neg, int any_neg, const uint8_t* __restrict__ active, int NS,
+    int identity_forall, float* __restrict__ g_x, float* __restrict__ g_prev, float* __restrict__ g_tile) {
+    extern __shared__ float relate_keep_bwd_lds[];         // (2 + waves) NS floats
+    float* sA = relate_keep_bwd_lds;                       // x on rows: the row aggregates; x on columns: the rows' prev gradients (sweep 2)
+    float* sD = sA + NS;                                   // d loss / d aggregate
+    float* part_base = sD + NS;                            // x on columns: the column aggregates' partials; x on rows: the columns' prev gradients
+    auto part = [&](int wave, int c) -> float& { return part_base[wave * NS + c]; };
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, tid = threadIdx.x, nw = (int)blockDim.x >> 6, nt = (int)blockDim.x;
+    const int p = blockIdx.x;
+    const int q = pred_q[p];
+    const int n = min(n_obj[q], NS);
+    const float* pv = prev_att + (int64_t)q * NS;
+    const float* gp = g_post + (int64_t)p * NS;
+    const float* tp = tile + (int64_t)p * NS * NS;
+    float* gt = g_tile + (int64_t)p * NS * NS;
+    float* gx = g_x + (int64_t)p * NS;
+    float* gpv = g_prev + (int64_t)p * NS;
+
+    if (active && !active[p]) {                            // posterior = prev: the gradient passes straight through
+        for (int c = tid; c < NS; c += nt) {
+            gpv[c] = c < n ? gp[c] : 0.f;
+            gx[c] = 0.f;
+        }
+        for (int e = tid; e < NS * NS; e += nt) gt[e] = 0.f;
+        return;
+    }
+    const bool xs = x_is_subject[p] != 0;
+    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
+    const float qf = quant_prev[p], kf = 1.f - 2.f * qf;
+    const bool ident = identity_forall && qf == 0.f;
+
+    // sweep 1: the aggregate over prev's axis (lane = column, this wavefront's rows in order)
+    for (int c0 = 0; c0 < NS; c0 += 64) {
+        const int c = c0 + lane;
+        if (xs) {                                          // S[r] = sum_c F(l' + prev[c])
+            const float pc = c < n ? pv[c] : 0.f;
+            for (int r = w; r < n; r += nw) {
+                float s_part = 0.f;
+                if (c < n && c != r) {
+                    const float u = dfol_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn) + pc;
+                    s_part = ident ? u : dfol_pnot(u, qf, kf);
+                }
+                s_part = dfol_wave_sum(s_part);
+                if (lane == 0) sA[r] = (c0 == 0 ? 0.f : sA[r]) + s_part;
+            }
+        } else {                                           // T[c] = sum_r F(l' + prev[r])
+            float t_acc = 0.f;
+            for (int r = w; r < n; r += nw) {
+                if (c < n && c != r) {
+                    const float u = dfol_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn) + pv[r];
+                    t_acc += ident ? u : dfol_pnot(u, qf, kf);
+                }
+            }
+            if (c < NS) part(w, c) = t_acc;
+        }
+    }
+    __syncthreads();
+    // the outer derivative, by the thread that owns element i (T[i]: the partials in wavefront order); d x = g
+    for (int i = tid; i < NS; i += nt) {
+        float d = 0.f, g = 0.f;
+        if (i < n) {
+            float A;
+            if (xs) {
+                A = sA[i];
+            } else {
+                A = part(0, i);
+                for (int j = 1; j < nw; ++j) A += part(j, i);
+            }
+            g = gp[i];
+            d = g * (ident ? 1.f : dfol_dpnot(A, qf, kf));
+        }
+        sD[i] = d;
+        gx[i] = g;
+    }
+    __syncthreads();
+    // sweep 2: the element gradients
+    for (int c0 = 0; c0 < NS; c0 += 64) {
+        const int c = c0 + lane;
+        if (xs) {
+            const float pc = c < n ? pv[c] : 0.f;
+            float dpc = 0.f;
+            for (int r = w; r < NS; r += nw) {
+                float dl = 0.f;
+                if (r < n && c < n && c != r) {
+                    const float raw = tp[(int64_t)r * NS + c];
+                    const float v = dfol_prep(raw, any_neg, alpha_n, cn);
+                    const float g1 = sD[r] * (ident ? 1.f : dfol_dpnot(v + pc, qf, kf));
+                    dl = g1 * dfol_dprep(raw, any_neg, alpha_n, cn);
+                    dpc += g1;
+                }
+                if (c < NS) gt[(int64_t)r * NS + c] = dl;
+            }
+            if (c < NS) part(w, c) = dpc;
+        } else {
+            const float dcc = c < n ? sD[c] : 0.f;
+            for (int r = w; r < NS; r += nw) {
+                float dl = 0.f, dpr = 0.f;
+                if (r < n && c < n && c != r) {
+                    const float raw = tp[(int64_t)r * NS + c];
+                    const float v = dfol_prep(raw, any_neg, alpha_n, cn);
+                    dpr = dcc * (ident ? 1.f : dfol_dpnot(v + pv[r], qf, kf));
+                    dl = dpr * dfol_dprep(raw, any_neg, alpha_n, cn);
+                }
+                if (c < NS) gt[(int64_t)r * NS + c] = dl;
+                dpr = dfol_wave_sum(dpr);                  // row totals over the column chunks collect in LDS (sA is free by now)
+                if (lane == 0 && r < n) sA[r] = (c0 == 0 ? 0.f : sA[r]) + dpr;
+            }
+        }
+    }
+    __syncthreads();
+    for (int c = tid; c < NS; c += nt) {
+        float t = 0.f;
+        if (c < n) {
+            if (xs) {
+                t = part(0, c);
+                for (int j = 1; j < nw; ++j) t += part(j, c);
+            } else {
+                t = sA[c];
+            }
+        }
+        gpv[c] = t;
+    }
+}
+
+extern "C" int dfol_relate_keep_bwd_f32(const float* g_post, const float* x_att, const float* prev_att, const float* tile,
+                                        const int32_t* pred_q, const int32_t* n_obj, const float* quant_prev, const uint8_t* x_is_subject,
+                                        const uint8_t* neg, int32_t any_neg, const uint8_t* active, int32_t P, int32_t NS,
+                                        int32_t lone_forall_identity, float* g_x, float* g_prev, float* g_tile, void* stream) {
+    DFOL_REQUIRE(P >= 0 && NS > 0 && NS % 4 == 0 && NS <= 2048, "relate_keep_bwd: bad sizes P=%d NS=%d (NS: a multiple of 4, <= 2048)", P, NS);
+    if (P == 0) return 0;
+    DFOL_REQUIRE(g_post && x_att && prev_att && tile && pred_q && n_obj && quant_prev && x_is_subject && g_x && g_prev && g_tile,
+                 "relate_keep_bwd: null pointer");
+    DFOL_REQUIRE(!any_neg || neg, "relate_keep_bwd: any_neg set but neg is NULL");
+    const int waves = (size_t)(2 + RB_WAVES) * NS * sizeof(float) <= 48 * 1024 ? RB_WAVES : 4;
+    hipLaunchKernelGGL(relate_keep_bwd_kernel, dim3(P), dim3(64 * waves), (size_t)(2 + waves) * NS * sizeof(float), (hipStream_t)stream, g_post,
+                       x_att, prev_att, tile, pred_q, n_obj, quant_prev, x_is_subject, neg, any_neg, active, NS, lone_forall_identity, g_x, g_prev,
+                       g_tile);
+    DFOL_LAUNCH_CHECK("relate_keep_bwd");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // quantify:  lp = F(sum_o F(att[o]))
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void quantify_bwd_kernel(const float* __restrict__ g_lp, const float* __restrict__ att,

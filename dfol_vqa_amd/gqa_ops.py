@@ -361,13 +361,15 @@ class GQARelateBatch(GQABatchOperatorBase):
                                 prev_variable_sets_num=x._prev_variable_sets_num + prev._prev_variable_sets_num + 1)
 
     def _forward_train_one(self, op_id, world, x, prev, relation_list, flag, host_flags):
-        """Train-side fast path of a gated cell (DFOL_GATE_TRAIN=1): the three gates and the arity-2 cell in ONE launch forward
-        (dfol_relate_keep_gate_fwd_f32) and ONE backward (dfol_relate_keep_gate_bwd_f32, the kept direction only), on the subject-row tile
-        RelateBatch.forward asks the oracle for.  Same value as the generic route below it to rounding (another summation order)."""
+        """Train-side fast path: the three gates and the arity-2 cell in ONE launch forward and ONE backward (the kept direction only), on the
+        subject-row tile RelateBatch.forward asks the oracle for - a gated cell under DFOL_GATE_TRAIN=1 (dfol_relate_keep_gate_fwd_f32 /
+        dfol_relate_keep_gate_bwd_f32), an ungated one under DFOL_RELATE_TRAIN=1 (dfol_relate_keep_fwd_f32 / dfol_relate_keep_bwd_f32).  Same
+        value as the generic route below it to rounding (another summation order)."""
         rel = self._relate
-        if not (rel._blc.gated() and L.gate_train() and torch.is_grad_enabled()):
+        gated = rel._blc.gated()
+        if not (torch.is_grad_enabled() and (L.gate_train() if gated else L.relate_train())):
             return None
-        gates = (*rel._blc._gate(0), *rel._blc._gate(1))
+        gates = (*rel._blc._gate(0), *rel._blc._gate(1)) if gated else ()
         if not (x._log_attention.requires_grad or prev._log_attention.requires_grad or any(g.requires_grad for g in gates)):
             return None
         calibrated = op_id in rel._subject_modulations
@@ -389,10 +391,10 @@ class GQARelateBatch(GQABatchOperatorBase):
         # the request RelateBatch.forward makes, argument for argument: the train-side pair branch and its readers see the same one
         tile = self._oracle.block_likelihood(TokenType.RELATION, low, world._ident, range(predicate_num), world, -30, True)
         xs = upload(np.asarray([1 if f > 0 else 0 for f in host_flags], np.uint8), world._device)
-        post = L.relate_keep_gate(x._log_attention, prev._log_attention, tile, world._ident, world._n_obj, prev._quantifier, xs, *gates,
-                                  neg_dev if low.any_neg else None, None if low.all_valid else valid_dev,
-                                  lone_forall_identity=(predicate_num == 1))
-        L.note("relate_gate_train_one")
+        keep = L.relate_keep_gate if gated else L.relate_keep
+        post = keep(x._log_attention, prev._log_attention, tile, world._ident, world._n_obj, prev._quantifier, xs, *gates,
+                    neg_dev if low.any_neg else None, None if low.all_valid else valid_dev, lone_forall_identity=(predicate_num == 1))
+        L.note("relate_gate_train_one" if gated else "relate_train_one")
         if calibrated:                                         # the kept side's modulations, as _forward_fused; L.modulate carries their gradient
             mods = torch.where(flag.unsqueeze(1) > 0, rel._subject_modulations.pop(op_id), rel._object_modulations.pop(op_id))
             post = L.modulate(post, mods, world._ident, world._n_obj)

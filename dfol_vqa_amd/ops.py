@@ -49,6 +49,33 @@ def relate_fwd(prior_s, prior_o, tile, pred_q, n_obj, quant_s, quant_o, neg=None
                            need_s, need_o, diag_absent)
 
 
+class _RelateKeep(torch.autograd.Function):
+    """The one posterior an ungated relate hop keeps, forward and backward in one launch each (DFOL_RELATE_TRAIN=1): only the inputs are saved,
+    the aggregate is recomputed by the backward."""
+
+    @staticmethod
+    def forward(ctx, x, prev, tile, pred_q, n_obj, quant_prev, x_is_subject, neg, active, lone):
+        ctx.save_for_backward(x, prev, tile, pred_q, n_obj, quant_prev, x_is_subject, neg, active)
+        ctx.lone, ctx.identity = lone, _lib.is_identity_map(pred_q, prev.shape[0])
+        return _lib.relate_keep_fwd(x, prev, tile, pred_q, n_obj, quant_prev, x_is_subject, neg, active, lone)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, prev, tile, pred_q, n_obj, quant_prev, x_is_subject, neg, active = ctx.saved_tensors
+        g_x, g_prev, g_tile = _lib.relate_keep_bwd(g.contiguous(), x, prev, tile, pred_q, n_obj, quant_prev, x_is_subject, neg, active, ctx.lone,
+                                                   identity=ctx.identity)
+        return (g_x if ctx.needs_input_grad[0] else None), (g_prev if ctx.needs_input_grad[1] else None), \
+            (g_tile if ctx.needs_input_grad[2] else None), None, None, None, None, None, None, None
+
+
+def relate_keep(x, prev, tile, pred_q, n_obj, quant_prev, x_is_subject, neg=None, active=None, lone_forall_identity=False):
+    """The posterior GQARelateBatch keeps, on the train step's subject-row tile: x [P, NS] the selected variable, prev [Q, NS] the incoming
+    one, x_is_subject uint8 [P] (which axis x is on; the other is summed out)."""
+    if _needs_grad(x, prev, tile):
+        return _RelateKeep.apply(x, prev, tile, pred_q, n_obj, quant_prev, x_is_subject, neg, active, bool(lone_forall_identity))
+    return _lib.relate_keep_fwd(x, prev, tile, pred_q, n_obj, quant_prev, x_is_subject, neg, active, lone_forall_identity)
+
+
 # ---- the cell with the trainable gate (csrc/dfol_logic_gate.hip) -------------------------------------
 def _gate_grads(g_gate, ctx, at):
     return (g_gate[:12].view(6, 2) if ctx.needs_input_grad[at] else None), (g_gate[12:] if ctx.needs_input_grad[at + 1] else None)

@@ -55,7 +55,8 @@ extern "C" {
  * executor: dfol_relate_one_gate_fwd_f32, dfol_set_program_gates and DFOL_OP_FILTER_GATE / DFOL_OP_RELATE_ONE_GATE / DFOL_OP_RELATE_GATE (no
  * struct grows: the gate table travels beside the call, as dfol_set_feature_rows' arrays do), and the one-posterior gated Relate of the train
  * step: dfol_relate_keep_gate_fwd_f32 and dfol_relate_keep_gate_bwd_f32, and the one-posterior gated Relate on bf16 tiles:
- * dfol_relate_one_gate_fwd_bf16 and DFOL_TILE_BF16 as DFOL_OP_RELATE_ONE_GATE's tile dtype (an older library refuses that operand);
+ * dfol_relate_one_gate_fwd_bf16 and DFOL_TILE_BF16 as DFOL_OP_RELATE_ONE_GATE's tile dtype (an older library refuses that operand), and the
+ * one-posterior Relate of the ungated train step: dfol_relate_keep_fwd_f32 and dfol_relate_keep_bwd_f32;
  * a caller that needs them checks for the symbol, and a table that names an opcode an older library lacks is refused by it ("unknown opcode"). */
 #define DFOL_ABI_VERSION 3
 
@@ -236,6 +237,19 @@ int dfol_relate_keep_gate_fwd_f32(const float* x_att, const float* prev_att, con
 int dfol_relate_one_fwd_f32(const float* x_att, const float* prev_att, const float* tile, const int32_t* pred_q,
                             const int32_t* n_obj, const float* quant_prev, const uint8_t* neg, int32_t any_neg,
                             const uint8_t* active, int32_t P, int32_t NS, int32_t lone_forall_identity, float* post, void* stream);
+
+/* The same one posterior on the tile of the TRAIN step (DFOL_RELATE_TRAIN=1): batch_gqa_ops.py:364-371 around batch_base_ops.py:99-102,
+ * :108-112 and :133-138, i.e. the sequence gate, gate, dfol_relate_fwd_f32(want), gate.  The arguments are dfol_relate_one_fwd_f32's, but
+ * tile holds SUBJECTS along rows for every predicate (DFOL_TILE_SUBJECT_ROWS, what the oracle writes under autograd), fp32, and
+ * x_is_subject [P] (uint8) picks the axis that is summed out:
+ *     x_is_subject[p] = 1:  post[p][i] = F( agg_{j < n, j != i} F( l'[i][j] + prev[j] ) ) + x_att[p][i]     (row aggregate)
+ *     x_is_subject[p] = 0:  post[p][i] = F( agg_{j < n, j != i} F( l'[j][i] + prev[j] ) ) + x_att[p][i]     (column aggregate)
+ * prev = prev_att[pred_q[p]], F and agg by quant_prev[p], with the arithmetic of dfol_relate_fwd_f32's wanted side (the lone predicate's
+ * literal FOR_ALL branch and the batch-wide negation clamp included); a no-op row is prev's row; padding is +0.  No atomics: two launches
+ * give the same bits. */
+int dfol_relate_keep_fwd_f32(const float* x_att, const float* prev_att, const float* tile, const int32_t* pred_q, const int32_t* n_obj,
+                             const float* quant_prev, const uint8_t* x_is_subject, const uint8_t* neg, int32_t any_neg,
+                             const uint8_t* active, int32_t P, int32_t NS, int32_t lone_forall_identity, float* post, void* stream);
 
 /* The same operator on bf16 tiles (BASELINE configs[4]: 256-object scenes; the stored likelihoods are rounded to bf16, which halves
  * the HBM bytes of the tile stream; arithmetic stays fp32).  tile [P, NS, NS] of bf16 bit patterns, NS a multiple of 8, written by
@@ -859,6 +873,17 @@ int dfol_relate_keep_gate_bwd_f32(const float* g_post, const float* x_att, const
                                   int32_t any_neg, const uint8_t* active, int32_t P, int32_t NS, int32_t lone_forall_identity,
                                   const float* gate_s, const float* gate_o, float* scratch, float* g_x, float* g_prev, float* g_tile,
                                   float* g_gate_s, float* g_gate_o, void* stream);
+
+/* Backward of dfol_relate_keep_fwd_f32 (the reference differentiates batch_gqa_ops.py:364-371 and batch_base_ops.py:99-138 by autograd):
+ * dfol_relate_bwd_f32's two sweeps for the kept direction of each predicate only - the other direction's cotangent is exactly zero.  The
+ * formulas as written, clamps included (zero gradient below the floor).  g_post [P, NS] is the posterior's cotangent.  WRITTEN: g_x
+ * [P, NS]; g_prev [P, NS] PER PREDICATE (reduce it with dfol_reduce_by_question_f32 when pred_q is not the identity); g_tile [P, NS, NS]
+ * with subjects along rows.  A no-op predicate hands g_post to g_prev and writes zeros elsewhere; padding, the diagonal and a no-op
+ * predicate's tile are +0.  No atomics: two launches give the same bits.  NS <= 2048 ((2 + 4) NS floats of LDS = 48 KB). */
+int dfol_relate_keep_bwd_f32(const float* g_post, const float* x_att, const float* prev_att, const float* tile, const int32_t* pred_q,
+                             const int32_t* n_obj, const float* quant_prev, const uint8_t* x_is_subject, const uint8_t* neg,
+                             int32_t any_neg, const uint8_t* active, int32_t P, int32_t NS, int32_t lone_forall_identity, float* g_x,
+                             float* g_prev, float* g_tile, void* stream);
 
 int dfol_quantify_bwd_f32(const float* g_lp, const float* att, const float* quant, const int32_t* pred_q, const int32_t* n_obj,
                           int32_t P, int32_t NS, float* g_att, void* stream);

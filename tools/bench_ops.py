@@ -17,6 +17,11 @@ and set, on the one-hop program and on ragged 1..3-hop programs.
 Then one leg for the gated model over bf16 relation tiles (DFOL_GATE_BF16=1; `--gate-bf16-only` runs it alone): the one-launch gated Relate on
 bf16 tiles against the same launch on fp32 tiles, at `--batch` predicates x `--nmax` objects and x 256 objects (BASELINE configs[4]'s size), with
 the tile bytes of both.
+
+       python tools/bench_ops.py --relate-train-only [--relate-train-unset] [--batch 256] [--nmax 100] [--rounds 15] [--reps 20] [--out FILE]
+The ungated train step's one-posterior Relate (DFOL_RELATE_TRAIN=1): the forward and the backward launch against the generic sequence and its
+autograd backward, then a whole train step, eager and replayed, with the switch unset and set, on the one-hop program and on ragged 1..3-hop
+programs, all alternating in one process.  `--relate-train-unset` times the unset step alone (a tree from before the switch runs it too).
 """
 import argparse
 import json
@@ -373,6 +378,167 @@ def gated_train_step(args, hops="aligned"):
     return lines
 
 
+def relate_train_launches(args):
+    """The one-posterior Relate under autograd for the ungated model (dfol_relate_keep_fwd_f32 / dfol_relate_keep_bwd_f32, DFOL_RELATE_TRAIN=1)
+    against the generic sequence an ungated relate hop runs without it - forward: gate, gate, relate_fwd under `want`, gate; backward: that
+    sequence's autograd backward (dfol_relate_bwd_f32 over both directions, two _Gate.backward, the want masks, the reductions by question) - on
+    the subject-row tile with mixed subject flags, through the Python wrappers, alternating in one process.  A backward is timed as
+    torch.autograd.grad over a retained graph, so the forward is not inside it."""
+    from dfol_vqa_amd import _lib as L
+    from dfol_vqa_amd import ops
+    from dfol_vqa_amd import synthetic as syn
+    dev = torch.device("cuda", 0)
+    rng = np.random.RandomState(17)
+    P, n = args.batch, args.nmax
+    NS = (n + 3) // 4 * 4
+    t = lambda a, dt=torch.float32: torch.tensor(np.ascontiguousarray(a), dtype=dt, device=dev)
+    tile = np.full((P, NS, NS), -30, np.float32)
+    tile[:, :n, :n] = syn.table_log_likelihood(rng, (P, n, n), "mix10")
+    tile[:, np.arange(n), np.arange(n)] = -30
+    prior = np.zeros((P, NS), np.float32)
+    prior[:, :n] = -rng.uniform(0.01, 2.0, (P, n))
+    x, prev, tile = t(prior), t(prior[::-1]), t(tile)
+    pq, n_obj, ones = t(np.arange(P), torch.int32), t(np.full(P, n), torch.int32), t(np.ones(P))
+    pq._dfol_sorted = pq._dfol_identity = True                    # (what BatchWorld marks its identity map with: no reduction by question)
+    flag = (np.arange(P) % 2).astype(np.float32)
+    flag_f, flag_u8 = t(flag), t(flag, torch.uint8)
+    want = t(np.where(flag > 0, L.WANT_SUBJECT, L.WANT_OBJECT), torch.uint8)
+    leaf = lambda a: a.detach().clone().requires_grad_(True)
+    leaves = [leaf(x), leaf(prev), leaf(tile)]
+    cot = t(rng.normal(size=tuple(x.shape)))
+
+    def sequence(a=x, b=prev, c=tile):
+        s, q_s = ops.gate(a, b, ones, ones, flag_f)
+        o, q_o = ops.gate(b, a, ones, ones, flag_f)
+        ps, po = ops.relate_fwd(s, o, c, pq, n_obj, q_s, q_o, None, None, want, diag_absent=True)
+        return ops.gate(ps, po, q_s, q_s, flag_f)[0]
+
+    def one(a=x, b=prev, c=tile):
+        return ops.relate_keep(a, b, c, pq, n_obj, ones, flag_u8)
+
+    with torch.no_grad():
+        gap = float((torch.exp(sequence()) - torch.exp(one())).abs().max())
+    assert gap <= 1e-5, gap
+    out_seq, out_one = sequence(*leaves), one(*leaves)
+    g_seq = torch.autograd.grad(out_seq, leaves, cot, retain_graph=True)
+    g_one = torch.autograd.grad(out_one, leaves, cot, retain_graph=True)
+    grad_gap = max(float((a - b).abs().max() / max(1e-30, float(a.abs().max()))) for a, b in zip(g_seq, g_one))
+    assert grad_gap <= 2e-3, grad_gap                            # the same gradients, relative to each tensor's scale
+
+    def fwd_seq():
+        with torch.no_grad():
+            sequence()
+
+    def fwd_one():
+        with torch.no_grad():
+            one()
+
+    launches = [("train forward, sequence(gate,gate,relate_fwd,gate)", fwd_seq),
+                ("train forward, relate_keep_fwd", fwd_one),
+                ("train backward, autograd of the sequence", lambda: torch.autograd.grad(out_seq, leaves, cot, retain_graph=True)),
+                ("train backward, relate_keep_bwd", lambda: torch.autograd.grad(out_one, leaves, cot, retain_graph=True))]
+    for _, fn in launches:
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name, _ in launches}
+    for _ in range(args.rounds):
+        for name, fn in launches:
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(args.reps):
+                fn()
+            e.record()
+            e.synchronize()
+            times[name].append(s.elapsed_time(e) * 1e3 / args.reps)
+    more = dict(predicates=P, objects=n, rounds=args.rounds, reps=args.reps, max_abs_probability_gap=gap, max_rel_gradient_gap=grad_gap,
+                note="event time over back-to-back calls of the Python wrappers: host-side allocation and autograd bookkeeping are inside")
+    lines = [_summary(name, times[name], **more) for name, _ in launches]
+    for a, b, what in ((0, 1, "forward"), (2, 3, "backward")):
+        ta, tb = np.asarray(times[launches[a][0]]), np.asarray(times[launches[b][0]])
+        lines.append(json.dumps({"ratio": "train %s: sequence / one launch (medians)" % what, "value": float(np.median(ta) / np.median(tb)),
+                                 "ranges_apart": bool(ta.min() > tb.max() or tb.min() > ta.max())}))
+        print(lines[-1], flush=True)
+    return lines
+
+
+def relate_train_step(args, hops="aligned", switches=("0", "1")):
+    """An ungated train step (zero grads -> forward -> loss -> backward -> clip -> Adam; the oracle and the featurizer train, as bench.py --mode
+    train) on bench.py's one-hop program (select -> filter -> relate -> exist) or its ragged 1..3-hop programs, eager and replayed
+    (GraphedTrainStep), with DFOL_RELATE_TRAIN unset and set: the variants alternate in one process, each on its own copy of the model, wall time
+    per step with a device synchronisation per round.  switches=("0",): the unset variants alone - what a tree without the switch can run, for
+    the parent commit's step in the same session."""
+    import copy
+    from dfol_vqa_amd import _lib, experiment, parallel, training
+    from dfol_vqa_amd import synthetic as syn
+    device = torch.device("cuda", 0)
+    paths, names = syn.write_synthetic_ontology(tempfile.mkdtemp(prefix="dfol_relate_train_"))
+    cfg = syn.reference_config(paths, dropout=0.0, freeze_featurizer=False, freeze_attribute_network=False, freeze_relation_network=False,
+                               freeze_embedding_network=False)      # bench.py --mode train's oracle-training phases
+    ontology = experiment.build_ontology(cfg)
+    torch.manual_seed(0)
+    base = experiment.build_model(cfg, ontology)
+    bench.init_weights(base)
+    base = base.to(device).train()
+    shape = argparse.Namespace(batch=args.batch, objects=args.nmax, ragged=0, hops=hops, workload="north_star", questions_per_image=1, share_scenes=1)
+    _, pbs = bench.build_batch(shape, 0, ontology, names, device)
+    variants, counts = {}, {}
+    for switch in switches:
+        os.environ["DFOL_RELATE_TRAIN"] = switch
+        for graphed in (False, True):
+            model = copy.deepcopy(base)
+            params = [p for p in model.parameters() if p.requires_grad]
+            opt = torch.optim.Adam(params, lr=1e-4, capturable=True)
+            bucket = parallel.GradBucket(params)
+            _lib.PATH_COUNTS.clear()
+            if graphed:
+                step = training.GraphedTrainStep(model, opt, pbs, 0.65, bucket=bucket, warmup=2)
+            else:
+                step = (lambda m, o, b: (lambda: training.train_batch(m, o, pbs, 0.65, bucket=b, sync_loss=False)))(model, opt, bucket)
+                step()
+                step()
+            torch.cuda.synchronize()
+            took = _lib.PATH_COUNTS.get("relate_train_one", 0)
+            assert (took > 0) == (switch == "1"), (switch, graphed, took)
+            variants[switch, graphed] = step
+            counts[switch, graphed] = took
+    order = [(s, g) for g in (False, True) for s in switches]
+    times = {k: [] for k in order}
+    rounds, n = max(4, args.rounds // 2), 4
+    for r in range(rounds):
+        for k in (order if r % 2 == 0 else order[::-1]):           # (who goes first alternates)
+            os.environ["DFOL_RELATE_TRAIN"] = k[0]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                variants[k]()
+            torch.cuda.synchronize()
+            times[k].append((time.perf_counter() - t0) / n * 1e6)
+    os.environ.pop("DFOL_RELATE_TRAIN", None)
+    lines = []
+    for k in order:
+        lines.append(_summary("train step, %s hops, %s, DFOL_RELATE_TRAIN %s" % (hops, "replayed" if k[1] else "eager", "set" if k[0] == "1" else "unset"),
+                              times[k], questions=args.batch, objects=args.nmax, rounds=rounds, steps_per_round=n,
+                              relate_train_one_hops_in_setup=counts[k]))
+    for graphed in (False, True) if len(switches) == 2 else ():
+        a, b = np.asarray(times["0", graphed]), np.asarray(times["1", graphed])
+        lines.append(json.dumps({"ratio": "train step, %s hops, %s: unset / set (medians)" % (hops, "replayed" if graphed else "eager"),
+                                 "value": float(np.median(a) / np.median(b)), "ranges_apart": bool(a.min() > b.max() or b.min() > a.max())}))
+        print(lines[-1], flush=True)
+    return lines
+
+
+def relate_train_legs(args):
+    """--relate-train-only: the launches, then the train step on the one-hop and on the ragged programs (--relate-train-unset: the step with the
+    switch unset alone, no launches - the form a tree from before the switch can run)."""
+    switches = ("0",) if args.relate_train_unset else ("0", "1")
+    lines = [] if args.relate_train_unset else relate_train_launches(args)
+    lines += relate_train_step(args, switches=switches) + relate_train_step(args, hops="ragged", switches=switches)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def gated_stream(args):
     """A stream of unseen gated batches (every batch collated afresh: no plan, no uploaded side array is reused) with DFOL_GATE_NATIVE=1 (the
     native executor; the plan is lowered at collate time, where a collate worker does it) against the same stream with the switch unset (the
@@ -446,6 +612,8 @@ def main():
     ap.add_argument("--out", default=None, help="--trainable-gate: also write the JSON lines to this file")
     ap.add_argument("--gate-train-only", action="store_true", help="--trainable-gate: only the two legs of the gated train step (DFOL_GATE_TRAIN)")
     ap.add_argument("--gate-bf16-only", action="store_true", help="--trainable-gate: only the leg of the one-launch gated Relate on bf16 tiles (DFOL_GATE_BF16)")
+    ap.add_argument("--relate-train-only", action="store_true", help="only the legs of the ungated train step's one-posterior Relate (DFOL_RELATE_TRAIN)")
+    ap.add_argument("--relate-train-unset", action="store_true", help="--relate-train-only: the train step with the switch unset alone")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--nmin", type=int, default=10)
     ap.add_argument("--nmax", type=int, default=100)
@@ -453,6 +621,8 @@ def main():
     ap.add_argument("--kinds", default=",".join(KINDS))
     ap.add_argument("--graph", type=int, default=1, help="1: also time the forward replayed as a captured HIP graph")
     args = ap.parse_args()
+    if args.relate_train_only:
+        return relate_train_legs(args)
     if args.trainable_gate:
         return trainable_gate_launches(args)
     device = torch.device("cuda", 0)
