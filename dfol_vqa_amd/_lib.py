@@ -214,6 +214,10 @@ SIGNATURES = {
     "dfol_clip_adam_f32": [_p, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _i32, _p, _f, _f, _f, _f, _f, _f, _f, _p, _p],
     "dfol_linear_wide_h2_f32": [_p, _i64, _p, _p, _p, _i64, _i32, _i32, _i32, _i32, _p],
     "dfol_linear_wide_rows_h2_f32": [_p, _i64, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _i32, _p],
+    "dfol_linear_wide_rows_bf16t_supported": [_i64, _i32, _i32, _i64],  # returns 0 / 1
+    "dfol_linear_wide_rows_bf16t_h2_f32": [_p, _i64, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _i32, _p],
+    "dfol_linear_wide_rows_bf16t_f16_h2_f32": [_p, _i64, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _p],
+    "dfol_store_bf16_is_f16": [_p, _i64, _p, _p],
     "dfol_pair_w2_f16x2_bytes": [_i32],
     "dfol_pair_pack_w2_f16x2": [_p, _i64, _i32, _i32, _p, _p],
     "dfol_pair_ll_h2_f32": [_p, _i64, _i32, _p, _i64, _p, _p, _p, _i32, _p, _i64, _p, _p, _p, _i32, _i32, _p, _p, _p, _i32, _i32, _f,
@@ -226,6 +230,8 @@ SIGNATURES = {
     "dfol_set_range_status": [_p],
     "dfol_set_feature_rows": [_p, _p],
     "dfol_set_feature_rows_bf16": [_p, _p],
+    "dfol_set_feature_rows_bf16_h2": [_p, _p],
+    "dfol_set_feature_rows_bf16_h2_f16": [_p, _p],
     "dfol_set_program_gates": [_p, _i32],
     "dfol_set_feature_cache": [_p, _i64, _i32, _p, _p],
     "dfol_pair_features_bwd_f32": [_p, _i64, _i32, _p, _p, _i32, _i32, _p, _i64, _p],
@@ -930,6 +936,46 @@ def linear_wide_rows(table, src_row, weight, bias, act, out=None):
         out = torch.empty(M, N, dtype=F32, device=table.device)
     call("dfol_linear_wide_rows_h2_f32", _dp(table), table.stride(0), _ptr(src_row, I32), _ptr(linear_pack_w_split(weight, False, 2), torch.bfloat16),
          _ptr(bias, F32, True), _dp(out), out.stride(0), M, N, K, act, _stream())
+    return out
+
+
+def store_bf16_direct():
+    """DFOL_STORE_BF16_DIRECT=1 (opt-in, read when a forward starts): the default arithmetic ("f16x2") reads a bf16 feature store's rows in place
+    on the inference route (linear_wide_rows_bf16t) instead of the gathered, widened matrix - the same bits.  Unset: every route as before."""
+    return os.environ.get("DFOL_STORE_BF16_DIRECT", "0") == "1"
+
+
+def linear_wide_rows_bf16t_supported(M, N, K, ld_table):
+    """dfol_linear_wide_rows_bf16t_supported: the wide kernel takes the shape and it pays (linear_wide_supported), over a bf16 table of row
+    stride ld_table (elements, a multiple of 4, at least K)."""
+    return bool(load().dfol_linear_wide_rows_bf16t_supported(int(M), int(N), int(K), int(ld_table)))
+
+
+def store_bf16_is_f16(table):
+    """dfol_store_bf16_is_f16: True when every element of the bfloat16 tensor `table` (contiguous) is finite and an fp16 value,
+    float(half(x)) == x - the certificate the two-product form of linear_wide_rows_bf16t stands on.  One pass over the table and a host wait."""
+    if table.dtype != torch.bfloat16 or not table.is_contiguous():
+        raise DfolError("store_bf16_is_f16: a contiguous bfloat16 tensor (got %s)" % table.dtype)
+    flag = torch.ones(1, dtype=I32, device=table.device)
+    call("dfol_store_bf16_is_f16", _dp(table), table.numel(), _ptr(flag, I32), _stream())
+    return bool(flag.item())
+
+
+def linear_wide_rows_bf16t(table, src_row, weight, bias, act, out=None, store=None):
+    """linear_wide over the indexed rows of a bf16 table: y[r] = act(table[src_row[r]] @ weight.T + bias), table [rows, K] bfloat16 (a bf16 feature
+    store's features as a matrix), src_row [M] int32, fp32 y, the packed weight image of linear_wide_rows.  Bit for bit
+    linear_wide(table.float()[src_row]) - the stored values are widened exactly and split in the kernel (csrc/dfol_dense_wide.hip, BF16T) - without
+    the widened copy, range report included.  Any M.  store: the DeviceFeatureStore whose table this is - a request for the two-product form,
+    which runs only when the store's certificate `f16_exact` holds (every value an fp16 value: the same bits); otherwise three products."""
+    M, K = src_row.numel(), table.shape[1]
+    N = weight.shape[0]
+    if weight.shape[1] != K or table.dtype != torch.bfloat16 or table.stride(1) != 1:
+        raise DfolError("linear_wide_rows_bf16t: table [rows, %d] bfloat16 with unit column stride, weight [N, %d]" % (K, K))
+    if out is None:
+        out = torch.empty(M, N, dtype=F32, device=table.device)
+    two = store is not None and bool(store.f16_exact)
+    call("dfol_linear_wide_rows_bf16t_f16_h2_f32", _dp(table), table.stride(0), _ptr(src_row, I32), _ptr(linear_pack_w_split(weight, False, 2), torch.bfloat16),
+         _ptr(bias, F32, True), _dp(out), out.stride(0), M, N, K, act, 1 if two else 0, _stream())
     return out
 
 

@@ -37,7 +37,16 @@ constexpr size_t WD_LDS = (size_t)6 * WD_TILE * 16 + 2 * WD_NMAX * 4 + 8 * 4096;
 // ROWS: row r of the product is row src_row[r] of X (dfol_linear_wide_rows_h2_f32: X is a feature store's table, src_row from dfol_store_rows_f32).
 // The index is read where a row's address is formed - at the start and at each block transition of load_x, never per k-step - and nothing
 // else differs: the instantiations without ROWS never touch src_row and compile to the code they had before it existed.
-template <int ACT, int XV, bool ROWS = false>
+// BF16T: X is a bf16 table (uint16_t elements behind the float pointer, ldx in elements; dfol_linear_wide_rows_bf16t_h2_f32 - a bf16 feature
+// store's table, in place of dfol_gather_object_rows_bf16_f32's widened matrix).  XV counts elements per load there: 8 - a step's 8 k of a
+// thread as one 16-byte load (rows 16-byte aligned and K % 8 == 0) - or 4 - two 8-byte loads, clamped as the fp32 form's two float4 loads
+// (rows 8-byte aligned; the K % 8 == 4 tail).  The ring holds WD_XD sets of 4 registers instead of 8; store_a widens them exactly
+// (dfol_widen) to the very floats the gathered matrix would hold and splits those as ever, so the bits are the matrix route's for every
+// table - the range report included.  Everything else is the one body; the instantiations without BF16T compile to the code they had.
+// TWO (with BF16T): the table is certified to hold fp16 values only (dfol_store_bf16_is_f16: every element finite and float(half(x)) == x), so
+// the low piece x - half(x) is +0 for every element: store_a writes the high piece only and the multiply runs xh wl, then xh wh.  The dropped
+// xl wh would have added exact zeros to accumulators that start at +0 and never hold -0 (weights are finite): the same bits.
+template <int ACT, int XV, bool ROWS = false, bool BF16T = false, bool TWO = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void wide_h2_kernel(
     const float* __restrict__ X, int64_t ldx, const u32x4* __restrict__ Wp, const float* __restrict__ bias, float* __restrict__ Y, int64_t ldy, int M,
     int N, int K, int ksteps, int nbn, uint32_t* __restrict__ status, const int32_t* __restrict__ src_row) {
@@ -59,26 +68,37 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         for (int j = 0; j < 8; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
 
     // ---- X rows: a ring of WD_XD register sets; the loader's position runs ahead of the multiplier's across block boundaries
-    float4 xa[WD_XD][2];
+    using XT = std::conditional_t<BF16T, uint16_t, float>;            // an element of X
+    using XR = std::conditional_t<BF16T, u32x2, float4>;               // four of them in registers
+    XR xa[WD_XD][2];
     int lb = first, lks = 0;
     const int r0 = min(lb * WD_BM + arow, M - 1);                      // (clamped: the index read stays inside src_row [M], the row inside X)
-    const float* xrow = X + (int64_t)(ROWS ? src_row[r0] : r0) * ldx + aq * 8;
+    const XT* xrow = reinterpret_cast<const XT*>(X) + (int64_t)(ROWS ? src_row[r0] : r0) * ldx + aq * 8;
     auto load_x = [&](auto set_tag) __attribute__((always_inline)) {
         constexpr int S = decltype(set_tag)::value;
         const int k = lks * WD_BK + aq * 8;
         const int c0 = min(k, K - 4) - aq * 8, c1 = min(k + 4, K - 4) - aq * 8;          // (K % 4 == 0; clamped, zeroed when used)
-        auto ld4 = [&](const float* p) __attribute__((always_inline)) {
-            if (XV == 4) return *reinterpret_cast<const float4*>(p);
-            const float2 lo = *reinterpret_cast<const float2*>(p), hi = *reinterpret_cast<const float2*>(p + 2);
-            return make_float4(lo.x, lo.y, hi.x, hi.y);
-        };
-        xa[S][0] = ld4(xrow + c0);
-        xa[S][1] = ld4(xrow + c1);
+        if constexpr (BF16T && XV == 8) {                              // (K % 8 == 0: a thread's 8 k are all inside the row or all past it)
+            const u32x4 v = *reinterpret_cast<const u32x4*>(xrow + min(k, K - 8) - aq * 8);
+            xa[S][0] = u32x2{v.x, v.y};
+            xa[S][1] = u32x2{v.z, v.w};
+        } else if constexpr (BF16T) {
+            xa[S][0] = *reinterpret_cast<const u32x2*>(xrow + c0);
+            xa[S][1] = *reinterpret_cast<const u32x2*>(xrow + c1);
+        } else {
+            auto ld4 = [&](const float* p) __attribute__((always_inline)) {
+                if (XV == 4) return *reinterpret_cast<const float4*>(p);
+                const float2 lo = *reinterpret_cast<const float2*>(p), hi = *reinterpret_cast<const float2*>(p + 2);
+                return make_float4(lo.x, lo.y, hi.x, hi.y);
+            };
+            xa[S][0] = ld4(xrow + c0);
+            xa[S][1] = ld4(xrow + c1);
+        }
         if (++lks == ksteps) {                                         // (uniform) on to the next block of this workgroup; past the last: clamped rows, never used
             lks = 0;
             lb += stride;
             const int64_t r = min((int64_t)lb * WD_BM + arow, (int64_t)M - 1);
-            xrow = X + (ROWS ? (int64_t)src_row[r] : r) * ldx + aq * 8;
+            xrow = reinterpret_cast<const XT*>(X) + (ROWS ? (int64_t)src_row[r] : r) * ldx + aq * 8;
         }
     };
     // ---- weight tiles: the two column blocks of a half, one half-step ahead in registers
@@ -106,7 +126,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int k = sks * WD_BK + aq * 8;
         const int at = A0 + buf * WD_TILE + arow * 4 + (aq ^ dfol_swz(arow));
         const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-        const float4 v0 = k < K ? xa[S][0] : z, v1 = k + 4 < K ? xa[S][1] : z;
+        auto f32 = [](const XR& v) __attribute__((always_inline)) {   // (a bf16 table: widened exactly)
+            if constexpr (BF16T) return dfol_widen(v); else return v;
+        };
+        const float4 v0 = k < K ? f32(xa[S][0]) : z, v1 = k + 4 < K ? f32(xa[S][1]) : z;
         xmax = fmaxf(fmaxf(xmax, fabsf(v0.x)), fabsf(v0.y));
         xmax = fmaxf(fmaxf(xmax, fabsf(v0.z)), fabsf(v0.w));
         xmax = fmaxf(fmaxf(xmax, fabsf(v1.x)), fabsf(v1.y));
@@ -114,7 +137,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         u32x4 ph, pl;
         dfol_split2hx8(v0, v1, ph, pl);
         wd_sm[at] = ph;
-        wd_sm[at + WD_BM * 4] = pl;
+        if constexpr (!TWO) wd_sm[at + WD_BM * 4] = pl;
         if (++sks == ksteps) sks = 0;
     };
 
@@ -127,7 +150,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int p = 0; p < 2; ++p) afr[i][p] = wd_sm[A0 + abuf * WD_TILE + aoff + p * WD_BM * 4 + i * 64];
+            for (int p = 0; p < (TWO ? 1 : 2); ++p) afr[i][p] = wd_sm[A0 + abuf * WD_TILE + aoff + p * WD_BM * 4 + i * 64];
     };
     auto multiply = [&](int bbuf, auto half_tag) __attribute__((always_inline)) {
         constexpr int JB = 4 * decltype(half_tag)::value;
@@ -138,7 +161,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
             for (int p = 0; p < 2; ++p) b[p] = wd_sm[bo + p * 128 * 4 + j * 64];
 #pragma unroll
-            for (int x = 0; x < 3; ++x)                                // (per accumulator the three products keep their order; its next MFMA is four issues on)
+            for (int x = TWO ? 1 : 0; x < 3; ++x)                          // (per accumulator the three products keep their order; its next MFMA is four issues on)
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
                     acc[i][JB + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, afr[i][PA3[x]]), __builtin_bit_cast(f16x8, b[PB3[x]]),
@@ -257,43 +280,72 @@ extern "C" int dfol_linear_wide_supported(int64_t M, int32_t N, int32_t K) {
     return on == 2 || 4 * blocks >= 3 * rounds * wd_cus();
 }
 
-// one launch path for both forms: src_row == nullptr is the plain product over X's own rows
-static int wd_launch(const char* name, const float* X, int64_t ldx, const int32_t* src_row, const void* W_split, const float* bias, float* Y, int64_t ldy,
-                     int32_t M, int32_t N, int32_t K, int32_t act, void* stream);
+// The same question for the rows of a bf16 table of row stride ld_table (elements): the shape above, and rows the 8-byte loads can take
+extern "C" int dfol_linear_wide_rows_bf16t_supported(int64_t M, int32_t N, int32_t K, int64_t ld_table) {
+    return dfol_linear_wide_supported(M, N, K) && ld_table % 4 == 0 && ld_table >= K ? 1 : 0;
+}
+
+// one launch path for all forms: src_row == nullptr is the plain product over X's own rows; bf16t: X is a bf16 table (ldx in elements)
+// (two: the two-product form for a bf16 table certified to hold fp16 values only)
+static int wd_launch(const char* name, const void* X, int64_t ldx, bool bf16t, bool two, const int32_t* src_row, const void* W_split, const float* bias,
+                     float* Y, int64_t ldy, int32_t M, int32_t N, int32_t K, int32_t act, void* stream);
 
 extern "C" int dfol_linear_wide_h2_f32(const float* X, int64_t ldx, const void* W_split, const float* bias, float* Y, int64_t ldy, int32_t M, int32_t N,
                                        int32_t K, int32_t act, void* stream) {
-    return wd_launch("linear_wide_h2", X, ldx, nullptr, W_split, bias, Y, ldy, M, N, K, act, stream);
+    return wd_launch("linear_wide_h2", X, ldx, false, false, nullptr, W_split, bias, Y, ldy, M, N, K, act, stream);
 }
 
 extern "C" int dfol_linear_wide_rows_h2_f32(const float* X_table, int64_t ld_table, const int32_t* src_row, const void* W_split, const float* bias,
                                             float* Y, int64_t ldy, int32_t M, int32_t N, int32_t K, int32_t act, void* stream) {
     DFOL_REQUIRE(src_row, "linear_wide_rows_h2: null pointer");
-    return wd_launch("linear_wide_rows_h2", X_table, ld_table, src_row, W_split, bias, Y, ldy, M, N, K, act, stream);
+    return wd_launch("linear_wide_rows_h2", X_table, ld_table, false, false, src_row, W_split, bias, Y, ldy, M, N, K, act, stream);
 }
 
-static int wd_launch(const char* name, const float* X, int64_t ldx, const int32_t* src_row, const void* W_split, const float* bias, float* Y, int64_t ldy,
-                     int32_t M, int32_t N, int32_t K, int32_t act, void* stream) {
+extern "C" int dfol_linear_wide_rows_bf16t_h2_f32(const void* X_table_bf16, int64_t ld_table, const int32_t* src_row, const void* W_split,
+                                                  const float* bias, float* Y, int64_t ldy, int32_t M, int32_t N, int32_t K, int32_t act, void* stream) {
+    DFOL_REQUIRE(src_row, "linear_wide_rows_bf16t_h2: null pointer");
+    return wd_launch("linear_wide_rows_bf16t_h2", X_table_bf16, ld_table, true, false, src_row, W_split, bias, Y, ldy, M, N, K, act, stream);
+}
+
+extern "C" int dfol_linear_wide_rows_bf16t_f16_h2_f32(const void* X_table_bf16, int64_t ld_table, const int32_t* src_row, const void* W_split,
+                                                      const float* bias, float* Y, int64_t ldy, int32_t M, int32_t N, int32_t K, int32_t act,
+                                                      int32_t table_is_f16, void* stream) {
+    DFOL_REQUIRE(src_row, "linear_wide_rows_bf16t_f16_h2: null pointer");
+    return wd_launch("linear_wide_rows_bf16t_f16_h2", X_table_bf16, ld_table, true, table_is_f16 != 0, src_row, W_split, bias, Y, ldy, M, N, K, act, stream);
+}
+
+static int wd_launch(const char* name, const void* X, int64_t ldx, bool bf16t, bool two, const int32_t* src_row, const void* W_split, const float* bias,
+                     float* Y, int64_t ldy, int32_t M, int32_t N, int32_t K, int32_t act, void* stream) {
     DFOL_REQUIRE(M > 0 && N > 256 && N <= WD_NMAX && K >= 4 * WD_BK && K % 4 == 0 && ldx % 2 == 0 && ldx >= K && ldy >= N,
                  "%s: bad sizes M=%d N=%d K=%d (256 < N <= 512, K >= 128, K %% 4, ldx %% 2)", name, M, N, K);
+    DFOL_REQUIRE(!bf16t || ldx % 4 == 0, "%s: a bf16 table's row stride %lld must be a multiple of 4 elements (8-byte rows)", name, (long long)ldx);
     DFOL_REQUIRE(X && W_split && Y, "%s: null pointer", name);
     DFOL_REQUIRE(((uintptr_t)X % 8 == 0) && ((uintptr_t)W_split % 16 == 0), "%s: X must be 8-byte and W_split 16-byte aligned", name);
-    const bool x16 = (uintptr_t)X % 16 == 0 && ldx % 4 == 0;
+    // 16-byte loads: four floats of a row, or the 8 bf16 of a thread's step (there K % 8 as well: the K % 8 == 4 tail goes by 8-byte loads)
+    const bool x16 = (uintptr_t)X % 16 == 0 && ldx % (bf16t ? 8 : 4) == 0 && (!bf16t || K % 8 == 0);
     const int ksteps = dfol_cdiv(K, WD_BK), nbn = dfol_cdiv(N, 128);
     const int grid = std::min(dfol_cdiv(M, WD_BM), wd_cus());
     uint32_t* status = dfol_range_status_ptr();
     hipStream_t st = (hipStream_t)stream;
-#define DFOL_WD_K(A, XVV, R)                                                                                                                \
+#define DFOL_WD_K(A, XVV, R, B, T)                                                                                                           \
     {                                                                                                                                      \
-        static const hipError_t ok = hipFuncSetAttribute((const void*)wide_h2_kernel<A, XVV, R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WD_LDS); \
+        static const hipError_t ok = hipFuncSetAttribute((const void*)wide_h2_kernel<A, XVV, R, B, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WD_LDS); \
         DFOL_REQUIRE(ok == hipSuccess, "%s: cannot reserve %zu bytes of LDS (%s)", name, WD_LDS, hipGetErrorString(ok));                    \
-        hipLaunchKernelGGL((wide_h2_kernel<A, XVV, R>), dim3(grid), dim3(512), WD_LDS, st, X, ldx, (const u32x4*)W_split, bias, Y, ldy, M, N, K, ksteps, \
-                           nbn, status, src_row);                                                                                          \
+        hipLaunchKernelGGL((wide_h2_kernel<A, XVV, R, B, T>), dim3(grid), dim3(512), WD_LDS, st, static_cast<const float*>(X), ldx, (const u32x4*)W_split, \
+                           bias, Y, ldy, M, N, K, ksteps, nbn, status, src_row);                                                           \
     }
 #define DFOL_WD_X(A, R)                                                                                                                     \
-    if (x16) DFOL_WD_K(A, 4, R) else DFOL_WD_K(A, 2, R)
+    if (x16) DFOL_WD_K(A, 4, R, false, false) else DFOL_WD_K(A, 2, R, false, false)
 #define DFOL_WD(A)                                                                                                                          \
-    if (src_row) { DFOL_WD_X(A, true) } else { DFOL_WD_X(A, false) }
+    if (bf16t && two) {                                                                                                                    \
+        if (x16) DFOL_WD_K(A, 8, true, true, true) else DFOL_WD_K(A, 4, true, true, true)                                                  \
+    } else if (bf16t) {                                                                                                                    \
+        if (x16) DFOL_WD_K(A, 8, true, true, false) else DFOL_WD_K(A, 4, true, true, false)                                                \
+    } else if (src_row) {                                                                                                                  \
+        DFOL_WD_X(A, true)                                                                                                                 \
+    } else {                                                                                                                               \
+        DFOL_WD_X(A, false)                                                                                                                \
+    }
     switch (act) {
         case DFOL_ACT_NONE: DFOL_WD(DFOL_ACT_NONE); break;
         case DFOL_ACT_SIGMOID: DFOL_WD(DFOL_ACT_SIGMOID); break;

@@ -127,6 +127,8 @@ static_assert(DFOL_PAIR_PACKED == 1 && DFOL_PAIR_BF16X3 == 2 && DFOL_PAIR_F16X2 
 thread_local const int32_t* g_feature_src_row = nullptr;
 thread_local const float* g_feature_box6 = nullptr;
 thread_local bool g_feature_rows_bf16 = false;                       // dfol_set_feature_rows_bf16: scene->features is a bf16 table
+thread_local bool g_feature_rows_f16 = false;                        // dfol_set_feature_rows_bf16_h2_f16: ... and the table is certified to hold fp16 values
+thread_local bool g_feature_rows_bf16_h2 = false;                    // dfol_set_feature_rows_bf16_h2: a bf16 table in front of a two-piece fp16 first layer
 // dfol_set_feature_cache: the cached form of the same (the featurizer's outputs instead of its inputs)
 struct FeatureCache {
     const float* cache;
@@ -153,7 +155,7 @@ extern "C" int dfol_set_feature_rows(const int32_t* src_row, const float* box6) 
     DFOL_REQUIRE((src_row == nullptr) == (box6 == nullptr), "set_feature_rows: src_row and box6 come together");
     g_feature_src_row = src_row;
     g_feature_box6 = box6;
-    g_feature_rows_bf16 = false;
+    g_feature_rows_bf16 = g_feature_rows_bf16_h2 = g_feature_rows_f16 = false;
     return 0;
 }
 
@@ -162,6 +164,26 @@ extern "C" int dfol_set_feature_rows_bf16(const int32_t* src_row, const float* b
     g_feature_src_row = src_row;
     g_feature_box6 = box6;
     g_feature_rows_bf16 = src_row != nullptr;
+    g_feature_rows_bf16_h2 = g_feature_rows_f16 = false;
+    return 0;
+}
+
+extern "C" int dfol_set_feature_rows_bf16_h2(const int32_t* src_row, const float* box6) {
+    DFOL_REQUIRE((src_row == nullptr) == (box6 == nullptr), "set_feature_rows_bf16_h2: src_row and box6 come together");
+    g_feature_src_row = src_row;
+    g_feature_box6 = box6;
+    g_feature_rows_bf16 = false;
+    g_feature_rows_bf16_h2 = src_row != nullptr;
+    g_feature_rows_f16 = false;
+    return 0;
+}
+
+extern "C" int dfol_set_feature_rows_bf16_h2_f16(const int32_t* src_row, const float* box6) {
+    DFOL_REQUIRE((src_row == nullptr) == (box6 == nullptr), "set_feature_rows_bf16_h2_f16: src_row and box6 come together");
+    g_feature_src_row = src_row;
+    g_feature_box6 = box6;
+    g_feature_rows_bf16 = false;
+    g_feature_rows_bf16_h2 = g_feature_rows_f16 = src_row != nullptr;
     return 0;
 }
 
@@ -178,10 +200,10 @@ extern "C" int dfol_run_program(const DfolProgramModel* model, const DfolProgram
                                 const void* blob, void* workspace, void* stream) {
     const int32_t* src_row = g_feature_src_row;                      // (taken and cleared first: an early return must not leave it to the next batch)
     const float* box6 = g_feature_box6;
-    const bool rows_bf16 = g_feature_rows_bf16;
+    const bool rows_bf16 = g_feature_rows_bf16, rows_bf16_h2 = g_feature_rows_bf16_h2, rows_f16 = g_feature_rows_f16;
     g_feature_src_row = nullptr;
     g_feature_box6 = nullptr;
-    g_feature_rows_bf16 = false;
+    g_feature_rows_bf16 = g_feature_rows_bf16_h2 = g_feature_rows_f16 = false;
     const FeatureCache cached = g_feature_cache;
     g_feature_cache = FeatureCache{nullptr, 0, 0, nullptr, nullptr};
     const float* gates = g_gate_table;
@@ -223,6 +245,20 @@ extern "C" int dfol_run_program(const DfolProgramModel* model, const DfolProgram
                                      (long long)scene->ld_features, layer.kind);
                         rc = dfol_linear_act_rows_bf16t_f32(scene->features, scene->ld_features, src_row, layer.packed, layer.bias,
                                                             static_cast<float*>(at(workspace, a[6])), a[7], M, layer.N, layer.K, layer.act, stream);
+                        break;
+                    }
+                    if (rows_bf16_h2) {                             // a bf16 table in front of the default arithmetic: split in place, the matrix route's bits
+                        DFOL_REQUIRE(layer.kind == DFOL_DENSE_F16X2,
+                                     "run_program[%d]: a scene in bf16 index form for the two-piece fp16 product (dfol_set_feature_rows_bf16_h2) needs a "
+                                     "DFOL_DENSE_F16X2 first layer, this one is of kind %d: dfol_set_feature_rows_bf16 serves a DFOL_DENSE_BF16 layer, every "
+                                     "other arithmetic takes the gathered matrix", i, layer.kind);
+                        DFOL_REQUIRE(a[4] == 0 && layer.packed != nullptr && dfol_linear_wide_rows_bf16t_supported(M, layer.N, layer.K, scene->ld_features),
+                                     "run_program[%d]: a scene in bf16 index form (dfol_set_feature_rows_bf16_h2) needs a first layer of a shape "
+                                     "dfol_linear_wide_rows_bf16t_supported takes (M %d N %d K %d ld %lld): hand over the gathered matrix", i, M, layer.N, layer.K,
+                                     (long long)scene->ld_features);
+                        rc = dfol_linear_wide_rows_bf16t_f16_h2_f32(scene->features, scene->ld_features, src_row, layer.packed, layer.bias,
+                                                                    static_cast<float*>(at(workspace, a[6])), a[7], M, layer.N, layer.K, layer.act,
+                                                                    rows_f16 ? 1 : 0, stream);
                         break;
                     }
                     DFOL_REQUIRE(a[4] == 0 && layer.kind == DFOL_DENSE_F16X2 && layer.packed != nullptr && dfol_linear_wide_supported(M, layer.N, layer.K),

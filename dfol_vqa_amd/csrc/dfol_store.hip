@@ -155,6 +155,20 @@ __global__ __launch_bounds__(RB_THREADS) void round_bf16_kernel(const float* __r
     }
 }
 
+// The certificate of a bf16 table whose every value is an fp16 value (dfol_store_bf16_is_f16): a grid-stride pass that clears *flag (set to
+// a non-zero value by the caller) when an element is not finite or does not survive the conversion to fp16 and back.  Such a table's low
+// fp16 piece is +0 everywhere, which is what the wide kernel's two-product form stands on (csrc/dfol_dense_wide.hip, TWO).
+__global__ __launch_bounds__(RB_THREADS) void bf16_is_f16_kernel(const uint16_t* __restrict__ t, int64_t n, uint32_t* __restrict__ flag) {
+    const int64_t step = (int64_t)gridDim.x * RB_THREADS;
+    bool bad = false;
+    for (int64_t i = (int64_t)blockIdx.x * RB_THREADS + threadIdx.x; i < n; i += step) {
+        const float x = __uint_as_float((uint32_t)t[i] << 16);
+        const float back = (float)(_Float16)x;                        // (inf beyond 65504, NaN stays NaN)
+        bad |= !(fabsf(x) <= 65504.0f) || !(back == x);
+    }
+    if (bad) atomicAnd(flag, 0u);
+}
+
 // grid (I, row slices of SR_THREADS): thread (i, j) writes row obj_off[i] + j - its table row and (W, H, x1, y1, x2 - x1, y2 - y1), the gather's own
 // six values by the gather's own subtractions
 constexpr int SR_THREADS = 128;
@@ -266,6 +280,20 @@ extern "C" int dfol_store_round_bf16(const float* src, int64_t n, void* dst, voi
     blocks = blocks < 8192 ? blocks : 8192;
     hipLaunchKernelGGL(round_bf16_kernel, dim3((unsigned)blocks), dim3(RB_THREADS), 0, (hipStream_t)stream, src, n, static_cast<uint16_t*>(dst));
     DFOL_LAUNCH_CHECK("store_round_bf16");
+    return 0;
+}
+
+extern "C" int dfol_store_bf16_is_f16(const void* table_bf16, int64_t n, void* flag_out, void* stream) {
+    DFOL_REQUIRE(n >= 0, "store_bf16_is_f16: bad size n=%lld", (long long)n);
+    DFOL_REQUIRE(flag_out, "store_bf16_is_f16: null pointer");
+    if (n == 0) return 0;
+    DFOL_REQUIRE(table_bf16, "store_bf16_is_f16: null pointer");
+    DFOL_REQUIRE((uintptr_t)table_bf16 % 2 == 0 && (uintptr_t)flag_out % 4 == 0, "store_bf16_is_f16: the table must be 2-byte and the flag 4-byte aligned");
+    int64_t blocks = (n + RB_THREADS - 1) / RB_THREADS;
+    blocks = blocks < 8192 ? blocks : 8192;
+    hipLaunchKernelGGL(bf16_is_f16_kernel, dim3((unsigned)blocks), dim3(RB_THREADS), 0, (hipStream_t)stream, static_cast<const uint16_t*>(table_bf16), n,
+                       static_cast<uint32_t*>(flag_out));
+    DFOL_LAUNCH_CHECK("store_bf16_is_f16");
     return 0;
 }
 

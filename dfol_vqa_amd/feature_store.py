@@ -19,7 +19,11 @@ A store built with `feature_dtype="bf16"` (which implies the index form too) hol
 dense kernels' own rounding (dfol_store_round_bf16): half the memory.  In the bf16 arithmetic (`mlp_math: bf16`) the featurizer's first product
 and its weight gradient round every feature that way before they multiply, so there they read the table in place (dfol_linear_act_rows_bf16t_f32,
 dfol_linear_wgrad_bias_rows_bf16t) and no result bit changes; every other consumer gets the `[O, F + 6]` fp32 matrix of the ROUNDED features
-(dfol_gather_object_rows_bf16_f32) - reduced precision outside the bf16 arithmetic, never a default.
+(dfol_gather_object_rows_bf16_f32) - reduced precision outside the bf16 arithmetic, never a default.  With DFOL_STORE_BF16_DIRECT=1 (opt-in,
+read when a forward starts) the default arithmetic's inference reads the table in place as well: the wide kernel widens each stored value
+exactly and splits it into the two fp16 pieces the matrix route would have built (dfol_linear_wide_rows_bf16t_h2_f32), so the matrix is never
+written and no result bit changes - still on the ROUNDED features; a store whose every value is an fp16 value (`f16_exact`, one pass over the
+table on first use) gets the two-product form of that kernel, again with the same bits; a featurizer that trains and every other arithmetic keep the matrix.
 
 Three kinds of object, by who may hold them:
   DeviceFeatureStore   main process only: the device tensors, `gather`.  Registers itself by id in this process' table.
@@ -274,6 +278,7 @@ class DeviceFeatureStore(object):
         self.S, self.max_obj, self.F = S, max_obj, F
         self.featurized = bool(featurized)
         self.feature_dtype = feature_dtype
+        self._f16_exact = None                             # (the certificate of a bf16 table, computed on first use: `f16_exact`)
         self.direct = bool(direct) or self.featurized or bf16
         self._featurized = FeaturizedRows()
         self.cache_nbytes = 0                              # (the cache of featurize(), beside `nbytes` of chunk data)
@@ -282,6 +287,16 @@ class DeviceFeatureStore(object):
         self.nbytes = S * lay.row_bytes
         self.resident_chunks = len(base) - 1
         _STORES[self.id] = self
+
+    @property
+    def f16_exact(self):
+        """A bf16 store's certificate that every feature it holds is finite and an fp16 value (dfol_store_bf16_is_f16): the wide kernel's
+        two-product form then gives the three-product bits.  Computed on first use - under DFOL_STORE_BF16_DIRECT=1 when the first batch's rows
+        are resolved, never at construction - and cached: the table does not change after upload.  False for an fp32 store.  Not inside a
+        stream capture (it waits for the device)."""
+        if self._f16_exact is None:
+            self._f16_exact = self.feature_dtype == "bf16" and self.features is not None and _lib.store_bf16_is_f16(self.features)
+        return self._f16_exact
 
     def upload_index(self, ref):
         """The ref's index arrays on the device, checked against the store first (the kernel trusts them): -> int32 [slot (I) | obj_off (I + 1)].
@@ -404,6 +419,8 @@ class DeviceFeatureStore(object):
         out=: an existing StoreRows of this store with the same image and object counts, rewritten in place - how the owner of a captured forward
         serves a new scene BETWEEN replays: like upload_index, not inside a stream capture.  index=: an earlier upload_index(ref)."""
         check_row_space(self.S, self.max_obj)
+        if self.feature_dtype == "bf16" and self._f16_exact is None and _lib.store_bf16_direct():
+            self.f16_exact                                 # (the certificate, here and not in a forward: a captured one cannot wait for the device)
         O, I = int(ref.counts.sum(dtype=np.int64)), len(ref.slots)
         idx = self.upload_index(ref) if index is None else index
         if idx.numel() != 2 * I + 1:

@@ -52,20 +52,27 @@ def store_layers_of(net, F, M, bf16_ld=None):
     (dfol_linear_wide_supported) - else (None, why not).  ONE predicate for the direct route (M = the batch's rows), the executor and the store's
     cache builder (M = its row block).  bf16_ld: the store's table is bfloat16 with this row stride (feature_dtype="bf16") - then the question is
     the bf16 arithmetic's: `mlp_math: bf16`, whose first product rounds a feature to the value the table holds, on a weight of the split
-    kernels' size, any M (dfol_linear_rows_bf16t_supported)."""
+    kernels' size, any M (dfol_linear_rows_bf16t_supported).  With DFOL_STORE_BF16_DIRECT=1 a bf16 table also says yes to the two-piece fp16
+    arithmetic of a featurizer that does not train, where the wide kernel splits the table's rows in place
+    (dfol_linear_wide_rows_bf16t_supported: the fp32 table's question and rows the kernel can load); the dense arithmetic tells the two apart."""
     from . import _lib, native_exec
     if net is None or getattr(net, "_network", None) is None or not hasattr(net, "output_width"):
         return None, "the featurizer has no network"
     layers = native_exec._layers(net._network)
     if not layers:
         return None, "the featurizer network is not a chain of Linear layers and activations (or a Dropout is active)"
-    want = "f16x2" if bf16_ld is None else "bf16"
+    h2 = bf16_ld is not None and _lib.store_bf16_direct() and _lib._dense_math() == "f16x2" and not featurizer_trains(net)
+    want = "f16x2" if bf16_ld is None or h2 else "bf16"
     if _lib._dense_math() != want:
         return None, "the dense arithmetic is %r, not %r" % (_lib._dense_math(), want)
     w = layers[0][0].weight
     N, K = w.shape
     if K != F:
         return None, "the featurizer's first layer takes %d features, the store holds %d" % (K, F)
+    if h2:
+        if N * K < _lib.SPLIT_MIN_WEIGHT or w.stride(1) != 1 or not _lib.linear_wide_rows_bf16t_supported(M, N, K, bf16_ld):
+            return None, "the wide kernel does not take a %d -> %d product over %d rows of a bf16 table of row stride %d" % (K, N, M, bf16_ld)
+        return layers, None
     if bf16_ld is not None:
         if N * K < _lib.SPLIT_MIN_WEIGHT or w.stride(1) != 1 or not _lib.linear_rows_bf16t_supported(N, K, bf16_ld):
             return None, "the bf16 mode's tiled kernel does not take a %d -> %d product over a bf16 table of row stride %d" % (K, N, bf16_ld)
@@ -138,13 +145,19 @@ class BatchGQABoxFeaturizer(nn.Module):
                 D = net.output_width() + 4
                 obj = torch.empty(rows.O, D, dtype=torch.float32, device=device)
                 x = None
-                first = _lib.linear_wide_rows if getattr(rows, "bf16_ld", None) is None else _lib.linear_rows_bf16t       # (a bf16 table: the bf16 mode's product)
+                # (a bf16 table: the bf16 mode's product, or - DFOL_STORE_BF16_DIRECT=1 - the default arithmetic's over the table's own rows)
+                bf16_h2 = getattr(rows, "bf16_ld", None) is not None and _lib._dense_math() == "f16x2"      # (what store_layers_of admitted)
+                certified = bf16_h2 and rows.store._f16_exact is True                                       # (two products: the same bits)
+                first = _lib.linear_wide_rows if getattr(rows, "bf16_ld", None) is None else \
+                    (_lib.linear_wide_rows_bf16t if bf16_h2 else _lib.linear_rows_bf16t)
                 for k, (lin, act) in enumerate(layers):
                     out = obj[:, :D - 4] if k == len(layers) - 1 else None
-                    x = first(rows.table, rows.src_row, lin.weight, lin.bias, act, out) if k == 0 else \
+                    x = first(rows.table, rows.src_row, lin.weight, lin.bias, act, out, **({"store": rows.store} if certified else {})) if k == 0 else \
                         L.linear_act(x, lin.weight, lin.bias, act, out)
                 L.box_positions(rows.box6, obj, D - 4)
                 _lib.note("feature_store_direct")
+                if bf16_h2:
+                    _lib.note("feature_store_direct_bf16_h2")
                 return self._with_pairs(obj, D, rows.O, world_geometry)
             layers = self._store_train_layers(objects_list)
             if layers is not None:

@@ -315,6 +315,7 @@ def run(model, program_batch, plan, queue, give_answer=True):
     device = feats.device
     nm = native_model(model)
     rows = cache = None
+    bf16_h2 = False
     if hasattr(feats, "materialize") and getattr(feats.store, "featurized", False):
         # A featurized store's batch: the featurizer's rows come from the store's cache (built on first use, rebuilt once per weight version) -
         # the question BatchGQABoxFeaturizer._cached_objects asks; the executor skips the featurizer's products (dfol_set_feature_cache).
@@ -328,14 +329,19 @@ def run(model, program_batch, plan, queue, give_answer=True):
         # A direct feature store's batch (feature_store.StoreRows).  The plan is lowered as for any batch; where the featurizer's first product
         # is one the wide kernel takes - the question BatchGQABoxFeaturizer._store_layers asks - the executor reads the store's rows in place
         # (dfol_set_feature_rows), otherwise it gets the gathered matrix.  A bf16 store's batch likewise where the model's first featurizer layer
-        # is the bf16 mode's and store_layers_of admits it (dfol_set_feature_rows_bf16).
+        # is the bf16 mode's and store_layers_of admits it (dfol_set_feature_rows_bf16) - or, with DFOL_STORE_BF16_DIRECT=1, the default
+        # arithmetic's and store_layers_of admits that (dfol_set_feature_rows_bf16_h2): the one predicate answers for the layer's own kind.
         first = nm.struct.featurizer[0]
         if getattr(feats, "bf16_ld", None) is not None:
             from .interpreter import store_layers_of
-            if feats.O and first.kind == DENSE_BF16 and \
+            math = _lib._dense_math()
+            if feats.O and math in ("bf16", "f16x2") and first.kind == (DENSE_BF16 if math == "bf16" else DENSE_F16X2) and \
                     store_layers_of(model._featurizer._featurizer_network, feats.store.F, feats.O, feats.bf16_ld)[0] is not None:
                 rows = feats
+                bf16_h2 = first.kind == DENSE_F16X2
                 _lib.note("feature_store_direct")
+                if bf16_h2:
+                    _lib.note("feature_store_direct_bf16_h2")
             else:
                 feats = feats.materialize()
                 _lib.note("feature_store_direct_materialized")
@@ -363,8 +369,10 @@ def run(model, program_batch, plan, queue, give_answer=True):
         _lib.call("dfol_set_feature_cache", cache.data_ptr(), cache.stride(0), cache.shape[1], rows.src_row.data_ptr(), rows.box6.data_ptr())
     elif rows is not None:
         sc.features, sc.ld_features, sc.raw_cols, sc.O = rows.table.data_ptr(), rows.table.stride(0), rows.shape[1], plan.scene["O"]
-        _lib.call("dfol_set_feature_rows" if getattr(rows, "bf16_ld", None) is None else "dfol_set_feature_rows_bf16", rows.src_row.data_ptr(),
-                  rows.box6.data_ptr())                                                            # (picked up, and cleared, by the call below)
+        setter = "dfol_set_feature_rows" if getattr(rows, "bf16_ld", None) is None else \
+            ("dfol_set_feature_rows_bf16" if not bf16_h2 else
+             "dfol_set_feature_rows_bf16_h2_f16" if rows.store._f16_exact is True else "dfol_set_feature_rows_bf16_h2")
+        _lib.call(setter, rows.src_row.data_ptr(), rows.box6.data_ptr())                           # (picked up, and cleared, by the call below)
     else:
         sc.features, sc.ld_features, sc.raw_cols, sc.O = feats.data_ptr(), feats.stride(0), feats.shape[1], plan.scene["O"]
     sc.NS, sc.max_n = plan.scene["NS"], plan.scene["max_n"]

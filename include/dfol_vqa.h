@@ -56,7 +56,9 @@ extern "C" {
  * struct grows: the gate table travels beside the call, as dfol_set_feature_rows' arrays do), and the one-posterior gated Relate of the train
  * step: dfol_relate_keep_gate_fwd_f32 and dfol_relate_keep_gate_bwd_f32, and the one-posterior gated Relate on bf16 tiles:
  * dfol_relate_one_gate_fwd_bf16 and DFOL_TILE_BF16 as DFOL_OP_RELATE_ONE_GATE's tile dtype (an older library refuses that operand), and the
- * one-posterior Relate of the ungated train step: dfol_relate_keep_fwd_f32 and dfol_relate_keep_bwd_f32;
+ * one-posterior Relate of the ungated train step: dfol_relate_keep_fwd_f32 and dfol_relate_keep_bwd_f32, and the default arithmetic over a bf16
+ * table in place: dfol_linear_wide_rows_bf16t_supported, dfol_linear_wide_rows_bf16t_h2_f32 and dfol_set_feature_rows_bf16_h2, with
+ * dfol_store_bf16_is_f16, dfol_linear_wide_rows_bf16t_f16_h2_f32 and dfol_set_feature_rows_bf16_h2_f16 for a table of fp16 values;
  * a caller that needs them checks for the symbol, and a table that names an opcode an older library lacks is refused by it ("unknown opcode"). */
 #define DFOL_ABI_VERSION 3
 
@@ -405,6 +407,27 @@ int dfol_linear_wide_h2_f32(const float* X, int64_t ldx, const void* W_split, co
  * it takes every M (the caller asks dfol_linear_wide_supported whether the shape pays). */
 int dfol_linear_wide_rows_h2_f32(const float* X_table, int64_t ld_table, const int32_t* src_row, const void* W_split, const float* bias, float* Y,
                                  int64_t ldy, int32_t M, int32_t N, int32_t K, int32_t act, void* stream);
+/* The same over the indexed rows of a BF16 table (a feature store built with feature_dtype="bf16"; ld_table in elements): it replaces
+ * dfol_gather_object_rows_bf16_f32 followed by dfol_linear_wide_h2_f32 over the widened [M, K + 6] matrix.  The kernel widens each stored value
+ * exactly to the float that matrix would hold and splits it into the same two fp16 pieces, so results - NaN included - and the
+ * DFOL_RANGE_X_OVERFLOW report are bit for bit that route's, for every table.  The W_split image is dfol_linear_pack_w_f16x2's, unchanged.
+ * A thread's 8 consecutive k of a step are one 16-byte load when the table is 16-byte aligned, ld_table % 8 == 0 and K % 8 == 0, two 8-byte
+ * loads otherwise.  Refused before any launch, with a message: null pointers, sizes dfol_linear_wide_h2_f32 refuses, ld_table % 4 != 0 or
+ * ld_table < K, a table that is not 8-byte aligned.  Every M is taken; dfol_linear_wide_rows_bf16t_supported says 1 when
+ * dfol_linear_wide_supported(M, N, K) does and the table's rows can be read (ld_table % 4 == 0, ld_table >= K). */
+int dfol_linear_wide_rows_bf16t_supported(int64_t M, int32_t N, int32_t K, int64_t ld_table);
+int dfol_linear_wide_rows_bf16t_h2_f32(const void* X_table_bf16, int64_t ld_table, const int32_t* src_row, const void* W_split, const float* bias,
+                                       float* Y, int64_t ldy, int32_t M, int32_t N, int32_t K, int32_t act, void* stream);
+/* The same with a flag: table_is_f16 != 0 promises that dfol_store_bf16_is_f16 certified the table (every element finite and an fp16 value), and
+ * the kernel then runs TWO products, xh wl and xh wh: the low piece of every element is +0, and the dropped xl wh would have added exact zeros
+ * (weights finite), so the bits are dfol_linear_wide_rows_bf16t_h2_f32's.  table_is_f16 == 0 is that entry point, three products.  It replaces
+ * nothing: a faster form of the entry above for a certified table.  A false promise is not detected (results then differ in the last bits). */
+int dfol_linear_wide_rows_bf16t_f16_h2_f32(const void* X_table_bf16, int64_t ld_table, const int32_t* src_row, const void* W_split, const float* bias,
+                                           float* Y, int64_t ldy, int32_t M, int32_t N, int32_t K, int32_t act, int32_t table_is_f16, void* stream);
+/* The certificate: clears the device word *flag_out (4 bytes, set non-zero by the caller beforehand) if any of the n bf16 elements is not finite
+ * or fails float(half(x)) == x - values beyond 65504, and values below 2^-14 whose low significand bits fp16's subnormals cannot hold.  One
+ * grid-stride pass, plain vector atomics; n == 0 returns without a launch. */
+int dfol_store_bf16_is_f16(const void* table_bf16, int64_t n, void* flag_out, void* stream);
 
 /* The bf16 mode of the same kernel (BASELINE configs[3] "bf16 fwd / fp32 logic"; config key `mlp_math: bf16`): both operands rounded to
  * bf16 (nearest even), ONE product per operand pair, fp32 accumulation, fp32 output.  NOT the reference's numerics (relative error
@@ -1100,6 +1123,14 @@ int dfol_set_feature_rows(const int32_t* src_row, const float* box6);
  * DFOL_OP_DENSE runs dfol_linear_act_rows_bf16t_f32 - it must be a DFOL_DENSE_BF16 layer that dfol_linear_rows_bf16t_supported takes; any other
  * layer kind is refused - and DFOL_OP_BOX_POSITIONS reads box6.  Either setting replaces the other. */
 int dfol_set_feature_rows_bf16(const int32_t* src_row, const float* box6);
+/* A bf16 table in front of the DEFAULT arithmetic: the source-0 DFOL_OP_DENSE runs dfol_linear_wide_rows_bf16t_h2_f32 (in place of the gathered
+ * fp32 matrix and dfol_linear_wide_h2_f32 over it - the same bits) - it must be a DFOL_DENSE_F16X2 layer of a shape
+ * dfol_linear_wide_rows_bf16t_supported(O, N, K, ld_features) takes; any other layer is refused with the reason - and DFOL_OP_BOX_POSITIONS
+ * reads box6.  Each of the three settings replaces the others. */
+int dfol_set_feature_rows_bf16_h2(const int32_t* src_row, const float* box6);
+/* The same for a table that dfol_store_bf16_is_f16 certified: the product is dfol_linear_wide_rows_bf16t_f16_h2_f32 with its flag set (two
+ * products, the same bits).  Conditions and refusals as dfol_set_feature_rows_bf16_h2. */
+int dfol_set_feature_rows_bf16_h2_f16(const int32_t* src_row, const float* box6);
 /* The same for a scene whose featurizer output is CACHED (a frozen featurizer; dfol_store_objects_f32): the NEXT dfol_run_program of the calling
  * thread runs no featurizer product - every DFOL_OP_DENSE of set 0 is skipped, scene->features is not read and may be NULL - and its
  * DFOL_OP_BOX_POSITIONS writes the whole object matrix: cache rows src_row [O] of cache [rows, ld_cache] (W = the instruction's pos_col columns,

@@ -31,7 +31,12 @@ layer reads the table in place - dfol_linear_act_rows_bf16t_f32, dfol_linear_wgr
 (`direct=False`), alternating in one session; beside the replayed step and the weight gradient it times the first product with what runs in
 front of it (dfol_store_rows_f32 + the row kernel against the gather + dfol_linear_act_bf16_f32) and reports both stores' bytes.
 
-usage: python tools/bench_feature_store.py [--leg stream|train|bf16] [--images 2048] [--objects 100] [--features 2048] [--batch 256] [--batches 24] [--runs 4]
+`--leg bf16-direct` is inference in the DEFAULT arithmetic over the bf16 store, DFOL_STORE_BF16_DIRECT unset against set, alternating in one
+process: the featurizer's first product with what runs in front of it (dfol_gather_object_rows_bf16_f32 + dfol_linear_wide_h2_f32 over the
+widened matrix against dfol_store_rows_f32 + dfol_linear_wide_rows_bf16t_h2_f32 over the table), the rate of `--batches` unseen batches
+(collated on the host beforehand; upload, forward and read-back are timed), the peak device memory of a pass, and "same bits" for each pair.
+
+usage: python tools/bench_feature_store.py [--leg stream|train|bf16|bf16-direct] [--images 2048] [--objects 100] [--features 2048] [--batch 256] [--batches 24] [--runs 4]
                                            [--workers 5] [--steps 20]
 """
 import argparse
@@ -249,10 +254,160 @@ def train_leg(args, bf16=False):
             "routes": counts}
 
 
+def bf16_direct_leg(args):
+    """The default arithmetic over a bf16 store, DFOL_STORE_BF16_DIRECT unset against set (see the module's docstring) -> the result dictionary."""
+    from dfol_vqa_amd import _lib
+    import bench
+    device = torch.device("cuda", 0)
+    tmp = tempfile.mkdtemp(prefix="dfol_store_bf16_direct_bench_")
+    os.environ.pop("DFOL_STORE_BF16_DIRECT", None)
+    try:
+        paths, names = syn.write_synthetic_ontology(os.path.join(tmp, "ontology"))
+        cfg = syn.reference_config(paths, box_features_dim=args.features)
+        ontology = experiment.build_ontology(cfg)
+        torch.manual_seed(0)
+        model = experiment.build_model(cfg, ontology)
+        bench.init_weights(model)
+        model = model.to(device).eval()
+        chunks, info_path, _ = write_corpus(tmp, args.images, args.objects, args.features, args.per_chunk)
+        store = data.DeviceFeatureStore(tmp, "objs", chunks, info_path, device, feature_dtype="bf16")
+        with open(paths["attribute_file"]) as f:
+            cats = json.load(f)
+        rng = np.random.RandomState(9)
+        host = []
+        for b in range(args.batches):                        # every batch other programs on other images
+            qs = syn.full_size_questions(KINDS[b % len(KINDS)], args.batch, args.objects, args.objects, names, cats, 7000 + b, with_scene=False)
+            for q in qs:
+                q["image_id"] = "img%05d" % rng.randint(args.images)
+            pbs = data.BatchGQABoxFeaturesCollator(tmp, "objs", chunks, info_path, ontology, 1, device_store=store.index).collate(qs)
+            for pb in pbs:
+                pb.create_sparse_tensors()
+            host.append((pbs, [q["image_id"] for q in qs]))
+
+        def kernel_ms(fn, n=20):
+            for _ in range(3):
+                fn()
+            evs = []
+            for _ in range(n):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                evs.append((a, b))
+            torch.cuda.synchronize()
+            return float(np.median([a.elapsed_time(b) for a, b in evs]))
+
+        # the first product with what runs in front of it, on the first batch's rows
+        first = [m for m in model._featurizer._featurizer_network._network if isinstance(m, torch.nn.Linear)][0]
+        ref = store.index.ref(host[0][1])
+        idx = store.upload_index(ref)
+        rows = store.rows(ref)
+        mat = torch.empty(rows.O, args.features + 6, device=device)
+        y, act = torch.empty(rows.O, first.out_features, device=device), _lib.ACT_SIGMOID
+        wide = load_wide(_lib, rows.O, first.out_features, args.features)
+
+        def by_matrix():                                     # dfol_gather_object_rows_bf16_f32 + dfol_linear_wide_h2_f32 over the matrix
+            store.gather(ref, out=mat, index=idx)
+            _lib.linear_wide(mat[:, :args.features], first.weight, first.bias, act, out=y)
+
+        def by_rows():                                       # dfol_store_rows_f32 + dfol_linear_wide_rows_bf16t_h2_f32
+            store.rows(ref, out=rows, index=idx)
+            _lib.linear_wide_rows_bf16t(rows.table, rows.src_row, first.weight, first.bias, act, out=y)
+        by_matrix()
+        y0 = y.clone()
+        y.fill_(-1.0)
+        by_rows()
+        product_same = bool(torch.equal(y0.view(torch.int32), y.view(torch.int32)))
+        # (c) the two-product form on a CERTIFIED table: a copy of the store's table with every magnitude below 2^-10 set to zero (random
+        # features hold a few values below 2^-17 whose low bits fp16 cannot keep); against the three-product kernel on the same copy
+        class Certified(object):
+            f16_exact = True
+        store_certifies = bool(store.f16_exact)
+        tab_c = rows.table.clone()
+        tab_c[tab_c.float().abs() < 2.0 ** -10] = 0
+        assert _lib.store_bf16_is_f16(tab_c)
+
+        def by_rows_c3():
+            store.rows(ref, out=rows, index=idx)
+            _lib.linear_wide_rows_bf16t(tab_c, rows.src_row, first.weight, first.bias, act, out=y)
+
+        def by_rows_c2():
+            store.rows(ref, out=rows, index=idx)
+            _lib.linear_wide_rows_bf16t(tab_c, rows.src_row, first.weight, first.bias, act, out=y, store=Certified)
+        by_rows_c3()
+        y0 = y.clone()
+        y.fill_(-1.0)
+        by_rows_c2()
+        two_same = bool(torch.equal(y0.view(torch.int32), y.view(torch.int32)))
+        product = {"matrix": [], "rows": [], "rows_c3": [], "rows_c2": []}
+        for _ in range(args.runs):
+            product["matrix"].append(kernel_ms(by_matrix))
+            product["rows"].append(kernel_ms(by_rows))
+            product["rows_c3"].append(kernel_ms(by_rows_c3))
+            product["rows_c2"].append(kernel_ms(by_rows_c2))
+        del mat, y, y0, tab_c
+
+        # unseen batches: upload (to_cuda resolves the batch's ref from the store), forward, answers read back; the host collation is outside
+        def run(on):
+            if on:
+                os.environ["DFOL_STORE_BF16_DIRECT"] = "1"
+            else:
+                os.environ.pop("DFOL_STORE_BF16_DIRECT", None)
+            before = dict(_lib.PATH_COUNTS)
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            lps = []
+            t0 = time.perf_counter()
+            with torch.no_grad():
+                for pbs, _ in host:
+                    res = model([pb.to_cuda(device) for pb in pbs], False)
+                    lps.append(res["log_probability"])
+            torch.cuda.synchronize()
+            s = time.perf_counter() - t0
+            peak = torch.cuda.max_memory_allocated() - base
+            counts = {k: _lib.PATH_COUNTS.get(k, 0) - before.get(k, 0)
+                      for k in ("feature_store_direct", "feature_store_direct_bf16_h2", "feature_store_direct_materialized", "native_program")}
+            return args.batches * args.batch / s, peak, counts, torch.cat([lp.flatten() for lp in lps])
+        rate, peak, counts, lp = {}, {}, {}, {}
+        for on in (False, True):                             # (warm-up: plans, packed weights, allocator)
+            run(on)
+        rate = {False: [], True: []}
+        for _ in range(args.runs):
+            for on in (False, True):
+                r, peak[on], counts[on], lp[on] = run(on)
+                rate[on].append(r)
+        os.environ.pop("DFOL_STORE_BF16_DIRECT", None)
+        forward_same = bool(torch.equal(lp[False].view(torch.int32), lp[True].view(torch.int32)))
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    a, b = span(product["matrix"]), span(product["rows"])
+    off, on = span(rate[False]), span(rate[True])
+    return {"tool": "bench_feature_store", "leg": "bf16-direct",
+            "shape": {"images": args.images, "objects": args.objects, "features": args.features, "batch": args.batch, "rows": rows.O,
+                      "batches": args.batches, "runs": args.runs, "wide_kernel_takes_the_shape": bool(wide)},
+            "first_product_ms": {"a_gather_bf16_and_wide_over_the_matrix": a, "b_store_rows_and_in_place_three_products": b,
+                                 "b_vs_a": apart(b, a), "same_bits": product_same,
+                                 "b_on_the_certified_copy": span(product["rows_c3"]), "c_in_place_two_products_on_the_certified_copy": span(product["rows_c2"]),
+                                 "c_vs_b_on_the_same_copy": apart(span(product["rows_c2"]), span(product["rows_c3"])), "c_same_bits_as_b": two_same,
+                                 "the_random_store_itself_certifies": store_certifies,
+                                 "caveat": "every sample launches on the same rows back to back: the bf16 routes' 105 MB fit the 256 MB last-level "
+                                           "cache between launches, route (a)'s matrix traffic does not - a stream of unseen batches has no such help"},
+            "unseen_batches_questions_per_s": {"switch_off": off, "switch_on": on,
+                                               "on_vs_off": "faster, ranges apart" if on["min"] > off["max"] else
+                                               "slower, ranges apart" if on["max"] < off["min"] else "ranges overlap: no difference shown",
+                                               "same_bits": forward_same},
+            "peak_bytes_of_a_pass": {"switch_off": peak[False], "switch_on": peak[True], "on_minus_off": peak[True] - peak[False]},
+            "matrix_bytes": rows.O * (args.features + 6) * 4, "store_bytes": store.nbytes,
+            "routes": {"switch_off": counts[False], "switch_on": counts[True]}}
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("stream", "train", "bf16"), default="stream",
-                    help="the stream of unseen inference batches, replayed train steps, or the train leg in mlp_math: bf16 over the bf16 store")
+    ap.add_argument("--leg", choices=("stream", "train", "bf16", "bf16-direct"), default="stream",
+                    help="the stream of unseen inference batches, replayed train steps, the train leg in mlp_math: bf16 over the bf16 store, or the "
+                         "default arithmetic's inference over the bf16 store with DFOL_STORE_BF16_DIRECT unset and set")
     ap.add_argument("--steps", type=int, default=20, help="--leg train: replays per timed run")
     ap.add_argument("--images", type=int, default=2048)
     ap.add_argument("--objects", type=int, default=100)
@@ -265,6 +420,9 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_feature_store: needs a GPU (there is no CPU form of this measurement)")
+    if args.leg == "bf16-direct":
+        print(json.dumps(bf16_direct_leg(args)))
+        return
     if args.leg in ("train", "bf16"):
         print(json.dumps(train_leg(args, bf16=args.leg == "bf16")))
         return
