@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/dfol_vqa.h"
 
 #define DFOL_EPS 1e-20f          // util.py:25
@@ -179,3 +181,18 @@ __device__ __forceinline__ void bf16x8_to_f32(const uint4 w, float (&l)[8]) {
 }
 
 static inline int dfol_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// ---- host: lanes per row of the wavefront-per-predicate kernels -------------------------------------------------------------------
+// A row of `groups` 16-byte column groups is covered by LPR lanes, LPR the smallest power of two >= groups (at most MAX_LPR, 32 or 64: the
+// bf16 kernels own eight columns per lane and stop at 32).  launch(std::integral_constant<int, LPR>) gets it as a compile-time value.
+template <int MAX_LPR = 64, class Launch>
+static inline void dfol_dispatch_lpr(int groups, Launch&& launch) {
+    static_assert(MAX_LPR == 32 || MAX_LPR == 64, "dfol_dispatch_lpr: the ladders end at 32 or 64");
+    if (groups <= 1) launch(std::integral_constant<int, 1>{});
+    else if (groups <= 2) launch(std::integral_constant<int, 2>{});
+    else if (groups <= 4) launch(std::integral_constant<int, 4>{});
+    else if (groups <= 8) launch(std::integral_constant<int, 8>{});
+    else if (groups <= 16) launch(std::integral_constant<int, 16>{});
+    else if (MAX_LPR == 32 || groups <= 32) launch(std::integral_constant<int, 32>{});
+    else if constexpr (MAX_LPR == 64) launch(std::integral_constant<int, 64>{});
+}

@@ -216,6 +216,8 @@ extern "C" int dfol_filter_fwd_f32(const float* att_in, const float* ll, const i
 // element, which measured 7 % FASTER than an unmasked instantiation with the diagonal's term taken out afterwards); padding rows and
 // columns get P = 0.
 template <int LPR> struct RelateUnroll { static constexpr int value = LPR == 64 ? 4 : LPR == 32 ? 5 : LPR == 16 ? 3 : LPR == 8 ? 2 : 1; };
+// row batches in flight in relate_one_fwd_kernel (its UNR)
+template <int LPR> struct RelateOneUnroll { static constexpr int value = LPR >= 16 ? 4 : LPR == 8 ? 2 : 1; };
 
 template <int LPR, bool WR, bool WC>
 __device__ __forceinline__ bool relate_exists_fast(const float* __restrict__ tp, const float* __restrict__ pR,
@@ -742,17 +744,9 @@ extern "C" int dfol_relate_fwd_f32(const float* prior_s, const float* prior_o, c
         DFOL_LAUNCH_CHECK("relate_fwd (NS > 256)");
         return 0;
     }
-    const int groups = NS / 4;
-#define DFOL_RELATE_CASE(L)                                                                                                   \
-    launch_relate<L>(st, pR, pC, tile, pred_q, n_obj, qR, qC, neg, any_neg, active, want, bR, bC, P, NS, flags, oR, oC)
-    if (groups <= 1) DFOL_RELATE_CASE(1);
-    else if (groups <= 2) DFOL_RELATE_CASE(2);
-    else if (groups <= 4) DFOL_RELATE_CASE(4);
-    else if (groups <= 8) DFOL_RELATE_CASE(8);
-    else if (groups <= 16) DFOL_RELATE_CASE(16);
-    else if (groups <= 32) DFOL_RELATE_CASE(32);
-    else DFOL_RELATE_CASE(64);
-#undef DFOL_RELATE_CASE
+    dfol_dispatch_lpr(NS / 4, [&](auto lpr) {
+        launch_relate<decltype(lpr)::value>(st, pR, pC, tile, pred_q, n_obj, qR, qC, neg, any_neg, active, want, bR, bC, P, NS, flags, oR, oC);
+    });
     DFOL_LAUNCH_CHECK("relate_fwd");
     return 0;
 }
@@ -986,18 +980,11 @@ extern "C" int dfol_relate_one_fwd_f32(const float* x_att, const float* prev_att
         DFOL_LAUNCH_CHECK("relate_one_fwd (NS > 256)");
         return 0;
     }
-    const int groups = NS / 4;
-#define DFOL_REL1(L, U)                                                                                                       \
-    hipLaunchKernelGGL((relate_one_fwd_kernel<L, U>), dim3(dfol_cdiv(P, 4)), dim3(256), 0, st, x_att, prev_att, tile, pred_q, n_obj, \
-                       quant_prev, neg, any_neg, active, P, NS, lone_forall_identity, post)
-    if (groups <= 1) DFOL_REL1(1, 1);
-    else if (groups <= 2) DFOL_REL1(2, 1);
-    else if (groups <= 4) DFOL_REL1(4, 1);
-    else if (groups <= 8) DFOL_REL1(8, 2);
-    else if (groups <= 16) DFOL_REL1(16, 4);
-    else if (groups <= 32) DFOL_REL1(32, 4);
-    else DFOL_REL1(64, 4);
-#undef DFOL_REL1
+    dfol_dispatch_lpr(NS / 4, [&](auto lpr) {
+        constexpr int L = decltype(lpr)::value;
+        hipLaunchKernelGGL((relate_one_fwd_kernel<L, RelateOneUnroll<L>::value>), dim3(dfol_cdiv(P, 4)), dim3(256), 0, st, x_att, prev_att, tile,
+                           pred_q, n_obj, quant_prev, neg, any_neg, active, P, NS, lone_forall_identity, post);
+    });
     DFOL_LAUNCH_CHECK("relate_one_fwd");
     return 0;
 }
@@ -1317,18 +1304,10 @@ extern "C" int dfol_relate_keep_fwd_f32(const float* x_att, const float* prev_at
         DFOL_LAUNCH_CHECK("relate_keep_fwd (NS > 256)");
         return 0;
     }
-    const int groups = NS / 4;
-#define DFOL_RELK(L)                                                                                                                  \
-    hipLaunchKernelGGL(relate_keep_fwd_kernel<L>, dim3(dfol_cdiv(P, 4)), dim3(256), 0, st, x_att, prev_att, tile, pred_q, n_obj, quant_prev, \
-                       x_is_subject, neg, any_neg, active, P, NS, lone_forall_identity, post)
-    if (groups <= 1) DFOL_RELK(1);
-    else if (groups <= 2) DFOL_RELK(2);
-    else if (groups <= 4) DFOL_RELK(4);
-    else if (groups <= 8) DFOL_RELK(8);
-    else if (groups <= 16) DFOL_RELK(16);
-    else if (groups <= 32) DFOL_RELK(32);
-    else DFOL_RELK(64);
-#undef DFOL_RELK
+    dfol_dispatch_lpr(NS / 4, [&](auto lpr) {
+        hipLaunchKernelGGL(relate_keep_fwd_kernel<decltype(lpr)::value>, dim3(dfol_cdiv(P, 4)), dim3(256), 0, st, x_att, prev_att, tile, pred_q, n_obj,
+                           quant_prev, x_is_subject, neg, any_neg, active, P, NS, lone_forall_identity, post);
+    });
     DFOL_LAUNCH_CHECK("relate_keep_fwd");
     return 0;
 }
@@ -1449,17 +1428,10 @@ extern "C" int dfol_relate_one_fwd_bf16(const float* x_att, const float* prev_at
     DFOL_REQUIRE(x_att && prev_att && tile && pred_q && n_obj && quant_prev && post, "relate_one_fwd_bf16: null pointer");
     DFOL_REQUIRE(!any_neg || neg, "relate_one_fwd_bf16: any_neg set but neg is NULL");
     hipStream_t st = (hipStream_t)stream;
-    const int groups = NS / 8;
-#define DFOL_REL1B(L)                                                                                                          \
-    hipLaunchKernelGGL((relate_one_bf16_kernel<L>), dim3(dfol_cdiv(P, 4)), dim3(256), 0, st, x_att, prev_att, tile, pred_q, n_obj, \
-                       quant_prev, neg, any_neg, active, P, NS, lone_forall_identity, post)
-    if (groups <= 1) DFOL_REL1B(1);
-    else if (groups <= 2) DFOL_REL1B(2);
-    else if (groups <= 4) DFOL_REL1B(4);
-    else if (groups <= 8) DFOL_REL1B(8);
-    else if (groups <= 16) DFOL_REL1B(16);
-    else DFOL_REL1B(32);
-#undef DFOL_REL1B
+    dfol_dispatch_lpr<32>(NS / 8, [&](auto lpr) {
+        hipLaunchKernelGGL(relate_one_bf16_kernel<decltype(lpr)::value>, dim3(dfol_cdiv(P, 4)), dim3(256), 0, st, x_att, prev_att, tile, pred_q, n_obj,
+                           quant_prev, neg, any_neg, active, P, NS, lone_forall_identity, post);
+    });
     DFOL_LAUNCH_CHECK("relate_one_fwd_bf16");
     return 0;
 }
@@ -1547,18 +1519,14 @@ extern "C" int dfol_quantify_fwd_f32(const float* att, const float* quant, const
     DFOL_REQUIRE(att && quant && pred_q && n_obj && lp, "quantify_fwd: null pointer");
     hipStream_t st = (hipStream_t)stream;
     const int groups = NS / 4;
-#define DFOL_QUANT4(L)                                                                                                                  \
-    hipLaunchKernelGGL(quantify_fwd4_kernel<L>, dim3(dfol_cdiv(P, 4 * QUANT_UNR * (64 / L))), dim3(256), 0, st, att, quant, pred_q, n_obj, P, NS, lp)
     if (NS % 4 != 0 || groups > 64)
         hipLaunchKernelGGL(quantify_fwd_kernel, dim3(dfol_cdiv(P, 4)), dim3(256), 0, st, att, quant, pred_q, n_obj, P, NS, lp);
-    else if (groups <= 1) DFOL_QUANT4(1);
-    else if (groups <= 2) DFOL_QUANT4(2);
-    else if (groups <= 4) DFOL_QUANT4(4);
-    else if (groups <= 8) DFOL_QUANT4(8);
-    else if (groups <= 16) DFOL_QUANT4(16);
-    else if (groups <= 32) DFOL_QUANT4(32);
-    else DFOL_QUANT4(64);
-#undef DFOL_QUANT4
+    else
+        dfol_dispatch_lpr(groups, [&](auto lpp) {
+            constexpr int L = decltype(lpp)::value;
+            hipLaunchKernelGGL(quantify_fwd4_kernel<L>, dim3(dfol_cdiv(P, 4 * QUANT_UNR * (64 / L))), dim3(256), 0, st, att, quant, pred_q, n_obj, P, NS,
+                               lp);
+        });
     DFOL_LAUNCH_CHECK("quantify_fwd");
     return 0;
 }

@@ -18,6 +18,18 @@
 // Backward: the formulas as written, clamps included (zero gradient below a floor), recomputed from the inputs.  The parameter
 // gradient is a sum over every element of the launch: per-thread sums -> wavefront (shuffles) -> workgroup (LDS, wavefront order) ->
 // one row of a scratch buffer per workgroup -> a second kernel adds the rows in a fixed order.  No atomics: two runs give the same bits.
+//
+// Layout of the Relate family.  Every forward kernel computes, for one predicate, one or two aggregations of the same shape
+//     post[i] = G_out( F( agg_{j < n, j != i} F( G_in(l'[.], pv[j]) ) ), xv[i] ),     F and agg by the quantifier of the summed-out axis j,
+// described by a GatePred record (whose prior is summed out, whose is kept, the two gates, quantifier, negation).  The kernels differ only in
+// which axis of the tile j runs along and in the tile's number format, and are put together from
+//     gate_col_sweep   j along rows, NS <= 256: the aggregates stay in a lane's registers                     (fp32: 4 columns per lane, bf16: 8)
+//     gate_row_put / gate_row_finish   j along columns, NS <= 256: group reduction per row into the wavefront's LDS row, outer gate per row
+//     gate_big_cols / gate_big_rows   the same two directions for NS > 256, a workgroup per predicate
+// The two-posterior kernel relate_gate_fwd_kernel keeps its own fused loop (one tile load and one e^l' serve both directions) around the
+// element step and the two tails.  relate_keep_gate_fwd_kernel is written out on its own: built from the shared sweeps it computed the same
+// bits 2 - 3 % slower (profiles/r23_gate_refactor.txt).  The backward kernels share the record and the parameter-sum epilogue; their sweeps
+// are their own.
 #include "dfol_common.h"
 
 namespace {
@@ -103,10 +115,24 @@ __device__ __forceinline__ void gate_bwd(const GateW& G, float a, float b, float
     db = xb;
 }
 
+// A predicate's negation: alpha_n = 1 for a negated predicate of a launch that has any, cn = 1 - 2 alpha_n
+struct GateNeg {
+    int any_neg;
+    float alpha_n, cn;
+};
+
+__device__ __forceinline__ GateNeg gate_neg_load(const uint8_t* __restrict__ neg, int any_neg, int p) {
+    GateNeg N;
+    N.any_neg = any_neg;
+    N.alpha_n = (any_neg && neg[p]) ? 1.f : 0.f;
+    N.cn = 1.f - 2.f * N.alpha_n;
+    return N;
+}
+
 // l' = negation(min(ll, 0)) (batch_base_ops.py:194, :212-213) and its derivative
-__device__ __forceinline__ float gate_prep(float ll, int any_neg, float alpha_n, float cn) {
+__device__ __forceinline__ float gate_prep(float ll, const GateNeg& N) {
     float v = fminf(ll, 0.f);
-    if (any_neg) v = dfol_pnot(v, alpha_n, cn);
+    if (N.any_neg) v = dfol_pnot(v, N.alpha_n, N.cn);
     return v;
 }
 
@@ -115,19 +141,34 @@ __device__ __forceinline__ float gate_dpnot(float x, float alpha, float c) {
     return d > DFOL_EPS ? c * e / d : 0.f;
 }
 
-__device__ __forceinline__ float gate_dprep(float ll, int any_neg, float alpha_n, float cn) {
+__device__ __forceinline__ float gate_dprep(float ll, const GateNeg& N) {
     float d = ll < 0.f ? 1.f : 0.f;
-    if (any_neg) d *= gate_dpnot(fminf(ll, 0.f), alpha_n, cn);
+    if (N.any_neg) d *= gate_dpnot(fminf(ll, 0.f), N.alpha_n, N.cn);
     return d;
+}
+
+// The quantifier of a summed-out axis: kf = 1 - 2 qf, ex = EXISTS, ident = a lone predicate's literal FOR_ALL branch (:104-108)
+struct GateQuant {
+    float qf, kf;
+    bool ex, ident;
+};
+
+__device__ __forceinline__ GateQuant gate_quant_load(const float* __restrict__ quant, int p, int identity_forall) {
+    GateQuant Q;
+    Q.qf = quant[p];
+    Q.kf = 1.f - 2.f * Q.qf;
+    Q.ex = Q.qf == 1.f;
+    Q.ident = identity_forall && Q.qf == 0.f;
+    return Q;
 }
 
 // One inner term of an aggregation from m = e^G: EXISTS keeps the probability (complement form), otherwise F(G) = log(max(q + k m, eps))
 // (FOR_ALL: log m = G itself, also in the lone predicate's literal branch, :104-108)
-__device__ __forceinline__ float gate_term(float m, bool ex, float q, float k) { return ex ? m : dfol_slog(fmaf(k, m, q)); }
+__device__ __forceinline__ float gate_term(float m, const GateQuant& Q) { return Q.ex ? m : dfol_slog(fmaf(Q.kf, m, Q.qf)); }
 __device__ __forceinline__ float gate_join(float acc, float t, bool ex) { return ex ? dfol_or(acc, t) : acc + t; }
 // the aggregate after the outer transform (:129-133): a log-probability
-__device__ __forceinline__ float gate_outer(float agg, bool ex, bool ident, float q, float k) {
-    return ex ? dfol_slog(agg) : (ident ? agg : dfol_pnot(agg, q, k));
+__device__ __forceinline__ float gate_outer(float agg, const GateQuant& Q) {
+    return Q.ex ? dfol_slog(agg) : (Q.ident ? agg : dfol_pnot(agg, Q.qf, Q.kf));
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -147,11 +188,11 @@ __global__ __launch_bounds__(256) void filter_gate_fwd_kernel(const float* __res
     const float av[4] = {a4.x, a4.y, a4.z, a4.w}, l[4] = {l4.x, l4.y, l4.z, l4.w};
     float o[4];
     const bool act = active == nullptr || active[p];
-    const float alpha = (any_neg && neg[p]) ? 1.f : 0.f, cc = 1.f - 2.f * alpha;
+    const GateNeg N = gate_neg_load(neg, any_neg, p);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         o[j] = av[j];                                                         // no-op token: the prior row (:385)
-        if (act) o[j] = gate_log(G, gate_prep(l[j], any_neg, alpha, cc), av[j]);      // :135-136
+        if (act) o[j] = gate_log(G, gate_prep(l[j], N), av[j]);               // :135-136
         if (c0 + j >= n) o[j] = 0.f;
     }
     *reinterpret_cast<float4*>(att_out + idx * 4) = make_float4(o[0], o[1], o[2], o[3]);
@@ -179,11 +220,11 @@ __global__ __launch_bounds__(FG_THREADS) void filter_gate_bwd_kernel(const float
         if (c < n) {
             const float g = g_out[i];
             if (active == nullptr || active[p]) {
-                const float alpha = (any_neg && neg[p]) ? 1.f : 0.f, cc = 1.f - 2.f * alpha;
+                const GateNeg N = gate_neg_load(neg, any_neg, p);
                 const float raw = ll[i];
                 float da;
-                gate_bwd(G, gate_prep(raw, any_neg, alpha, cc), att_in[(int64_t)q * NS + c], g, true, da, dp, acc);
-                dl = da * gate_dprep(raw, any_neg, alpha, cc);
+                gate_bwd(G, gate_prep(raw, N), att_in[(int64_t)q * NS + c], g, true, da, dp, acc);
+                dl = da * gate_dprep(raw, N);
             } else {
                 dp = g;                                                       // posterior = prior
             }
@@ -223,118 +264,211 @@ __global__ __launch_bounds__(64) void gate_param_reduce_kernel(const float* __re
 }
 
 // ---------------------------------------------------------------------------------------------------
-// relate (arity 2), NS <= 256: one wavefront per predicate tile, the geometry of relate_fwd_kernel (a lane owns four consecutive columns,
-// LPR lanes cover a row, 64 / LPR rows per iteration).  Rows = variable R, columns = variable C:
-//   post_R[r] = G_R( F_C( sum_{c != r} F_C( G_C(l'[r,c], prior_C[c]) ) ), prior_R[r] )        row aggregates (cross-lane)
-//   post_C[c] = G_C( F_R( sum_{r != c} F_R( G_R(l'[r,c], prior_R[r]) ) ), prior_C[c] )        column aggregates (in-register)
+// relate (arity 2): the predicate record
 // ---------------------------------------------------------------------------------------------------
-template <int LPR>
-__global__ __launch_bounds__(256) void relate_gate_fwd_kernel(
-    const float* __restrict__ prior_R, const float* __restrict__ prior_C, const float* __restrict__ tile,
-    const int32_t* __restrict__ pred_q, const int32_t* __restrict__ n_obj, const float* __restrict__ quant_R,
-    const float* __restrict__ quant_C, const uint8_t* __restrict__ neg, int any_neg, const uint8_t* __restrict__ active,
-    const uint8_t* __restrict__ want, int want_R_bit, int want_C_bit, int P, int NS, int flags,
-    const float* __restrict__ gate_R, const float* __restrict__ gate_C, float* __restrict__ post_R, float* __restrict__ post_C) {
-    constexpr int RPI = 64 / LPR;
-    __shared__ float row_agg[4][256];
-    const int wave_in_block = threadIdx.x >> 6;
-    const int p = blockIdx.x * 4 + wave_in_block;
-    if (p >= P) return;
-    const int lane = threadIdx.x & 63;
+// One aggregation of one predicate: post[i] = G_out( F( agg_{j < n, j != i} F( G_in(l'[.], pv[j]) ) ), xv[i] ), F and agg by Q.
+template <class TileT = float>
+struct GatePred {
+    int q, n, NS;
+    const float* pv;          // the summed-out variable's attention (rows of question q)
+    const float* xv;          // the kept variable's attention
+    const TileT* tp;          // the predicate's NS x NS tile
+    float* out;
+    bool xs;                  // single posterior: the kept variable is the subject (axis 0)
+    GateNeg N;
+    GateQuant Q;
+    GateW GI, GO;             // inner gate: the summed-out axis', outer gate: the kept axis'
+};
+
+// The single-posterior kernels' record.  x = the freshly selected variable (kept), prev = the incoming one (summed out).  The two axes hold
+// different gates, so the launch says which axis x is on: x_is_subject[p] -> x on axis 0 (outer gate = gate_s, inner gate = gate_o), else x
+// on axis 1 (outer = gate_o, inner = gate_s).  False for a no-op predicate (a question without this operator): its gates and quantifier are
+// not read.  `post` may be NULL (backward).
+template <class TileT>
+__device__ __forceinline__ bool gate_pred_load(GatePred<TileT>& g, int p, const float* __restrict__ x_att, const float* __restrict__ prev_att,
+                                               const TileT* __restrict__ tile, const int32_t* __restrict__ pred_q, const int32_t* __restrict__ n_obj,
+                                               const float* __restrict__ quant_prev, const uint8_t* __restrict__ x_is_subject,
+                                               const uint8_t* __restrict__ neg, int any_neg, const uint8_t* __restrict__ active, int NS,
+                                               int identity_forall, const float* __restrict__ gate_s, const float* __restrict__ gate_o,
+                                               float* __restrict__ post) {
+    g.q = pred_q[p];
+    g.n = min(n_obj[g.q], NS);
+    g.NS = NS;
+    g.pv = prev_att + (int64_t)g.q * NS;
+    g.xv = x_att + (int64_t)p * NS;
+    g.tp = tile + (int64_t)p * NS * NS;
+    g.out = post ? post + (int64_t)p * NS : nullptr;
+    if (active && !active[p]) return false;
+    g.xs = x_is_subject[p] != 0;
+    g.GI = gate_load(g.xs ? gate_o : gate_s);
+    g.GO = gate_load(g.xs ? gate_s : gate_o);
+    g.N = gate_neg_load(neg, any_neg, p);
+    g.Q = gate_quant_load(quant_prev, p, identity_forall);
+    return true;
+}
+
+// the no-op predicate of a single-posterior kernel: attention passes through (as relate_one_fwd_kernel); stride = the threads on the predicate
+template <class TileT>
+__device__ __forceinline__ void gate_passthrough(const GatePred<TileT>& g, int tid, int stride) {
+    for (int c = tid; c < g.NS; c += stride) g.out[c] = c < g.n ? g.pv[c] : 0.f;
+}
+
+// The two-posterior kernels' records.  Rows = variable R, columns = variable C:
+//   vR:  post_R[r] = G_R( F_C( agg_{c != r} F_C( G_C(l'[r,c], prior_C[c]) ) ), prior_R[r] )        summed out along columns
+//   vC:  post_C[c] = G_C( F_R( agg_{r != c} F_R( G_R(l'[r,c], prior_R[r]) ) ), prior_C[c] )        summed out along rows
+// Writes what needs no arithmetic - a no-op predicate's posterior = prior (batch_base_ops.py:563-564), zeros for a posterior nobody wants -
+// and returns false when nothing is left to compute.
+__device__ __forceinline__ bool gate_pred_load2(GatePred<>& vR, GatePred<>& vC, bool& wantR, bool& wantC, int p, const float* __restrict__ prior_R,
+                                                const float* __restrict__ prior_C, const float* __restrict__ tile,
+                                                const int32_t* __restrict__ pred_q, const int32_t* __restrict__ n_obj,
+                                                const float* __restrict__ quant_R, const float* __restrict__ quant_C, const uint8_t* __restrict__ neg,
+                                                int any_neg, const uint8_t* __restrict__ active, const uint8_t* __restrict__ want, int want_R_bit,
+                                                int want_C_bit, int NS, int flags, const float* __restrict__ gate_R, const float* __restrict__ gate_C,
+                                                float* __restrict__ post_R, float* __restrict__ post_C, int tid, int stride) {
     const int q = pred_q[p];
     const int n = min(n_obj[q], NS);
     const int wbits = want ? want[p] : 3;
-    const bool wantR = (wbits & want_R_bit) && post_R;
-    const bool wantC = (wbits & want_C_bit) && post_C;
+    wantR = (wbits & want_R_bit) && post_R;
+    wantC = (wbits & want_C_bit) && post_C;
     const float* pR = prior_R + (int64_t)q * NS;
     const float* pC = prior_C + (int64_t)q * NS;
     float* oR = post_R ? post_R + (int64_t)p * NS : nullptr;
     float* oC = post_C ? post_C + (int64_t)p * NS : nullptr;
-
-    if (active && !active[p]) {                         // no-op predicate: posterior = prior (batch_base_ops.py:563-564)
-        for (int c = lane; c < NS; c += 64) {
+    if (active && !active[p]) {
+        for (int c = tid; c < NS; c += stride) {
             if (oR) oR[c] = (wantR && c < n) ? pR[c] : 0.f;
             if (oC) oC[c] = (wantC && c < n) ? pC[c] : 0.f;
         }
-        return;
+        return false;
     }
     if (!wantR && oR)
-        for (int c = lane; c < NS; c += 64) oR[c] = 0.f;
+        for (int c = tid; c < NS; c += stride) oR[c] = 0.f;
     if (!wantC && oC)
-        for (int c = lane; c < NS; c += 64) oC[c] = 0.f;
-    if (!wantR && !wantC) return;
-
+        for (int c = tid; c < NS; c += stride) oC[c] = 0.f;
+    if (!wantR && !wantC) return false;
     const GateW GR = gate_load(gate_R), GC = gate_load(gate_C);
     const int identity_forall = flags & DFOL_RELATE_LONE_FORALL_IDENTITY;
-    const int cg = lane % LPR, rs = lane / LPR, c0 = cg * 4, cl = min(c0, NS - 4);
-    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
-    const float qR = quant_R[p], qC = quant_C[p], kR = 1.f - 2.f * qR, kC = 1.f - 2.f * qC;
-    const bool exR = qR == 1.f, exC = qC == 1.f;
-    const bool idR = identity_forall && qR == 0.f, idC = identity_forall && qC == 0.f;
+    const GateNeg N = gate_neg_load(neg, any_neg, p);
     const float* tp = tile + (int64_t)p * NS * NS;
+    vR = {q, n, NS, pC, pR, tp, oR, false, N, gate_quant_load(quant_C, p, identity_forall), GC, GR};
+    vC = {q, n, NS, pR, pC, tp, oC, false, N, gate_quant_load(quant_R, p, identity_forall), GR, GC};
+    return true;
+}
 
-    // this lane's four columns: prior, its exponential, its share of the six pre-activations (once per wavefront)
-    const float4 pc4 = *reinterpret_cast<const float4*>(pC + cl);
-    const float pc[4] = {pc4.x, pc4.y, pc4.z, pc4.w};
-    float zbC[4][6], ebC[4];
+// ---------------------------------------------------------------------------------------------------
+// relate forward, NS <= 256: one wavefront per predicate.  A lane owns CPL consecutive columns (one 16-byte load: four floats, or eight bf16
+// widened exactly), LPR lanes cover a row, 64 / LPR rows per iteration; lanes beyond the width read valid columns (cl) and rows beyond n read
+// row n - 1, and both are masked.  Padding and self-relations contribute nothing (:112).  An element costs six sigmoids and one e^l'.
+// ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void load_cols(const float* __restrict__ a, float (&l)[4]) {
+    const float4 t = *reinterpret_cast<const float4*>(a);
+    l[0] = t.x, l[1] = t.y, l[2] = t.z, l[3] = t.w;
+}
+__device__ __forceinline__ void load_cols(const uint16_t* __restrict__ a, float (&l)[8]) { bf16x8_to_f32(*reinterpret_cast<const uint4*>(a), l); }
+
+// the inner term F(G_in(v, b)) of one element (:99-100, :108) from v = l', ea = e^v and the summed-out object's zb = W[:,1] b + c, eb = e^b
+template <class TileT>
+__device__ __forceinline__ float gate_elem(const GatePred<TileT>& g, float v, float ea, const float* zb, float eb) {
+    return gate_term(gate_m(g.GI, v, ea, zb, eb), g.Q);
+}
+
+// Tail of a column aggregation: the row slots are joined by shuffles, the outer gate (:133, :135-136) runs once per column in the lanes of
+// row slot 0, CPL / 4 16-byte stores.
+template <int LPR, int CPL, class TileT>
+__device__ __forceinline__ void gate_col_finish(const GatePred<TileT>& g, float (&cacc)[CPL], int rs, int c0) {
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+#pragma unroll
+        for (int m = 32; m >= LPR; m >>= 1) cacc[j] = gate_join(cacc[j], __shfl_xor(cacc[j], m, 64), g.Q.ex);
+    }
+    if (rs == 0 && c0 < g.NS) {
+#pragma unroll
+        for (int h = 0; h < CPL / 4; ++h) {
+            float xj[4], o[4];
+            load_cols(g.xv + c0 + 4 * h, xj);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = (c0 + 4 * h + j < g.n) ? gate_log(g.GO, gate_outer(cacc[4 * h + j], g.Q), xj[j]) : 0.f;
+            *reinterpret_cast<float4*>(g.out + c0 + 4 * h) = make_float4(o[0], o[1], o[2], o[3]);
+        }
+    }
+}
+
+// The column sweep: the summed-out variable along rows, the aggregates of a lane's columns in its registers; a row's prior, its exponential
+// and its share of the six pre-activations are computed once per row.
+template <int LPR, int CPL, class TileT>
+__device__ __forceinline__ void gate_col_sweep(const GatePred<TileT>& g, int lane) {
+    constexpr int RPI = 64 / LPR;
+    const int cg = lane % LPR, rs = lane / LPR, c0 = cg * CPL, cl = min(c0, g.NS - CPL);
+    float cacc[CPL];
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) cacc[j] = 0.f;
+    for (int r0 = 0; r0 < g.n; r0 += RPI) {
+        const int r = r0 + rs, rc = min(r, g.n - 1);
+        float l[CPL];
+        load_cols(g.tp + (int64_t)rc * g.NS + cl, l);
+        const float pr = g.pv[rc];
+        float zb[6];
+        gate_zb(g.GI, pr, zb);
+        const float eb = dfol_exp(pr);
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) {
+            const int c = c0 + j;
+            const bool keep = r < g.n && c < g.n && c != r;
+            const float v = gate_prep(l[j], g.N);
+            const float t = gate_elem(g, v, dfol_exp(v), zb, eb);
+            cacc[j] = gate_join(cacc[j], keep ? t : 0.f, g.Q.ex);
+        }
+    }
+    gate_col_finish<LPR, CPL>(g, cacc, rs, c0);
+}
+
+// A lane's four columns as summed-out objects: their share of the pre-activations and e^prior (once per wavefront)
+__device__ __forceinline__ void gate_cols_prior(const GateW& G, const float* __restrict__ prior4, float (&zb)[4][6], float (&eb)[4]) {
+    float pc[4];
+    load_cols(prior4, pc);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        gate_zb(GC, pc[j], zbC[j]);
-        ebC[j] = dfol_exp(pc[j]);
+        gate_zb(G, pc[j], zb[j]);
+        eb[j] = dfol_exp(pc[j]);
     }
-    float cacc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int r0 = 0; r0 < n; r0 += RPI) {
-        const int r = r0 + rs, rc = min(r, n - 1);
-        const float4 t4 = *reinterpret_cast<const float4*>(tp + (int64_t)rc * NS + cl);
-        const float l[4] = {t4.x, t4.y, t4.z, t4.w};
-        const float pr = pR[rc];
-        float zbR[6];
-        gate_zb(GR, pr, zbR);
-        const float ebR = dfol_exp(pr);
-        float racc = 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int c = c0 + j;
-            const bool keep = r < n && c < n && c != r;       // padding and self-relations contribute nothing (:112)
-            const float v = gate_prep(l[j], any_neg, alpha_n, cn);
-            const float ea = dfol_exp(v);
-            if (wantR) {
-                const float t = gate_term(gate_m(GC, v, ea, zbC[j], ebC[j]), exC, qC, kC);      // :99-100, :108
-                racc = gate_join(racc, keep ? t : 0.f, exC);
-            }
-            if (wantC) {
-                const float t = gate_term(gate_m(GR, v, ea, zbR, ebR), exR, qR, kR);
-                cacc[j] = gate_join(cacc[j], keep ? t : 0.f, exR);
-            }
-        }
-        if (wantR) {
-            racc = exC ? dfol_group_or<LPR>(racc) : dfol_group_sum<LPR>(racc);
-            if (cg == LPR - 1 && r < n) row_agg[wave_in_block][r] = racc;
-        }
+}
+
+// a row's aggregate over the LPR lanes that share it (valid in the last lane of the group) into the wavefront's LDS row
+template <int LPR>
+__device__ __forceinline__ void gate_row_put(float* row_agg, float racc, bool ex, int cg, int r, int n) {
+    racc = ex ? dfol_group_or<LPR>(racc) : dfol_group_sum<LPR>(racc);
+    if (cg == LPR - 1 && r < n) row_agg[r] = racc;
+}
+
+// tail of a row aggregation: the outer gate (:133, :135-136) in the lane that owns the row
+__device__ __forceinline__ void gate_row_finish(const GatePred<>& g, const float* row_agg, int lane) {
+    __builtin_amdgcn_wave_barrier();                     // LDS is in order within a wavefront; this only pins the schedule
+    for (int c = lane; c < g.NS; c += 64) {
+        float o = 0.f;
+        if (c < g.n) o = gate_log(g.GO, gate_outer(row_agg[c], g.Q), g.xv[c]);
+        g.out[c] = o;
     }
-    if (wantR) {
-        __builtin_amdgcn_wave_barrier();                 // LDS is in order within a wavefront; this only pins the schedule
-        for (int c = lane; c < NS; c += 64) {
-            float o = 0.f;
-            if (c < n) o = gate_log(GR, gate_outer(row_agg[wave_in_block][c], exC, idC, qC, kC), pR[c]);      // :133, :135-136
-            oR[c] = o;
-        }
-    }
-    if (wantC) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-#pragma unroll
-            for (int m = 32; m >= LPR; m >>= 1) cacc[j] = gate_join(cacc[j], __shfl_xor(cacc[j], m, 64), exR);
-        }
-        if (rs == 0 && c0 < NS) {
-            float o[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float a = gate_outer(cacc[j], exR, idR, qR, kR);
-                o[j] = (c0 + j < n) ? dfol_log(gate_m(GC, a, dfol_exp(a), zbC[j], ebC[j])) : 0.f;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// relate forward, NS > 256: one workgroup of 256 threads per predicate
+// ---------------------------------------------------------------------------------------------------
+// summed out along rows: a thread per column, rows in order
+__device__ __forceinline__ void gate_big_cols(const GatePred<>& g, int tid) {
+    for (int c = tid; c < g.NS; c += 256) {
+        float o = 0.f;
+        if (c < g.n) {
+            float acc = 0.f;
+            for (int r = 0; r < g.n; ++r) {
+                if (r == c) continue;
+                const float v = gate_prep(g.tp[(int64_t)r * g.NS + c], g.N);
+                float zb[6];
+                gate_zb(g.GI, g.pv[r], zb);
+                acc = gate_join(acc, gate_elem(g, v, dfol_exp(v), zb, dfol_exp(g.pv[r])), g.Q.ex);
             }
-            *reinterpret_cast<float4*>(oC + c0) = make_float4(o[0], o[1], o[2], o[3]);
+            o = gate_log(g.GO, gate_outer(acc, g.Q), g.xv[c]);
         }
+        g.out[c] = o;
     }
 }
 
@@ -344,8 +478,92 @@ __device__ __forceinline__ float gate_wave_join(float x, bool ex) {
     return x;
 }
 
-// NS > 256: one workgroup per predicate, a thread per column for the column aggregates (rows in order), a workgroup reduction per row
-// for the row aggregates (wavefront partials joined in wavefront order), as relate_big_fwd_kernel.
+// summed out along columns: a workgroup reduction per row - thread partials, the wavefront's shuffle tree, the four wavefronts' partials joined in
+// wavefront order.  The loop runs over all NS rows and holds barriers: call it only under a condition that is the same for the whole
+// workgroup, so that every thread reaches every barrier.
+__device__ __forceinline__ void gate_big_rows(const GatePred<>& g, float* part, int tid) {
+    const int w = tid >> 6, lane = tid & 63;
+    for (int r = 0; r < g.NS; ++r) {
+        float s = 0.f;
+        if (r < g.n)
+            for (int c = tid; c < g.n; c += 256) {
+                if (c == r) continue;
+                const float v = gate_prep(g.tp[(int64_t)r * g.NS + c], g.N);
+                float zb[6];
+                gate_zb(g.GI, g.pv[c], zb);
+                s = gate_join(s, gate_elem(g, v, dfol_exp(v), zb, dfol_exp(g.pv[c])), g.Q.ex);
+            }
+        s = gate_wave_join(s, g.Q.ex);
+        if (lane == 0) part[w] = s;
+        __syncthreads();
+        if (tid == 0) {
+            const float tot = gate_join(gate_join(gate_join(part[0], part[1], g.Q.ex), part[2], g.Q.ex), part[3], g.Q.ex);
+            g.out[r] = r < g.n ? gate_log(g.GO, gate_outer(tot, g.Q), g.xv[r]) : 0.f;
+        }
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// relate, both posteriors
+// ---------------------------------------------------------------------------------------------------
+// NS <= 256, the geometry of relate_fwd_kernel.  One loop serves both directions - a tile load and an e^l' per element are shared - so it is
+// neither sweep but their element steps side by side, with the sweeps' tails.
+template <int LPR>
+__global__ __launch_bounds__(256) void relate_gate_fwd_kernel(
+    const float* __restrict__ prior_R, const float* __restrict__ prior_C, const float* __restrict__ tile,
+    const int32_t* __restrict__ pred_q, const int32_t* __restrict__ n_obj, const float* __restrict__ quant_R,
+    const float* __restrict__ quant_C, const uint8_t* __restrict__ neg, int any_neg, const uint8_t* __restrict__ active,
+    const uint8_t* __restrict__ want, int want_R_bit, int want_C_bit, int P, int NS, int flags,
+    const float* __restrict__ gate_R, const float* __restrict__ gate_C, float* __restrict__ post_R, float* __restrict__ post_C) {
+    constexpr int RPI = 64 / LPR;
+    __shared__ float row_agg[4][256];
+    // (the predicate is the same for the whole wavefront: said so, everything derived from it - the gates' 36 parameters among it - is scalar)
+    const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int p = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    if (p >= P) return;
+    const int lane = threadIdx.x & 63;
+    GatePred<> vR, vC;
+    bool wantR, wantC;
+    if (!gate_pred_load2(vR, vC, wantR, wantC, p, prior_R, prior_C, tile, pred_q, n_obj, quant_R, quant_C, neg, any_neg, active, want, want_R_bit,
+                         want_C_bit, NS, flags, gate_R, gate_C, post_R, post_C, lane, 64))
+        return;
+    const int n = vC.n;
+    const int cg = lane % LPR, rs = lane / LPR, c0 = cg * 4, cl = min(c0, NS - 4);
+    float zbC[4][6], ebC[4];
+    gate_cols_prior(vR.GI, vR.pv + cl, zbC, ebC);
+    float cacc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int r0 = 0; r0 < n; r0 += RPI) {
+        const int r = r0 + rs, rc = min(r, n - 1);
+        float l[4];
+        load_cols(vC.tp + (int64_t)rc * NS + cl, l);
+        const float pr = vC.pv[rc];
+        float zbR[6];
+        gate_zb(vC.GI, pr, zbR);
+        const float ebR = dfol_exp(pr);
+        float racc = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = c0 + j;
+            const bool keep = r < n && c < n && c != r;
+            const float v = gate_prep(l[j], vC.N);
+            const float ea = dfol_exp(v);
+            if (wantR) {
+                const float t = gate_elem(vR, v, ea, zbC[j], ebC[j]);
+                racc = gate_join(racc, keep ? t : 0.f, vR.Q.ex);
+            }
+            if (wantC) {
+                const float t = gate_elem(vC, v, ea, zbR, ebR);
+                cacc[j] = gate_join(cacc[j], keep ? t : 0.f, vC.Q.ex);
+            }
+        }
+        if (wantR) gate_row_put<LPR>(row_agg[wave_in_block], racc, vR.Q.ex, cg, r, n);
+    }
+    if (wantR) gate_row_finish(vR, row_agg[wave_in_block], lane);
+    if (wantC) gate_col_finish<LPR, 4>(vC, cacc, rs, c0);
+}
+
+// NS > 256, as relate_big_fwd_kernel
 __global__ __launch_bounds__(256) void relate_gate_big_fwd_kernel(
     const float* __restrict__ prior_R, const float* __restrict__ prior_C, const float* __restrict__ tile,
     const int32_t* __restrict__ pred_q, const int32_t* __restrict__ n_obj, const float* __restrict__ quant_R,
@@ -353,76 +571,42 @@ __global__ __launch_bounds__(256) void relate_gate_big_fwd_kernel(
     const uint8_t* __restrict__ want, int want_R_bit, int want_C_bit, int NS, int flags, const float* __restrict__ gate_R,
     const float* __restrict__ gate_C, float* __restrict__ post_R, float* __restrict__ post_C) {
     __shared__ float part[4];
-    const int p = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    const int q = pred_q[p], n = min(n_obj[q], NS);
-    const int wbits = want ? want[p] : 3;
-    const bool wantR = (wbits & want_R_bit) && post_R, wantC = (wbits & want_C_bit) && post_C;
-    const float* pR = prior_R + (int64_t)q * NS;
-    const float* pC = prior_C + (int64_t)q * NS;
-    float* oR = post_R ? post_R + (int64_t)p * NS : nullptr;
-    float* oC = post_C ? post_C + (int64_t)p * NS : nullptr;
-    if (active && !active[p]) {
-        for (int c = tid; c < NS; c += 256) {
-            if (oR) oR[c] = (wantR && c < n) ? pR[c] : 0.f;
-            if (oC) oC[c] = (wantC && c < n) ? pC[c] : 0.f;
-        }
+    const int p = blockIdx.x, tid = threadIdx.x;
+    GatePred<> vR, vC;
+    bool wantR, wantC;
+    if (!gate_pred_load2(vR, vC, wantR, wantC, p, prior_R, prior_C, tile, pred_q, n_obj, quant_R, quant_C, neg, any_neg, active, want, want_R_bit,
+                         want_C_bit, NS, flags, gate_R, gate_C, post_R, post_C, tid, 256))
         return;
-    }
-    if (!wantR && oR)
-        for (int c = tid; c < NS; c += 256) oR[c] = 0.f;
-    if (!wantC && oC)
-        for (int c = tid; c < NS; c += 256) oC[c] = 0.f;
-    const GateW GR = gate_load(gate_R), GC = gate_load(gate_C);
-    const int identity_forall = flags & DFOL_RELATE_LONE_FORALL_IDENTITY;
-    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
-    const float qR = quant_R[p], qC = quant_C[p], kR = 1.f - 2.f * qR, kC = 1.f - 2.f * qC;
-    const bool exR = qR == 1.f, exC = qC == 1.f;
-    const bool idR = identity_forall && qR == 0.f, idC = identity_forall && qC == 0.f;
-    const float* tp = tile + (int64_t)p * NS * NS;
-    if (wantC)
-        for (int c = tid; c < NS; c += 256) {
-            float o = 0.f;
-            if (c < n) {
-                float acc = 0.f;
-                for (int r = 0; r < n; ++r) {
-                    if (r == c) continue;
-                    const float v = gate_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn);
-                    float zb[6];
-                    gate_zb(GR, pR[r], zb);
-                    acc = gate_join(acc, gate_term(gate_m(GR, v, dfol_exp(v), zb, dfol_exp(pR[r])), exR, qR, kR), exR);
-                }
-                o = gate_log(GC, gate_outer(acc, exR, idR, qR, kR), pC[c]);
-            }
-            oC[c] = o;
-        }
-    if (wantR)                                           // (wave-uniform per workgroup: every thread reaches the barriers)
-        for (int r = 0; r < NS; ++r) {
-            float s = 0.f;
-            if (r < n)
-                for (int c = tid; c < n; c += 256) {
-                    if (c == r) continue;
-                    const float v = gate_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn);
-                    float zb[6];
-                    gate_zb(GC, pC[c], zb);
-                    s = gate_join(s, gate_term(gate_m(GC, v, dfol_exp(v), zb, dfol_exp(pC[c])), exC, qC, kC), exC);
-                }
-            s = gate_wave_join(s, exC);
-            if (lane == 0) part[w] = s;
-            __syncthreads();
-            if (tid == 0) {
-                const float tot = gate_join(gate_join(gate_join(part[0], part[1], exC), part[2], exC), part[3], exC);
-                oR[r] = r < n ? gate_log(GR, gate_outer(tot, exC, idC, qC, kC), pR[r]) : 0.f;
-            }
-            __syncthreads();
-        }
+    if (wantC) gate_big_cols(vC, tid);
+    if (wantR) gate_big_rows(vR, part, tid);             // (wantR is the workgroup's: every thread reaches the barriers)
 }
 
 // ---------------------------------------------------------------------------------------------------
-// relate backward: one workgroup per predicate, its wavefronts on rows r = w, w + waves, ..., lane = column (the scheme of
+// relate backward, both posteriors: one workgroup per predicate, its wavefronts on rows r = w, w + waves, ..., lane = column (the scheme of
 // relate_bwd_kernel): sweep 1 recomputes the aggregates as written (S[r] = sum_c F_C(G_C), T[c] = sum_r F_R(G_R)), the outer gates are
 // differentiated by the thread that owns the row / column, sweep 2 takes the element gradients.  Every thread keeps the 2 x 18 parameter
 // sums of its elements; the workgroup's total goes to scratch[p][36] (R's 18, then C's).
 // ---------------------------------------------------------------------------------------------------
+// The parameter sums of a workgroup: wavefront totals into wsum [waves][36] (`first`'s 18, then `second`'s), a barrier - which also publishes
+// whatever else the caller left in LDS - and the wavefronts added in order into sc[36].
+__device__ __forceinline__ void gate_param_sums(const float (&first)[18], const float (&second)[18], float* wsum, float* __restrict__ sc) {
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, tid = threadIdx.x, nw = (int)blockDim.x >> 6;
+#pragma unroll
+    for (int k = 0; k < 18; ++k) {
+        const float a = dfol_wave_sum(first[k]), b = dfol_wave_sum(second[k]);
+        if (lane == 0) {
+            wsum[w * 36 + k] = a;
+            wsum[w * 36 + 18 + k] = b;
+        }
+    }
+    __syncthreads();
+    if (tid < 36) {
+        float s = wsum[tid];
+        for (int j = 1; j < nw; ++j) s += wsum[j * 36 + tid];
+        sc[tid] = s;
+    }
+}
+
 constexpr int GB_WAVES = 8;
 __global__ __launch_bounds__(64 * GB_WAVES) void relate_gate_bwd_kernel(
     const float* __restrict__ prior_R, const float* __restrict__ prior_C, const float* __restrict__ tile,
@@ -463,9 +647,8 @@ __global__ __launch_bounds__(64 * GB_WAVES) void relate_gate_bwd_kernel(
         return;
     }
     const GateW GR = gate_load(gate_R), GC = gate_load(gate_C);
-    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
-    const float qR = quant_R[p], qC = quant_C[p], kR = 1.f - 2.f * qR, kC = 1.f - 2.f * qC;
-    const bool idR = identity_forall && qR == 0.f, idC = identity_forall && qC == 0.f;
+    const GateNeg N = gate_neg_load(neg, any_neg, p);
+    const GateQuant QR = gate_quant_load(quant_R, p, identity_forall), QC = gate_quant_load(quant_C, p, identity_forall);
     float accR[18], accC[18];
 #pragma unroll
     for (int k = 0; k < 18; ++k) accR[k] = accC[k] = 0.f;
@@ -481,12 +664,12 @@ __global__ __launch_bounds__(64 * GB_WAVES) void relate_gate_bwd_kernel(
         for (int r = w; r < n; r += nw) {
             float s_part = 0.f;
             if (c < n && c != r) {
-                const float v = gate_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn), ea = dfol_exp(v);
-                if (gR) s_part = dfol_slog(fmaf(kC, gate_m(GC, v, ea, zbc, ebc), qC));
+                const float v = gate_prep(tp[(int64_t)r * NS + c], N), ea = dfol_exp(v);
+                if (gR) s_part = dfol_slog(fmaf(QC.kf, gate_m(GC, v, ea, zbc, ebc), QC.qf));
                 if (gC) {
                     float zbr[6];
                     gate_zb(GR, pR[r], zbr);
-                    t_acc += dfol_slog(fmaf(kR, gate_m(GR, v, ea, zbr, dfol_exp(pR[r])), qR));
+                    t_acc += dfol_slog(fmaf(QR.kf, gate_m(GR, v, ea, zbr, dfol_exp(pR[r])), QR.qf));
                 }
             }
             s_part = dfol_wave_sum(s_part);
@@ -501,16 +684,16 @@ __global__ __launch_bounds__(64 * GB_WAVES) void relate_gate_bwd_kernel(
         for (int j = 1; j < nw; ++j) T += part(j, i);
         float dS = 0.f, dT = 0.f, dbr = 0.f, dbc = 0.f;
         if (gR) {
-            const float S = sS[i], a = idC ? S : dfol_pnot(S, qC, kC);
+            const float S = sS[i], a = QC.ident ? S : dfol_pnot(S, QC.qf, QC.kf);
             float da;
             gate_bwd(GR, a, pR[i], gR[i], true, da, dbr, accR);
-            dS = da * (idC ? 1.f : gate_dpnot(S, qC, kC));
+            dS = da * (QC.ident ? 1.f : gate_dpnot(S, QC.qf, QC.kf));
         }
         if (gC) {
-            const float a = idR ? T : dfol_pnot(T, qR, kR);
+            const float a = QR.ident ? T : dfol_pnot(T, QR.qf, QR.kf);
             float da;
             gate_bwd(GC, a, pC[i], gC[i], true, da, dbc, accC);
-            dT = da * (idR ? 1.f : gate_dpnot(T, qR, kR));
+            dT = da * (QR.ident ? 1.f : gate_dpnot(T, QR.qf, QR.kf));
         }
         sGR[i] = dS;
         sGC[i] = dT;
@@ -528,13 +711,13 @@ __global__ __launch_bounds__(64 * GB_WAVES) void relate_gate_bwd_kernel(
             float dl = 0.f, dpr_part = 0.f;
             if (r < n && c < n && c != r) {
                 const float raw = tp[(int64_t)r * NS + c];
-                const float v = gate_prep(raw, any_neg, alpha_n, cn), ea = dfol_exp(v);
+                const float v = gate_prep(raw, N), ea = dfol_exp(v);
                 float dv = 0.f;
                 if (gR) {                                      // t = log(max(qC + kC m, eps)), m = e^G_C(v, pc)
                     float zb[6];
                     gate_zb(GC, pc, zb);
-                    const float u = fmaf(kC, gate_m(GC, v, ea, zb, dfol_exp(pc)), qC);
-                    const float dm = u > DFOL_EPS ? sGR[r] * kC / u : 0.f;
+                    const float u = fmaf(QC.kf, gate_m(GC, v, ea, zb, dfol_exp(pc)), QC.qf);
+                    const float dm = u > DFOL_EPS ? sGR[r] * QC.kf / u : 0.f;
                     float da, db;
                     gate_bwd(GC, v, pc, dm, false, da, db, accC);
                     dv += da;
@@ -544,14 +727,14 @@ __global__ __launch_bounds__(64 * GB_WAVES) void relate_gate_bwd_kernel(
                     const float pr = pR[r];
                     float zb[6];
                     gate_zb(GR, pr, zb);
-                    const float u = fmaf(kR, gate_m(GR, v, ea, zb, dfol_exp(pr)), qR);
-                    const float dm = u > DFOL_EPS ? gcc * kR / u : 0.f;
+                    const float u = fmaf(QR.kf, gate_m(GR, v, ea, zb, dfol_exp(pr)), QR.qf);
+                    const float dm = u > DFOL_EPS ? gcc * QR.kf / u : 0.f;
                     float da, db;
                     gate_bwd(GR, v, pr, dm, false, da, db, accR);
                     dv += da;
                     dpr_part = db;
                 }
-                dl = dv * gate_dprep(raw, any_neg, alpha_n, cn);
+                dl = dv * gate_dprep(raw, N);
             }
             if (gt && c < NS) gt[(int64_t)r * NS + c] = dl;
             if (g_prior_R) {                                   // row totals over the column chunks collect in LDS (sS is free by now)
@@ -561,16 +744,7 @@ __global__ __launch_bounds__(64 * GB_WAVES) void relate_gate_bwd_kernel(
         }
         if (c < NS) part(w, c) = dpc;
     }
-    // the parameter sums of this workgroup: wavefront totals, then the wavefronts in order
-#pragma unroll
-    for (int k = 0; k < 18; ++k) {
-        const float a = dfol_wave_sum(accR[k]), b = dfol_wave_sum(accC[k]);
-        if (lane == 0) {
-            wsum[w * 36 + k] = a;
-            wsum[w * 36 + 18 + k] = b;
-        }
-    }
-    __syncthreads();
+    gate_param_sums(accR, accC, wsum, sc);                 // (its barrier also publishes sweep 2's sS and part)
     for (int c = tid; c < NS; c += nt) {
         if (g_prior_C) {
             float t = part(0, c);
@@ -579,22 +753,11 @@ __global__ __launch_bounds__(64 * GB_WAVES) void relate_gate_bwd_kernel(
         }
         if (g_prior_R) g_prior_R[(int64_t)p * NS + c] = c < n ? sS[c] : 0.f;
     }
-    if (tid < 36) {
-        float s = wsum[tid];
-        for (int j = 1; j < nw; ++j) s += wsum[j * 36 + tid];
-        sc[tid] = s;
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------
 // relate, single posterior (the gated form of relate_one_fwd_kernel, dfol_logic.hip): the three gates of GQARelateBatch and the arity-2
-// cell in one launch, only the kept posterior written.  x = the freshly selected variable (columns), prev = the incoming one (rows, summed
-// out); the tile comes with prev's objects along rows.  The two axes hold different gates, so the launch is told which axis x is on:
-// x_is_subject[p] -> x on axis 0 (outer gate = gate_s, inner gate = gate_o), else x on axis 1 (outer = gate_o, inner = gate_s).
-//     post[p][i] = G_out( F( agg_{j < n, j != i} F( G_in(l'[j][i], prev[j]) ) ), x[p][i] ),   F and agg by quant_prev[p]
-// This is the column half of relate_gate_fwd_kernel (R = prev, C = x): a wavefront per predicate, a lane owns four columns, 64 / LPR rows per
-// iteration, the column aggregates stay in registers; a row's prior, its exponential and its share of the six pre-activations are computed
-// once per row, so an element costs six sigmoids and one e^l'.  The outer gate runs once per column, in the lanes of row slot 0.
+// cell in one launch, only the kept posterior written.  The tile comes with prev's objects along rows: the column sweep.
 // ---------------------------------------------------------------------------------------------------
 template <int LPR>
 __global__ __launch_bounds__(256) void relate_one_gate_fwd_kernel(
@@ -602,176 +765,66 @@ __global__ __launch_bounds__(256) void relate_one_gate_fwd_kernel(
     const int32_t* __restrict__ n_obj, const float* __restrict__ quant_prev, const uint8_t* __restrict__ x_is_subject,
     const uint8_t* __restrict__ neg, int any_neg, const uint8_t* __restrict__ active, int P, int NS, int identity_forall,
     const float* __restrict__ gate_s, const float* __restrict__ gate_o, float* __restrict__ post) {
-    constexpr int RPI = 64 / LPR;
     // (the predicate is the same for the whole wavefront: said so, everything derived from it - the gates' 36 parameters among it - is scalar)
     const int p = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
     if (p >= P) return;
     const int lane = threadIdx.x & 63;
-    const int q = pred_q[p];
-    const int n = min(n_obj[q], NS);
-    const float* pv = prev_att + (int64_t)q * NS;
-    const float* xv = x_att + (int64_t)p * NS;
-    float* out = post + (int64_t)p * NS;
-    if (active && !active[p]) {                         // question without this operator: attention passes through (as relate_one_fwd_kernel)
-        for (int c = lane; c < NS; c += 64) out[c] = c < n ? pv[c] : 0.f;
+    GatePred<> g;
+    if (!gate_pred_load(g, p, x_att, prev_att, tile, pred_q, n_obj, quant_prev, x_is_subject, neg, any_neg, active, NS, identity_forall, gate_s,
+                        gate_o, post)) {
+        gate_passthrough(g, lane, 64);
         return;
     }
-    const bool xs = x_is_subject[p] != 0;
-    const GateW GI = gate_load(xs ? gate_o : gate_s), GO = gate_load(xs ? gate_s : gate_o);      // inner: prev's axis, outer: x's
-    const int cg = lane % LPR, rs = lane / LPR, c0 = cg * 4, cl = min(c0, NS - 4);               // (lanes beyond the width read a valid column)
-    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
-    const float qf = quant_prev[p], kf = 1.f - 2.f * qf;
-    const bool ex = qf == 1.f, ident = identity_forall && qf == 0.f;
-    const float* tp = tile + (int64_t)p * NS * NS;
-    float cacc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int r0 = 0; r0 < n; r0 += RPI) {
-        const int r = r0 + rs, rc = min(r, n - 1);
-        const float4 t4 = *reinterpret_cast<const float4*>(tp + (int64_t)rc * NS + cl);
-        const float l[4] = {t4.x, t4.y, t4.z, t4.w};
-        const float pr = pv[rc];
-        float zb[6];
-        gate_zb(GI, pr, zb);
-        const float eb = dfol_exp(pr);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int c = c0 + j;
-            const bool keep = r < n && c < n && c != r;       // padding and self-relations contribute nothing (:112)
-            const float v = gate_prep(l[j], any_neg, alpha_n, cn);
-            const float t = gate_term(gate_m(GI, v, dfol_exp(v), zb, eb), ex, qf, kf);      // :99-100, :108
-            cacc[j] = gate_join(cacc[j], keep ? t : 0.f, ex);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-        for (int m = 32; m >= LPR; m >>= 1) cacc[j] = gate_join(cacc[j], __shfl_xor(cacc[j], m, 64), ex);
-    }
-    if (rs == 0 && c0 < NS) {
-        const float4 x4 = *reinterpret_cast<const float4*>(xv + c0);
-        const float xj[4] = {x4.x, x4.y, x4.z, x4.w};
-        float o[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (c0 + j < n) ? gate_log(GO, gate_outer(cacc[j], ex, ident, qf, kf), xj[j]) : 0.f;      // :133, :135-136
-        *reinterpret_cast<float4*>(out + c0) = make_float4(o[0], o[1], o[2], o[3]);
-    }
+    gate_col_sweep<LPR, 4>(g, lane);
 }
 
-// NS > 256: one workgroup per predicate, a thread per column, rows in order (as relate_one_big_kernel)
+// NS > 256, as relate_one_big_kernel
 __global__ __launch_bounds__(256) void relate_one_gate_big_kernel(
     const float* __restrict__ x_att, const float* __restrict__ prev_att, const float* __restrict__ tile, const int32_t* __restrict__ pred_q,
     const int32_t* __restrict__ n_obj, const float* __restrict__ quant_prev, const uint8_t* __restrict__ x_is_subject,
     const uint8_t* __restrict__ neg, int any_neg, const uint8_t* __restrict__ active, int NS, int identity_forall,
     const float* __restrict__ gate_s, const float* __restrict__ gate_o, float* __restrict__ post) {
     const int p = blockIdx.x, tid = threadIdx.x;
-    const int q = pred_q[p], n = min(n_obj[q], NS);
-    const float* pv = prev_att + (int64_t)q * NS;
-    const float* xv = x_att + (int64_t)p * NS;
-    float* out = post + (int64_t)p * NS;
-    if (active && !active[p]) {
-        for (int c = tid; c < NS; c += 256) out[c] = c < n ? pv[c] : 0.f;
+    GatePred<> g;
+    if (!gate_pred_load(g, p, x_att, prev_att, tile, pred_q, n_obj, quant_prev, x_is_subject, neg, any_neg, active, NS, identity_forall, gate_s,
+                        gate_o, post)) {
+        gate_passthrough(g, tid, 256);
         return;
     }
-    const bool xs = x_is_subject[p] != 0;
-    const GateW GI = gate_load(xs ? gate_o : gate_s), GO = gate_load(xs ? gate_s : gate_o);
-    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
-    const float qf = quant_prev[p], kf = 1.f - 2.f * qf;
-    const bool ex = qf == 1.f, ident = identity_forall && qf == 0.f;
-    const float* tp = tile + (int64_t)p * NS * NS;
-    for (int c = tid; c < NS; c += 256) {
-        float o = 0.f;
-        if (c < n) {
-            float acc = 0.f;
-            for (int r = 0; r < n; ++r) {
-                if (r == c) continue;
-                const float v = gate_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn);
-                float zb[6];
-                gate_zb(GI, pv[r], zb);
-                acc = gate_join(acc, gate_term(gate_m(GI, v, dfol_exp(v), zb, dfol_exp(pv[r])), ex, qf, kf), ex);
-            }
-            o = gate_log(GO, gate_outer(acc, ex, ident, qf, kf), xv[c]);
-        }
-        out[c] = o;
-    }
+    gate_big_cols(g, tid);
 }
 
 // The same one posterior on bf16 tiles (relation_tile_dtype: bf16 with trainable_gate: True, DFOL_GATE_BF16=1; NS a multiple of 8, <= 256): the
-// geometry of relate_one_bf16_kernel (dfol_logic.hip) - a lane owns EIGHT consecutive columns, one 16-byte load = 8 bf16 per row widened
-// exactly, LPR = NS / 8 lanes cover a row, 64 / LPR rows per iteration - around the arithmetic of relate_one_gate_fwd_kernel, term for term.
-// Only the stored likelihoods are rounded; which rows share a lane differs from the fp32 kernel, so the two agree to rounding, not to the bit.
+// geometry of relate_one_bf16_kernel (dfol_logic.hip) - a lane owns EIGHT consecutive columns, LPR = NS / 8 lanes cover a row - around the
+// same column sweep, term for term.  Only the stored likelihoods are rounded; which rows share a lane differs from the fp32 kernel, so the two
+// agree to rounding, not to the bit.
 template <int LPR>
 __global__ __launch_bounds__(256) void relate_one_gate_bf16_kernel(
     const float* __restrict__ x_att, const float* __restrict__ prev_att, const uint16_t* __restrict__ tile, const int32_t* __restrict__ pred_q,
     const int32_t* __restrict__ n_obj, const float* __restrict__ quant_prev, const uint8_t* __restrict__ x_is_subject,
     const uint8_t* __restrict__ neg, int any_neg, const uint8_t* __restrict__ active, int P, int NS, int identity_forall,
     const float* __restrict__ gate_s, const float* __restrict__ gate_o, float* __restrict__ post) {
-    constexpr int RPI = 64 / LPR;
     const int p = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));      // (wave-uniform: the gates' 36 parameters stay scalar)
     if (p >= P) return;
     const int lane = threadIdx.x & 63;
-    const int q = pred_q[p];
-    const int n = min(n_obj[q], NS);
-    const float* pv = prev_att + (int64_t)q * NS;
-    const float* xv = x_att + (int64_t)p * NS;
-    float* out = post + (int64_t)p * NS;
-    if (active && !active[p]) {                         // question without this operator: attention passes through
-        for (int c = lane; c < NS; c += 64) out[c] = c < n ? pv[c] : 0.f;
+    GatePred<uint16_t> g;
+    if (!gate_pred_load(g, p, x_att, prev_att, tile, pred_q, n_obj, quant_prev, x_is_subject, neg, any_neg, active, NS, identity_forall, gate_s,
+                        gate_o, post)) {
+        gate_passthrough(g, lane, 64);
         return;
     }
-    const bool xs = x_is_subject[p] != 0;
-    const GateW GI = gate_load(xs ? gate_o : gate_s), GO = gate_load(xs ? gate_s : gate_o);      // inner: prev's axis, outer: x's
-    const int cg = lane % LPR, rs = lane / LPR, c0 = cg * 8;
-    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
-    const float qf = quant_prev[p], kf = 1.f - 2.f * qf;
-    const bool ex = qf == 1.f, ident = identity_forall && qf == 0.f;
-    const uint16_t* tp = tile + (int64_t)p * NS * NS + min(c0, NS - 8);      // lanes beyond the tile width read valid columns and are discarded
-    float cacc[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) cacc[j] = 0.f;
-    for (int r0 = 0; r0 < n; r0 += RPI) {
-        const int r = r0 + rs, rc = min(r, n - 1);      // rows beyond n read row n - 1 and are masked
-        float l[8];
-        bf16x8_to_f32(*reinterpret_cast<const uint4*>(tp + (int64_t)rc * NS), l);
-        const float pr = pv[rc];
-        float zb[6];
-        gate_zb(GI, pr, zb);
-        const float eb = dfol_exp(pr);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int c = c0 + j;
-            const bool keep = r < n && c < n && c != r;       // padding and self-relations contribute nothing (:112)
-            const float v = gate_prep(l[j], any_neg, alpha_n, cn);
-            const float t = gate_term(gate_m(GI, v, dfol_exp(v), zb, eb), ex, qf, kf);      // :99-100, :108
-            cacc[j] = gate_join(cacc[j], keep ? t : 0.f, ex);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-#pragma unroll
-        for (int m = 32; m >= LPR; m >>= 1) cacc[j] = gate_join(cacc[j], __shfl_xor(cacc[j], m, 64), ex);
-    }
-    if (rs == 0 && c0 < NS) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const float4 x4 = *reinterpret_cast<const float4*>(xv + c0 + 4 * h);
-            const float xj[4] = {x4.x, x4.y, x4.z, x4.w};
-            float o[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                o[j] = (c0 + 4 * h + j < n) ? gate_log(GO, gate_outer(cacc[4 * h + j], ex, ident, qf, kf), xj[j]) : 0.f;      // :133, :135-136
-            *reinterpret_cast<float4*>(out + c0 + 4 * h) = make_float4(o[0], o[1], o[2], o[3]);
-        }
-    }
+    gate_col_sweep<LPR, 8>(g, lane);
 }
 
 // ---------------------------------------------------------------------------------------------------
 // relate, single posterior, on the SUBJECT-ROW tile of the train step (oracle.block_likelihood stores subjects along rows for every
 // predicate; the inference prefetch that turns prev's objects onto the rows does not run under autograd).  The predicate's flag picks,
 // wave-uniformly, which axis is summed out:
-//     x_is_subject[p]:  post[p][i] = G_0( F( agg_{j != i} F( G_1(l'[i][j], prev[j]) ) ), x[p][i] )      row aggregate    (inner gate_o, outer gate_s)
-//     otherwise:        post[p][i] = G_1( F( agg_{j != i} F( G_0(l'[j][i], prev[j]) ) ), x[p][i] )      column aggregate (inner gate_s, outer gate_o)
-// The column branch is relate_one_gate_fwd_kernel's loop; the row branch is the row half of relate_gate_fwd_kernel (a column's prev, e^prev
-// and share of the pre-activations once per wavefront, the row aggregate by the group reduction, the outer gate in the lane that owns the
-// row).  Everything else - l', eps, the lone predicate's literal FOR_ALL branch, the no-op rows - is relate_one_gate_fwd_kernel's.
+//     x_is_subject[p]:  prev along columns: row aggregates      (inner gate_o, outer gate_s)
+//     otherwise:        prev along rows: column aggregates      (inner gate_s, outer gate_o)
+// The column branch is gate_col_sweep's loop; the row branch is the row half of relate_gate_fwd_kernel (a column's prev, e^prev and share of
+// the pre-activations once per wavefront, the row aggregate by the group reduction, the outer gate in the lane that owns the row).  Both are
+// written out here and not taken from the shared helpers: that form measured 2 - 3 % slower at the same bits (see the top of the file).
 // ---------------------------------------------------------------------------------------------------
 template <int LPR>
 __global__ __launch_bounds__(256) void relate_keep_gate_fwd_kernel(
@@ -797,9 +850,9 @@ __global__ __launch_bounds__(256) void relate_keep_gate_fwd_kernel(
     const bool xs = x_is_subject[p] != 0;
     const GateW GI = gate_load(xs ? gate_o : gate_s), GO = gate_load(xs ? gate_s : gate_o);      // inner: prev's axis, outer: x's
     const int cg = lane % LPR, rs = lane / LPR, c0 = cg * 4, cl = min(c0, NS - 4);               // (lanes beyond the width read a valid column)
-    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
-    const float qf = quant_prev[p], kf = 1.f - 2.f * qf;
-    const bool ex = qf == 1.f, ident = identity_forall && qf == 0.f;
+    const GateNeg N = gate_neg_load(neg, any_neg, p);
+    const GateQuant Q = gate_quant_load(quant_prev, p, identity_forall);
+    const bool ex = Q.ex;
     const float* tp = tile + (int64_t)p * NS * NS;
     if (xs) {                                           // prev along columns: row aggregates
         const float4 pc4 = *reinterpret_cast<const float4*>(pv + cl);
@@ -819,8 +872,8 @@ __global__ __launch_bounds__(256) void relate_keep_gate_fwd_kernel(
             for (int j = 0; j < 4; ++j) {
                 const int c = c0 + j;
                 const bool keep = r < n && c < n && c != r;
-                const float v = gate_prep(l[j], any_neg, alpha_n, cn);
-                const float t = gate_term(gate_m(GI, v, dfol_exp(v), zbC[j], ebC[j]), ex, qf, kf);
+                const float v = gate_prep(l[j], N);
+                const float t = gate_term(gate_m(GI, v, dfol_exp(v), zbC[j], ebC[j]), Q);
                 racc = gate_join(racc, keep ? t : 0.f, ex);
             }
             racc = ex ? dfol_group_or<LPR>(racc) : dfol_group_sum<LPR>(racc);
@@ -829,7 +882,7 @@ __global__ __launch_bounds__(256) void relate_keep_gate_fwd_kernel(
         __builtin_amdgcn_wave_barrier();                 // LDS is in order within a wavefront; this only pins the schedule
         for (int c = lane; c < NS; c += 64) {
             float o = 0.f;
-            if (c < n) o = gate_log(GO, gate_outer(row_agg[wave_in_block][c], ex, ident, qf, kf), xv[c]);
+            if (c < n) o = gate_log(GO, gate_outer(row_agg[wave_in_block][c], Q), xv[c]);
             out[c] = o;
         }
         return;
@@ -847,8 +900,8 @@ __global__ __launch_bounds__(256) void relate_keep_gate_fwd_kernel(
         for (int j = 0; j < 4; ++j) {
             const int c = c0 + j;
             const bool keep = r < n && c < n && c != r;
-            const float v = gate_prep(l[j], any_neg, alpha_n, cn);
-            const float t = gate_term(gate_m(GI, v, dfol_exp(v), zb, eb), ex, qf, kf);
+            const float v = gate_prep(l[j], N);
+            const float t = gate_term(gate_m(GI, v, dfol_exp(v), zb, eb), Q);
             cacc[j] = gate_join(cacc[j], keep ? t : 0.f, ex);
         }
     }
@@ -862,71 +915,27 @@ __global__ __launch_bounds__(256) void relate_keep_gate_fwd_kernel(
         const float xj[4] = {x4.x, x4.y, x4.z, x4.w};
         float o[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (c0 + j < n) ? gate_log(GO, gate_outer(cacc[j], ex, ident, qf, kf), xj[j]) : 0.f;
+        for (int j = 0; j < 4; ++j) o[j] = (c0 + j < n) ? gate_log(GO, gate_outer(cacc[j], Q), xj[j]) : 0.f;
         *reinterpret_cast<float4*>(out + c0) = make_float4(o[0], o[1], o[2], o[3]);
     }
 }
 
-// NS > 256: one workgroup per predicate; a thread per column, rows in order, for the column aggregate, a workgroup reduction per row (wavefront
-// partials joined in wavefront order) for the row aggregate, as relate_gate_big_fwd_kernel.
+// NS > 256, as relate_gate_big_fwd_kernel
 __global__ __launch_bounds__(256) void relate_keep_gate_big_kernel(
     const float* __restrict__ x_att, const float* __restrict__ prev_att, const float* __restrict__ tile, const int32_t* __restrict__ pred_q,
     const int32_t* __restrict__ n_obj, const float* __restrict__ quant_prev, const uint8_t* __restrict__ x_is_subject,
     const uint8_t* __restrict__ neg, int any_neg, const uint8_t* __restrict__ active, int NS, int identity_forall,
     const float* __restrict__ gate_s, const float* __restrict__ gate_o, float* __restrict__ post) {
     __shared__ float part[4];
-    const int p = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    const int q = pred_q[p], n = min(n_obj[q], NS);
-    const float* pv = prev_att + (int64_t)q * NS;
-    const float* xv = x_att + (int64_t)p * NS;
-    float* out = post + (int64_t)p * NS;
-    if (active && !active[p]) {
-        for (int c = tid; c < NS; c += 256) out[c] = c < n ? pv[c] : 0.f;
+    const int p = blockIdx.x, tid = threadIdx.x;
+    GatePred<> g;
+    if (!gate_pred_load(g, p, x_att, prev_att, tile, pred_q, n_obj, quant_prev, x_is_subject, neg, any_neg, active, NS, identity_forall, gate_s,
+                        gate_o, post)) {
+        gate_passthrough(g, tid, 256);
         return;
     }
-    const bool xs = x_is_subject[p] != 0;
-    const GateW GI = gate_load(xs ? gate_o : gate_s), GO = gate_load(xs ? gate_s : gate_o);
-    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
-    const float qf = quant_prev[p], kf = 1.f - 2.f * qf;
-    const bool ex = qf == 1.f, ident = identity_forall && qf == 0.f;
-    const float* tp = tile + (int64_t)p * NS * NS;
-    if (!xs) {
-        for (int c = tid; c < NS; c += 256) {
-            float o = 0.f;
-            if (c < n) {
-                float acc = 0.f;
-                for (int r = 0; r < n; ++r) {
-                    if (r == c) continue;
-                    const float v = gate_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn);
-                    float zb[6];
-                    gate_zb(GI, pv[r], zb);
-                    acc = gate_join(acc, gate_term(gate_m(GI, v, dfol_exp(v), zb, dfol_exp(pv[r])), ex, qf, kf), ex);
-                }
-                o = gate_log(GO, gate_outer(acc, ex, ident, qf, kf), xv[c]);
-            }
-            out[c] = o;
-        }
-        return;
-    }
-    for (int r = 0; r < NS; ++r) {                       // (xs is the workgroup's: every thread reaches the barriers)
-        float s = 0.f;
-        if (r < n)
-            for (int c = tid; c < n; c += 256) {
-                if (c == r) continue;
-                const float v = gate_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn);
-                float zb[6];
-                gate_zb(GI, pv[c], zb);
-                s = gate_join(s, gate_term(gate_m(GI, v, dfol_exp(v), zb, dfol_exp(pv[c])), ex, qf, kf), ex);
-            }
-        s = gate_wave_join(s, ex);
-        if (lane == 0) part[w] = s;
-        __syncthreads();
-        if (tid == 0) {
-            const float tot = gate_join(gate_join(gate_join(part[0], part[1], ex), part[2], ex), part[3], ex);
-            out[r] = r < n ? gate_log(GO, gate_outer(tot, ex, ident, qf, kf), xv[r]) : 0.f;
-        }
-        __syncthreads();
-    }
+    if (g.xs) gate_big_rows(g, part, tid);               // (xs is the workgroup's: every thread reaches the barriers)
+    else gate_big_cols(g, tid);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -951,31 +960,28 @@ __global__ __launch_bounds__(64 * KB_WAVES) void relate_keep_gate_bwd_kernel(
     float* wsum = part_base + (size_t)nw * NS;            // [nw][36]
     auto part = [&](int wave, int c) -> float& { return part_base[wave * NS + c]; };
     const int p = blockIdx.x;
-    const int q = pred_q[p];
-    const int n = min(n_obj[q], NS);
-    const float* pv = prev_att + (int64_t)q * NS;
-    const float* xv = x_att + (int64_t)p * NS;
     const float* gp = g_post + (int64_t)p * NS;
-    const float* tp = tile + (int64_t)p * NS * NS;
     float* gt = g_tile + (int64_t)p * NS * NS;
     float* gx = g_x + (int64_t)p * NS;
     float* gpv = g_prev + (int64_t)p * NS;
     float* sc = scratch + (int64_t)p * 36;
-
-    if (active && !active[p]) {                            // posterior = prev: the gradient passes straight through, the gates see nothing
+    GatePred<> g;
+    if (!gate_pred_load(g, p, x_att, prev_att, tile, pred_q, n_obj, quant_prev, x_is_subject, neg, any_neg, active, NS, identity_forall, gate_s,
+                        gate_o, (float*)nullptr)) {        // posterior = prev: the gradient passes straight through, the gates see nothing
         for (int c = tid; c < NS; c += nt) {
-            gpv[c] = c < n ? gp[c] : 0.f;
+            gpv[c] = c < g.n ? gp[c] : 0.f;
             gx[c] = 0.f;
         }
         for (int e = tid; e < NS * NS; e += nt) gt[e] = 0.f;
         if (tid < 36) sc[tid] = 0.f;
         return;
     }
-    const bool xs = x_is_subject[p] != 0;                  // (the workgroup's: every branch on it is uniform)
-    const GateW GI = gate_load(xs ? gate_o : gate_s), GO = gate_load(xs ? gate_s : gate_o);
-    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
-    const float qf = quant_prev[p], kf = 1.f - 2.f * qf;
-    const bool ident = identity_forall && qf == 0.f;
+    const int n = g.n;
+    const float *pv = g.pv, *xv = g.xv, *tp = g.tp;
+    const bool xs = g.xs;                                  // (the workgroup's: every branch on it is uniform)
+    const GateW &GI = g.GI, &GO = g.GO;
+    const float qf = g.Q.qf, kf = g.Q.kf;
+    const bool ident = g.Q.ident;
     float accI[18], accO[18];
 #pragma unroll
     for (int k = 0; k < 18; ++k) accI[k] = accO[k] = 0.f;
@@ -991,7 +997,7 @@ __global__ __launch_bounds__(64 * KB_WAVES) void relate_keep_gate_bwd_kernel(
             for (int r = w; r < n; r += nw) {
                 float s_part = 0.f;
                 if (c < n && c != r) {
-                    const float v = gate_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn);
+                    const float v = gate_prep(tp[(int64_t)r * NS + c], g.N);
                     s_part = dfol_slog(fmaf(kf, gate_m(GI, v, dfol_exp(v), zbc, ebc), qf));
                 }
                 s_part = dfol_wave_sum(s_part);
@@ -1001,7 +1007,7 @@ __global__ __launch_bounds__(64 * KB_WAVES) void relate_keep_gate_bwd_kernel(
             float t_acc = 0.f;
             for (int r = w; r < n; r += nw) {
                 if (c < n && c != r) {
-                    const float v = gate_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn);
+                    const float v = gate_prep(tp[(int64_t)r * NS + c], g.N);
                     const float pr = pv[r];
                     float zbr[6];
                     gate_zb(GI, pr, zbr);
@@ -1045,13 +1051,13 @@ __global__ __launch_bounds__(64 * KB_WAVES) void relate_keep_gate_bwd_kernel(
                 float dl = 0.f;
                 if (r < n && c < n && c != r) {            // t = log(max(q + k m, eps)), m = e^G_in(v, prev[c])
                     const float raw = tp[(int64_t)r * NS + c];
-                    const float v = gate_prep(raw, any_neg, alpha_n, cn);
+                    const float v = gate_prep(raw, g.N);
                     const float u = fmaf(kf, gate_m(GI, v, dfol_exp(v), zbc, ebc), qf);
                     const float dm = u > DFOL_EPS ? sG[r] * kf / u : 0.f;
                     float da, db;
                     gate_bwd(GI, v, pc, dm, false, da, db, accI);
                     dpc += db;
-                    dl = da * gate_dprep(raw, any_neg, alpha_n, cn);
+                    dl = da * gate_dprep(raw, g.N);
                 }
                 if (c < NS) gt[(int64_t)r * NS + c] = dl;
             }
@@ -1062,7 +1068,7 @@ __global__ __launch_bounds__(64 * KB_WAVES) void relate_keep_gate_bwd_kernel(
                 float dl = 0.f, dpr = 0.f;
                 if (r < n && c < n && c != r) {
                     const float raw = tp[(int64_t)r * NS + c];
-                    const float v = gate_prep(raw, any_neg, alpha_n, cn);
+                    const float v = gate_prep(raw, g.N);
                     const float pr = pv[r];
                     float zbr[6];
                     gate_zb(GI, pr, zbr);
@@ -1070,7 +1076,7 @@ __global__ __launch_bounds__(64 * KB_WAVES) void relate_keep_gate_bwd_kernel(
                     const float dm = u > DFOL_EPS ? gcc * kf / u : 0.f;
                     float da;
                     gate_bwd(GI, v, pr, dm, false, da, dpr, accI);
-                    dl = da * gate_dprep(raw, any_neg, alpha_n, cn);
+                    dl = da * gate_dprep(raw, g.N);
                 }
                 if (c < NS) gt[(int64_t)r * NS + c] = dl;
                 dpr = dfol_wave_sum(dpr);                  // row totals over the column chunks collect in LDS
@@ -1078,16 +1084,13 @@ __global__ __launch_bounds__(64 * KB_WAVES) void relate_keep_gate_bwd_kernel(
             }
         }
     }
-    // the parameter sums of this workgroup: wavefront totals, then the wavefronts in order; axis 0's gate first
+    float acc0[18], acc1[18];                              // axis 0's gate first
 #pragma unroll
     for (int k = 0; k < 18; ++k) {
-        const float a = dfol_wave_sum(xs ? accO[k] : accI[k]), b = dfol_wave_sum(xs ? accI[k] : accO[k]);
-        if (lane == 0) {
-            wsum[w * 36 + k] = a;
-            wsum[w * 36 + 18 + k] = b;
-        }
+        acc0[k] = xs ? accO[k] : accI[k];
+        acc1[k] = xs ? accI[k] : accO[k];
     }
-    __syncthreads();
+    gate_param_sums(acc0, acc1, wsum, sc);                 // (its barrier also publishes sweep 2's sA and part)
     for (int c = tid; c < NS; c += nt) {
         float t = 0.f;
         if (c < n) {
@@ -1100,19 +1103,6 @@ __global__ __launch_bounds__(64 * KB_WAVES) void relate_keep_gate_bwd_kernel(
         }
         gpv[c] = t;
     }
-    if (tid < 36) {
-        float s = wsum[tid];
-        for (int j = 1; j < nw; ++j) s += wsum[j * 36 + tid];
-        sc[tid] = s;
-    }
-}
-
-template <int LPR>
-void launch_relate_gate(hipStream_t st, const float* pR, const float* pC, const float* tile, const int32_t* pred_q, const int32_t* n_obj,
-                        const float* qR, const float* qC, const uint8_t* neg, int any_neg, const uint8_t* active, const uint8_t* want, int bR,
-                        int bC, int P, int NS, int flags, const float* gR, const float* gC, float* oR, float* oC) {
-    hipLaunchKernelGGL(relate_gate_fwd_kernel<LPR>, dim3(dfol_cdiv(P, 4)), dim3(256), 0, st, pR, pC, tile, pred_q, n_obj, qR, qC, neg, any_neg,
-                       active, want, bR, bC, P, NS, flags, gR, gC, oR, oC);
 }
 
 }      // namespace
@@ -1181,17 +1171,10 @@ extern "C" int dfol_relate_gate_fwd_f32(const float* prior_s, const float* prior
         DFOL_LAUNCH_CHECK("relate_gate_fwd (NS > 256)");
         return 0;
     }
-    const int groups = NS / 4;
-#define DFOL_GATE_CASE(L) \
-    launch_relate_gate<L>(st, pR, pC, tile, pred_q, n_obj, qR, qC, neg, any_neg, active, want, bR, bC, P, NS, flags, gR, gC, oR, oC)
-    if (groups <= 1) DFOL_GATE_CASE(1);
-    else if (groups <= 2) DFOL_GATE_CASE(2);
-    else if (groups <= 4) DFOL_GATE_CASE(4);
-    else if (groups <= 8) DFOL_GATE_CASE(8);
-    else if (groups <= 16) DFOL_GATE_CASE(16);
-    else if (groups <= 32) DFOL_GATE_CASE(32);
-    else DFOL_GATE_CASE(64);
-#undef DFOL_GATE_CASE
+    dfol_dispatch_lpr(NS / 4, [&](auto lpr) {
+        hipLaunchKernelGGL(relate_gate_fwd_kernel<decltype(lpr)::value>, dim3(dfol_cdiv(P, 4)), dim3(256), 0, st, pR, pC, tile, pred_q, n_obj, qR, qC, neg,
+                           any_neg, active, want, bR, bC, P, NS, flags, gR, gC, oR, oC);
+    });
     DFOL_LAUNCH_CHECK("relate_gate_fwd");
     return 0;
 }
@@ -1212,18 +1195,10 @@ extern "C" int dfol_relate_one_gate_fwd_f32(const float* x_att, const float* pre
         DFOL_LAUNCH_CHECK("relate_one_gate_fwd (NS > 256)");
         return 0;
     }
-    const int groups = NS / 4;
-#define DFOL_GATE1(L)                                                                                                                          \
-    hipLaunchKernelGGL(relate_one_gate_fwd_kernel<L>, dim3(dfol_cdiv(P, 4)), dim3(256), 0, st, x_att, prev_att, tile, pred_q, n_obj, quant_prev, \
-                       x_is_subject, neg, any_neg, active, P, NS, lone_forall_identity, gate_s, gate_o, post)
-    if (groups <= 1) DFOL_GATE1(1);
-    else if (groups <= 2) DFOL_GATE1(2);
-    else if (groups <= 4) DFOL_GATE1(4);
-    else if (groups <= 8) DFOL_GATE1(8);
-    else if (groups <= 16) DFOL_GATE1(16);
-    else if (groups <= 32) DFOL_GATE1(32);
-    else DFOL_GATE1(64);
-#undef DFOL_GATE1
+    dfol_dispatch_lpr(NS / 4, [&](auto lpr) {
+        hipLaunchKernelGGL(relate_one_gate_fwd_kernel<decltype(lpr)::value>, dim3(dfol_cdiv(P, 4)), dim3(256), 0, st, x_att, prev_att, tile, pred_q,
+                           n_obj, quant_prev, x_is_subject, neg, any_neg, active, P, NS, lone_forall_identity, gate_s, gate_o, post);
+    });
     DFOL_LAUNCH_CHECK("relate_one_gate_fwd");
     return 0;
 }
@@ -1238,17 +1213,10 @@ extern "C" int dfol_relate_one_gate_fwd_bf16(const float* x_att, const float* pr
                  "relate_one_gate_fwd_bf16: null pointer");
     DFOL_REQUIRE(!any_neg || neg, "relate_one_gate_fwd_bf16: any_neg set but neg is NULL");
     hipStream_t st = (hipStream_t)stream;
-    const int groups = NS / 8;
-#define DFOL_GATE1B(L)                                                                                                                          \
-    hipLaunchKernelGGL(relate_one_gate_bf16_kernel<L>, dim3(dfol_cdiv(P, 4)), dim3(256), 0, st, x_att, prev_att, tile, pred_q, n_obj, quant_prev, \
-                       x_is_subject, neg, any_neg, active, P, NS, lone_forall_identity, gate_s, gate_o, post)
-    if (groups <= 1) DFOL_GATE1B(1);
-    else if (groups <= 2) DFOL_GATE1B(2);
-    else if (groups <= 4) DFOL_GATE1B(4);
-    else if (groups <= 8) DFOL_GATE1B(8);
-    else if (groups <= 16) DFOL_GATE1B(16);
-    else DFOL_GATE1B(32);
-#undef DFOL_GATE1B
+    dfol_dispatch_lpr<32>(NS / 8, [&](auto lpr) {
+        hipLaunchKernelGGL(relate_one_gate_bf16_kernel<decltype(lpr)::value>, dim3(dfol_cdiv(P, 4)), dim3(256), 0, st, x_att, prev_att, tile, pred_q,
+                           n_obj, quant_prev, x_is_subject, neg, any_neg, active, P, NS, lone_forall_identity, gate_s, gate_o, post);
+    });
     DFOL_LAUNCH_CHECK("relate_one_gate_fwd_bf16");
     return 0;
 }
@@ -1301,18 +1269,10 @@ extern "C" int dfol_relate_keep_gate_fwd_f32(const float* x_att, const float* pr
         DFOL_LAUNCH_CHECK("relate_keep_gate_fwd (NS > 256)");
         return 0;
     }
-    const int groups = NS / 4;
-#define DFOL_GATEK(L)                                                                                                                           \
-    hipLaunchKernelGGL(relate_keep_gate_fwd_kernel<L>, dim3(dfol_cdiv(P, 4)), dim3(256), 0, st, x_att, prev_att, tile, pred_q, n_obj, quant_prev, \
-                       x_is_subject, neg, any_neg, active, P, NS, lone_forall_identity, gate_s, gate_o, post)
-    if (groups <= 1) DFOL_GATEK(1);
-    else if (groups <= 2) DFOL_GATEK(2);
-    else if (groups <= 4) DFOL_GATEK(4);
-    else if (groups <= 8) DFOL_GATEK(8);
-    else if (groups <= 16) DFOL_GATEK(16);
-    else if (groups <= 32) DFOL_GATEK(32);
-    else DFOL_GATEK(64);
-#undef DFOL_GATEK
+    dfol_dispatch_lpr(NS / 4, [&](auto lpr) {
+        hipLaunchKernelGGL(relate_keep_gate_fwd_kernel<decltype(lpr)::value>, dim3(dfol_cdiv(P, 4)), dim3(256), 0, st, x_att, prev_att, tile, pred_q,
+                           n_obj, quant_prev, x_is_subject, neg, any_neg, active, P, NS, lone_forall_identity, gate_s, gate_o, post);
+    });
     DFOL_LAUNCH_CHECK("relate_keep_gate_fwd");
     return 0;
 }
