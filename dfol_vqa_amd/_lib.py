@@ -190,6 +190,8 @@ SIGNATURES = {
     "dfol_linear_wgrad_bias_rows_bf16": [_p, _i64, _p, _i64, _p, _i64, _i32, _i32, _p, _p, _p, _p],
     "dfol_linear_wgrad_rows_bf16t_supported": [_i32, _i32, _i64, _i64],
     "dfol_linear_wgrad_bias_rows_bf16t": [_p, _i64, _p, _i64, _p, _i64, _i32, _i32, _p, _p, _p, _p],
+    "dfol_linear_wgrad_rows_bf16t_x3_supported": [_i32, _i32, _i64, _i64],
+    "dfol_linear_wgrad_bias_rows_bf16t_x3": [_p, _i64, _p, _i64, _p, _i64, _i32, _i32, _p, _p, _p, _p],
     "dfol_linear_rows_bf16t_supported": [_i32, _i32, _i64],            # returns 0 / 1
     "dfol_linear_act_rows_bf16t_f32": [_p, _i64, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _i32, _p],
     "dfol_act_bwd_f32": [_p, _p, _i64, _i32, _p, _p],
@@ -1054,6 +1056,39 @@ def linear_wgrad_rows(dy, table, src_row, bias=False):
     if ws is not None:
         call("dfol_linear_wgrad_bias_rows_bf16t" if bf16t else "dfol_linear_wgrad_bias_rows_bf16" if bf16 else "dfol_linear_wgrad_bias_rows_f32", _dp(dy), dy.stride(0), _dp(table), table.stride(0),
              _ptr(src_row, I32), M, N, K, _ptr(ws), _ptr(dw), _ptr(db, F32, True), _stream())
+    return (dw, db) if bias else dw
+
+
+def store_bf16_train():
+    """DFOL_STORE_BF16_TRAIN=1 (opt-in, read when a forward starts): a featurizer that TRAINS in the default arithmetic ("f16x2") reads a bf16
+    feature store's rows in place, forward (linear_wide_rows_bf16t) and first-layer weight gradient (linear_wgrad_rows_bf16t_x3), instead of
+    the gathered, widened matrix - the same bits.  Unset: every route as before."""
+    return os.environ.get("DFOL_STORE_BF16_TRAIN", "0") == "1"
+
+
+def linear_wgrad_rows_bf16t_x3_supported(N, K, ld_dy, ld_table):
+    """dfol_linear_wgrad_rows_bf16t_x3_supported: linear_wgrad_rows_bf16t_x3 exists for the shape over a bf16 table of row stride ld_table
+    (elements) - never under DFOL_WGRAD_MATH=f32."""
+    return bool(load().dfol_linear_wgrad_rows_bf16t_x3_supported(int(N), int(K), int(ld_dy), int(ld_table)))
+
+
+def linear_wgrad_rows_bf16t_x3(dy, table, src_row, bias=False):
+    """The default arithmetic's linear_wgrad over the indexed rows of a bf16 table: dW [N, K] = dy^T table[src_row] for dy [M, N] fp32, table
+    [rows, K] bfloat16 (a bf16 feature store's features as a matrix), src_row [M] int32; bias=True: (dW, db).  Bit for bit what linear_wgrad(dy,
+    table.float()[src_row]) gives in "f16x2" on its bf16-pipe kernel, without the gathered copy: dy in three bf16 pieces, a table value its own
+    one piece, three products (csrc/dfol_dense_wgrad.hip).  Shapes linear_wgrad_rows_bf16t_x3_supported does not take are refused."""
+    M, N = dy.shape
+    K = table.shape[1]
+    if not dy.is_cuda or not table.is_cuda or dy.dtype != F32 or table.dtype != torch.bfloat16 or dy.stride(1) != 1 or table.stride(1) != 1:
+        raise DfolError("linear_wgrad_rows_bf16t_x3 needs an fp32 GPU matrix and a bfloat16 GPU table with unit column stride")
+    if src_row.numel() != M:
+        raise DfolError("linear_wgrad_rows_bf16t_x3: src_row has %d entries for %d rows of dy" % (src_row.numel(), M))
+    ws, dw, db, bf16 = _linear_wgrad_buffers(dy.device, M, N, K, bias)
+    if bf16:
+        raise DfolError("linear_wgrad_rows_bf16t_x3: the bf16 mode applies to this layer (weight [%d, %d]): its form is linear_wgrad_rows" % (N, K))
+    if ws is not None:
+        call("dfol_linear_wgrad_bias_rows_bf16t_x3", _dp(dy), dy.stride(0), _dp(table), table.stride(0), _ptr(src_row, I32), M, N, K, _ptr(ws), _ptr(dw),
+             _ptr(db, F32, True), _stream())
     return (dw, db) if bias else dw
 
 

@@ -383,11 +383,16 @@ __device__ __forceinline__ u32x4 w3_gather8(uint32_t w0, uint32_t w1, uint32_t w
 // ROWS form's 64-bit address, assembled into operand registers as the bf16-storage form below does it: the table holds what w3_rne8 makes of
 // an fp32 feature, so every operand register has the bits the first form builds from the gathered, widened rows.  A row past the range
 // loads neither its index nor the table and counts as zero.
+// NP = 3 is the DEFAULT arithmetic over the same table (dfol_linear_wgrad_bias_rows_bf16t_x3): dY split by w3_split8 as in the first form, X
+// as above.  A value out of a bf16 table is its own h piece - what w3_split8 makes of the widened value is (x, 0, 0) - so of the six products
+// of PA6 / PB6 the three whose B piece is m or l multiply by zero and are not issued; the other three keep their order: l*h, m*h, h*h.  An
+// accumulator that starts at +0 and has only +-0 added stays +0 (round to nearest: x + -x = +0, and -0 comes only of -0 + -0), so dropping
+// them changes no bit of the first form's result over the gathered, widened rows.  12 AV MFMAs per step, no B-side split, half the X bytes.
 template <int AV, int NP, bool ROWS = false>
 __device__ __forceinline__ void wgrad_tn3_accumulate(const float* __restrict__ dY, int64_t ld_dy, const uint16_t* __restrict__ X, int64_t ld_x,
                                                      const int32_t* __restrict__ src_row, int rows, int steps, int N, int K, int n0, int k0,
                                                      int lane, bool want_bias, f32x16 (&acc)[AV][4], float (&bs)[AV]) {
-    static_assert(NP == 1 && ROWS, "a bf16 table under fp32 gradients is the bf16 mode's indexed form");
+    static_assert((NP == 1 || NP == 3) && ROWS, "a bf16 table under fp32 gradients is an indexed form: the bf16 mode's, or the three-piece dY's");
     const int col = lane & 31, half = lane >> 5;
     const int ca = min(n0 + AV * col, N - AV), cb = min(k0 + 4 * col, K - 4);
     int va[8];
@@ -434,7 +439,7 @@ __device__ __forceinline__ void wgrad_tn3_accumulate(const float* __restrict__ d
     index(1);
     __builtin_amdgcn_sched_barrier(0);
     for (int s = 0; s < steps; ++s) {
-        u32x4 ap[AV], bp[4];
+        u32x4 ap[AV][NP], bp[4];
         if (want_bias) {
 #pragma unroll
             for (int t = 0; t < AV; ++t)
@@ -445,7 +450,8 @@ __device__ __forceinline__ void wgrad_tn3_accumulate(const float* __restrict__ d
             float v[8];
 #pragma unroll
             for (int r = 0; r < 8; ++r) v[r] = ra[r][t];
-            ap[t] = w3_rne8(v);
+            if constexpr (NP == 1) ap[t][0] = w3_rne8(v);
+            else w3_split8(v, ap[t][0], ap[t][1], ap[t][2]);
             __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
@@ -459,7 +465,9 @@ __device__ __forceinline__ void wgrad_tn3_accumulate(const float* __restrict__ d
         for (int u = 0; u < 4; ++u)
 #pragma unroll
             for (int t = 0; t < AV; ++t)
-                acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ap[t]), __builtin_bit_cast(bf16x8, bp[u]), acc[t][u], 0, 0, 0);
+#pragma unroll
+                for (int x = NP - 1; x >= 0; --x)                                 // (A piece l, m, h against the table's value: its own h piece)
+                    acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ap[t][x]), __builtin_bit_cast(bf16x8, bp[u]), acc[t][u], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -852,6 +860,27 @@ extern "C" int dfol_linear_wgrad_bias_rows_bf16t(const float* dY, int64_t ld_dy,
     DFOL_REQUIRE((uintptr_t)X_table_bf16 % 8 == 0 && (uintptr_t)src_row % 4 == 0, "linear_wgrad_rows_bf16t: the table must be 8-byte and the index 4-byte aligned");
     return wgrad_tn3_run<1, float, true, uint16_t>("linear_wgrad_rows_bf16t", dY, ld_dy, (const uint16_t*)X_table_bf16, ld_table, src_row, M, N, K, workspace,
                                                    dW, db, (hipStream_t)stream);
+}
+
+// The DEFAULT arithmetic's weight gradient over the indexed rows of a bf16 TABLE: dY fp32 in three bf16 pieces, the table's values their own
+// one piece, three products per pair (wgrad_tn3_accumulate, NP = 3 over uint16_t X).  Bit for bit dfol_linear_wgrad_bias_f32 over the gathered
+// rows widened to fp32 where that runs the bf16-pipe kernel; slabs, workspace layout and reductions are that launch path's.  The fp32 pipe
+// (DFOL_WGRAD_MATH=f32) has no indexed form: the predicate says 0 and the entry point refuses.
+extern "C" int dfol_linear_wgrad_rows_bf16t_x3_supported(int32_t N, int32_t K, int64_t ld_dy, int64_t ld_table) {
+    return wgrad_rows_bf16t_refusal(N, K, ld_dy, ld_table) == nullptr && !wgrad_f32_pipe_asked();
+}
+
+extern "C" int dfol_linear_wgrad_bias_rows_bf16t_x3(const float* dY, int64_t ld_dy, const void* X_table_bf16, int64_t ld_table, const int32_t* src_row,
+                                                    int64_t M, int32_t N, int32_t K, float* workspace, float* dW, float* db, void* stream) {
+    DFOL_REQUIRE(M > 0 && M < (1ll << 31) && N > 0 && K > 0, "linear_wgrad_rows_bf16t_x3: bad sizes M=%lld N=%d K=%d", (long long)M, N, K);
+    DFOL_REQUIRE(dY && X_table_bf16 && src_row && workspace && dW, "linear_wgrad_rows_bf16t_x3: null pointer");
+    const char* why = wgrad_rows_bf16t_refusal(N, K, ld_dy, ld_table);
+    if (!why && wgrad_f32_pipe_asked()) why = "DFOL_WGRAD_MATH=f32 asks for the fp32 matrix pipe, which has no indexed form";
+    DFOL_REQUIRE(!why, "linear_wgrad_rows_bf16t_x3: %s (N=%d K=%d ld_dy=%lld ld_table=%lld)", why, N, K, (long long)ld_dy, (long long)ld_table);
+    DFOL_REQUIRE((uintptr_t)dY % 16 == 0, "linear_wgrad_rows_bf16t_x3: dY rows must be 16-byte aligned (dY=%p)", (const void*)dY);
+    DFOL_REQUIRE((uintptr_t)X_table_bf16 % 8 == 0 && (uintptr_t)src_row % 4 == 0, "linear_wgrad_rows_bf16t_x3: the table must be 8-byte and the index 4-byte aligned");
+    return wgrad_tn3_run<3, float, true, uint16_t>("linear_wgrad_rows_bf16t_x3", dY, ld_dy, (const uint16_t*)X_table_bf16, ld_table, src_row, M, N, K,
+                                                   workspace, dW, db, (hipStream_t)stream);
 }
 
 // bf16 mode with bf16 STORAGE of both operands (the per-pair activations dpre2 [M, N] and Z [M, K] as bfloat16, rows 4-byte / 8-byte

@@ -23,7 +23,10 @@ dfol_linear_wgrad_bias_rows_bf16t) and no result bit changes; every other consum
 read when a forward starts) the default arithmetic's inference reads the table in place as well: the wide kernel widens each stored value
 exactly and splits it into the two fp16 pieces the matrix route would have built (dfol_linear_wide_rows_bf16t_h2_f32), so the matrix is never
 written and no result bit changes - still on the ROUNDED features; a store whose every value is an fp16 value (`f16_exact`, one pass over the
-table on first use) gets the two-product form of that kernel, again with the same bits; a featurizer that trains and every other arithmetic keep the matrix.
+table on first use) gets the two-product form of that kernel, again with the same bits.  With DFOL_STORE_BF16_TRAIN=1 (opt-in, read the same way) a featurizer that
+TRAINS in the default arithmetic without an active Dropout reads the table in place too: the same forward product, and a weight gradient whose
+dY keeps its three bf16 pieces while a table value is its own one piece (dfol_linear_wgrad_bias_rows_bf16t_x3: three products, not six) - the
+matrix route's bits, no `[O, F + 6]` matrix.  Every other arithmetic, an active Dropout and DFOL_WGRAD_MATH=f32 keep the matrix.
 
 Three kinds of object, by who may hold them:
   DeviceFeatureStore   main process only: the device tensors, `gather`.  Registers itself by id in this process' table.
@@ -291,7 +294,7 @@ class DeviceFeatureStore(object):
     @property
     def f16_exact(self):
         """A bf16 store's certificate that every feature it holds is finite and an fp16 value (dfol_store_bf16_is_f16): the wide kernel's
-        two-product form then gives the three-product bits.  Computed on first use - under DFOL_STORE_BF16_DIRECT=1 when the first batch's rows
+        two-product form then gives the three-product bits.  Computed on first use - under DFOL_STORE_BF16_DIRECT=1 or DFOL_STORE_BF16_TRAIN=1 when the first batch's rows
         are resolved, never at construction - and cached: the table does not change after upload.  False for an fp32 store.  Not inside a
         stream capture (it waits for the device)."""
         if self._f16_exact is None:
@@ -419,7 +422,7 @@ class DeviceFeatureStore(object):
         out=: an existing StoreRows of this store with the same image and object counts, rewritten in place - how the owner of a captured forward
         serves a new scene BETWEEN replays: like upload_index, not inside a stream capture.  index=: an earlier upload_index(ref)."""
         check_row_space(self.S, self.max_obj)
-        if self.feature_dtype == "bf16" and self._f16_exact is None and _lib.store_bf16_direct():
+        if self.feature_dtype == "bf16" and self._f16_exact is None and (_lib.store_bf16_direct() or _lib.store_bf16_train()):
             self.f16_exact                                 # (the certificate, here and not in a forward: a captured one cannot wait for the device)
         O, I = int(ref.counts.sum(dtype=np.int64)), len(ref.slots)
         idx = self.upload_index(ref) if index is None else index

@@ -54,14 +54,16 @@ def store_layers_of(net, F, M, bf16_ld=None):
     the bf16 arithmetic's: `mlp_math: bf16`, whose first product rounds a feature to the value the table holds, on a weight of the split
     kernels' size, any M (dfol_linear_rows_bf16t_supported).  With DFOL_STORE_BF16_DIRECT=1 a bf16 table also says yes to the two-piece fp16
     arithmetic of a featurizer that does not train, where the wide kernel splits the table's rows in place
-    (dfol_linear_wide_rows_bf16t_supported: the fp32 table's question and rows the kernel can load); the dense arithmetic tells the two apart."""
+    (dfol_linear_wide_rows_bf16t_supported: the fp32 table's question and rows the kernel can load); the dense arithmetic tells the two apart.
+    With DFOL_STORE_BF16_TRAIN=1 the same holds for a featurizer that TRAINS in that arithmetic (the forward is the same product; the caller,
+    BatchGQABoxFeaturizer._store_train_layers, asks for the weight gradient's form besides: dfol_linear_wgrad_rows_bf16t_x3_supported)."""
     from . import _lib, native_exec
     if net is None or getattr(net, "_network", None) is None or not hasattr(net, "output_width"):
         return None, "the featurizer has no network"
     layers = native_exec._layers(net._network)
     if not layers:
         return None, "the featurizer network is not a chain of Linear layers and activations (or a Dropout is active)"
-    h2 = bf16_ld is not None and _lib.store_bf16_direct() and _lib._dense_math() == "f16x2" and not featurizer_trains(net)
+    h2 = bf16_ld is not None and _lib._dense_math() == "f16x2" and (_lib.store_bf16_train() if featurizer_trains(net) else _lib.store_bf16_direct())
     want = "f16x2" if bf16_ld is None or h2 else "bf16"
     if _lib._dense_math() != want:
         return None, "the dense arithmetic is %r, not %r" % (_lib._dense_math(), want)
@@ -105,7 +107,8 @@ class BatchGQABoxFeaturizer(nn.Module):
     def _store_train_layers(self, rows):
         """The same layers when the featurizer TRAINS and its first layer can run as visual_oracle.StoreRowsLinear: forward as on the inference
         route (so store_layers_of decides - an active Dropout, another arithmetic, a narrow first layer or a small batch say no), and a weight
-        gradient that reads the table through src_row too (dfol_linear_wgrad_rows_supported; dz is a contiguous [O, N]).  None: the matrix."""
+        gradient that reads the table through src_row too (dfol_linear_wgrad_rows_supported; dz is a contiguous [O, N]).  A bf16 table in the
+        default arithmetic (DFOL_STORE_BF16_TRAIN=1, what store_layers_of admitted) asks dfol_linear_wgrad_rows_bf16t_x3_supported.  None: the matrix."""
         from . import _lib
         net = self._featurizer_network
         if rows.O == 0 or rows.table is None or net is None or not featurizer_trains(net) or active_dropout(net) is not None:
@@ -114,7 +117,10 @@ class BatchGQABoxFeaturizer(nn.Module):
         if layers is None:
             return None
         N, K = layers[0][0].weight.shape
-        return layers if _lib.linear_wgrad_rows_supported(N, K, N, rows.table.stride(0), bf16_table=getattr(rows, "bf16_ld", None) is not None) else None
+        bf16t = getattr(rows, "bf16_ld", None) is not None
+        if bf16t and _lib._dense_math() == "f16x2":
+            return layers if _lib.linear_wgrad_rows_bf16t_x3_supported(N, K, N, rows.table.stride(0)) else None
+        return layers if _lib.linear_wgrad_rows_supported(N, K, N, rows.table.stride(0), bf16_table=bf16t) else None
 
     def _cached_objects(self, rows):
         """The object matrix of a `featurized` store's batch from the store's cached featurizer rows (feature_store.DeviceFeatureStore.featurize:
@@ -166,7 +172,8 @@ class BatchGQABoxFeaturizer(nn.Module):
                 from .visual_oracle import StoreRowsLinear
                 rows = objects_list
                 lin, act = layers[0]
-                f = StoreRowsLinear.apply(lin.weight, lin.bias, rows.table, rows.src_row, act)
+                bf16_x3 = getattr(rows, "bf16_ld", None) is not None and _lib._dense_math() == "f16x2"     # (DFOL_STORE_BF16_TRAIN=1: what was admitted)
+                f = StoreRowsLinear.apply(lin.weight, lin.bias, rows.table, rows.src_row, act, bf16_x3 and rows.store._f16_exact is True)
                 for lin, act in layers[1:]:
                     f = L.linear_act(f, lin.weight, lin.bias, act)
                 D = f.size(1) + 4
@@ -175,6 +182,8 @@ class BatchGQABoxFeaturizer(nn.Module):
                 L.box_positions(rows.box6, obj, D - 4)
                 _lib.note("feature_store_direct")                 # (a batch whose featurizer read the store in place ...
                 _lib.note("feature_store_direct_train")           # ... and, of those, one whose weight gradient will too)
+                if bf16_x3:
+                    _lib.note("feature_store_direct_train_bf16_x3")
                 return self._with_pairs(obj, D, rows.O, world_geometry)
             objects_list = objects_list.materialize()             # a Dropout that drops, another arithmetic, a narrow first layer, a small batch: the matrix
             _lib.note("feature_store_direct_materialized")

@@ -87,13 +87,23 @@ class StoreRowsLinear(torch.autograd.Function):
     the bf16-table entry point from the table's dtype likewise).  Backward: the activation's backward as the trained dense layer does it
     (torch_ops._linear_backward), then dW, db = linear_wgrad_rows: the weight-gradient kernel forms an X row's address through src_row and is
     otherwise the matrix kernel, so every result has the bits of the dense layer over the materialised matrix.  The features are data: no
-    gradient for the table.  Saved: y, src_row and the table's handle - never an [O, F] matrix."""
+    gradient for the table.  Saved: y, src_row and the table's handle - never an [O, F] matrix.
+    A bf16 table in the DEFAULT arithmetic ("f16x2", DFOL_STORE_BF16_TRAIN=1): forward linear_wide_rows_bf16t - `f16_exact`: the store's
+    certificate holds, the two-product form, the same bits - and backward linear_wgrad_rows_bf16t_x3; the rest of the node is the same."""
+
+    class _Certified(object):                                # (what linear_wide_rows_bf16t reads of a store: its certificate)
+        f16_exact = True
 
     @staticmethod
-    def forward(ctx, weight, bias, table, src_row, act):
+    def forward(ctx, weight, bias, table, src_row, act, f16_exact=False):
         w = weight.detach()
-        product = _lib.linear_rows_bf16t if table.dtype == torch.bfloat16 else _lib.linear_wide_rows
-        y = product(table, src_row, w, None if bias is None else bias.detach(), act)
+        ctx.bf16_x3 = table.dtype == torch.bfloat16 and _lib._dense_math() == "f16x2"
+        if ctx.bf16_x3:
+            y = _lib.linear_wide_rows_bf16t(table, src_row, w, None if bias is None else bias.detach(), act,
+                                            store=StoreRowsLinear._Certified if f16_exact else None)
+        else:
+            product = _lib.linear_rows_bf16t if table.dtype == torch.bfloat16 else _lib.linear_wide_rows
+            y = product(table, src_row, w, None if bias is None else bias.detach(), act)
         ctx.save_for_backward(y, src_row, table)
         ctx.act, ctx.has_bias, ctx.math = act, bias is not None, _lib._dense_math()
         return y
@@ -117,8 +127,8 @@ class StoreRowsLinear(torch.autograd.Function):
         gw = gb = None
         if ctx.needs_input_grad[0] or (ctx.has_bias and ctx.needs_input_grad[1]):
             with _lib.dense_math(ctx.math):
-                gw, gb = _lib.linear_wgrad_rows(dz.contiguous(), table, src_row, bias=True)
-        return (gw if ctx.needs_input_grad[0] else None), (gb if ctx.has_bias and ctx.needs_input_grad[1] else None), None, None, None
+                gw, gb = (_lib.linear_wgrad_rows_bf16t_x3 if ctx.bf16_x3 else _lib.linear_wgrad_rows)(dz.contiguous(), table, src_row, bias=True)
+        return (gw if ctx.needs_input_grad[0] else None), (gb if ctx.has_bias and ctx.needs_input_grad[1] else None), None, None, None, None
 
 
 class EmbeddingLayer(nn.Module):

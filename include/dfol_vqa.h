@@ -58,7 +58,8 @@ extern "C" {
  * dfol_relate_one_gate_fwd_bf16 and DFOL_TILE_BF16 as DFOL_OP_RELATE_ONE_GATE's tile dtype (an older library refuses that operand), and the
  * one-posterior Relate of the ungated train step: dfol_relate_keep_fwd_f32 and dfol_relate_keep_bwd_f32, and the default arithmetic over a bf16
  * table in place: dfol_linear_wide_rows_bf16t_supported, dfol_linear_wide_rows_bf16t_h2_f32 and dfol_set_feature_rows_bf16_h2, with
- * dfol_store_bf16_is_f16, dfol_linear_wide_rows_bf16t_f16_h2_f32 and dfol_set_feature_rows_bf16_h2_f16 for a table of fp16 values;
+ * dfol_store_bf16_is_f16, dfol_linear_wide_rows_bf16t_f16_h2_f32 and dfol_set_feature_rows_bf16_h2_f16 for a table of fp16 values, and the
+ * default arithmetic's weight gradient over it: dfol_linear_wgrad_rows_bf16t_x3_supported and dfol_linear_wgrad_bias_rows_bf16t_x3;
  * a caller that needs them checks for the symbol, and a table that names an opcode an older library lacks is refused by it ("unknown opcode"). */
 #define DFOL_ABI_VERSION 3
 
@@ -837,6 +838,14 @@ int dfol_linear_wgrad_bias_rows_bf16(const float* dY, int64_t ld_dy, const float
 int dfol_linear_wgrad_rows_bf16t_supported(int32_t N, int32_t K, int64_t ld_dy, int64_t ld_table);
 int dfol_linear_wgrad_bias_rows_bf16t(const float* dY, int64_t ld_dy, const void* X_table_bf16, int64_t ld_table, const int32_t* src_row, int64_t M,
                                       int32_t N, int32_t K, float* workspace, float* dW, float* db, void* stream);
+/* ... over the indexed rows of a bf16 TABLE in the DEFAULT arithmetic: dY fp32 in its three bf16 pieces as dfol_linear_wgrad_bias_f32 splits
+ * it, a table value its own one piece (the other two are zero and their products are not issued: three products per pair, not six); bit
+ * for bit dfol_linear_wgrad_bias_f32 over the gathered rows widened to fp32, for finite inputs.  The conditions are
+ * dfol_linear_wgrad_rows_bf16t_supported's, and DFOL_WGRAD_MATH=f32 is refused as dfol_linear_wgrad_rows_supported refuses it (the fp32 pipe
+ * has no indexed form).  Same workspace. */
+int dfol_linear_wgrad_rows_bf16t_x3_supported(int32_t N, int32_t K, int64_t ld_dy, int64_t ld_table);
+int dfol_linear_wgrad_bias_rows_bf16t_x3(const float* dY, int64_t ld_dy, const void* X_table_bf16, int64_t ld_table, const int32_t* src_row, int64_t M,
+                                         int32_t N, int32_t K, float* workspace, float* dW, float* db, void* stream);
 /* ... with both operands STORED as bfloat16 (dpre2 [M, N] and Z [M, K] of the bf16 mode; ld in elements, multiples of 4; N, K multiples
  * of 4): no rounding left to do, one product, fp32 accumulation, fp32 dW and db.  Same workspace. */
 int dfol_linear_wgrad_bias_bf16_bf16(const void* dY_bf16, int64_t ld_dy, const void* X_bf16, int64_t ld_x, int64_t M, int32_t N, int32_t K,

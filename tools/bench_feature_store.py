@@ -36,7 +36,13 @@ process: the featurizer's first product with what runs in front of it (dfol_gath
 widened matrix against dfol_store_rows_f32 + dfol_linear_wide_rows_bf16t_h2_f32 over the table), the rate of `--batches` unseen batches
 (collated on the host beforehand; upload, forward and read-back are timed), the peak device memory of a pass, and "same bits" for each pair.
 
-usage: python tools/bench_feature_store.py [--leg stream|train|bf16|bf16-direct] [--images 2048] [--objects 100] [--features 2048] [--batch 256] [--batches 24] [--runs 4]
+`--leg bf16-train` is the train step in the DEFAULT arithmetic over the bf16 store, DFOL_STORE_BF16_TRAIN unset against set, alternating in one
+process: the first-layer forward with what runs in front of it (gather + product over the widened matrix against dfol_store_rows_f32 + the
+in-place product), the weight gradient alone (dfol_linear_wgrad_bias_f32 over the matrix against dfol_linear_wgrad_bias_rows_bf16t_x3 over the
+table), replayed GraphedTrainStep steps of `--batch` questions x `--objects` objects (each route trains a copy of the model from the same state:
+"same bits" compares the copies after the same number of steps), and the peak device memory of each route's upload, warm-up and capture.
+
+usage: python tools/bench_feature_store.py [--leg stream|train|bf16|bf16-direct|bf16-train][--images 2048] [--objects 100] [--features 2048] [--batch 256] [--batches 24] [--runs 4]
                                            [--workers 5] [--steps 20]
 """
 import argparse
@@ -403,11 +409,154 @@ def bf16_direct_leg(args):
             "routes": {"switch_off": counts[False], "switch_on": counts[True]}}
 
 
+def bf16_train_leg(args):
+    """The default arithmetic's train step over a bf16 store, DFOL_STORE_BF16_TRAIN unset against set (see the module's docstring) -> the result
+    dictionary."""
+    from dfol_vqa_amd import _lib, training
+    import bench
+    device = torch.device("cuda", 0)
+    tmp = tempfile.mkdtemp(prefix="dfol_store_bf16_train_bench_")
+    for k in ("DFOL_STORE_BF16_TRAIN", "DFOL_STORE_BF16_DIRECT"):
+        os.environ.pop(k, None)
+
+    def switch(on):
+        if on:
+            os.environ["DFOL_STORE_BF16_TRAIN"] = "1"
+        else:
+            os.environ.pop("DFOL_STORE_BF16_TRAIN", None)
+    try:
+        paths, names = syn.write_synthetic_ontology(os.path.join(tmp, "ontology"))
+        cfg = syn.reference_config(paths, box_features_dim=args.features, freeze_featurizer=False, freeze_attribute_network=False,
+                                   freeze_relation_network=False, freeze_embedding_network=False, dropout=0.0)
+        ontology = experiment.build_ontology(cfg)
+        torch.manual_seed(0)
+        model = experiment.build_model(cfg, ontology)
+        bench.init_weights(model)
+        model = model.to(device).train()
+        chunks, info_path, _ = write_corpus(tmp, args.images, args.objects, args.features, args.per_chunk)
+        store = data.DeviceFeatureStore(tmp, "objs", chunks, info_path, device, feature_dtype="bf16")
+        with open(paths["attribute_file"]) as f:
+            cats = json.load(f)
+        rng = np.random.RandomState(9)
+        qs = syn.full_size_questions("verify_rel", args.batch, args.objects, args.objects, names, cats, 7100, with_scene=False)
+        for q in qs:
+            q["image_id"] = "img%05d" % rng.randint(args.images)
+        ids = [q["image_id"] for q in qs]
+        steps, nets, peak, counts = {}, {}, {}, {}
+        for on in (False, True):                             # (the route is baked into the capture: the switch matters here only)
+            switch(on)
+            pbs = data.BatchGQABoxFeaturesCollator(tmp, "objs", chunks, info_path, ontology, 1, device_store=store.index).collate([dict(q) for q in qs])
+            for pb in pbs:
+                pb.create_sparse_tensors()
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            dev = [pb.to_cuda(device) for pb in pbs]
+            nets[on] = copy.deepcopy(model)                  # (a graph bakes its parameters' addresses in: each route trains a copy of its own)
+            opt = torch.optim.Adam([p for p in nets[on].parameters() if p.requires_grad], lr=1e-4, capturable=True)
+            before = dict(_lib.PATH_COUNTS)
+            steps[on] = training.GraphedTrainStep(nets[on], opt, dev, 0.65)
+            torch.cuda.synchronize()
+            peak[on] = torch.cuda.max_memory_allocated() - base
+            counts[on] = {k: _lib.PATH_COUNTS.get(k, 0) - before.get(k, 0)
+                          for k in ("feature_store_direct_train", "feature_store_direct_train_bf16_x3", "feature_store_direct_materialized", "python_program")}
+        switch(False)
+
+        def replay_ms(step):
+            step()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(args.steps):
+                step()
+            b.record()
+            torch.cuda.synchronize()
+            return a.elapsed_time(b) / args.steps
+        ms = {False: [], True: []}
+        for _ in range(args.runs):
+            for on in (False, True):
+                ms[on].append(replay_ms(steps[on]))
+        # both copies have taken the same number of steps from the same state on the same batch
+        losses = {on: float(steps[on]()[0]) for on in (False, True)}
+        torch.cuda.synchronize()
+        step_same = losses[False] == losses[True] and all(
+            torch.equal(p.view(torch.int32), q.view(torch.int32)) for p, q in zip(nets[False].parameters(), nets[True].parameters()))
+
+        def kernel_ms(fn, n=20):
+            for _ in range(3):
+                fn()
+            evs = []
+            for _ in range(n):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                evs.append((a, b))
+            torch.cuda.synchronize()
+            return float(np.median([a.elapsed_time(b) for a, b in evs]))
+
+        # the first-layer forward with what runs in front of it, and the weight gradient alone, on the batch's own rows
+        first = [m for m in model._featurizer._featurizer_network._network if isinstance(m, torch.nn.Linear)][0]
+        ref = store.index.ref(ids)
+        idx = store.upload_index(ref)
+        rows = store.rows(ref)
+        mat = torch.empty(rows.O, args.features + 6, device=device)
+        y, act = torch.empty(rows.O, first.out_features, device=device), _lib.ACT_SIGMOID
+        dy = torch.randn(rows.O, first.out_features, device=device) * 0.01
+        wide = load_wide(_lib, rows.O, first.out_features, args.features)
+
+        if not wide:
+            raise SystemExit("bench_feature_store: --leg bf16-train needs a shape the wide kernel takes (the route's own condition)")
+
+        def by_matrix():                                     # dfol_gather_object_rows_bf16_f32 + dfol_linear_wide_h2_f32 over the widened matrix
+            store.gather(ref, out=mat, index=idx)
+            _lib.linear_wide(mat[:, :args.features], first.weight, first.bias, act, out=y)
+
+        def by_rows():                                       # dfol_store_rows_f32 + dfol_linear_wide_rows_bf16t_h2_f32 over the table
+            store.rows(ref, out=rows, index=idx)
+            _lib.linear_wide_rows_bf16t(rows.table, rows.src_row, first.weight, first.bias, act, out=y)
+        with torch.no_grad():
+            by_matrix()
+            y0 = y.clone()
+            y.fill_(-1.0)
+            by_rows()
+            product_same = bool(torch.equal(y0.view(torch.int32), y.view(torch.int32)))
+            w0, b0 = _lib.linear_wgrad(dy, mat[:, :args.features], bias=True)
+            w1, b1 = _lib.linear_wgrad_rows_bf16t_x3(dy, rows.table, rows.src_row, bias=True)
+            wgrad_same = bool(torch.equal(w0.view(torch.int32), w1.view(torch.int32)) and torch.equal(b0.view(torch.int32), b1.view(torch.int32)))
+            product, kernel = {"matrix": [], "rows": []}, {"matrix": [], "rows": []}
+            for _ in range(args.runs):
+                product["matrix"].append(kernel_ms(by_matrix))
+                product["rows"].append(kernel_ms(by_rows))
+                kernel["matrix"].append(kernel_ms(lambda: _lib.linear_wgrad(dy, mat[:, :args.features], bias=True)))
+                kernel["rows"].append(kernel_ms(lambda: _lib.linear_wgrad_rows_bf16t_x3(dy, rows.table, rows.src_row, bias=True)))
+    finally:
+        switch(False)
+        shutil.rmtree(tmp, ignore_errors=True)
+    off, on = span(ms[False]), span(ms[True])
+    pa, pb_ = span(product["matrix"]), span(product["rows"])
+    ka, kb = span(kernel["matrix"]), span(kernel["rows"])
+    return {"tool": "bench_feature_store", "leg": "bf16-train",
+            "shape": {"images": args.images, "objects": args.objects, "features": args.features, "batch": args.batch, "rows": rows.O,
+                      "runs": args.runs, "replays_per_run": args.steps, "wide_kernel_takes_the_shape": bool(wide)},
+            "first_layer_forward_ms": {"gather_bf16_and_product_over_the_matrix": pa, "store_rows_and_in_place_product": pb_, "in_place_vs_matrix": apart(pb_, pa),
+                                       "same_bits": product_same,
+                                       "caveat": "every sample launches on the same rows back to back: the in-place route's 105 MB fit the 256 MB last-level "
+                                                 "cache between launches, the matrix route's traffic does not - a stream of unseen batches has no such help"},
+            "wgrad_kernel_ms": {"six_products_over_the_matrix": ka, "three_products_over_the_table": kb, "table_vs_matrix": apart(kb, ka), "same_bits": wgrad_same},
+            "train_step_ms": {"switch_off": off, "switch_on": on, "on_vs_off": apart(on, off), "same_bits": bool(step_same),
+                              "loss_after_the_same_steps": {"switch_off": losses[False], "switch_on": losses[True]}},
+            "peak_bytes_of_upload_warm_up_and_capture": {"switch_off": peak[False], "switch_on": peak[True], "on_minus_off": peak[True] - peak[False]},
+            "matrix_bytes": rows.O * (args.features + 6) * 4, "store_bytes": store.nbytes,
+            "routes": {"switch_off": counts[False], "switch_on": counts[True]}}
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("stream", "train", "bf16", "bf16-direct"), default="stream",
-                    help="the stream of unseen inference batches, replayed train steps, the train leg in mlp_math: bf16 over the bf16 store, or the "
-                         "default arithmetic's inference over the bf16 store with DFOL_STORE_BF16_DIRECT unset and set")
+    ap.add_argument("--leg", choices=("stream", "train", "bf16", "bf16-direct", "bf16-train"), default="stream",
+                    help="the stream of unseen inference batches, replayed train steps, the train leg in mlp_math: bf16 over the bf16 store, the "
+                         "default arithmetic's inference over the bf16 store with DFOL_STORE_BF16_DIRECT unset and set, or its train step over the "
+                         "bf16 store with DFOL_STORE_BF16_TRAIN unset and set")
     ap.add_argument("--steps", type=int, default=20, help="--leg train: replays per timed run")
     ap.add_argument("--images", type=int, default=2048)
     ap.add_argument("--objects", type=int, default=100)
@@ -422,6 +571,9 @@ def main():
         raise SystemExit("bench_feature_store: needs a GPU (there is no CPU form of this measurement)")
     if args.leg == "bf16-direct":
         print(json.dumps(bf16_direct_leg(args)))
+        return
+    if args.leg == "bf16-train":
+        print(json.dumps(bf16_train_leg(args)))
         return
     if args.leg in ("train", "bf16"):
         print(json.dumps(train_leg(args, bf16=args.leg == "bf16")))
