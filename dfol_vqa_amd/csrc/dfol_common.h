@@ -101,7 +101,21 @@ __device__ __forceinline__ void dfol_offdiag_slot(int e, int n, int& s, int& o) 
     const int oo = e - s * (n - 1);
     o = oo + (oo >= s);
 }
-// The same without the integer-division sequence: (e + 0.5) / (n - 1) is at least 0.5 / (n - 1) away from an integer
+// The same without the integer-division sequence: (e + 0.5) / (n - 1) is at least 0.5 / (n - 1) away from an integer.
+// How far that carries.  m = n - 1, e < m (m + 1), x = e + 0.5.  The exact quotient is x / m = s + (oo + 0.5) / m with 0 <= oo <= m - 1, so
+// truncation yields s as long as the computed quotient p is off by LESS than 0.5 / m.  What is rounded on the way:
+//   (float)e, (float)m  exact (integers below 2^24);   (float)e + 0.5f  exact while e < 2^23 (2 e + 1 fits 24 bits);
+//   r = v_rcp_f32(m)    within 1 ulp of 1 / m (the instruction's documented accuracy), and an ulp of v is at most 2^-23 |v|: r = (1 + d1) / m,
+//                       |d1| <= 2^-23;
+//   p = fl(x r)         one rounding to nearest: p = x r (1 + d2), |d2| <= 2^-24  (p >= 0.5 / m is far from the denormals).
+// |p - x / m| <= (x / m) ((1 + 2^-23)(1 + 2^-24) - 1) < (x / m) 1.5000001 2^-23, which is below 0.5 / m iff x < 2^23 / 3.0000002 = 2 796 202.5.
+// The largest x is m (m + 1) - 0.5:  m = 1671 gives 2 793 911.5 (in; also below 2^23, so the sum above is exact), m = 1672 gives 2 797 255.5
+// (out).  The decode therefore equals dfol_offdiag_slot for every pair of an image of n <= 1672 objects; the launchers that use it refuse
+// max_n above DFOL_OFFDIAG_RCP_MAX_N, a round figure well inside that (at 1024 the error term uses 0.375 of the 0.5 / m it has).  The bound
+// rests on this derivation: on the device the decode has run at up to 300 objects (tests/test_pair_infer_shapes_gpu.py against float64, and
+// the 100-object launches of the other pair tests), never at the bound itself; tests/test_pair_infer_shapes_gpu.py restates the arithmetic on
+// the host with the reciprocal off by an ulp either way.
+#define DFOL_OFFDIAG_RCP_MAX_N 1024
 __device__ __forceinline__ void dfol_offdiag_slot_rcp(int e, int n, int& s, int& o) {
     s = (int)(((float)e + 0.5f) * __builtin_amdgcn_rcpf((float)(n - 1)));
     const int oo = e - s * (n - 1);

@@ -953,6 +953,8 @@ static int h2_pair_ll(const char* name, const float* UV, int64_t ld_uv, int32_t 
     DFOL_REQUIRE(Q >= 0 && K >= 0 && NS > 0 && NS % 4 == 0 && max_n >= 0 && max_n <= NS, "%s: bad sizes Q=%d K=%d NS=%d max_n=%d", name, Q, K, NS, max_n);
     DFOL_REQUIRE(HID1 > 0 && HID1 <= 256 && HID1 % H2_CH == 0 && ld_uv % 4 == 0, "%s: HID1=%d must be a multiple of %d, <= 256, UV rows 16-byte aligned", name, HID1, H2_CH);
     DFOL_REQUIRE(HID2 > 256 && HID2 <= 320, "%s: HID2=%d must be in (256, 320]", name, HID2);
+    DFOL_REQUIRE(max_n <= DFOL_OFFDIAG_RCP_MAX_N, "%s: max_n=%d is above %d objects per image, the range of the epilogue's reciprocal pair decode (dfol_common.h)",
+                 name, max_n, DFOL_OFFDIAG_RCP_MAX_N);
     if (Q == 0 || K == 0 || max_n < 2) return 0;
     DFOL_REQUIRE(UV && pos && Wg && W2_split && b2 && E && n_obj && obj_off && req_col && req_tile && tiles_v, "%s: null pointer", name);
     DFOL_REQUIRE(((uintptr_t)UV % 16 == 0) && ((uintptr_t)W2_split % 16 == 0) && ((uintptr_t)Wg % 16 == 0), "%s: operands must be 16-byte aligned", name);

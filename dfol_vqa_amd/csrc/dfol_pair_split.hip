@@ -451,6 +451,8 @@ extern "C" int dfol_pair_ll_split_f32(const float* UV, int64_t ld_uv, int32_t HI
     DFOL_REQUIRE(Q >= 0 && K >= 0 && NS > 0 && NS % 4 == 0 && max_n >= 0 && max_n <= NS, "pair_ll_split: bad sizes Q=%d K=%d NS=%d max_n=%d", Q, K, NS, max_n);
     DFOL_REQUIRE(HID1 > 0 && HID1 <= 256 && HID1 % SP_CH == 0 && ld_uv % 4 == 0, "pair_ll_split: HID1=%d must be a multiple of %d, <= 256, UV rows 16-byte aligned", HID1, SP_CH);
     DFOL_REQUIRE(HID2 > 256 && HID2 <= 320, "pair_ll_split: HID2=%d must be in (256, 320]", HID2);
+    DFOL_REQUIRE(max_n <= DFOL_OFFDIAG_RCP_MAX_N, "pair_ll_split: max_n=%d is above %d objects per image, the range of the epilogue's reciprocal pair decode (dfol_common.h)",
+                 max_n, DFOL_OFFDIAG_RCP_MAX_N);
     if (Q == 0 || K == 0 || max_n < 2) return 0;
     DFOL_REQUIRE(UV && pos && Wg && W2_split && b2 && E && n_obj && obj_off && req_col && req_tile && tiles_v, "pair_ll_split: null pointer");
     DFOL_REQUIRE(((uintptr_t)UV % 16 == 0) && ((uintptr_t)W2_split % 16 == 0) && ((uintptr_t)Wg % 16 == 0), "pair_ll_split: operands must be 16-byte aligned");

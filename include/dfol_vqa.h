@@ -616,7 +616,8 @@ int dfol_pair_ll_packed_f32(const float* UV, int64_t ld_uv, int32_t HID1, const 
  * and 8-19) of [3 pieces][rows][32] bf16, rows >= HID2 zero, k-groups swizzled for conflict-free LDS reads.
  * All other arguments as dfol_pair_ll_packed_f32, with ONE difference: this kernel enumerates the ordered pairs s != o only and never
  * touches a tile's diagonal - pre-fill the tiles with default_ll (the diagonal and the padding keep that fill).
- * Limits: HID1 <= 256 and a multiple of 32, 256 < HID2 <= 320.
+ * Limits: HID1 <= 256 and a multiple of 32, 256 < HID2 <= 320, max_n <= 1024 (DFOL_OFFDIAG_RCP_MAX_N, csrc/dfol_common.h: the range of
+ * the epilogue's reciprocal pair decode; a larger max_n is refused before any launch).
  */
 int dfol_pair_pack_w2_bf16x3(const float* W2, int64_t ld_w2, int32_t HID2, int32_t HID1, void* W2_split, void* stream);
 int dfol_pair_ll_split_f32(const float* UV, int64_t ld_uv, int32_t HID1, const float* pos, int64_t ld_pos, const float* Wg,
@@ -641,7 +642,7 @@ int dfol_pair_ll_split_f32(const float* UV, int64_t ld_uv, int32_t HID1, const f
  * instruction count (csrc/dfol_pair_h2.hip).  Activations saturate at 6e4 in those units, i.e. at ELU outputs of 4.16e4; with a status
  * word set (dfol_set_range_status) a saturating batch is flagged DFOL_RANGE_PAIR_SATURATED.
  * All other arguments, the ordered-pairs-only enumeration (pre-fill the tiles with default_ll: the diagonal and the padding keep that
- * fill) and the limits as dfol_pair_ll_split_f32: HID1 <= 256 and a multiple of 32, 256 < HID2 <= 320.
+ * fill) and the limits as dfol_pair_ll_split_f32: HID1 <= 256 and a multiple of 32, 256 < HID2 <= 320, max_n <= 1024.
  * Replaces classifier_oracle.py:145-156 for the relation columns a program names (gqa_interpreter_experiments.py:18-36, 60-77). */
 int64_t dfol_pair_w2_f16x2_bytes(int32_t HID1);
 int dfol_pair_pack_w2_f16x2(const float* W2, int64_t ld_w2, int32_t HID2, int32_t HID1, void* W2_split, void* stream);
