@@ -1606,16 +1606,66 @@ def g24_setup(tmp_path_factory):
     return model.to(DEV).train(), ont, a, meta
 
 
-@pytest.mark.parametrize("backward", ["hip", "autograd"])
-@pytest.mark.parametrize("kind", G24_KINDS)
-def test_g24_calibrator_phase_train_step_against_the_reference(g24_setup, kind, backward, monkeypatch):
+def _g24_relate_hops(questions):
+    """The relate calls of the collated batch, from the programs' structure: a branch is aligned on its relate operators, so it runs as many
+    GQARelateBatch calls as its longest chain of relates (each holds at least one valid token), and verify_rel owns one more."""
+    hops = sum(max(sum(o["operator"] == "relate" for o in q["program"]["branches"][b]) if b < len(q["program"]["branches"]) else 0 for q in questions)
+               for b in range(max(len(q["program"]["branches"]) for q in questions)))
+    return hops + any(q["program"]["last_op"]["operator"] == "verify_rel" for q in questions)
+
+
+class _G24RelateCalls(object):
+    """Forward pre-hooks on every GQARelateBatch (the relate operator's and the one verify_rel owns): the calls whose relation tokens include a
+    valid one, and how many of those found their op_id in BOTH modulation dictionaries of their RelateBatch (the calibrated branch)."""
+
+    def __init__(self, model):
+        from dfol_vqa_amd import gqa_ops
+        from dfol_vqa_amd.host_util import is_valid_token
+        self.valid = self.calibrated = 0
+        self._is_valid = is_valid_token
+        self._handles = [m.register_forward_pre_hook(self._hop, with_kwargs=True) for m in model.modules() if isinstance(m, gqa_ops.GQARelateBatch)]
+        assert len(self._handles) >= 2
+
+    def _hop(self, module, args, kwargs):
+        op_id = args[0] if args else kwargs["op_id"]
+        rel = args[3] if len(args) > 3 else kwargs["relation_list"]
+        if any(self._is_valid(v) for v in (rel if isinstance(rel, list) else [rel])):
+            self.valid += 1
+            r = module._relate
+            self.calibrated += (r._subject_modulations.get(op_id) is not None and r._object_modulations.get(op_id) is not None)
+
+    def close(self):
+        for h in self._handles:
+            h.remove()
+
+
+# route: generic = every kind under both backwards, under the ids these cases have always had; relate_train = every kind with the HIP backward,
+# and verify_rel under autograd (ops._RelateKeep.backward feeding torch's autograd through the modulate restatement)
+@pytest.mark.parametrize("kind,backward,route", [pytest.param(k, b, "generic", id="%s-%s" % (k, b)) for b in ("hip", "autograd") for k in G24_KINDS] +
+                         [pytest.param(k, b, "relate_train", id="%s-%s-relate_train" % (k, b))
+                          for k, b in [(k, "hip") for k in G24_KINDS] + [("verify_rel", "autograd")]])
+def test_g24_calibrator_phase_train_step_against_the_reference(g24_setup, kind, backward, route, monkeypatch):
     """ONE train-mode forward + loss + backward of the full-size model in the curriculum's CALIBRATOR phases (cur6-7: oracle frozen,
     LSTMCell(318 -> 50) x 2 + Linear(100 -> 4) train) against the REFERENCE's own `_train_batch` (golden g24: loss, log-probabilities, norm +
     sampled entries of all ten calibrator gradients, fp32 and fp64; trainer.py:181-262, 429-442 over batch_base_ops.py:407-467, 598-684) on
     ragged 10..40-object scenes, BINARY and QUERY losses.  `hip`: the hand-written LSTM-cell and modulate backward kernels (the defaults);
-    `autograd`: the same forward with torch's autograd through those two ops."""
+    `autograd`: the same forward with torch's autograd through those two ops.
+
+    route `relate_train`: the same step under DFOL_RELATE_TRAIN=1, every assertion unchanged - the one-posterior ungated route
+    (gqa_ops.GQARelateBatch._forward_train_one: dfol_relate_keep_fwd_f32 / dfol_relate_keep_bwd_f32, then the kept side's modulations through
+    ops.modulate) against the reference.  Every relate call with a valid token takes the route, and takes its calibrated branch: the oracle is
+    frozen, but each branch starts at select(<noun>) in some question, a calibrated filter, so the incoming variable carries the calibrator's
+    gradient; the interpreter's op ids end in a digit (never 'n'), so both modulation dictionaries hold the hop; and the incoming set of a
+    relate operator never carries a predicate-question map.  No hop steps aside, and the count is the one the programs' structure gives
+    (_g24_relate_hops: exist 3, verify_rel 2 + 1, choose_rel 1, query_attr 1, and 3).  choose_rel's own two-posterior cell is a RelateBatch
+    without a GQARelateBatch around it and stays on the generic route, as it does for an uncalibrated model."""
     from test_interpreter_gpu import CalibrationCollater
+    from dfol_vqa_amd import _lib, logic_ops
     model, ont, a, meta = g24_setup
+    if route == "relate_train":
+        monkeypatch.setenv("DFOL_RELATE_TRAIN", "1")
+    else:
+        monkeypatch.delenv("DFOL_RELATE_TRAIN", raising=False)
     for k in ("DFOL_LSTM_BWD", "DFOL_MODULATE_BWD"):
         monkeypatch.setenv(k, "hip" if backward == "hip" else "torch")
     trainable = sorted(k for k, p in model.named_parameters() if p.requires_grad)
@@ -1625,10 +1675,28 @@ def test_g24_calibrator_phase_train_step_against_the_reference(g24_setup, kind, 
                        syn.feature_scene(q["question_id"], q["n"], meta["feature_dim"])) for q in cm["questions"]]
     pbs = [pb.to_cuda(DEV) for pb in CalibrationCollater(ont).collate([dict(q) for q in qs])]
     model.zero_grad(set_to_none=True)
-    res = model(pbs, True)
+    calls = _G24RelateCalls(model)
+    _lib.PATH_COUNTS.clear()
+    try:
+        res = model(pbs, True)
+    finally:
+        calls.close()
     assert int(res["type"]) == cm["type"]
     loss = training.compute_loss(pbs, res) / len(qs)
     loss.backward()
+    counts = dict(_lib.PATH_COUNTS)
+    if route == "relate_train":
+        expected = {"exist": 3, "verify_rel": 3, "choose_rel": 1, "query_attr": 1, "and": 3}[kind]
+        assert _g24_relate_hops(cm["questions"]) == expected == calls.valid, (kind, _g24_relate_hops(cm["questions"]), calls.valid)
+        assert counts.get("relate_train_one", 0) == calls.valid, (kind, counts, calls.valid)
+        assert calls.calibrated == calls.valid, (kind, calls.calibrated, calls.valid)              # the calibrated branch ran in every one of them
+        assert not [k for k in counts if k.startswith("fallback:")], counts
+        for mod in model.modules():                                 # a leak would hand a stale modulation to the next batch's hop of the same op_id
+            if isinstance(mod, logic_ops.RelateBatch):
+                for attr in ("_subject_modulations", "_object_modulations", "_forward_subject_state", "_forward_object_state"):
+                    assert not getattr(mod, attr), (kind, attr, list(getattr(mod, attr)))
+    else:
+        assert "relate_train_one" not in counts, counts
     l32, l64, got_loss = float(a[kind + ":loss_f32"]), float(a[kind + ":loss_f64"]), float(loss.detach())
     assert abs(got_loss - l64) <= 8 * abs(l32 - l64) + 2e-5 * max(1.0, abs(l64)), (got_loss, l32, l64)
     gu.check_logprob(res["log_probability"].detach().cpu().numpy(), a[kind + ":lp_f32"], a[kind + ":lp_f64"], "g24 " + kind)
@@ -1650,6 +1718,7 @@ def test_g24_calibrator_phase_train_step_against_the_reference(g24_setup, kind, 
         ref64, ref32 = g["sample64"].astype(np.float64), g["sample32"].astype(np.float64)
         scale = max(np.abs(ref64).max(), g["norm64"] / np.sqrt(full.size)) + 1e-30
         own, err = np.abs(ref32 - ref64).max(), np.abs(smp - ref64).max()
+        print("  g24 %s %s %s d%s: |dgrad| %.3g  bound %.3g" % (kind, backward, route, pname, err, 8 * own + 2e-3 * scale))
         assert err <= 8 * own + 2e-3 * scale, "g24 %s d%s: |dgrad| %.3g vs the reference's own %.3g (scale %.3g)" % (kind, pname, err, own, scale)
         norm = np.sqrt((full ** 2).sum())
         assert abs(norm - g["norm64"]) <= 8 * abs(g["norm32"] - g["norm64"]) + 2e-3 * g["norm64"] + 1e-30, (kind, pname, norm, g["norm64"], g["norm32"])
