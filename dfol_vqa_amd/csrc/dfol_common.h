@@ -59,6 +59,28 @@ __device__ __forceinline__ float dfol_slog(float x) { return dfol_log(fmaxf(x, D
 __device__ __forceinline__ float dfol_lnot(float x) { return dfol_slog(1.0f - dfol_exp(x)); }
 // util.py:46-47 with beta = 1:  log(max(alpha + (1 - 2 alpha) e^x, eps)); c = 1 - 2 alpha
 __device__ __forceinline__ float dfol_pnot(float x, float alpha, float c) { return dfol_slog(alpha + c * dfol_exp(x)); }
+// d/dx log(max(alpha + c e^x, eps)),  c = 1 - 2 alpha  (the clamp has zero gradient below the floor)
+__device__ __forceinline__ float dfol_dpnot(float x, float alpha, float c) {
+    const float e = dfol_exp(x);
+    const float d = alpha + c * e;
+    return d > DFOL_EPS ? c * e / d : 0.f;
+}
+
+// A stored likelihood as every logic cell reads it:  v = min(ll, 0)  (batch_base_ops.py:194), then the predicate's negation  l' = pnot(v)
+// (:212-213) in a launch that has any negated predicate (alpha_n = 1 for a negated one, cn = 1 - 2 alpha_n).  One spelling for the ungated
+// and gated forward and backward kernels.
+__device__ __forceinline__ float dfol_prep(float ll, int any_neg, float alpha_n, float cn) {
+    float v = fminf(ll, 0.f);
+    if (any_neg) v = dfol_pnot(v, alpha_n, cn);
+    return v;
+}
+// d l' / d ll
+__device__ __forceinline__ float dfol_dprep(float ll, int any_neg, float alpha_n, float cn) {
+    const float v = fminf(ll, 0.f);
+    float d = ll < 0.f ? 1.f : 0.f;                        // -relu(-x): subgradient 0 at and above 0 (torch relu)
+    if (any_neg) d *= dfol_dpnot(v, alpha_n, cn);
+    return d;
+}
 
 // ---- activations ------------------------------------------------------------------------------------------------------------------
 // Sigmoid on the hardware exp2 / rcp (1 ulp each, absolute error < 2e-7), the form of the streaming kernels and the producers of the

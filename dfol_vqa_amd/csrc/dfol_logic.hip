@@ -603,11 +603,60 @@ __global__ __launch_bounds__(256) void relate_fwd_kernel(
 // The kernels above keep a whole tile row in the registers of one wavefront (a lane owns four columns: NS <= 256).  Wider tiles - scenes
 // of more than 256 objects, which no configuration of the reference reaches - take these plain forms of the general code: one workgroup
 // per predicate, a thread per column for the column sums (rows in order, coalesced), a workgroup reduction per row for the row sums
-// (wavefront partials added in wavefront order): deterministic, the same formulas, no fast paths.
-__device__ __forceinline__ float relate_prep(float ll, int any_neg, float alpha_n, float cn) {
-    float v = fminf(ll, 0.f);                                            // batch_base_ops.py:194
-    if (any_neg) v = dfol_pnot(v, alpha_n, cn);                          // :212-213
-    return v;
+// (wavefront partials added in wavefront order): deterministic, the same formulas, no fast paths.  The two loops are written once
+// (relate_big_cols, relate_big_rows); the three kernels are a preamble plus calls.
+
+// What the two loops share: the predicate's tile and its negation.  Each loop takes the quantifier of the axis it sums out: qf, and id = the lone
+// FOR_ALL's literal branch.
+struct RelateBig {
+    const float* tp;
+    int n, NS, any_neg;
+    float alpha_n, cn;
+};
+
+// Rows summed out: out[c] = own[c] + F( sum_{r != c} F( l'[r][c] + other[r] ) ).  A thread per column, rows in order.  skip_diagonal = false
+// keeps the diagonal's term (relate_one_big_kernel, where it contributes exactly 0).
+__device__ __forceinline__ void relate_big_cols(const RelateBig& g, const float* __restrict__ other, const float* __restrict__ own,
+                                                float* __restrict__ out, float qf, bool id, bool skip_diagonal, int tid) {
+    const float kf = 1.f - 2.f * qf;
+    for (int c = tid; c < g.NS; c += 256) {
+        float acc = 0.f;
+        if (c < g.n) {
+            for (int r = 0; r < g.n; ++r) {
+                if (skip_diagonal && r == c) continue;                    // self-relations contribute 0 (:112)
+                const float u = dfol_prep(g.tp[(int64_t)r * g.NS + c], g.any_neg, g.alpha_n, g.cn) + other[r];
+                acc += id ? u : dfol_pnot(u, qf, kf);
+            }
+            acc = own[c] + (id ? acc : dfol_pnot(acc, qf, kf));
+        }
+        out[c] = acc;
+    }
+}
+
+// Columns summed out: out[r] = own[r] + F( sum_{c != r} F( l'[r][c] + other[c] ) ).  A workgroup reduction per row, the four wavefronts'
+// partials (part[4], LDS) added in wavefront order.  The loop runs over all NS rows and holds a pair of __syncthreads(): call it only under a
+// condition that is the same for the whole workgroup, so that every thread reaches every barrier.
+__device__ __forceinline__ void relate_big_rows(const RelateBig& g, const float* __restrict__ other, const float* __restrict__ own,
+                                                float* __restrict__ out, float qf, bool id, float* part, int tid) {
+    const float kf = 1.f - 2.f * qf;
+    const int w = tid >> 6, lane = tid & 63;
+    for (int r = 0; r < g.NS; ++r) {
+        float s = 0.f;
+        if (r < g.n)
+            for (int c = tid; c < g.n; c += 256) {
+                if (c == r) continue;
+                const float u = dfol_prep(g.tp[(int64_t)r * g.NS + c], g.any_neg, g.alpha_n, g.cn) + other[c];     // :102
+                s += id ? u : dfol_pnot(u, qf, kf);                                                             // :108
+            }
+        s = dfol_wave_sum(s);
+        if (lane == 0) part[w] = s;
+        __syncthreads();
+        if (tid == 0) {
+            const float tot = ((part[0] + part[1]) + part[2]) + part[3];
+            out[r] = r < g.n ? own[r] + (id ? tot : dfol_pnot(tot, qf, kf)) : 0.f;                           // :133, :138
+        }
+        __syncthreads();
+    }
 }
 
 __global__ __launch_bounds__(256) void relate_big_fwd_kernel(
@@ -617,7 +666,7 @@ __global__ __launch_bounds__(256) void relate_big_fwd_kernel(
     const uint8_t* __restrict__ want, int want_R_bit, int want_C_bit, int NS, int flags, float* __restrict__ post_R,
     float* __restrict__ post_C) {
     __shared__ float part[4];
-    const int p = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    const int p = blockIdx.x, tid = threadIdx.x;
     const int q = pred_q[p], n = n_obj[q];
     const int wbits = want ? want[p] : 3;
     const bool wantR = (wbits & want_R_bit) && post_R, wantC = (wbits & want_C_bit) && post_C;
@@ -637,42 +686,11 @@ __global__ __launch_bounds__(256) void relate_big_fwd_kernel(
     if (!wantC && oC)
         for (int c = tid; c < NS; c += 256) oC[c] = 0.f;
     const int identity_forall = flags & DFOL_RELATE_LONE_FORALL_IDENTITY;
-    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
-    const float qR = quant_R[p], qC = quant_C[p], kR = 1.f - 2.f * qR, kC = 1.f - 2.f * qC;
-    const bool idR = identity_forall && qR == 0.f, idC = identity_forall && qC == 0.f;
-    const float* tp = tile + (int64_t)p * NS * NS;
-    if (wantC)
-        for (int c = tid; c < NS; c += 256) {
-            float acc = 0.f;
-            if (c < n) {
-                const float pc = pC[c];
-                for (int r = 0; r < n; ++r) {
-                    if (r == c) continue;                                 // self-relations contribute 0 (:112)
-                    const float u = relate_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn) + pR[r];
-                    acc += idR ? u : dfol_pnot(u, qR, kR);
-                }
-                acc = pc + (idR ? acc : dfol_pnot(acc, qR, kR));
-            }
-            oC[c] = acc;
-        }
-    if (wantR)
-        for (int r = 0; r < NS; ++r) {
-            float s = 0.f;
-            if (r < n)
-                for (int c = tid; c < n; c += 256) {
-                    if (c == r) continue;
-                    const float u = relate_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn) + pC[c];     // :102
-                    s += idC ? u : dfol_pnot(u, qC, kC);                                                 // :108
-                }
-            s = dfol_wave_sum(s);
-            if (lane == 0) part[w] = s;
-            __syncthreads();
-            if (tid == 0) {
-                const float tot = ((part[0] + part[1]) + part[2]) + part[3];
-                oR[r] = r < n ? pR[r] + (idC ? tot : dfol_pnot(tot, qC, kC)) : 0.f;                     // :133, :138
-            }
-            __syncthreads();
-        }
+    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f;
+    const float qR = quant_R[p], qC = quant_C[p];
+    const RelateBig g = {tile + (int64_t)p * NS * NS, n, NS, any_neg, alpha_n, 1.f - 2.f * alpha_n};
+    if (wantC) relate_big_cols(g, pR, pC, oC, qR, identity_forall && qR == 0.f, true, tid);
+    if (wantR) relate_big_rows(g, pC, pR, oR, qC, identity_forall && qC == 0.f, part, tid);     // (wantR is the workgroup's)
 }
 
 __global__ __launch_bounds__(256) void relate_one_big_kernel(
@@ -690,22 +708,10 @@ __global__ __launch_bounds__(256) void relate_one_big_kernel(
     }
     const bool negated = any_neg && neg[p];
     const float alpha_n = negated ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
-    const float qf = quant_prev[p], kf = 1.f - 2.f * qf;
-    const bool ident = identity_forall && qf == 0.f;
+    const float qf = quant_prev[p];
     const bool mask = negated || qf != 1.f;              // (as relate_one_fwd_kernel: only then can the diagonal contribute)
-    const float* tp = tile + (int64_t)p * NS * NS;
-    for (int c = tid; c < NS; c += 256) {
-        float acc = 0.f;
-        if (c < n) {
-            for (int r = 0; r < n; ++r) {
-                if (mask && r == c) continue;
-                const float u = relate_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn) + pv[r];
-                acc += ident ? u : dfol_pnot(u, qf, kf);
-            }
-            acc = x_att[(int64_t)p * NS + c] + (ident ? acc : dfol_pnot(acc, qf, kf));
-        }
-        out[c] = acc;
-    }
+    const RelateBig g = {tile + (int64_t)p * NS * NS, n, NS, any_neg, alpha_n, cn};
+    relate_big_cols(g, pv, x_att + (int64_t)p * NS, out, qf, identity_forall && qf == 0.f, mask, tid);
 }
 
 template <int LPR>
@@ -958,7 +964,7 @@ __global__ __launch_bounds__(256) void relate_one_fwd_kernel(
         float o[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float s = acc[j] * (ident ? 0.69314718055994530942f / 1.0f : 0.69314718055994530942f);   // back from log2 to ln
+            const float s = acc[j] * 0.69314718055994530942f;                // back from log2 to ln
             o[j] = (c0 + j < n) ? xv[j] + (ident ? s : dfol_pnot(s, qf, kf)) : 0.f;
         }
         *reinterpret_cast<float4*>(out + c0) = make_float4(o[0], o[1], o[2], o[3]);
@@ -1000,6 +1006,10 @@ extern "C" int dfol_relate_one_fwd_f32(const float* x_att, const float* prev_att
 // row partials by the DPP group OR), the same transcendental-free FOR_ALL forms with their fall-back to the clamping loop, the same
 // diagonal and padding selects.  Column aggregates stay in registers and the row slots are joined by __shfl_xor; row aggregates go through
 // the DPP group reduction into the wavefront's LDS row.  A no-op row is prev's row.  No atomics: two launches give the same bits.
+// The body stays written out beside relate_fwd_kernel's: called from one inline function, relate_fwd_kernel compiled to other registers and
+// ran 2 - 9 % slower (profiles/r24_relate_refactor.txt).  A change to a guard or a clamp there belongs here too; the one difference is the
+// FOR_ALL range guard, which looks here only at the prior the aggregate reads and there at both.  tests/test_relate_one_body_gpu.py holds the
+// two to the same bits.
 template <int LPR>
 __global__ __launch_bounds__(256) void relate_keep_fwd_kernel(
     const float* __restrict__ x_att, const float* __restrict__ prev_att, const float* __restrict__ tile,
@@ -1233,15 +1243,15 @@ __global__ __launch_bounds__(256) void relate_keep_fwd_kernel(
     }
 }
 
-// NS > 256: one workgroup per predicate; a thread per column, rows in order, for the column aggregate, a workgroup reduction per row (wavefront
-// partials added in wavefront order) for the row aggregate, as relate_big_fwd_kernel.
+// NS > 256: one workgroup per predicate, the two plain loops of relate_big_fwd_kernel: rows summed out when x is the object, columns when it is
+// the subject.
 __global__ __launch_bounds__(256) void relate_keep_big_kernel(
     const float* __restrict__ x_att, const float* __restrict__ prev_att, const float* __restrict__ tile,
     const int32_t* __restrict__ pred_q, const int32_t* __restrict__ n_obj, const float* __restrict__ quant_prev,
     const uint8_t* __restrict__ x_is_subject, const uint8_t* __restrict__ neg, int any_neg, const uint8_t* __restrict__ active, int NS,
     int identity_forall, float* __restrict__ post) {
     __shared__ float part[4];
-    const int p = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    const int p = blockIdx.x, tid = threadIdx.x;
     const int q = pred_q[p], n = min(n_obj[q], NS);
     const float* pv = prev_att + (int64_t)q * NS;
     const float* xv = x_att + (int64_t)p * NS;
@@ -1250,43 +1260,12 @@ __global__ __launch_bounds__(256) void relate_keep_big_kernel(
         for (int c = tid; c < NS; c += 256) out[c] = c < n ? pv[c] : 0.f;
         return;
     }
-    const bool xs = x_is_subject[p] != 0;                // (the workgroup's: every thread reaches the barriers below)
-    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f, cn = 1.f - 2.f * alpha_n;
-    const float qf = quant_prev[p], kf = 1.f - 2.f * qf;
+    const float alpha_n = (any_neg && neg[p]) ? 1.f : 0.f;
+    const float qf = quant_prev[p];
     const bool ident = identity_forall && qf == 0.f;
-    const float* tp = tile + (int64_t)p * NS * NS;
-    if (!xs) {
-        for (int c = tid; c < NS; c += 256) {
-            float acc = 0.f;
-            if (c < n) {
-                for (int r = 0; r < n; ++r) {
-                    if (r == c) continue;                                 // self-relations contribute 0 (:112)
-                    const float u = relate_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn) + pv[r];
-                    acc += ident ? u : dfol_pnot(u, qf, kf);
-                }
-                acc = xv[c] + (ident ? acc : dfol_pnot(acc, qf, kf));
-            }
-            out[c] = acc;
-        }
-        return;
-    }
-    for (int r = 0; r < NS; ++r) {
-        float s = 0.f;
-        if (r < n)
-            for (int c = tid; c < n; c += 256) {
-                if (c == r) continue;
-                const float u = relate_prep(tp[(int64_t)r * NS + c], any_neg, alpha_n, cn) + pv[c];     // :102
-                s += ident ? u : dfol_pnot(u, qf, kf);                                               // :108
-            }
-        s = dfol_wave_sum(s);
-        if (lane == 0) part[w] = s;
-        __syncthreads();
-        if (tid == 0) {
-            const float tot = ((part[0] + part[1]) + part[2]) + part[3];
-            out[r] = r < n ? xv[r] + (ident ? tot : dfol_pnot(tot, qf, kf)) : 0.f;                    // :133, :138
-        }
-        __syncthreads();
-    }
+    const RelateBig g = {tile + (int64_t)p * NS * NS, n, NS, any_neg, alpha_n, 1.f - 2.f * alpha_n};
+    if (x_is_subject[p]) relate_big_rows(g, pv, xv, out, qf, ident, part, tid);      // (the workgroup's flag: every thread reaches the barriers)
+    else relate_big_cols(g, pv, xv, out, qf, ident, true, tid);
 }
 
 extern "C" int dfol_relate_keep_fwd_f32(const float* x_att, const float* prev_att, const float* tile, const int32_t* pred_q,

@@ -3,27 +3,6 @@
 // through the goldens g6 (tests/test_backward_gpu.py).  Same block layout and launch geometry as the forward.
 #include "dfol_common.h"
 
-// d/dx log(max(alpha + c e^x, eps)),  c = 1 - 2 alpha  (the clamp has zero gradient below the floor)
-__device__ __forceinline__ float dfol_dpnot(float x, float alpha, float c) {
-    const float e = dfol_exp(x);
-    const float d = alpha + c * e;
-    return d > DFOL_EPS ? c * e / d : 0.f;
-}
-
-// chain through  v = min(ll, 0)  and the optional negation  l' = pnot(v, neg)
-__device__ __forceinline__ float dfol_dprep(float ll, int any_neg, float alpha_n, float cn) {
-    const float v = fminf(ll, 0.f);
-    float d = ll < 0.f ? 1.f : 0.f;                        // -relu(-x): subgradient 0 at and above 0 (torch relu)
-    if (any_neg) d *= dfol_dpnot(v, alpha_n, cn);
-    return d;
-}
-
-__device__ __forceinline__ float dfol_prep(float ll, int any_neg, float alpha_n, float cn) {
-    float v = fminf(ll, 0.f);
-    if (any_neg) v = dfol_pnot(v, alpha_n, cn);
-    return v;
-}
-
 // Predicates of question q: [p0, p1) by binary search in the non-decreasing pred_q (the predicates of a question are contiguous,
 // as every operator builds them).  Every cross-predicate sum of the backward pass is taken by the OWNER of the output element,
 // walking this range in order: no atomics, bit-identical from run to run.

@@ -129,23 +129,10 @@ __device__ __forceinline__ GateNeg gate_neg_load(const uint8_t* __restrict__ neg
     return N;
 }
 
-// l' = negation(min(ll, 0)) (batch_base_ops.py:194, :212-213) and its derivative
-__device__ __forceinline__ float gate_prep(float ll, const GateNeg& N) {
-    float v = fminf(ll, 0.f);
-    if (N.any_neg) v = dfol_pnot(v, N.alpha_n, N.cn);
-    return v;
-}
-
-__device__ __forceinline__ float gate_dpnot(float x, float alpha, float c) {
-    const float e = dfol_exp(x), d = alpha + c * e;
-    return d > DFOL_EPS ? c * e / d : 0.f;
-}
-
-__device__ __forceinline__ float gate_dprep(float ll, const GateNeg& N) {
-    float d = ll < 0.f ? 1.f : 0.f;
-    if (N.any_neg) d *= gate_dpnot(fminf(ll, 0.f), N.alpha_n, N.cn);
-    return d;
-}
+// l' = negation(min(ll, 0)) (batch_base_ops.py:194, :212-213) and its derivative: dfol_prep / dfol_dprep (dfol_common.h) on a GateNeg
+__device__ __forceinline__ float gate_prep(float ll, const GateNeg& N) { return dfol_prep(ll, N.any_neg, N.alpha_n, N.cn); }
+__device__ __forceinline__ float gate_dpnot(float x, float alpha, float c) { return dfol_dpnot(x, alpha, c); }
+__device__ __forceinline__ float gate_dprep(float ll, const GateNeg& N) { return dfol_dprep(ll, N.any_neg, N.alpha_n, N.cn); }
 
 // The quantifier of a summed-out axis: kf = 1 - 2 qf, ex = EXISTS, ident = a lone predicate's literal FOR_ALL branch (:104-108)
 struct GateQuant {

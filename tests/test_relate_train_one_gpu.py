@@ -51,9 +51,15 @@ SHAPES = {
 def keep_problem(name):
     """Inputs of one shape, the restatement's kept posterior and its gradients (the problem's own random cotangent, zero on padding) in float32
     and float64; computed once, shared, never modified."""
-    if name in _CACHE:
-        return _CACHE[name]
-    NS, n_list, k_list, with_neg, with_inactive, quants, flags = SHAPES[name]
+    if name not in _CACHE:
+        _CACHE[name] = make_problem(name, SHAPES[name])
+    return _CACHE[name]
+
+
+def make_problem(name, spec, restate=True):
+    """The generator behind keep_problem for a shape tuple of SHAPES' form (the name seeds it); a new dict each call, nothing cached.
+    restate=False leaves the float32 / float64 restatement out, for a test that compares kernels with each other."""
+    NS, n_list, k_list, with_neg, with_inactive, quants, flags = spec
     rng = np.random.RandomState(sum(map(ord, name)))
     Q, pq = len(n_list), np.repeat(np.arange(len(n_list)), k_list).astype(np.int32)
     P = len(pq)
@@ -85,11 +91,10 @@ def keep_problem(name):
     kp["cot"] = rng.normal(size=(P, NS)).astype(np.float32)
     for p in range(P):
         kp["cot"][p, n_list[pq[p]]:] = 0
-    for tag, dt in (("f32", torch.float32), ("f64", torch.float64)):
+    for tag, dt in (("f32", torch.float32), ("f64", torch.float64)) if restate else ():
         kp[tag] = restate_keep(kp, dt, kp["cot"])
-    for tag, dt in (("f32", torch.float32), ("f64", torch.float64)):                      # the cotangent of the live rows alone
+    for tag, dt in (("f32", torch.float32), ("f64", torch.float64)) if restate else ():   # the cotangent of the live rows alone
         kp[tag + "_live"] = kp[tag]["g"] if kp["live"].all() else restate_keep(kp, dt, kp["cot"] * kp["live"][:, None])["g"]
-    _CACHE[name] = kp
     return kp
 
 
