@@ -239,6 +239,12 @@ SIGNATURES = {
     "dfol_pair_features_bwd_f32": [_p, _i64, _i32, _p, _p, _i32, _i32, _p, _i64, _p],
     "dfol_dropout_advance": [_p, _p],
     "dfol_dropout_f32": [_p, _i64, _p, _i64, _i64, _i32, _f, _p, ctypes.c_uint32, _p],
+    "dfol_scene_bce_supported": [_i32, _i32, _i32],         # 1 / 0, called directly
+    "dfol_scene_bce_fwd_workspace": [_i32, _i32, _i32],     # float counts (int64), called directly
+    "dfol_scene_bce_bwd_cols_workspace": [_i32, _i32, _i32],
+    "dfol_scene_bce_fwd_f32": [_p, _i64, _i32, _i32, _p, _i64, _i32, _p, _p, _i32, _p, _p, _f, _p, _p, _p],
+    "dfol_scene_bce_bwd_rows_f32": [_p, _p, _i64, _i32, _i32, _p, _i64, _i32, _p, _p, _i32, _p, _p, _p, _i64, _p],
+    "dfol_scene_bce_bwd_cols_f32": [_p, _p, _i64, _i32, _i32, _p, _i64, _i32, _p, _p, _i32, _p, _p, _p, _p, _p, _p],
 }
 
 
@@ -271,6 +277,8 @@ def load():
     lib.dfol_pair_wgrad_fused_workspace.restype = ctypes.c_int64
     lib.dfol_pair_wgrad_fused_sums_workspace.restype = ctypes.c_int64
     lib.dfol_set_range_status.restype = ctypes.c_int
+    lib.dfol_scene_bce_fwd_workspace.restype = ctypes.c_int64
+    lib.dfol_scene_bce_bwd_cols_workspace.restype = ctypes.c_int64
     _lib = lib
     return lib
 
@@ -1389,6 +1397,52 @@ def attr_head_h2(pre1, w2_h2, b2, hid2, emb_w, emb_b, obj_off, pred_q, pred_col,
          _ptr(emb_b, F32, True), _ptr(obj_off, I32), obj_off.numel() - 1, pre1.shape[0], _ptr(pred_q, I32), _ptr(pred_col, I32), P, NS, default_ll,
          _ptr(ll), _stream())
     return ll
+
+
+# ---- scene-graph supervision: the fused all-concepts BCE (csrc/dfol_scene.hip) ---------------------------------------------------------
+def scene_bce_supported(M, H, C):
+    """Sizes the fused kernels take (dfol_scene_bce_supported); what they decline runs the tensor-op route of ops.scene_bce."""
+    return bool(load().dfol_scene_bce_supported(int(M), int(H), int(C)))
+
+
+def _scene_args(h, emb_w, emb_b, cols, target, weight):
+    M, H = h.shape
+    C = cols.numel()
+    if emb_w.shape[1] != H or tuple(target.shape) != (M, C) or tuple(weight.shape) != (M, C):
+        raise DfolError("scene_bce: h %s, emb_w %s, cols [%d], target %s, weight %s do not fit together"
+                        % (tuple(h.shape), tuple(emb_w.shape), C, tuple(target.shape), tuple(weight.shape)))
+    if h.dtype != F32 or emb_w.dtype != F32 or (M and h.stride(1) != 1) or emb_w.stride(1) != 1:
+        raise DfolError("scene_bce: h and emb_w must be fp32 with unit column stride")
+    return M, H, C, (_dp(h), h.stride(0) if M else H, M, H, _dp(emb_w), emb_w.stride(0), emb_w.shape[0], _ptr(emb_b, F32, True), _ptr(cols, I32), C,
+                     _ptr(target, F32), _ptr(weight, F32))
+
+
+def scene_bce_fwd(h, emb_w, emb_b, cols, target, weight, thr):
+    """-> sums [3] = (loss, metric numerator, metric denominator) of the weighted BCE over emb_w's rows `cols` (dfol_scene_bce_fwd_f32)."""
+    M, H, C, args = _scene_args(h, emb_w, emb_b, cols, target, weight)
+    sums = torch.empty(3, dtype=F32, device=h.device)
+    n = load().dfol_scene_bce_fwd_workspace(M, H, C)
+    ws = torch.empty(n, dtype=F32, device=h.device) if n else None
+    call("dfol_scene_bce_fwd_f32", *args, float(thr), _ptr(ws, F32, True), _ptr(sums), _stream())
+    return sums
+
+
+def scene_bce_bwd_rows(g, h, emb_w, emb_b, cols, target, weight):
+    """-> dh [M, H] for the upstream gradient g of the loss (a device scalar): dfol_scene_bce_bwd_rows_f32."""
+    M, H, C, args = _scene_args(h, emb_w, emb_b, cols, target, weight)
+    dh = torch.empty(M, H, dtype=F32, device=h.device)
+    call("dfol_scene_bce_bwd_rows_f32", _ptr(g, F32), *args, _ptr(dh), H, _stream())
+    return dh
+
+
+def scene_bce_bwd_cols(g, h, emb_w, emb_b, cols, target, weight):
+    """-> (dE [C, H], db [C]) of emb_w's rows `cols` and their biases, compact: dfol_scene_bce_bwd_cols_f32."""
+    M, H, C, args = _scene_args(h, emb_w, emb_b, cols, target, weight)
+    dE, db = torch.empty(C, H, dtype=F32, device=h.device), torch.empty(C, dtype=F32, device=h.device)
+    n = load().dfol_scene_bce_bwd_cols_workspace(M, H, C)
+    ws = torch.empty(n, dtype=F32, device=h.device) if n else None
+    call("dfol_scene_bce_bwd_cols_f32", _ptr(g, F32), *args, _ptr(ws, F32, True), _ptr(dE), _ptr(db), _stream())
+    return dE, db
 
 
 def pair_ll(uv, hid1, pos, wg, w2, b2, emb_w, emb_b, n_obj, obj_off, max_n, req_col, req_tile, req_orient, tiles, default_ll=-30.0,

@@ -224,8 +224,10 @@ class ProgramDataset(torch.utils.data.Dataset):
             return _strip_negation(arguments), name
         if operator == 'compare':
             return _strip_negation([arguments[0]]), name
-        if operator in ('exist', 'and', 'or', 'end'):
+        if operator in ('exist', 'and', 'or', 'end', 'scene'):
             return [], name
+        from .gqa_ops import refuse_direct_supervision
+        refuse_direct_supervision(operator)
         raise KeyError(operator)
 
     def _collect_tokens(self, program):
@@ -270,6 +272,61 @@ class ProgramDataset(torch.utils.data.Dataset):
             w = q['weights']
             result['weights'] = [x for sub in w for x in sub] if len(w) > 0 and isinstance(w[0], (list, tuple)) else w
         return result
+
+
+def scene_meta_data(questions, object_nums, ontology):
+    """The collater's direct-supervision meta data (batch_gqa_boxfeatures_pipeline.py:94-155) for questions that carry them:
+      object_pairs    {'subject_id': [...per question], 'object_id': [...]}: the listed pairs of every image (:94-97)
+      attribute_answer / attribute_weight  [objects, attributes] from `attribute_dict` {object index: [(attribute, weight), ...]} (:103-130):
+                      a named attribute sets answer 1 and its weight; every object that is named also weighs its noun columns and the
+                      family of each named attribute with 1
+      relation_answer / relation_weight    [listed relations, relations] from `relation_list` [(relation, weight), ...] (:132-155): weights
+                      start at 1, a named relation sets answer 1 and its weight
+    as float32 arrays (the reference builds float64 and casts them to float32 for the loss).  -> the keys that apply, as a dict."""
+    out = {}
+    if any('object_pairs' in q for q in questions):
+        pick = lambda q, k: q['object_pairs'][k] if 'object_pairs' in q and k in q['object_pairs'] else []
+        out['object_pairs'] = {'subject_id': [pick(q, 'subject_id') for q in questions], 'object_id': [pick(q, 'object_id') for q in questions]}
+    a2i = ontology._vocabulary['arg_to_idx']
+    if any('attribute_dict' in q for q in questions):
+        A = len(ontology._attribute_index)
+        total = int(sum(object_nums))
+        answer, weight = np.zeros((total, A), np.float32), np.zeros((total, A), np.float32)
+        attributes = set(ontology._attributes)
+        offset = 0
+        for i, q in enumerate(questions):
+            ind1, ind2, w = [], [], []
+            for obj_index, att_list in q['attribute_dict'].items():
+                w_ind = set(ontology._noun_subindex)
+                for a in att_list:
+                    if a[0] in a2i and a[0] in attributes:
+                        ind1.append(int(obj_index) + offset)
+                        ind2.append(ontology._attribute_reveresed_index[a2i[a[0]] - 1])
+                        w.append(a[1])
+                        w_ind = w_ind | set(ontology.get_family_subindex(a[0]))
+                weight[int(obj_index) + offset, list(w_ind)] = 1.0
+            answer[ind1, ind2] = 1.0
+            weight[ind1, ind2] = w
+            offset += int(object_nums[i])
+        out['attribute_answer'], out['attribute_weight'] = answer, weight
+    if any('relation_list' in q for q in questions):
+        R = len(ontology._relation_index)
+        nums = [len(q['relation_list']) for q in questions]
+        answer, weight = np.zeros((sum(nums), R), np.float32), np.ones((sum(nums), R), np.float32)
+        relations = set(ontology._relations)
+        offset = 0
+        for i, q in enumerate(questions):
+            ind1, ind2, w = [], [], []
+            for j, rel in enumerate(q['relation_list']):
+                if rel[0] in a2i and rel[0] in relations:
+                    ind1.append(j + offset)
+                    ind2.append(ontology._relation_reveresed_index[a2i[rel[0]] - 1])
+                    w.append(rel[1])
+            answer[ind1, ind2] = 1.0
+            weight[ind1, ind2] = w
+            offset += nums[i]
+        out['relation_answer'], out['relation_weight'] = answer, weight
+    return out
 
 
 class BatchGQABoxFeaturesCollator(ProgramCollaterBase):
@@ -344,13 +401,16 @@ class BatchGQABoxFeaturesCollator(ProgramCollaterBase):
                     pb._feature_source = "host"             # (an image of the batch is not resident: ProgramBatch.to_cuda counts the miss)
         return result
 
-    def collate_meta_data(self, questions):             # :75-92 (the direct-supervision extras are out of scope)
+    def collate_meta_data(self, questions):             # :75-92, and the direct-supervision extras :94-155
         tokens = sorted({t for q in questions for t in q['tokens']}, key=str)
         emb = self._gqa_ontology.get_embeddings([str(t) for t in tokens])
-        return {'index': {t: i for i, t in enumerate(tokens)},
-                'embedding': torch.zeros(len(tokens), 1) if emb is None else torch.from_numpy(emb).float(),
-                'questions': [q.get('question') for q in questions], 'image_ids': [q['image_id'] for q in questions],
-                'question_ids': [q.get('question_id') for q in questions]}
+        result = {'index': {t: i for i, t in enumerate(tokens)},
+                  'embedding': torch.zeros(len(tokens), 1) if emb is None else torch.from_numpy(emb).float(),
+                  'questions': [q.get('question') for q in questions], 'image_ids': [q['image_id'] for q in questions],
+                  'question_ids': [q.get('question_id') for q in questions]}
+        if any(k in q for q in questions for k in ('object_pairs', 'attribute_dict', 'relation_list')):
+            result.update(scene_meta_data(questions, [int(self._object_info[q['image_id']]['objectsNum']) for q in questions], self._gqa_ontology))
+        return result
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -549,6 +549,47 @@ class GQAChooseRelBatch(GQABatchOperatorBase):
         return _result(answer, log_probability, relation_list_list, x, QuestionType.QUERY, x.cumulative_loss(), x._prev_variable_sets_num + 1, alp)
 
 
+_REFUSED_OPS = {
+    'object_attr': "operator object_attr and the OBJECT_STATEMENT loss need only existing kernels and host work: they are the follow-up of the "
+                   "scene-graph supervision (operator scene, DESIGN.md 3.8) and are not built yet",
+    'object_rel': "operator object_rel cannot run in the reference either: range(relation_list) at batch_gqa_ops.py:867 raises TypeError under "
+                  "give_answer, and nothing produces the relation_pairobject_map its oracle branch reads",
+}
+
+
+def refuse_direct_supervision(op_name):
+    """object_attr / object_rel stay refused, with the reason (the third direct-supervision operator, scene, is GQASceneOpBatch)."""
+    if op_name in _REFUSED_OPS:
+        raise NotImplementedError(_REFUSED_OPS[op_name])
+
+
+class GQASceneOpBatch(GQABatchOperatorBase):
+    """batch_gqa_ops.py:883-902: the scene-graph supervision's terminal operator, fan-in 0.  The world of a `scene` batch carries a
+    visual_oracle.SceneLikelihood (interpreter.build_scene_graph): the hidden rows of every object and of the listed pairs, not the two dense
+    tables; `log_probability` is that object.  `answer` follows the reference literally - (table > 0.5) on a LOG-likelihood, so every entry
+    is 0 - and is the one place that materialises the tables."""
+
+    def __init__(self, oracle, ontology):
+        # (the world carries the likelihood: the operator holds no oracle, so the interpreter's state_dict keeps its keys)
+        super(GQASceneOpBatch, self).__init__(None, ontology, is_terminal=True, fan_in=0, fan_out=0)
+
+    def forward(self, op_id, world, give_answer=True, predicate_question_map=None, likelihood_threshold=0, hard_mode=False):
+        from .visual_oracle import SCENE_THRESHOLD
+        like = getattr(world, "_scene_likelihood", None)
+        if like is None:
+            raise L.DfolError("operator `scene` runs on a batch whose program is `scene` alone (interpreter.build_scene_graph)")
+        answer, alp = [], []
+        if give_answer:
+            with torch.no_grad():
+                flags = [(t > SCENE_THRESHOLD).float() for t in like.tables()]
+            _reads(*flags)
+            answer, alp = _answers(lambda: ([_host(f) for f in flags], []))
+        return _result(answer, like, [], None, QuestionType.SCENE_GRAPH, 0, 0, alp)
+
+    def transform_attention(self, op_id, is_forward, world, attention_state, attribute_list, op_feature, predicate_question_map=None):
+        return attention_state
+
+
 def _lp_of(v, hard):
     return v.log_probability(hard) if isinstance(v, BatchVariableSet) else v['log_probability']
 

@@ -17,8 +17,13 @@ from .host_util import keeping, reverse_dependencies, upload
 
 def gather_results(outputs, target_device=None, is_cuda=True):
     """Concatenate per-ProgramBatch results (data_parallel.py:15-50)."""
-    if outputs[0]['type'] == QuestionType.SCENE_GRAPH:
-        raise NotImplementedError("scene-graph (direct supervision) results are out of scope (SURVEY.md §2 row 4)")
+    if outputs[0]['type'] == QuestionType.SCENE_GRAPH:       # data_parallel.py:16-30: each table along dim 0, each answer array along axis 0
+        from .visual_oracle import SceneLikelihood
+        n_answers = len(outputs[0]['answer'])
+        return {'answer': [np.concatenate([o['answer'][i] for o in outputs], axis=0) for i in range(n_answers)],
+                'log_probability': SceneLikelihood.concat([o['log_probability'] for o in outputs]), 'options': outputs[0]['options'],
+                'variable_set': None, 'type': outputs[0]['type'], 'cumulative_loss': sum(o['cumulative_loss'] for o in outputs),
+                'variable_sets_num': sum(o['variable_sets_num'] for o in outputs), 'answer_log_probability': []}
     log_probability = torch.cat([o['log_probability'].reshape(-1) for o in outputs]) if len(outputs) > 1 else \
         outputs[0]['log_probability'].reshape(-1)
     answer = [a for o in outputs for a in o['answer']]
@@ -539,6 +544,46 @@ class BatchInterpreterBase(nn.Module):
         geometry._relation_features = relation_features
         return geometry
 
+    def build_scene_graph(self, device, program_batch):
+        """The world of a batch whose program is `scene` alone (operator scene, batch_gqa_ops.py:883-902): the featurizer, the attribute
+        network over every object row, and the relation network over the pairs `meta_data['object_pairs']` lists - the rows
+        [subject, object, distance, angle, sides] of batch_gqa_boxfeatures_pipeline.py:225-279 for the listed (subject, object) indices,
+        offset per image (:238-249), in torch index ops (P is small) - never over all pairs of an image: no pair trunk runs.  The world
+        carries a SceneLikelihood (the hidden rows of both sides) instead of likelihood tables."""
+        from .visual_oracle import SceneLikelihood
+        if self._featurizer is None:
+            raise NotImplementedError("a featurizer is required (the reference's featurizer-less branch :62-67 is dead code)")
+        if getattr(program_batch, "_question_image", None) is not None:
+            raise NotImplementedError("a `scene` batch names one image per question: share_scenes is not built for it")
+        meta = program_batch._meta_data or {}
+        feats, batch_index = program_batch._object_features, program_batch._object_batch_index
+        world = BatchWorld(device, feats.size(0), None, None, batch_index, meta, attention_transfer_state_dim=self._attention_transfer_state_dim,
+                           object_nums=getattr(program_batch, "_object_nums", None))
+        if 'world_geometry' in inspect.signature(self._featurizer.featurize_scene).parameters:
+            obj = self._featurizer.featurize_scene(device, feats, batch_index, meta, world_geometry=None)['attribute_features']
+        else:
+            raise NotImplementedError("operator `scene` needs this package's featurizer (it builds the listed pairs' rows itself)")
+        first = np.concatenate([[0], np.cumsum(world._img_n_list)])[:-1]
+        pairs = meta.get('object_pairs') or {'subject_id': [], 'object_id': []}
+        ind_s = [int(i) + int(o) for o, ids in zip(first, pairs['subject_id']) for i in ids]          # :242-246
+        ind_o = [int(i) + int(o) for o, ids in zip(first, pairs['object_id']) for i in ids]
+        if len(ind_s) != len(ind_o) or any(not 0 <= i < world._object_num for i in ind_s + ind_o):
+            raise L.DfolError("object_pairs: subject and object lists differ in length or name an object the batch does not have")
+        D = obj.shape[1]
+        if ind_s:
+            s, o = obj.index_select(0, upload(np.asarray(ind_s, np.int64), device)), obj.index_select(0, upload(np.asarray(ind_o, np.int64), device))
+            ps, po = s[:, D - 4:], o[:, D - 4:]
+            dx = ps[:, 0] + ps[:, 2] / 2.0 - po[:, 0] - po[:, 2] / 2.0
+            dy = ps[:, 1] + ps[:, 3] / 2.0 - po[:, 1] - po[:, 3] / 2.0
+            dist = torch.sqrt(dx * dx + dy * dy)                                                       # :271-278
+            geo = torch.stack([dist, torch.asin(dy / dist.clamp(min=1e-10)), (po[:, 0] - ps[:, 0]).sign(), (po[:, 1] - ps[:, 1]).sign()], 1)
+            pair_rows = torch.cat([s, o, geo], 1).contiguous()
+        else:
+            pair_rows = obj.new_zeros(0, 2 * D + 4)
+        world._attribute_features, world._relation_features = obj, {'features': pair_rows, 'index': None}      # (the rows, as in the uncached reference)
+        world._scene_likelihood = SceneLikelihood(*self._oracle.scene_hidden(obj, pair_rows), self._oracle)
+        return world
+
     # `range_overflow` (config key, experiment.build_interpreter): what an INFERENCE forward does when a kernel of the default two-piece fp16
     # arithmetic left fp16's range - "raise" (DfolError naming the remedy) or "rerun" (that batch again on "bf16x3": range_rerun).  A forward a
     # gradient reaches - training.train_batch, GraphedTrainStep - raises under either: by the time the flag is read its backward has run, and
@@ -647,6 +692,20 @@ class BatchInterpreterBase(nn.Module):
         spec = self._native_spec(is_training, modulator_switch, return_trace)
         for program_batch in program_batch_list:
             feats = program_batch._object_features
+            if (program_batch.terminal_op_name() if hasattr(program_batch, "terminal_op_name") else None) == 'scene':
+                ops = list(program_batch._op_batch_list)
+                if any(ob._op_name != 'scene' for ob in ops):
+                    raise NotImplementedError("operator `scene` is served for a batch whose program is `scene` alone")
+                # scene-graph supervision: the Python operator on a world without likelihood tables; the native executor has no opcode for
+                # it and a graph capture is not built for it
+                if _lib.capturing():
+                    raise NotImplementedError("a `scene` batch inside a graph capture (GraphedForward / GraphedTrainStep) is not built")
+                _lib.note("scene_python")
+                world = self.build_scene_graph(program_batch.device, program_batch)
+                x, _ = self._execute(ops[-1]._op_id, world, ops[-1], (), True, is_training)
+                all_results.append(x)
+                all_traces.append([x])
+                continue
             if spec is not None and (isinstance(feats, torch.Tensor) or hasattr(feats, "materialize")) and feats.is_cuda:
                 from . import gqa_ops, native_exec
                 plan = native_exec.plan_for(self, program_batch, spec)
@@ -748,7 +807,7 @@ class BatchGQAInterpreter(BatchInterpreterBase):
             'verify_rel': gqa.GQAVerifyRelBatch(o, t, **kw), 'exist': gqa.GQAExistBatch(o, t), 'and': gqa.GQAAndBatch(o, t),
             'or': gqa.GQAOrBatch(o, t), 'all_same': gqa.GQAAllSameBatch(o, t, **kw), 'all_different': gqa.GQAAllDifferentBatch(o, t, **kw),
             'two_same': gqa.GQATwoSameBatch(o, t, **kw), 'two_different': gqa.GQATwoDifferentBatch(o, t, **kw),
-            'compare': gqa.GQACompareBatch(o, t, **kw), 'end': gqa.GQAEndBatch(o, t),
+            'compare': gqa.GQACompareBatch(o, t, **kw), 'end': gqa.GQAEndBatch(o, t), 'scene': gqa.GQASceneOpBatch(o, t),
         })
 
     # one-hot position of every operator in the LSTM input (batch_gqa_interpreter.py:67-70)
@@ -766,6 +825,7 @@ class BatchGQAInterpreter(BatchInterpreterBase):
         return x, is_terminal
 
     def _execute(self, op_id, world, operator_batch, input_tuple, is_terminal, is_training):
+        gqa.refuse_direct_supervision(operator_batch._op_name)
         op = self._ops[operator_batch._op_name]
         x = op(*((op_id, world) + input_tuple + tuple(operator_batch._arguments) +
                  (not is_training, operator_batch._predicate_question_map, self._likelihood_threshold, self._hard_mode)))

@@ -390,6 +390,68 @@ def linear_act(x, weight, bias, act, out=None):
     return _lib.linear_act(x, weight, bias, act, out)
 
 
+# ---- scene-graph supervision: weighted BCE of all concept columns (operator `scene`; trainer.py:235-256, :265-275) -----------------------
+SCENE_BCE_ROUTE = os.environ.get("DFOL_SCENE_BCE", "hip")     # "torch": the tensor-op route on the GPU too (A/B runs, tools/bench_scene.py)
+_SCENE_COLS_CHECKED = {}
+
+
+def _scene_cols_checked(cols, n_rows):
+    """cols names every embedding row at most once and none beyond the layer: the backward adds its compact rows into the layer's gradient with
+    index_add_, which is ordered only without repeats, and the kernels clamp a row index instead of faulting.  Checked once per index tensor
+    and content version (it is a registered buffer or a cached upload); the entry dies with the tensor, so a reused address is checked again.
+    (A direct call of torch.ops.dfol.scene_bce is the caller's own: this front is where the check lives.)"""
+    import weakref
+    key = id(cols)
+    hit = _SCENE_COLS_CHECKED.get(key)
+    if hit is not None and hit[0]() is cols and hit[1] == (cols._version, n_rows):
+        return
+    if cols.numel():
+        if torch.unique(cols).numel() != cols.numel():
+            raise DfolError("scene_bce: cols repeats a row of the embedding layer")
+        lo, hi = int(cols.min()), int(cols.max())
+        if lo < 0 or hi >= n_rows:
+            raise DfolError("scene_bce: cols names rows %d .. %d of an embedding layer of %d rows" % (lo, hi, n_rows))
+    _SCENE_COLS_CHECKED[key] = (weakref.ref(cols, lambda _, k=key: _SCENE_COLS_CHECKED.pop(k, None)), (cols._version, n_rows))
+
+
+def scene_bce_reference(h, emb_w, emb_b, cols, target, weight, thr):
+    """The reference's expressions in tensor ops, in the dtype of h (classifier_oracle.py:139-143, trainer.py:235-256, :265-275): the route of CPU
+    tensors and of sizes the kernels decline; tests run it in float64."""
+    idx = cols.to(torch.int64)
+    z = h @ emb_w[idx].t()
+    if emb_b is not None:
+        z = z + emb_b[idx]
+    lp = torch.nn.functional.logsigmoid(z)
+    loss = torch.nn.functional.binary_cross_entropy(lp.exp(), target, weight=weight, reduction="sum")
+    with torch.no_grad():
+        a = (lp > thr).to(target.dtype)
+        either = ((target + a) > 0).to(target.dtype)
+        num = (weight * either * (target != a).to(target.dtype)).sum()
+        den = (weight * either).sum()
+    return loss, num, den
+
+
+def scene_bce(h, emb_w, emb_b, cols, target, weight, thr):
+    """(loss, num, den) of the scene-graph supervision over the rows `cols` of the embedding layer: z = h emb_w[cols]^T + emb_b[cols],
+    loss = binary_cross_entropy(exp(logsigmoid(z)), target, weight, 'sum'); num / den = the weighted mismatch count of the metric and its
+    denominator at the threshold thr on the log-likelihood.  On the GPU one fused launch (+ an ordered sum) without any [M, C] array; the
+    gradient goes to h, emb_w and emb_b through two more.  CPU tensors, and sizes dfol_scene_bce_supported declines, take the tensor-op route."""
+    M, H = h.shape
+    if not h.is_cuda or SCENE_BCE_ROUTE == "torch" or h.dtype != torch.float32 or not _lib.scene_bce_supported(M, H, cols.numel()):
+        _lib.note("scene_bce_torch")
+        return scene_bce_reference(h, emb_w, emb_b, cols, target, weight, thr)
+    _scene_cols_checked(cols, emb_w.shape[0])
+    _lib.note("scene_bce_hip")
+    if h.stride(-1) != 1:
+        h = h.contiguous()
+    target, weight = target.contiguous(), weight.contiguous()
+    if _needs_grad(h, emb_w, emb_b):
+        s = torch.ops.dfol.scene_bce(h, emb_w, emb_b, cols, target, weight, float(thr))
+    else:
+        s = _lib.scene_bce_fwd(h, emb_w, emb_b, cols, target, weight, thr)
+    return s[0], s[1].detach(), s[2].detach()
+
+
 class _PairFeatures(torch.autograd.Function):
     """[obj_s, obj_o, geometry]: the gradient flows back to the two object rows (the geometry comes from the raw boxes).  Only the
     full-table compatibility dataflow (`_needed_columns = False`) builds the [pairs, 1036] matrix; its backward is torch's atomic

@@ -258,4 +258,58 @@ def _(uv, hid1, pos, wg, w2, b2, hid2, emb_w, emb_b, n_obj, obj_off, max_n, req_
     return None
 
 
+# ---- scene-graph supervision: the fused all-concepts weighted BCE (trainer.py:235-256, :265-275; csrc/dfol_scene.hip) ----------------------
+@_op("dfol::scene_bce", mutates_args=())
+def scene_bce(h: Tensor, emb_w: Tensor, emb_b: Optional[Tensor], cols: Tensor, target: Tensor, weight: Tensor, thr: float) -> Tensor:
+    """-> [3]: the loss, the metric's numerator and its denominator; only the loss carries a gradient."""
+    return _lib.scene_bce_fwd(h, emb_w, emb_b, cols, target, weight, thr)
+
+
+@scene_bce.register_fake
+def _(h, emb_w, emb_b, cols, target, weight, thr):
+    return h.new_empty(3)
+
+
+@_op("dfol::scene_bce_bwd", mutates_args=())
+def scene_bce_bwd(g: Tensor, h: Tensor, emb_w: Tensor, emb_b: Optional[Tensor], cols: Tensor, target: Tensor, weight: Tensor, need_h: bool,
+                  need_e: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """g: the loss's upstream gradient, one device word.  -> dh [M, H], and dE [C, H], db [C] of the rows `cols` (compact); a gradient that is
+    not needed comes back empty."""
+    e = h.new_empty(0)
+    dh = _lib.scene_bce_bwd_rows(g, h, emb_w, emb_b, cols, target, weight) if need_h else e
+    dE, db = _lib.scene_bce_bwd_cols(g, h, emb_w, emb_b, cols, target, weight) if need_e else (e, h.new_empty(0))
+    return dh, dE, db
+
+
+@scene_bce_bwd.register_fake
+def _(g, h, emb_w, emb_b, cols, target, weight, need_h, need_e):
+    C, H = cols.shape[0], h.shape[1]
+    return (h.new_empty(h.shape[0], H) if need_h else h.new_empty(0)), (h.new_empty(C, H) if need_e else h.new_empty(0)), \
+        (h.new_empty(C) if need_e else h.new_empty(0))
+
+
+def _scene_setup(ctx, inputs, output):
+    h, emb_w, emb_b, cols, target, weight, thr = inputs
+    ctx.save_for_backward(h, emb_w, emb_b, cols, target, weight)
+
+
+def _scene_backward(ctx, g):
+    h, emb_w, emb_b, cols, target, weight = ctx.saved_tensors
+    need_h = bool(ctx.needs_input_grad[0])
+    need_b = emb_b is not None and bool(ctx.needs_input_grad[2])
+    need_e = bool(ctx.needs_input_grad[1]) or need_b
+    dh, dE, db = torch.ops.dfol.scene_bce_bwd(g[:1].contiguous(), h.detach(), emb_w.detach(), None if emb_b is None else emb_b.detach(), cols, target,
+                                              weight, need_h, need_e)
+    g_w = g_b = None
+    idx = cols.to(torch.int64)
+    if ctx.needs_input_grad[1]:                              # (cols has no repeats - ops.scene_bce asserts it - so the adds are ordered)
+        g_w = torch.zeros_like(emb_w).index_add_(0, idx, dE)
+    if need_b:
+        g_b = torch.zeros_like(emb_b).index_add_(0, idx, db)
+    return (dh if need_h else None), g_w, g_b, None, None, None, None
+
+
+scene_bce.register_autograd(_scene_backward, setup_context=_scene_setup)
+
+
 CORE_OPS = ("filter_fwd", "relate_fwd", "relate_one_fwd", "quantify_fwd", "linear_act", "pair_ll")

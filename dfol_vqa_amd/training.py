@@ -29,7 +29,7 @@ def _targets(values, device):
 
 
 def compute_loss(program_batch_list, prediction, l1_lambda=0.0, parameters=None, l1_scale=1.0):
-    """trainer.py:181-262 for STATEMENT / BINARY / QUERY predictions (sum over the batch, not yet divided by it).
+    """trainer.py:181-262 for STATEMENT / BINARY / QUERY / SCENE_GRAPH predictions (sum over the batch, not yet divided by it).
 
     `l1_scale`: with R data-parallel ranks every rank adds the regulariser to its local loss and the gradients are then
     summed, so each rank passes 1/R and the summed gradient carries the term once, as the single-process step does."""
@@ -56,12 +56,54 @@ def compute_loss(program_batch_list, prediction, l1_lambda=0.0, parameters=None,
             seg = torch.tensor([i for i, t in enumerate(target) for _ in t], dtype=torch.int64, device=device)
             denom = torch.zeros(len(target), dtype=torch.float32, device=device).index_add(0, seg, lp.exp())
         loss = safe_log(denom).sum() - (tflat * lp).sum()
+    elif qtype == QuestionType.SCENE_GRAPH:              # :235-256: attr_loss + rel_loss, each one fused launch (SceneLikelihood.bce)
+        loss = sum(s[0] for s in _scene_sums(program_batch_list, prediction))
     else:
-        raise NotImplementedError("direct-supervision losses (OBJECT_STATEMENT / SCENE_GRAPH) are out of scope")
+        raise NotImplementedError("the OBJECT_STATEMENT loss (operator object_attr) is the follow-up of the scene-graph supervision; "
+                                  "object_rel cannot run in the reference either (batch_gqa_ops.py:867)")
     if l1_lambda and parameters is not None:             # :258-260
         allp = torch.cat([p.view(-1) for p in parameters if p.requires_grad])
         loss = loss + l1_scale * l1_lambda * torch.norm(allp, 1) / max(1, allp.numel())
     return loss
+
+
+_SCENE_UPLOAD_CACHE_BYTES = 1 << 20
+
+
+def _scene_sums(program_batch_list, prediction):
+    """[(loss, num, den) of the attribute side, of the relation side] of a SCENE_GRAPH prediction whose log_probability is a
+    visual_oracle.SceneLikelihood; the dense targets and weights of the batches' meta data (attribute_answer / attribute_weight [O, A],
+    relation_answer / relation_weight [P, R]: trainer.py:236-240) go through the upload cache while they are small (up to 1 MiB: the cache keys
+    on the content) and by a plain copy above that.  The sums are kept on the prediction: the metric after the loss launches nothing."""
+    import numpy as np
+    from .host_util import upload
+    from .visual_oracle import SCENE_THRESHOLD
+    kept = prediction.get('_scene_sums')
+    if kept is not None and kept[0] is program_batch_list:
+        return kept[1]
+    like = prediction['log_probability']
+    device = like.h_attr.device
+
+    def cat(key):
+        parts = [np.asarray(pb._meta_data[key], np.float32) for pb in program_batch_list]
+        a = np.ascontiguousarray(parts[0] if len(parts) == 1 else np.concatenate(parts, axis=0))
+        return upload(a, device) if a.nbytes <= _SCENE_UPLOAD_CACHE_BYTES else torch.from_numpy(a).to(device)
+    sums = [like.bce("attribute", cat('attribute_answer'), cat('attribute_weight'), SCENE_THRESHOLD),
+            like.bce("relation", cat('relation_answer'), cat('relation_weight'), SCENE_THRESHOLD)]
+    prediction['_scene_sums'] = (program_batch_list, sums)
+    return sums
+
+
+def scene_evaluation_metric(program_batch_list, prediction):
+    """trainer.py:265-275 from the fused sums of both sides: the weighted share of mismatches among the cells where target or answer is set.
+    A zero denominator gives what numpy's division gives in the reference (nan, or inf for a positive numerator)."""
+    import numpy as np
+    with torch.no_grad():
+        sums = _scene_sums(program_batch_list, prediction)
+        nom = np.float32(sum(float(s[1]) for s in sums))
+        denom = np.float32(sum(float(s[2]) for s in sums))
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return nom / denom
 
 
 def _direct_grad(on):
@@ -362,8 +404,14 @@ ERROR_DIM = len(OP_INDEX) + 1
 
 
 def compute_evaluation_metrics(program_batch_list, prediction, first_answer=False):
-    """Error rate of a batch (trainer.py:264-318): a QUERY answer set scores 1/|set| when it contains the gold answer."""
+    """Error rate of a batch (trainer.py:264-318): a QUERY answer set scores 1/|set| when it contains the gold answer.
+
+    SCENE_GRAPH: the prediction keeps the sums compute_loss launched for this list of batches (`prediction['_scene_sums']`, keyed by the
+    list's identity, loss tensor and its autograd graph included, for as long as the prediction lives), so the metric after the loss
+    launches nothing.  Meta data changed in place afterwards is not seen: drop the key, or pass a fresh prediction."""
     import numpy as np
+    if prediction['type'] == QuestionType.SCENE_GRAPH:   # :265-275
+        return scene_evaluation_metric(program_batch_list, prediction)
     answers = [a for pb in program_batch_list for a in pb._answers]
     if first_answer:
         match = [a in op[0] if len(op) > 0 else False for a, op in zip(answers, prediction['answer'])]

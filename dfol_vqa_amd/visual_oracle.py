@@ -682,6 +682,54 @@ class _EmbRows(torch.autograd.Function):
         return gw, gb, None, None
 
 
+SCENE_THRESHOLD = 0.5     # the reference thresholds the LOG-likelihood tables at 0.5 (batch_gqa_ops.py:883-902, trainer.py:265-275): no entry passes
+
+
+class SceneLikelihood(object):
+    """What operator `scene` returns as its log_probability: the hidden rows of both sides and the embedding layer, not the two dense tables.
+    tables() materialises [attribute table [O, A], relation table [P, R]] on request (classifier_oracle.py:139-143); bce() is the weighted BCE
+    of one side against dense targets with the metric's two sums, fused (ops.scene_bce) - the tables never exist."""
+
+    def __init__(self, h_attr, h_rel, oracle):
+        self.h_attr, self.h_rel, self._oracle = h_attr, h_rel, oracle
+
+    @property
+    def device(self):
+        return self.h_attr.device
+
+    @staticmethod
+    def concat(parts):
+        """The likelihoods of several ProgramBatches as one, rows in batch order (data_parallel.py:16-23 gathers each table along dim 0)."""
+        parts = list(parts)
+        if len(parts) == 1:
+            return parts[0]
+        return SceneLikelihood(torch.cat([p.h_attr for p in parts], 0), torch.cat([p.h_rel for p in parts], 0), parts[0]._oracle)
+
+    def _side(self, which):
+        if which not in ("attribute", "relation"):
+            raise ValueError("SceneLikelihood: side %r is neither 'attribute' nor 'relation'" % (which,))
+        return (self.h_attr if which == "attribute" else self.h_rel), self._oracle._index_rows(which)
+
+    def tables(self):
+        lin = self._oracle._embedding_network.linear
+        out = []
+        for which in ("attribute", "relation"):
+            h, cols = self._side(which)
+            if h.shape[0] == 0:
+                out.append(h.new_zeros(0, cols.numel()))
+                continue
+            idx = cols.to(torch.int64)
+            out.append(L.linear_act(h, lin.weight.index_select(0, idx).contiguous(),
+                                    None if lin.bias is None else lin.bias.index_select(0, idx).contiguous(), L.ACT_LOGSIGMOID))
+        return out
+
+    def bce(self, which, target, weight, thr=SCENE_THRESHOLD):
+        """-> (loss, num, den) of side `which` against dense target / weight [rows, concepts of that side] (trainer.py:235-256, :265-275)."""
+        h, cols = self._side(which)
+        lin = self._oracle._embedding_network.linear
+        return L.scene_bce(h, lin.weight, lin.bias, cols, target, weight, thr)
+
+
 class ClassifierOracle(OracleBase):
     """classifier_oracle.py:11-156 with cached tables (the only mode the reference's experiments use:
     gqa_interpreter_experiments.py:209-210 builds it with cached=True)."""
@@ -711,6 +759,32 @@ class ClassifierOracle(OracleBase):
         w = (lin.weight if live else lin.weight.detach()).index_select(0, idx).contiguous()
         b = None if lin.bias is None else (lin.bias if live else lin.bias.detach()).index_select(0, idx).contiguous()
         return w, b
+
+    # ---- scene-graph supervision: all concept columns at once (classifier_oracle.py:139-143) --------------
+    def _index_rows(self, which):
+        """The attribute (relation) rows of the embedding layer as an int32 device tensor, through the upload cache."""
+        index = self._ontology._attribute_index if which == "attribute" else self._ontology._relation_index
+        return upload(np.asarray(index, np.int32), self._embedding_network.linear.weight.device)
+
+    def scene_hidden(self, object_features, pair_rows):
+        """-> (h_attr [O, H], h_rel [P, H]): the rows entering the embedding layer's Linear, each after the embedding layer's own Dropout when
+        one is active (a site of its own per side, as in compute_all_log_likelihood_2).  pair_rows may have no rows."""
+        drop = self._embedding_network._network[0]
+        p = drop.p if isinstance(drop, nn.Dropout) and drop.training else 0.0
+        h_attr = L.dropout(self._attribute_network(object_features), p)
+        if pair_rows.shape[0]:
+            h_rel = L.dropout(self._relation_network(pair_rows), p)
+        else:
+            h_rel = pair_rows.new_zeros(0, self._embedding_network.linear.in_features)
+        return h_attr, h_rel
+
+    def compute_all_log_likelihood(self, object_features, pair_object_features):
+        """classifier_oracle.py:139-143: the [O, attributes] and [P, relations] log-likelihood tables of ALL concepts; only the indexed rows of
+        the embedding layer are multiplied ([:, index] commutes with the product).  pair_object_features: the pair rows, or the reference's
+        dict with them under 'features'."""
+        if isinstance(pair_object_features, dict):
+            pair_object_features = pair_object_features["features"]
+        return SceneLikelihood(*self.scene_hidden(object_features, pair_object_features), self).tables()
 
     def compute_all_log_likelihood_2(self, object_features, pair_object_features):
         if self._embedding_network is None or self._attribute_network is None:

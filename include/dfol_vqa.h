@@ -1153,6 +1153,34 @@ int dfol_set_program_gates(const float* table, int32_t n_gates);
 int dfol_run_program(const DfolProgramModel* model, const DfolProgramScene* scene, const int64_t* instr_host, int32_t n_instr,
                      const void* blob, void* workspace, void* stream);
 
+/* ---- scene-graph supervision: the weighted BCE of all concept columns, fused (csrc/dfol_scene.hip) -----------------------------------
+ * Operator `scene` (batch_gqa_ops.py:883-902) under the SCENE_GRAPH loss and metric (trainer.py:235-256, :265-275) without any [M, C] array:
+ *   z = h emb_w[cols]^T + emb_b[cols],  lp = LogSigmoid(z),  p = e^lp,  log(1 - p) taken as LogSigmoid(-z) = lp - z
+ *   h       [M, ldh >= H] the rows entering the embedding layer;  emb_w [C_all, lde >= H], emb_b [C_all] or NULL
+ *   cols    [C] int32 rows of emb_w in any order (clamped to [0, C_all) by the kernels; the gradient outputs assume no repeats)
+ *   target, weight  [M, C] dense fp32
+ * dfol_scene_bce_fwd_f32:  sums[0] = sum -w (t max(lp, -100) + (1 - t) max(log(1 - p), -100))   (binary_cross_entropy(p, t, w, 'sum')),
+ *   sums[1] = sum w [(t + a) > 0] [t != a],  sums[2] = sum w [(t + a) > 0],  a = [lp > thr].  workspace: dfol_scene_bce_fwd_workspace floats
+ *   (workgroup partials, added by a second ordered pass).  An element of h or emb_w[cols] beyond fp16's largest finite value (or NaN) ORs
+ *   DFOL_RANGE_X_OVERFLOW into the dfol_set_range_status word.
+ * dfol_scene_bce_bwd_rows_f32:  dh [M, ld_dh] = dz emb_w[cols],  dz = g[0] w (p - t) p (1 - p) / max(p (1 - p), 1e-12);  g is a device word.
+ * dfol_scene_bce_bwd_cols_f32:  dE [C, H] = dz^T h and db [C] = sum_rows dz, compact (row c belongs to emb_w row cols[c]); workspace:
+ *   dfol_scene_bce_bwd_cols_workspace floats (may be NULL when that is 0).
+ * No atomics on any sum: two runs give the same bits.  M = 0 or C = 0 launch nothing and zero the outputs.  1 <= H <= 320
+ * (dfol_scene_bce_supported; K is padded inside the kernels); two fp16 pieces per operand for z, three bf16 pieces for the backward products. */
+int dfol_scene_bce_supported(int32_t M, int32_t H, int32_t C); /* 1 / 0 */
+int64_t dfol_scene_bce_fwd_workspace(int32_t M, int32_t H, int32_t C);
+int64_t dfol_scene_bce_bwd_cols_workspace(int32_t M, int32_t H, int32_t C);
+int dfol_scene_bce_fwd_f32(const float* h, int64_t ldh, int32_t M, int32_t H, const float* emb_w, int64_t lde, int32_t C_all, const float* emb_b,
+                           const int32_t* cols, int32_t C, const float* target, const float* weight, float thr, float* workspace, float* sums,
+                           void* stream);
+int dfol_scene_bce_bwd_rows_f32(const float* g, const float* h, int64_t ldh, int32_t M, int32_t H, const float* emb_w, int64_t lde, int32_t C_all,
+                                const float* emb_b, const int32_t* cols, int32_t C, const float* target, const float* weight, float* dh, int64_t ld_dh,
+                                void* stream);
+int dfol_scene_bce_bwd_cols_f32(const float* g, const float* h, int64_t ldh, int32_t M, int32_t H, const float* emb_w, int64_t lde, int32_t C_all,
+                                const float* emb_b, const int32_t* cols, int32_t C, const float* target, const float* weight, float* workspace,
+                                float* dE, float* db, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
