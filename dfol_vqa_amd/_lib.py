@@ -245,6 +245,8 @@ SIGNATURES = {
     "dfol_scene_bce_fwd_f32": [_p, _i64, _i32, _i32, _p, _i64, _i32, _p, _p, _i32, _p, _p, _f, _p, _p, _p],
     "dfol_scene_bce_bwd_rows_f32": [_p, _p, _i64, _i32, _i32, _p, _i64, _i32, _p, _p, _i32, _p, _p, _p, _i64, _p],
     "dfol_scene_bce_bwd_cols_f32": [_p, _p, _i64, _i32, _i32, _p, _i64, _i32, _p, _p, _i32, _p, _p, _p, _p, _p, _p],
+    "dfol_scene_pair_rows_f32": [_p, _i64, _i32, _i32, _p, _p, _i32, _p, _i64, _p],
+    "dfol_scene_pair_rows_bwd_f32": [_p, _i64, _i32, _i32, _p, _p, _i32, _p, _i64, _p],
 }
 
 
@@ -1443,6 +1445,38 @@ def scene_bce_bwd_cols(g, h, emb_w, emb_b, cols, target, weight):
     ws = torch.empty(n, dtype=F32, device=h.device) if n else None
     call("dfol_scene_bce_bwd_cols_f32", _ptr(g, F32), *args, _ptr(ws, F32, True), _ptr(dE), _ptr(db), _stream())
     return dE, db
+
+
+# ---- scene-graph supervision: the rows of the listed pairs (csrc/dfol_scene_pairs.hip) ----------------------------------------------------
+def scene_pair_rows(obj, pair_s, pair_o):
+    """-> [P, 2 D + 4] rows [obj[s], obj[o], dist, angle, sign(xo - xs), sign(yo - ys)] of the listed pairs (dfol_scene_pair_rows_f32); obj [O, D]
+    fp32 with the box in its last four columns, pair_s / pair_o int32 [P] rows of obj (the kernel clamps an index, the caller has checked it)."""
+    if obj.dim() != 2 or obj.dtype != F32 or obj.shape[1] < 4 or (obj.shape[0] > 1 and obj.stride(1) != 1):
+        raise DfolError("scene_pair_rows: obj must be fp32 rows of unit column stride and at least the four box columns")
+    O, D = obj.shape
+    P = pair_s.numel()
+    if pair_o.numel() != P or (P and O == 0):
+        raise DfolError("scene_pair_rows: %d subjects, %d objects of the pairs, %d object rows" % (P, pair_o.numel(), O))
+    out = torch.empty(P, 2 * D + 4, dtype=F32, device=obj.device)
+    if P:
+        call("dfol_scene_pair_rows_f32", _dp(obj), obj.stride(0), O, D, _ptr(pair_s, I32), _ptr(pair_o, I32), P, _ptr(out), out.stride(0), _stream())
+    return out
+
+
+def scene_pair_rows_bwd(g, D, seg_off, slot, objects):
+    """-> d_obj [objects, D]: the sum of g's [P, >= 2 D] subject / object blocks per object in the order of the by-object list (seg_off
+    [objects + 1], slot [2 P], int32: data.scene_pair_csr), without atomics (dfol_scene_pair_rows_bwd_f32).  The geometry columns of g are not
+    propagated: they come from the box columns, which feed no parameter."""
+    if g.dim() != 2 or g.dtype != F32 or g.shape[1] < 2 * D or (g.shape[0] > 1 and g.stride(1) != 1):
+        raise DfolError("scene_pair_rows_bwd: g must be fp32 rows of unit column stride and at least 2 D = %d columns" % (2 * D))
+    P = g.shape[0]
+    if seg_off.numel() != objects + 1 or slot.numel() != 2 * P:
+        raise DfolError("scene_pair_rows_bwd: seg_off [%d] and slot [%d] do not describe %d objects and %d pairs" % (seg_off.numel(), slot.numel(), objects, P))
+    out = torch.empty(objects, D, dtype=F32, device=g.device)
+    if objects:
+        call("dfol_scene_pair_rows_bwd_f32", _dp(g), g.stride(0) if P else 2 * D, P, D, _ptr(seg_off, I32), _ptr(slot, I32), objects, _ptr(out),
+             out.stride(0), _stream())
+    return out
 
 
 def pair_ll(uv, hid1, pos, wg, w2, b2, emb_w, emb_b, n_obj, obj_off, max_n, req_col, req_tile, req_orient, tiles, default_ll=-30.0,

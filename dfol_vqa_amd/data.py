@@ -329,6 +329,161 @@ def scene_meta_data(questions, object_nums, ontology):
     return out
 
 
+# ---- a prepared scene batch: what a scene-graph train step reads, in persistent device tensors of fixed capacity ----------------------------------
+_SCENE_TARGETS = ('attribute_answer', 'attribute_weight', 'relation_answer', 'relation_weight')
+
+
+def scene_pair_csr(pair_s, pair_o, objects):
+    """The by-object list of a batch's listed pairs, for the ordered backward of ops.scene_pair_rows: -> (seg_off [objects + 1], slot [2 P]) int32.
+    Entry 2 p names the subject block of pair row p, 2 p + 1 its object block; slot[seg_off[t] : seg_off[t + 1]] are the entries of object t, by
+    pair number, the subject block before the object block of one pair (a stable sort of the 2 P entries by the object they name)."""
+    P = len(pair_s)
+    keys = np.empty(2 * P, np.int64)
+    keys[0::2], keys[1::2] = pair_s, pair_o
+    seg_off = np.zeros(objects + 1, np.int32)
+    seg_off[1:] = np.cumsum(np.bincount(keys, minlength=objects)[:objects])
+    return seg_off, np.argsort(keys, kind="stable").astype(np.int32)
+
+
+def scene_host_arrays(program_batch, objects=None, pairs=None):
+    """The index and target arrays of a scene batch at the capacities `objects` >= O and `pairs` >= P (default: the batch's own), as numpy arrays:
+    pair_s / pair_o [pairs] int32 (the listed pairs, offset per image as batch_gqa_boxfeatures_pipeline.py:238-249 does), their by-object list
+    seg_off [objects + 1] / slot [2 pairs] (scene_pair_csr), and the four dense target arrays [objects, A] / [pairs, R] of scene_meta_data.
+    Padding sits at the end: a padded pair names row 0 twice, every weight (and answer) of a padded row is 0.  -> (arrays, O, P)."""
+    from ._lib import DfolError
+    meta = program_batch._meta_data or {}
+    nums = [int(n) for n in program_batch._object_nums]
+    O = sum(nums)
+    first = np.concatenate([[0], np.cumsum(nums)])[:-1]
+    listed = meta.get('object_pairs') or {'subject_id': [], 'object_id': []}
+    ind_s = np.asarray([int(i) + int(o) for o, ids in zip(first, listed['subject_id']) for i in ids], np.int64)
+    ind_o = np.asarray([int(i) + int(o) for o, ids in zip(first, listed['object_id']) for i in ids], np.int64)
+    P = len(ind_s)
+    if len(ind_o) != P or (P and (min(ind_s.min(), ind_o.min()) < 0 or max(ind_s.max(), ind_o.max()) >= O)):
+        raise DfolError("object_pairs: subject and object lists differ in length or name an object the batch does not have")
+    missing = [k for k in _SCENE_TARGETS if k not in meta]
+    if missing:
+        raise DfolError("a scene batch carries attribute_dict and relation_list for every image: its meta data lack %s" % ", ".join(missing))
+    objects, pairs = O if objects is None else int(objects), P if pairs is None else int(pairs)
+    if objects < O:
+        raise DfolError("the batch has O = %d objects, above the capacity of %d object rows" % (O, objects))
+    if pairs < P:
+        raise DfolError("the batch lists P = %d pairs, above the capacity of %d pair rows" % (P, pairs))
+    if pairs and not objects:
+        raise DfolError("a capacity of %d pair rows over no object row" % pairs)
+    out = {'pair_s': np.zeros(pairs, np.int32), 'pair_o': np.zeros(pairs, np.int32)}
+    out['pair_s'][:P], out['pair_o'][:P] = ind_s, ind_o
+    out['seg_off'], out['slot'] = scene_pair_csr(out['pair_s'], out['pair_o'], objects)
+    for key, rows, real in zip(_SCENE_TARGETS, (objects, objects, pairs, pairs), (O, O, P, P)):
+        a = np.asarray(meta[key], np.float32)
+        if a.ndim != 2 or a.shape[0] != real:
+            raise DfolError("%s %s does not have the batch's %d rows" % (key, a.shape, real))
+        out[key] = np.zeros((rows, a.shape[1]), np.float32)
+        out[key][:real] = a
+    return out, O, P
+
+
+class PreparedScene(object):
+    """What prepare_scene_batch keeps for a scene batch: `features` [objects, F + 6] (the batch's rows, zero rows behind them), `pair_s`, `pair_o`,
+    `seg_off`, `slot` and the four target arrays of scene_host_arrays, as tensors on `device` whose addresses never change; O, P the real
+    counts, objects, pairs the capacities, images the batch size."""
+
+    def __init__(self, program_batch, device, objects=None, pairs=None):
+        from ._lib import DfolError
+        feats = program_batch._object_features
+        if not isinstance(feats, torch.Tensor) or feats.dim() != 2:
+            raise DfolError("prepare_scene_batch takes a batch that carries its object feature matrix (got %s)" % type(feats).__name__)
+        host, self.O, self.P = scene_host_arrays(program_batch, objects, pairs)
+        if feats.shape[0] != self.O:
+            raise DfolError("%d object feature rows for images of %d objects" % (feats.shape[0], self.O))
+        self.device = torch.device(device)
+        self.images = int(program_batch.batch_size())
+        self.objects, self.pairs = int(host['seg_off'].shape[0]) - 1, int(host['pair_s'].shape[0])
+        for key, a in host.items():
+            setattr(self, key, torch.from_numpy(a).to(self.device))
+        self.features = torch.zeros(self.objects, feats.shape[1], dtype=torch.float32, device=self.device)
+        self.features[:self.O].copy_(feats)
+        self._staging = self._event = None
+
+    def tensors(self):
+        return {key: getattr(self, key) for key in ('features', 'pair_s', 'pair_o', 'seg_off', 'slot') + _SCENE_TARGETS}
+
+    def load(self, program_batch):
+        """Another batch's arrays into the same tensors: the same number of images, O and P within the capacities (DfolError otherwise); the
+        padding is rewritten.  On a GPU the arrays travel from pinned memory on the current stream, without a host wait: call it on the stream
+        the step runs (replays) on, outside a capture."""
+        from ._lib import DfolError
+        if int(program_batch.batch_size()) != self.images:
+            raise DfolError("the batch has %d images, the prepared batch %d: the loss divisor of a captured step is fixed"
+                            % (program_batch.batch_size(), self.images))
+        feats = program_batch._object_features
+        if not isinstance(feats, torch.Tensor) or feats.dim() != 2 or feats.shape[1] != self.features.shape[1]:
+            raise DfolError("the batch's object features do not have the prepared batch's %d columns" % self.features.shape[1])
+        host, O, P = scene_host_arrays(program_batch, self.objects, self.pairs)
+        if feats.shape[0] != O:
+            raise DfolError("%d object feature rows for images of %d objects" % (feats.shape[0], O))
+        for key, a in host.items():
+            if tuple(a.shape) != tuple(getattr(self, key).shape):
+                raise DfolError("%s %s of the batch against %s of the prepared batch" % (key, a.shape, tuple(getattr(self, key).shape)))
+        if self.device.type != "cuda":
+            for key, a in host.items():
+                getattr(self, key).copy_(torch.from_numpy(a))
+            self.features[:O].copy_(feats)
+            self.features[O:].zero_()
+        else:
+            if self._staging is None:
+                self._staging = {key: torch.empty(t.shape, dtype=t.dtype).pin_memory() for key, t in self.tensors().items()}
+                self._event = torch.cuda.Event()
+            else:
+                self._event.synchronize()                             # the previous load's copies have read the pinned arrays
+            for key, a in host.items():
+                self._staging[key].copy_(torch.from_numpy(a))
+                getattr(self, key).copy_(self._staging[key], non_blocking=True)
+            if feats.is_cuda:
+                self.features[:O].copy_(feats)
+                self.features[O:].zero_()
+            else:
+                stage = self._staging['features']
+                stage[:O].copy_(feats)
+                stage[O:].zero_()
+                self.features.copy_(stage, non_blocking=True)
+            self._event.record()
+        self.O, self.P = O, P
+
+
+def prepare_scene_batch(program_batch, device, objects=None, pairs=None):
+    """A scene batch (a ProgramBatch whose program is `scene` alone, with the collater's direct-supervision meta data) with everything its train
+    step reads held in persistent tensors on `device` (PreparedScene, as `._scene_prepared`; `._object_features` is its padded feature matrix):
+    the interpreter then builds the listed pairs' rows with ops.scene_pair_rows and the loss reads the prepared targets, nothing is built from
+    host lists or uploaded per step, and training.GraphedTrainStep can capture the step and `load` further batches into it.  objects / pairs:
+    capacities (default the batch's own O and P: no padding; below them: DfolError).  Padded rows are exact: their weights are 0, so their loss,
+    metric sums and gradients are exactly zero, and the real rows keep their places (and their Dropout counters)."""
+    from .program import ProgramBatch
+    device = torch.device(device)
+    prepared = PreparedScene(program_batch, device, objects, pairs)
+    if device.type == "cuda" and torch.device(program_batch.device).type != "cuda":
+        pb = program_batch.to_cuda(device)
+    else:
+        pb = ProgramBatch.__new__(ProgramBatch)
+        pb.__dict__.update(program_batch.__dict__)
+    pb._scene_prepared, pb._object_features = prepared, prepared.features
+    return pb
+
+
+def load_scene_batch(prepared_batch, program_batch):
+    """`program_batch`'s scenes into a prepared batch's tensors (PreparedScene.load) and its host-side description (object counts, meta data,
+    answers) beside them, so that eager steps, the restatement of a test and the metric see the batch the tensors now hold."""
+    from ._lib import DfolError
+    prepared = getattr(prepared_batch, "_scene_prepared", None)
+    if prepared is None:
+        raise DfolError("load_scene_batch: the target is not a prepared scene batch (data.prepare_scene_batch)")
+    prepared.load(program_batch)
+    prepared_batch._object_nums = [int(n) for n in program_batch._object_nums]
+    prepared_batch._meta_data, prepared_batch._answers = program_batch._meta_data, program_batch._answers
+    prepared_batch._original_dicts = program_batch._original_dicts
+    return prepared_batch
+
+
 class BatchGQABoxFeaturesCollator(ProgramCollaterBase):
     """batch_gqa_boxfeatures_pipeline.py:15-189: object features of the questions' images from chunked containers.
 

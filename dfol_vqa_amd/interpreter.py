@@ -556,30 +556,33 @@ class BatchInterpreterBase(nn.Module):
         if getattr(program_batch, "_question_image", None) is not None:
             raise NotImplementedError("a `scene` batch names one image per question: share_scenes is not built for it")
         meta = program_batch._meta_data or {}
+        prepared = getattr(program_batch, "_scene_prepared", None)
         feats, batch_index = program_batch._object_features, program_batch._object_batch_index
-        world = BatchWorld(device, feats.size(0), None, None, batch_index, meta, attention_transfer_state_dim=self._attention_transfer_state_dim,
-                           object_nums=getattr(program_batch, "_object_nums", None))
+        if prepared is not None:
+            # data.prepare_scene_batch: the object rows (padded to the batch's capacity), the pairs and their by-object list sit in persistent
+            # device tensors - nothing is built from host lists here, so a graph capture can bake the addresses in and be fed another batch
+            feats = prepared.features
+        world = BatchWorld(device, sum(program_batch._object_nums) if prepared is not None else feats.size(0), None, None, batch_index, meta,
+                           attention_transfer_state_dim=self._attention_transfer_state_dim, object_nums=getattr(program_batch, "_object_nums", None))
         if 'world_geometry' in inspect.signature(self._featurizer.featurize_scene).parameters:
             obj = self._featurizer.featurize_scene(device, feats, batch_index, meta, world_geometry=None)['attribute_features']
         else:
             raise NotImplementedError("operator `scene` needs this package's featurizer (it builds the listed pairs' rows itself)")
-        first = np.concatenate([[0], np.cumsum(world._img_n_list)])[:-1]
-        pairs = meta.get('object_pairs') or {'subject_id': [], 'object_id': []}
-        ind_s = [int(i) + int(o) for o, ids in zip(first, pairs['subject_id']) for i in ids]          # :242-246
-        ind_o = [int(i) + int(o) for o, ids in zip(first, pairs['object_id']) for i in ids]
-        if len(ind_s) != len(ind_o) or any(not 0 <= i < world._object_num for i in ind_s + ind_o):
-            raise L.DfolError("object_pairs: subject and object lists differ in length or name an object the batch does not have")
-        D = obj.shape[1]
-        if ind_s:
-            s, o = obj.index_select(0, upload(np.asarray(ind_s, np.int64), device)), obj.index_select(0, upload(np.asarray(ind_o, np.int64), device))
-            ps, po = s[:, D - 4:], o[:, D - 4:]
-            dx = ps[:, 0] + ps[:, 2] / 2.0 - po[:, 0] - po[:, 2] / 2.0
-            dy = ps[:, 1] + ps[:, 3] / 2.0 - po[:, 1] - po[:, 3] / 2.0
-            dist = torch.sqrt(dx * dx + dy * dy)                                                       # :271-278
-            geo = torch.stack([dist, torch.asin(dy / dist.clamp(min=1e-10)), (po[:, 0] - ps[:, 0]).sign(), (po[:, 1] - ps[:, 1]).sign()], 1)
-            pair_rows = torch.cat([s, o, geo], 1).contiguous()
+        if prepared is not None:
+            from . import _lib
+            _lib.note("scene_pair_rows")
+            pair_rows = L.scene_pair_rows(obj, prepared.pair_s, prepared.pair_o, (prepared.seg_off, prepared.slot))
         else:
-            pair_rows = obj.new_zeros(0, 2 * D + 4)
+            first = np.concatenate([[0], np.cumsum(world._img_n_list)])[:-1]
+            pairs = meta.get('object_pairs') or {'subject_id': [], 'object_id': []}
+            ind_s = [int(i) + int(o) for o, ids in zip(first, pairs['subject_id']) for i in ids]          # :242-246
+            ind_o = [int(i) + int(o) for o, ids in zip(first, pairs['object_id']) for i in ids]
+            if len(ind_s) != len(ind_o) or any(not 0 <= i < world._object_num for i in ind_s + ind_o):
+                raise L.DfolError("object_pairs: subject and object lists differ in length or name an object the batch does not have")
+            if ind_s:
+                pair_rows = L.scene_pair_rows_reference(obj, upload(np.asarray(ind_s, np.int64), device), upload(np.asarray(ind_o, np.int64), device))
+            else:
+                pair_rows = obj.new_zeros(0, 2 * obj.shape[1] + 4)
         world._attribute_features, world._relation_features = obj, {'features': pair_rows, 'index': None}      # (the rows, as in the uncached reference)
         world._scene_likelihood = SceneLikelihood(*self._oracle.scene_hidden(obj, pair_rows), self._oracle)
         return world
@@ -697,9 +700,10 @@ class BatchInterpreterBase(nn.Module):
                 if any(ob._op_name != 'scene' for ob in ops):
                     raise NotImplementedError("operator `scene` is served for a batch whose program is `scene` alone")
                 # scene-graph supervision: the Python operator on a world without likelihood tables; the native executor has no opcode for
-                # it and a graph capture is not built for it
-                if _lib.capturing():
-                    raise NotImplementedError("a `scene` batch inside a graph capture (GraphedForward / GraphedTrainStep) is not built")
+                # it, and a graph capture takes it only as a prepared batch (data.prepare_scene_batch: DESIGN.md 3.8)
+                if _lib.capturing() and getattr(program_batch, "_scene_prepared", None) is None:
+                    raise NotImplementedError("a `scene` batch inside a graph capture (GraphedForward / GraphedTrainStep) must be prepared first: "
+                                              "data.prepare_scene_batch holds what the step reads in persistent device tensors")
                 _lib.note("scene_python")
                 world = self.build_scene_graph(program_batch.device, program_batch)
                 x, _ = self._execute(ops[-1]._op_id, world, ops[-1], (), True, is_training)

@@ -452,6 +452,39 @@ def scene_bce(h, emb_w, emb_b, cols, target, weight, thr):
     return s[0], s[1].detach(), s[2].detach()
 
 
+def scene_pair_rows_reference(obj, ind_s, ind_o):
+    """[obj[s], obj[o], distance, angle, sides] of the listed pairs in tensor ops (batch_gqa_boxfeatures_pipeline.py:225-279, the distance and
+    angle of :271-278): the route of CPU tensors and of a batch that was not prepared; its autograd sends the gradient back through index_add_.
+    ind_s / ind_o: int64 rows of obj, at least one."""
+    D = obj.shape[1]
+    s, o = obj.index_select(0, ind_s), obj.index_select(0, ind_o)
+    ps, po = s[:, D - 4:], o[:, D - 4:]
+    dx = ps[:, 0] + ps[:, 2] / 2.0 - po[:, 0] - po[:, 2] / 2.0
+    dy = ps[:, 1] + ps[:, 3] / 2.0 - po[:, 1] - po[:, 3] / 2.0
+    dist = torch.sqrt(dx * dx + dy * dy)                                                       # :271-278
+    geo = torch.stack([dist, torch.asin(dy / dist.clamp(min=1e-10)), (po[:, 0] - ps[:, 0]).sign(), (po[:, 1] - ps[:, 1]).sign()], 1)
+    return torch.cat([s, o, geo], 1).contiguous()
+
+
+def scene_pair_rows(obj, pair_s, pair_o, csr):
+    """The rows [P, 2 D + 4] of the listed pairs of a scene batch: obj [O, D] fp32 (the box in its last four columns), pair_s / pair_o int32 [P]
+    rows of obj, csr = (seg_off [O + 1], slot [2 P]) the by-object list of the pairs (data.scene_pair_csr).  On the GPU one launch forward and
+    one backward (dfol_scene_pair_rows_f32 / _bwd_f32): the gradient reaches obj without atomics, in the list's order, so two runs give the same
+    bits; the four geometry columns send none back (the box columns feed no parameter).  CPU tensors take the tensor-op expression."""
+    if pair_s.numel() == 0:
+        return obj.new_zeros(0, 2 * obj.shape[1] + 4)
+    if not obj.is_cuda or obj.dtype != torch.float32:
+        _lib.note("scene_pair_rows_torch")
+        return scene_pair_rows_reference(obj, pair_s.to(torch.int64), pair_o.to(torch.int64))
+    _lib.note("scene_pair_rows_hip")
+    if obj.stride(-1) != 1:
+        obj = obj.contiguous()
+    if _needs_grad(obj):
+        seg_off, slot = csr
+        return torch.ops.dfol.scene_pair_rows(obj, pair_s, pair_o, seg_off, slot)
+    return _lib.scene_pair_rows(obj, pair_s, pair_o)
+
+
 class _PairFeatures(torch.autograd.Function):
     """[obj_s, obj_o, geometry]: the gradient flows back to the two object rows (the geometry comes from the raw boxes).  Only the
     full-table compatibility dataflow (`_needed_columns = False`) builds the [pairs, 1036] matrix; its backward is torch's atomic

@@ -312,4 +312,45 @@ def _scene_backward(ctx, g):
 scene_bce.register_autograd(_scene_backward, setup_context=_scene_setup)
 
 
+# ---- scene-graph supervision: the rows of the listed pairs (batch_gqa_boxfeatures_pipeline.py:225-279; csrc/dfol_scene_pairs.hip) ----------
+@_op("dfol::scene_pair_rows", mutates_args=())
+def scene_pair_rows(obj: Tensor, pair_s: Tensor, pair_o: Tensor, seg_off: Tensor, slot: Tensor) -> Tensor:
+    """-> [P, 2 D + 4]; seg_off / slot (the by-object list of the pairs, data.scene_pair_csr) are the backward's."""
+    return _lib.scene_pair_rows(obj, pair_s, pair_o)
+
+
+@scene_pair_rows.register_fake
+def _(obj, pair_s, pair_o, seg_off, slot):
+    return obj.new_empty(pair_s.shape[0], 2 * obj.shape[1] + 4)
+
+
+@_op("dfol::scene_pair_rows_bwd", mutates_args=())
+def scene_pair_rows_bwd(g: Tensor, seg_off: Tensor, slot: Tensor, objects: int, D: int) -> Tensor:
+    """-> d_obj [objects, D]: g's subject / object blocks summed per object in the list's order, no atomics; the geometry columns of g are not
+    propagated (the box columns feed no parameter)."""
+    return _lib.scene_pair_rows_bwd(g, D, seg_off, slot, objects)
+
+
+@scene_pair_rows_bwd.register_fake
+def _(g, seg_off, slot, objects, D):
+    return g.new_empty(objects, D)
+
+
+def _scene_pair_rows_setup(ctx, inputs, output):
+    obj, pair_s, pair_o, seg_off, slot = inputs
+    ctx.save_for_backward(seg_off, slot)
+    ctx.meta = tuple(obj.shape)
+
+
+def _scene_pair_rows_backward(ctx, g):
+    seg_off, slot = ctx.saved_tensors
+    O, D = ctx.meta
+    if g.shape[0] > 1 and g.stride(1) != 1:
+        g = g.contiguous()
+    return torch.ops.dfol.scene_pair_rows_bwd(g, seg_off, slot, O, D), None, None, None, None
+
+
+scene_pair_rows.register_autograd(_scene_pair_rows_backward, setup_context=_scene_pair_rows_setup)
+
+
 CORE_OPS = ("filter_fwd", "relate_fwd", "relate_one_fwd", "quantify_fwd", "linear_act", "pair_ll")

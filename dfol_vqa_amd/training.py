@@ -74,7 +74,8 @@ def _scene_sums(program_batch_list, prediction):
     """[(loss, num, den) of the attribute side, of the relation side] of a SCENE_GRAPH prediction whose log_probability is a
     visual_oracle.SceneLikelihood; the dense targets and weights of the batches' meta data (attribute_answer / attribute_weight [O, A],
     relation_answer / relation_weight [P, R]: trainer.py:236-240) go through the upload cache while they are small (up to 1 MiB: the cache keys
-    on the content) and by a plain copy above that.  The sums are kept on the prediction: the metric after the loss launches nothing."""
+    on the content) and by a plain copy above that; prepared batches (data.prepare_scene_batch) bring them as persistent device tensors, padded
+    rows with weight 0, and nothing is concatenated or uploaded.  The sums are kept on the prediction: the metric after the loss launches nothing."""
     import numpy as np
     from .host_util import upload
     from .visual_oracle import SCENE_THRESHOLD
@@ -84,7 +85,11 @@ def _scene_sums(program_batch_list, prediction):
     like = prediction['log_probability']
     device = like.h_attr.device
 
+    prepared = [getattr(pb, "_scene_prepared", None) for pb in program_batch_list]
+
     def cat(key):
+        if prepared and all(p is not None for p in prepared):
+            return getattr(prepared[0], key) if len(prepared) == 1 else torch.cat([getattr(p, key) for p in prepared], 0)
         parts = [np.asarray(pb._meta_data[key], np.float32) for pb in program_batch_list]
         a = np.ascontiguousarray(parts[0] if len(parts) == 1 else np.concatenate(parts, axis=0))
         return upload(a, device) if a.nbytes <= _SCENE_UPLOAD_CACHE_BYTES else torch.from_numpy(a).to(device)
@@ -282,7 +287,9 @@ class GraphedTrainStep(object):
     phases are host-bound: 4.6 ms of GPU work in a 6.9 ms step), and its launch sequence is static for a given batch shape, exactly like
     the inference forward's (interpreter.GraphedForward).  The optimizer must be capturable (torch.optim.Adam(..., capturable=True): its
     step counter lives on the device); new scenes of the same shapes are served by copying into `program_batch._object_features`; a batch
-    with other programs or shapes needs its own capture.  `loss` is a 0-d device tensor that every replay overwrites (this rank's share of
+    with other programs or shapes needs its own capture.  A scene-graph step (operator `scene`) is captured over PREPARED batches
+    (data.prepare_scene_batch, padded to a capacity): `load(program_batch)` then serves any batch of the same number of images whose objects
+    and listed pairs fit the capacity.  `loss` is a 0-d device tensor that every replay overwrites (this rank's share of
     the summed loss).
 
     Data parallelism (`group`, one process per GPU; `data` is this rank's shard, the loss is divided by the GLOBAL batch size, the bucket
@@ -384,6 +391,15 @@ class GraphedTrainStep(object):
 
     def _back(self):
         clip_and_step(self._model, self._opt, self._clip, self._bucket, _fused_for(self._opt, self._bucket) if self._bucket is not None else None)
+
+    def load(self, program_batch, index=0):
+        """Another scene batch into the captured step's `index`-th batch, which must be a prepared one (data.prepare_scene_batch): its features,
+        pairs, by-object list and targets are copied into the tensors the graph reads - from pinned memory, on the current stream (the one
+        the replays run on), outside the graph - and the padding is rewritten.  DfolError, naming the limit, unless the batch has the same
+        number of images (the loss divisor is part of the graph), O <= the object capacity and P <= the pair capacity.  The next replay
+        trains on it; its sums are in `self.result` as after any replay."""
+        from . import data
+        data.load_scene_batch(self._data[index], program_batch)
 
     def __call__(self):
         self._graph.replay()

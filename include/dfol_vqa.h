@@ -59,7 +59,8 @@ extern "C" {
  * one-posterior Relate of the ungated train step: dfol_relate_keep_fwd_f32 and dfol_relate_keep_bwd_f32, and the default arithmetic over a bf16
  * table in place: dfol_linear_wide_rows_bf16t_supported, dfol_linear_wide_rows_bf16t_h2_f32 and dfol_set_feature_rows_bf16_h2, with
  * dfol_store_bf16_is_f16, dfol_linear_wide_rows_bf16t_f16_h2_f32 and dfol_set_feature_rows_bf16_h2_f16 for a table of fp16 values, and the
- * default arithmetic's weight gradient over it: dfol_linear_wgrad_rows_bf16t_x3_supported and dfol_linear_wgrad_bias_rows_bf16t_x3;
+ * default arithmetic's weight gradient over it: dfol_linear_wgrad_rows_bf16t_x3_supported and dfol_linear_wgrad_bias_rows_bf16t_x3, and the listed pairs' rows of the scene-graph supervision:
+ * dfol_scene_pair_rows_f32 and dfol_scene_pair_rows_bwd_f32;
  * a caller that needs them checks for the symbol, and a table that names an opcode an older library lacks is refused by it ("unknown opcode"). */
 #define DFOL_ABI_VERSION 3
 
@@ -1180,6 +1181,23 @@ int dfol_scene_bce_bwd_rows_f32(const float* g, const float* h, int64_t ldh, int
 int dfol_scene_bce_bwd_cols_f32(const float* g, const float* h, int64_t ldh, int32_t M, int32_t H, const float* emb_w, int64_t lde, int32_t C_all,
                                 const float* emb_b, const int32_t* cols, int32_t C, const float* target, const float* weight, float* workspace,
                                 float* dE, float* db, void* stream);
+
+/* ---- scene-graph supervision: the rows of the listed pairs (csrc/dfol_scene_pairs.hip) ---------------------------------------------------
+ * The relation side's input for the pairs meta_data['object_pairs'] lists (batch_gqa_boxfeatures_pipeline.py:225-279; the indices offset per
+ * image, :238-249), instead of index_select / cat / asin and the atomic index_add_ of their autograd.
+ *   obj     [O, ld_obj >= D] fp32 object rows; the last four of the D columns are the box (x, y, w, h)
+ *   pair_s, pair_o  [P] int32 rows of obj (clamped to [0, O): the host has refused an index outside it)
+ * dfol_scene_pair_rows_f32:  out [P, ld_out >= 2 D + 4] = [obj[s], obj[o], dist, angle, sign(xo - xs), sign(yo - ys)] with
+ *   dx = xs + ws / 2 - xo - wo / 2, dy likewise, dist = sqrt(dx dx + dy dy), angle = asin(dy / max(dist, 1e-10)) (:271-278).  P = 0 launches nothing.
+ * dfol_scene_pair_rows_bwd_f32:  d_obj [O, ld_d >= D] = the sum of g's blocks that the by-object list names, in the list's order, in fp32:
+ *   seg_off [O + 1] and slot [2 P] int32, entry 2 p + 0 the subject block (columns [0, D)) of row p of g [P, ld_g >= 2 D], 2 p + 1 its object
+ *   block (columns [D, 2 D)); the entries of object t are slot[seg_off[t] .. seg_off[t + 1]), sorted by pair number, subject before object.
+ *   An object no pair names gets zeros.  The four geometry columns carry no gradient back (the box columns feed no parameter).
+ * No atomics, one fixed order: two runs give the same bits.  16-byte loads and stores where D % 4 == 0 and the rows are 16-byte aligned. */
+int dfol_scene_pair_rows_f32(const float* obj, int64_t ld_obj, int32_t O, int32_t D, const int32_t* pair_s, const int32_t* pair_o, int32_t P, float* out,
+                             int64_t ld_out, void* stream);
+int dfol_scene_pair_rows_bwd_f32(const float* g, int64_t ld_g, int32_t P, int32_t D, const int32_t* seg_off, const int32_t* slot, int32_t O, float* d_obj,
+                                 int64_t ld_d, void* stream);
 
 #ifdef __cplusplus
 }
