@@ -230,12 +230,6 @@ SIGNATURES = {
                             _i32, _p, _p],
     "dfol_run_program": [_p, _p, _p, _i32, _p, _p, _p],
     "dfol_set_range_status": [_p],
-    "dfol_set_feature_rows": [_p, _p],
-    "dfol_set_feature_rows_bf16": [_p, _p],
-    "dfol_set_feature_rows_bf16_h2": [_p, _p],
-    "dfol_set_feature_rows_bf16_h2_f16": [_p, _p],
-    "dfol_set_program_gates": [_p, _i32],
-    "dfol_set_feature_cache": [_p, _i64, _i32, _p, _p],
     "dfol_pair_features_bwd_f32": [_p, _i64, _i32, _p, _p, _i32, _i32, _p, _i64, _p],
     "dfol_dropout_advance": [_p, _p],
     "dfol_dropout_f32": [_p, _i64, _p, _i64, _i64, _i32, _f, _p, ctypes.c_uint32, _p],
@@ -250,7 +244,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 3      # include/dfol_vqa.h: DFOL_ABI_VERSION
+ABI_VERSION = 4      # include/dfol_vqa.h: DFOL_ABI_VERSION
 
 
 def load():
@@ -264,7 +258,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     lib.dfol_last_error.restype = ctypes.c_char_p
     lib.dfol_abi_version.restype = ctypes.c_int
-    if lib.dfol_abi_version() != ABI_VERSION:        # a stale build answers wrongly without a message (UV units changed between 2 and 3)
+    if lib.dfol_abi_version() != ABI_VERSION:        # a stale build answers wrongly without a message (UV units changed between 2 and 3, struct layouts between 3 and 4)
         raise DfolError("%s has ABI version %d, this host side needs %d: rebuild it (make -C dfol_vqa_amd/csrc)"
                         % (LIB_PATH, lib.dfol_abi_version(), ABI_VERSION))
     for name, argtypes in SIGNATURES.items():

@@ -11,7 +11,9 @@
 // segment offsets, quantifiers, gate flags, pair-kernel requests), uploaded by the caller with ONE copy; `workspace` is one caller-owned
 // arena in which the plan has assigned every intermediate (object matrix, hidden activations, likelihood blocks, relation tiles,
 // attentions) and, at its start, the results the host reads back (log-probabilities, arg-max flags).  No allocation, no synchronisation,
-// no global state: the call only enqueues work on `stream`.
+// no global state: the call only enqueues work on `stream`, and everything it reads is in its arguments - the feature source in the scene
+// struct (DFOL_FEATURES_*), the gate table in the model struct.  The one thread-local the kernels it launches see is the fp16-range status
+// word (dfol_set_range_status, dfol_logic.hip), which every entry point of the library reads, not the executor alone.
 #include <string.h>
 
 #include "dfol_calib.h"
@@ -123,101 +125,72 @@ int pair_ll_packed(const float* uv, int64_t ld_uv, int32_t hid1, const float* po
 constexpr PairImageEntry kPairImageEntry[] = {nullptr, pair_ll_packed, dfol_pair_ll_split_f32, dfol_pair_ll_h2_f32, dfol_pair_ll_h1_f32};
 static_assert(DFOL_PAIR_PACKED == 1 && DFOL_PAIR_BF16X3 == 2 && DFOL_PAIR_F16X2 == 3 && DFOL_PAIR_F16 == 4, "kPairImageEntry is indexed by DFOL_PAIR_*");
 
-// dfol_set_feature_rows: the index form of the NEXT dfol_run_program's scene on this thread
-thread_local const int32_t* g_feature_src_row = nullptr;
-thread_local const float* g_feature_box6 = nullptr;
-thread_local bool g_feature_rows_bf16 = false;                       // dfol_set_feature_rows_bf16: scene->features is a bf16 table
-thread_local bool g_feature_rows_f16 = false;                        // dfol_set_feature_rows_bf16_h2_f16: ... and the table is certified to hold fp16 values
-thread_local bool g_feature_rows_bf16_h2 = false;                    // dfol_set_feature_rows_bf16_h2: a bf16 table in front of a two-piece fp16 first layer
-// dfol_set_feature_cache: the cached form of the same (the featurizer's outputs instead of its inputs)
-struct FeatureCache {
-    const float* cache;
-    int64_t ld;
-    int32_t W;
-    const int32_t* src_row;
-    const float* box6;
-};
-thread_local FeatureCache g_feature_cache = {nullptr, 0, 0, nullptr, nullptr};
-// dfol_set_program_gates: the gate table of the NEXT dfol_run_program on this thread ([n_gates][18] device floats)
-thread_local const float* g_gate_table = nullptr;
-thread_local int32_t g_gate_count = 0;
+constexpr const char* kFeatureForm[] = {"DFOL_FEATURES_MATRIX",       "DFOL_FEATURES_ROWS_F32",         "DFOL_FEATURES_ROWS_BF16",
+                                         "DFOL_FEATURES_ROWS_BF16_H2", "DFOL_FEATURES_ROWS_BF16_H2_F16", "DFOL_FEATURES_CACHED"};
+static_assert(DFOL_FEATURES_MATRIX == 0 && DFOL_FEATURES_ROWS_F32 == 1 && DFOL_FEATURES_ROWS_BF16 == 2 && DFOL_FEATURES_ROWS_BF16_H2 == 3 &&
+                  DFOL_FEATURES_ROWS_BF16_H2_F16 == 4 && DFOL_FEATURES_CACHED == 5,
+              "kFeatureForm is indexed by DFOL_FEATURES_*");
+inline bool rows_form(int32_t form) { return form >= DFOL_FEATURES_ROWS_F32 && form <= DFOL_FEATURES_ROWS_BF16_H2_F16; }
+
+// The source-0 DFOL_OP_DENSE of a scene in one of the index forms: the featurizer's first product reads the store's rows in place, by the
+// form's own kernel - the matrix route's bits.  A layer the form does not admit is refused before anything is launched.
+int run_first_layer_rows(const DfolProgramScene& sc, const DfolDenseLayer& L, int64_t x_off, float* Y, int64_t ldy, int32_t M, void* stream) {
+    const char* form = kFeatureForm[sc.feature_form];
+    switch (sc.feature_form) {
+        case DFOL_FEATURES_ROWS_F32:         // an fp32 table in front of the default arithmetic
+            DFOL_REQUIRE(x_off == 0 && L.kind == DFOL_DENSE_F16X2 && L.packed != nullptr && dfol_linear_wide_supported(M, L.N, L.K),
+                         "run_program: a scene in index form (%s) needs a two-piece fp16 product of a shape dfol_linear_wide_supported takes "
+                         "(M %d N %d K %d kind %d): hand over the gathered matrix", form, M, L.N, L.K, L.kind);
+            return dfol_linear_wide_rows_h2_f32(sc.features, sc.ld_features, sc.src_row, L.packed, L.bias, Y, ldy, M, L.N, L.K, L.act, stream);
+        case DFOL_FEATURES_ROWS_BF16:        // a bf16 table: the bf16 mode's product over its rows
+            DFOL_REQUIRE(x_off == 0 && L.kind == DFOL_DENSE_BF16 && L.packed != nullptr && dfol_linear_rows_bf16t_supported(L.N, L.K, sc.ld_features),
+                         "run_program: a scene in bf16 index form (%s) needs a DFOL_DENSE_BF16 first layer of a shape "
+                         "dfol_linear_rows_bf16t_supported takes (N %d K %d ld %lld kind %d): hand over the gathered matrix", form, L.N, L.K,
+                         (long long)sc.ld_features, L.kind);
+            return dfol_linear_act_rows_bf16t_f32(sc.features, sc.ld_features, sc.src_row, L.packed, L.bias, Y, ldy, M, L.N, L.K, L.act, stream);
+        case DFOL_FEATURES_ROWS_BF16_H2:     // a bf16 table in front of the default arithmetic: split in place
+        case DFOL_FEATURES_ROWS_BF16_H2_F16: // ... certified to hold fp16 values: two products instead of three
+            DFOL_REQUIRE(L.kind == DFOL_DENSE_F16X2,
+                         "run_program: a scene in bf16 index form for the two-piece fp16 product (%s) needs a DFOL_DENSE_F16X2 first layer, this one "
+                         "is of kind %d: DFOL_FEATURES_ROWS_BF16 serves a DFOL_DENSE_BF16 layer, every other arithmetic takes the gathered matrix", form,
+                         L.kind);
+            DFOL_REQUIRE(x_off == 0 && L.packed != nullptr && dfol_linear_wide_rows_bf16t_supported(M, L.N, L.K, sc.ld_features),
+                         "run_program: a scene in bf16 index form (%s) needs a first layer of a shape dfol_linear_wide_rows_bf16t_supported takes "
+                         "(M %d N %d K %d ld %lld): hand over the gathered matrix", form, M, L.N, L.K, (long long)sc.ld_features);
+            return dfol_linear_wide_rows_bf16t_f16_h2_f32(sc.features, sc.ld_features, sc.src_row, L.packed, L.bias, Y, ldy, M, L.N, L.K, L.act,
+                                                          sc.feature_form == DFOL_FEATURES_ROWS_BF16_H2_F16 ? 1 : 0, stream);
+    }
+    dfol_set_error("run_program: %s is no index form", form);
+    return 1;
+}
 
 }  // namespace
-
-extern "C" int dfol_set_feature_cache(const float* cache, int64_t ld_cache, int32_t W, const int32_t* src_row, const float* box6) {
-    DFOL_REQUIRE((cache == nullptr) == (src_row == nullptr) && (cache == nullptr) == (box6 == nullptr), "set_feature_cache: cache, src_row and box6 come together");
-    DFOL_REQUIRE(cache == nullptr || (W > 0 && ld_cache >= W), "set_feature_cache: bad sizes W=%d ld_cache=%lld", W, (long long)ld_cache);
-    g_feature_cache = FeatureCache{cache, ld_cache, W, src_row, box6};
-    return 0;
-}
-
-extern "C" int dfol_set_feature_rows(const int32_t* src_row, const float* box6) {
-    DFOL_REQUIRE((src_row == nullptr) == (box6 == nullptr), "set_feature_rows: src_row and box6 come together");
-    g_feature_src_row = src_row;
-    g_feature_box6 = box6;
-    g_feature_rows_bf16 = g_feature_rows_bf16_h2 = g_feature_rows_f16 = false;
-    return 0;
-}
-
-extern "C" int dfol_set_feature_rows_bf16(const int32_t* src_row, const float* box6) {
-    DFOL_REQUIRE((src_row == nullptr) == (box6 == nullptr), "set_feature_rows_bf16: src_row and box6 come together");
-    g_feature_src_row = src_row;
-    g_feature_box6 = box6;
-    g_feature_rows_bf16 = src_row != nullptr;
-    g_feature_rows_bf16_h2 = g_feature_rows_f16 = false;
-    return 0;
-}
-
-extern "C" int dfol_set_feature_rows_bf16_h2(const int32_t* src_row, const float* box6) {
-    DFOL_REQUIRE((src_row == nullptr) == (box6 == nullptr), "set_feature_rows_bf16_h2: src_row and box6 come together");
-    g_feature_src_row = src_row;
-    g_feature_box6 = box6;
-    g_feature_rows_bf16 = false;
-    g_feature_rows_bf16_h2 = src_row != nullptr;
-    g_feature_rows_f16 = false;
-    return 0;
-}
-
-extern "C" int dfol_set_feature_rows_bf16_h2_f16(const int32_t* src_row, const float* box6) {
-    DFOL_REQUIRE((src_row == nullptr) == (box6 == nullptr), "set_feature_rows_bf16_h2_f16: src_row and box6 come together");
-    g_feature_src_row = src_row;
-    g_feature_box6 = box6;
-    g_feature_rows_bf16 = false;
-    g_feature_rows_bf16_h2 = g_feature_rows_f16 = src_row != nullptr;
-    return 0;
-}
-
-extern "C" int dfol_set_program_gates(const float* table, int32_t n_gates) {
-    DFOL_REQUIRE(n_gates >= 0 && (table == nullptr) == (n_gates == 0), "set_program_gates: a table of %d gates at %p", n_gates, (const void*)table);
-    g_gate_table = table;
-    g_gate_count = n_gates;
-    return 0;
-}
 
 extern "C" int dfol_calib_walk_supported(int32_t KX, int32_t H) { return lc_walk_fits(KX, H) ? 1 : 0; }
 
 extern "C" int dfol_run_program(const DfolProgramModel* model, const DfolProgramScene* scene, const int64_t* instr_host, int32_t n_instr,
                                 const void* blob, void* workspace, void* stream) {
-    const int32_t* src_row = g_feature_src_row;                      // (taken and cleared first: an early return must not leave it to the next batch)
-    const float* box6 = g_feature_box6;
-    const bool rows_bf16 = g_feature_rows_bf16, rows_bf16_h2 = g_feature_rows_bf16_h2, rows_f16 = g_feature_rows_f16;
-    g_feature_src_row = nullptr;
-    g_feature_box6 = nullptr;
-    g_feature_rows_bf16 = g_feature_rows_bf16_h2 = g_feature_rows_f16 = false;
-    const FeatureCache cached = g_feature_cache;
-    g_feature_cache = FeatureCache{nullptr, 0, 0, nullptr, nullptr};
-    const float* gates = g_gate_table;
-    const int32_t n_gates = g_gate_count;
-    g_gate_table = nullptr;
-    g_gate_count = 0;
+    DFOL_REQUIRE(model && scene && instr_host && blob && workspace, "run_program: null pointer");
+    DFOL_REQUIRE(n_instr >= 0 && scene->NS > 0 && scene->NS % 4 == 0, "run_program: bad sizes (n_instr %d, NS %d)", n_instr, scene->NS);
+    const int32_t form = scene->feature_form;
+    DFOL_REQUIRE(form >= DFOL_FEATURES_MATRIX && form <= DFOL_FEATURES_CACHED, "run_program: scene->feature_form %d is no DFOL_FEATURES_* form", form);
+    DFOL_REQUIRE((scene->src_row != nullptr) == (form != DFOL_FEATURES_MATRIX) && (scene->box6 != nullptr) == (form != DFOL_FEATURES_MATRIX),
+                 "run_program: scene->src_row and scene->box6 come together, with every form but DFOL_FEATURES_MATRIX and not with it (%s, src_row %p, box6 %p)",
+                 kFeatureForm[form], (const void*)scene->src_row, (const void*)scene->box6);
+    DFOL_REQUIRE((scene->cache != nullptr) == (form == DFOL_FEATURES_CACHED), "run_program: scene->cache comes with DFOL_FEATURES_CACHED, and with it alone (%s, cache %p)",
+                 kFeatureForm[form], (const void*)scene->cache);
+    DFOL_REQUIRE(form != DFOL_FEATURES_CACHED || (scene->cache_cols > 0 && scene->ld_cache >= scene->cache_cols),
+                 "run_program: DFOL_FEATURES_CACHED: bad sizes cache_cols=%d ld_cache=%lld", scene->cache_cols, (long long)scene->ld_cache);
+    const float* gates = model->gates;
+    const int32_t n_gates = model->n_gates;
+    DFOL_REQUIRE(n_gates >= 0 && (gates == nullptr) == (n_gates == 0), "run_program: model->gates / model->n_gates: a table of %d gates at %p", n_gates,
+                 (const void*)gates);
     // the 18 floats of gate `slot` (+ k: the second axis of an arity-2 cell); the slot was checked by DFOL_GATE_SLOT
     auto gate_row = [&](int64_t slot, int k) { return gates + (slot + k) * 18; };
 #define DFOL_GATE_SLOT(slot, arity)                                                                                                                   \
     DFOL_REQUIRE(gates != nullptr && (slot) >= 0 && (slot) + (arity) <= n_gates,                                                                       \
-                 "run_program[%d]: opcode %lld names gate slot %lld (arity %d) of a table of %d gates (dfol_set_program_gates before the call)", i, \
-                 (long long)a[0], (long long)(slot), (arity), gates ? n_gates : 0)
-    DFOL_REQUIRE(model && scene && instr_host && blob && workspace, "run_program: null pointer");
-    DFOL_REQUIRE(n_instr >= 0 && scene->NS > 0 && scene->NS % 4 == 0, "run_program: bad sizes (n_instr %d, NS %d)", n_instr, scene->NS);
+                 "run_program[%d]: opcode %lld names gate slot %lld (arity %d) of a table of %d gates (DfolProgramModel.gates / n_gates)", i,        \
+                 (long long)a[0], (long long)(slot), (arity), n_gates)
     const int32_t NS = scene->NS;
     const int32_t* n_obj = static_cast<const int32_t*>(at(blob, scene->n_obj));            // per QUESTION
     const int32_t* img_n_obj = static_cast<const int32_t*>(at(blob, scene->img_n_obj));    // per SCENE (= n_obj without shared scenes)
@@ -231,56 +204,27 @@ extern "C" int dfol_run_program(const DfolProgramModel* model, const DfolProgram
                 const DfolDenseLayer* layers = a[1] == 0 ? model->featurizer : (a[1] == 1 ? model->attribute : &model->uv);
                 const int32_t count = a[1] == 0 ? model->n_featurizer : (a[1] == 1 ? model->n_attribute : 1);
                 DFOL_REQUIRE(layers && a[2] >= 0 && a[2] < count, "run_program[%d]: dense layer %lld of set %lld does not exist", i, (long long)a[2], (long long)a[1]);
-                if (a[1] == 0 && cached.cache != nullptr) break;    // the featurizer's output comes from the cache (DFOL_OP_BOX_POSITIONS writes it)
+                if (a[1] == 0 && form == DFOL_FEATURES_CACHED) break;    // the featurizer's output comes from the cache (DFOL_OP_BOX_POSITIONS writes it)
                 const float* X = a[3] == 0 ? scene->features + a[4] / 4 : static_cast<const float*>(at(workspace, a[4]));
                 DfolDenseLayer layer = layers[a[2]];
                 if (a[9]) layer.act = DFOL_ACT_NONE;
-                if (a[3] == 0 && src_row != nullptr) {              // the scene in index form: the featurizer's first product reads the store's rows
-                    const int32_t M = static_cast<int32_t>(a[8]);
-                    if (rows_bf16) {                                // a bf16 table: the bf16 mode's product over its rows, the matrix route's bits
-                        DFOL_REQUIRE(a[4] == 0 && layer.kind == DFOL_DENSE_BF16 && layer.packed != nullptr &&
-                                         dfol_linear_rows_bf16t_supported(layer.N, layer.K, scene->ld_features),
-                                     "run_program[%d]: a scene in bf16 index form (dfol_set_feature_rows_bf16) needs a DFOL_DENSE_BF16 first layer of a shape "
-                                     "dfol_linear_rows_bf16t_supported takes (N %d K %d ld %lld kind %d): hand over the gathered matrix", i, layer.N, layer.K,
-                                     (long long)scene->ld_features, layer.kind);
-                        rc = dfol_linear_act_rows_bf16t_f32(scene->features, scene->ld_features, src_row, layer.packed, layer.bias,
-                                                            static_cast<float*>(at(workspace, a[6])), a[7], M, layer.N, layer.K, layer.act, stream);
-                        break;
-                    }
-                    if (rows_bf16_h2) {                             // a bf16 table in front of the default arithmetic: split in place, the matrix route's bits
-                        DFOL_REQUIRE(layer.kind == DFOL_DENSE_F16X2,
-                                     "run_program[%d]: a scene in bf16 index form for the two-piece fp16 product (dfol_set_feature_rows_bf16_h2) needs a "
-                                     "DFOL_DENSE_F16X2 first layer, this one is of kind %d: dfol_set_feature_rows_bf16 serves a DFOL_DENSE_BF16 layer, every "
-                                     "other arithmetic takes the gathered matrix", i, layer.kind);
-                        DFOL_REQUIRE(a[4] == 0 && layer.packed != nullptr && dfol_linear_wide_rows_bf16t_supported(M, layer.N, layer.K, scene->ld_features),
-                                     "run_program[%d]: a scene in bf16 index form (dfol_set_feature_rows_bf16_h2) needs a first layer of a shape "
-                                     "dfol_linear_wide_rows_bf16t_supported takes (M %d N %d K %d ld %lld): hand over the gathered matrix", i, M, layer.N, layer.K,
-                                     (long long)scene->ld_features);
-                        rc = dfol_linear_wide_rows_bf16t_f16_h2_f32(scene->features, scene->ld_features, src_row, layer.packed, layer.bias,
-                                                                    static_cast<float*>(at(workspace, a[6])), a[7], M, layer.N, layer.K, layer.act,
-                                                                    rows_f16 ? 1 : 0, stream);
-                        break;
-                    }
-                    DFOL_REQUIRE(a[4] == 0 && layer.kind == DFOL_DENSE_F16X2 && layer.packed != nullptr && dfol_linear_wide_supported(M, layer.N, layer.K),
-                                 "run_program[%d]: a scene in index form (dfol_set_feature_rows) needs a two-piece fp16 product of a shape "
-                                 "dfol_linear_wide_supported takes (M %d N %d K %d kind %d): hand over the gathered matrix", i, M, layer.N, layer.K, layer.kind);
-                    rc = dfol_linear_wide_rows_h2_f32(scene->features, scene->ld_features, src_row, layer.packed, layer.bias,
-                                                      static_cast<float*>(at(workspace, a[6])), a[7], M, layer.N, layer.K, layer.act, stream);
+                if (a[3] == 0 && rows_form(form)) {                 // the scene in index form: the featurizer's first product reads the store's rows
+                    rc = run_first_layer_rows(*scene, layer, a[4], static_cast<float*>(at(workspace, a[6])), a[7], static_cast<int32_t>(a[8]), stream);
                     break;
                 }
                 rc = run_dense(layer, X, a[3] == 0 ? scene->ld_features : a[5], static_cast<float*>(at(workspace, a[6])), a[7], static_cast<int32_t>(a[8]), stream);
                 break;
             }
             case DFOL_OP_BOX_POSITIONS:  // obj, ld_obj, pos_col
-                if (cached.cache != nullptr) {                      // (cached form: the object matrix's feature columns and its positions in one launch)
-                    DFOL_REQUIRE(a[3] == cached.W, "run_program[%d]: cached featurizer rows of %d columns for an object matrix of %lld + 4", i, cached.W,
-                                 (long long)a[3]);
-                    rc = dfol_store_objects_f32(cached.cache, cached.ld, cached.src_row, cached.box6, scene->O, cached.W, static_cast<float*>(at(workspace, a[1])),
-                                                a[2], stream);
+                if (form == DFOL_FEATURES_CACHED) {                 // (cached form: the object matrix's feature columns and its positions in one launch)
+                    DFOL_REQUIRE(a[3] == scene->cache_cols, "run_program[%d]: cached featurizer rows of %d columns (DFOL_FEATURES_CACHED: cache_cols) for an object matrix of %lld + 4",
+                                 i, scene->cache_cols, (long long)a[3]);
+                    rc = dfol_store_objects_f32(scene->cache, scene->ld_cache, scene->src_row, scene->box6, scene->O, scene->cache_cols,
+                                                static_cast<float*>(at(workspace, a[1])), a[2], stream);
                     break;
                 }
-                if (box6 != nullptr) {                              // (index form: the six box columns travel beside the row numbers)
-                    rc = dfol_box_positions_f32(box6, 6, 6, scene->O, static_cast<float*>(at(workspace, a[1])), a[2], static_cast<int32_t>(a[3]), stream);
+                if (rows_form(form)) {                              // (index form: the six box columns travel beside the row numbers)
+                    rc = dfol_box_positions_f32(scene->box6, 6, 6, scene->O, static_cast<float*>(at(workspace, a[1])), a[2], static_cast<int32_t>(a[3]), stream);
                     break;
                 }
                 rc = dfol_box_positions_f32(scene->features, scene->ld_features, scene->raw_cols, scene->O, static_cast<float*>(at(workspace, a[1])), a[2],

@@ -19,6 +19,8 @@ from . import native_plan as NP
 
 _p, _i32, _i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
 DENSE_F32, DENSE_F16X2, DENSE_BF16X3, DENSE_BF16, DENSE_HEAD_F16X2 = 0, 1, 2, 3, 4
+# DFOL_FEATURES_*: where a scene's featurizer input (or, cached, its output) comes from
+FEATURES_MATRIX, FEATURES_ROWS_F32, FEATURES_ROWS_BF16, FEATURES_ROWS_BF16_H2, FEATURES_ROWS_BF16_H2_F16, FEATURES_CACHED = range(6)
 
 
 class DenseLayer(ctypes.Structure):
@@ -30,12 +32,14 @@ class ProgramModel(ctypes.Structure):
                 ("uv", DenseLayer), ("pair_kind", _i32), ("hid1", _i32), ("hid2", _i32), ("w2_rows", _i32), ("wg", _p), ("w2", _p), ("ld_w2", _i64),
                 ("b2", _p), ("emb_w", _p), ("ld_e", _i64), ("emb_b", _p), ("emb_in", _i32), ("D", _i32),
                 ("lstm_wih_t", _p * 2), ("lstm_whh_t", _p * 2), ("lstm_ld_wih", _i64 * 2), ("lstm_ld_whh", _i64 * 2), ("lstm_bih", _p * 2), ("lstm_bhh", _p * 2),
-                ("lstm_kx", _i32), ("lstm_h", _i32), ("att_out_w", _p), ("ld_att_out", _i64), ("att_out_b", _p), ("att_out_n", _i32)]
+                ("lstm_kx", _i32), ("lstm_h", _i32), ("att_out_w", _p), ("ld_att_out", _i64), ("att_out_b", _p), ("att_out_n", _i32),
+                ("gates", _p), ("n_gates", _i32)]
 
 
 class ProgramScene(ctypes.Structure):
     _fields_ = [("features", _p), ("ld_features", _i64), ("raw_cols", _i32), ("O", _i32), ("NS", _i32), ("max_n", _i32), ("n_obj", _i64),
-                ("img_n_obj", _i64), ("obj_off", _i64)]
+                ("img_n_obj", _i64), ("obj_off", _i64),
+                ("feature_form", _i32), ("src_row", _p), ("box6", _p), ("cache", _p), ("ld_cache", _i64), ("cache_cols", _i32)]
 
 
 _SUSPENDED = [0]
@@ -225,7 +229,7 @@ class NativeModel(object):
             m.att_out_w, m.ld_att_out, m.att_out_n = ow.data_ptr(), ow.stride(0), int(ow.shape[0])
             m.att_out_b = None if nets[2].bias is None else nets[2].bias.detach().data_ptr()
             self._hold += [ow, nets[2].bias]
-        # the gate table of a model with trainable gates: one row of 18 floats per gate, cells in gated_cells' order (dfol_set_program_gates)
+        # the gate table of a model with trainable gates: one row of 18 floats per gate, cells in gated_cells' order (the struct's gates / n_gates)
         cells = gated_cells(model)
         self.gates, self._gate_views = None, None
         if cells:
@@ -235,6 +239,7 @@ class NativeModel(object):
                 # views of the parameters in the table's order: run() gathers them again with one launch (refresh_gates)
                 self._gate_views = [v for w, b in pairs for v in (w.detach().view(12), b.detach().view(6))]
             self._hold += [self.gates, pairs]
+            m.gates, m.n_gates = self.gates.data_ptr(), self.gates.shape[0]
         self.struct = m
         self.D = int(D)
 
@@ -243,7 +248,6 @@ class NativeModel(object):
         gather the parameters again before every run (one launch over the views taken at construction; their addresses are in the key)."""
         if self._gate_views is not None:
             torch.cat(self._gate_views, out=self.gates.view(-1))
-        return self.gates
 
     @staticmethod
     def version_key(model):
@@ -318,7 +322,7 @@ def run(model, program_batch, plan, queue, give_answer=True):
     bf16_h2 = False
     if hasattr(feats, "materialize") and getattr(feats.store, "featurized", False):
         # A featurized store's batch: the featurizer's rows come from the store's cache (built on first use, rebuilt once per weight version) -
-        # the question BatchGQABoxFeaturizer._cached_objects asks; the executor skips the featurizer's products (dfol_set_feature_cache).
+        # the question BatchGQABoxFeaturizer._cached_objects asks; the executor skips the featurizer's products (DFOL_FEATURES_CACHED).
         from .interpreter import featurizer_trains
         net = model._featurizer._featurizer_network
         cache = None if featurizer_trains(net) else feats.store.cached_for(net, build=True)
@@ -328,9 +332,9 @@ def run(model, program_batch, plan, queue, give_answer=True):
     elif hasattr(feats, "materialize"):
         # A direct feature store's batch (feature_store.StoreRows).  The plan is lowered as for any batch; where the featurizer's first product
         # is one the wide kernel takes - the question BatchGQABoxFeaturizer._store_layers asks - the executor reads the store's rows in place
-        # (dfol_set_feature_rows), otherwise it gets the gathered matrix.  A bf16 store's batch likewise where the model's first featurizer layer
-        # is the bf16 mode's and store_layers_of admits it (dfol_set_feature_rows_bf16) - or, with DFOL_STORE_BF16_DIRECT=1, the default
-        # arithmetic's and store_layers_of admits that (dfol_set_feature_rows_bf16_h2): the one predicate answers for the layer's own kind.
+        # (DFOL_FEATURES_ROWS_F32), otherwise it gets the gathered matrix.  A bf16 store's batch likewise where the model's first featurizer layer
+        # is the bf16 mode's and store_layers_of admits it (DFOL_FEATURES_ROWS_BF16) - or, with DFOL_STORE_BF16_DIRECT=1, the default
+        # arithmetic's and store_layers_of admits that (DFOL_FEATURES_ROWS_BF16_H2): the one predicate answers for the layer's own kind.
         first = nm.struct.featurizer[0]
         if getattr(feats, "bf16_ld", None) is not None:
             from .interpreter import store_layers_of
@@ -366,21 +370,20 @@ def run(model, program_batch, plan, queue, give_answer=True):
     sc = ProgramScene()
     if cache is not None:
         sc.features, sc.ld_features, sc.raw_cols, sc.O = None, rows.shape[1], rows.shape[1], plan.scene["O"]      # (no raw feature is read)
-        _lib.call("dfol_set_feature_cache", cache.data_ptr(), cache.stride(0), cache.shape[1], rows.src_row.data_ptr(), rows.box6.data_ptr())
+        sc.feature_form, sc.cache, sc.ld_cache, sc.cache_cols = FEATURES_CACHED, cache.data_ptr(), cache.stride(0), cache.shape[1]
     elif rows is not None:
         sc.features, sc.ld_features, sc.raw_cols, sc.O = rows.table.data_ptr(), rows.table.stride(0), rows.shape[1], plan.scene["O"]
-        setter = "dfol_set_feature_rows" if getattr(rows, "bf16_ld", None) is None else \
-            ("dfol_set_feature_rows_bf16" if not bf16_h2 else
-             "dfol_set_feature_rows_bf16_h2_f16" if rows.store._f16_exact is True else "dfol_set_feature_rows_bf16_h2")
-        _lib.call(setter, rows.src_row.data_ptr(), rows.box6.data_ptr())                           # (picked up, and cleared, by the call below)
+        sc.feature_form = FEATURES_ROWS_F32 if getattr(rows, "bf16_ld", None) is None else \
+            (FEATURES_ROWS_BF16 if not bf16_h2 else
+             FEATURES_ROWS_BF16_H2_F16 if rows.store._f16_exact is True else FEATURES_ROWS_BF16_H2)
     else:
         sc.features, sc.ld_features, sc.raw_cols, sc.O = feats.data_ptr(), feats.stride(0), feats.shape[1], plan.scene["O"]
+    if rows is not None:
+        sc.src_row, sc.box6 = rows.src_row.data_ptr(), rows.box6.data_ptr()
     sc.NS, sc.max_n = plan.scene["NS"], plan.scene["max_n"]
     sc.n_obj, sc.img_n_obj, sc.obj_off = plan.scene["n_obj"], plan.scene["img_n_obj"], plan.scene["obj_off"]
     instrs = plan.instrs
-    if nm.gates is not None:                                 # (picked up, and cleared, by the call below)
-        gates = nm.refresh_gates()
-        _lib.call("dfol_set_program_gates", gates.data_ptr(), gates.shape[0])
+    nm.refresh_gates()                                       # (the table the struct points at, at its fixed address)
     _lib.call("dfol_run_program", ctypes.byref(nm.struct), ctypes.byref(sc), instrs.ctypes.data, instrs.shape[0], blob.data_ptr(), ws.data_ptr(),
               _lib._stream())
     r = plan.result

@@ -37,7 +37,10 @@
 extern "C" {
 #endif
 
-/* 3 (round 6): dfol_pair_ll_h2_f32 takes UV in units of ln 2 and dfol_pair_pack_w2_f16x2 folds ln 2 into W2 (the round-5 change of contract that
+/* 4: what dfol_run_program reads travels in the structs it takes - DfolProgramScene gained the feature source (feature_form, src_row, box6, cache,
+ * ld_cache, cache_cols) and DfolProgramModel the gate table (gates, n_gates) - and the six thread-local setters that armed them for "the next call"
+ * (four for the index forms of a store-backed scene, one for the cached form, one for the gate table) are gone: a struct whose layout changes.
+ * 3 (round 6): dfol_pair_ll_h2_f32 takes UV in units of ln 2 and dfol_pair_pack_w2_f16x2 folds ln 2 into W2 (the round-5 change of contract that
  * kept version 2: a caller written against 2 passes unscaled UV and must be refused, not answered wrongly); dfol_pair_ll_h2_f32 reports saturated
  * ELU outputs through the dfol_set_range_status word (DFOL_RANGE_PAIR_SATURATED); dfol_run_program knows the calibration instructions.
  * The rule: the version changes when a caller written against the old one would be answered wrongly - an entry point whose arguments or units
@@ -45,24 +48,23 @@ extern "C" {
  * operand of DFOL_OP_DENSE (a slot that instruction tables written before it hold as zero = the layer's own activation) were added under 3,
  * and so were dfol_pair_ll_h1_f32, dfol_pair_pack_w2_f16, dfol_pair_w2_f16_bytes and DFOL_PAIR_F16 (an older library refuses the kind) and
  * dfol_gather_object_rows_f32, and the two size queries dfol_lstm_cell_supported and dfol_calib_walk_supported, and the index form of a store-backed
- * batch: dfol_store_rows_f32, dfol_linear_wide_rows_h2_f32 and dfol_set_feature_rows (no struct and no instruction table changes for it), and
- * its cached form: dfol_store_objects_f32 and dfol_set_feature_cache (likewise), and the dropout training route: dfol_dropout_advance,
+ * batch: dfol_store_rows_f32 and dfol_linear_wide_rows_h2_f32 (no instruction table changes for it), and
+ * its cached form: dfol_store_objects_f32 (likewise), and the dropout training route: dfol_dropout_advance,
  * dfol_dropout_f32 and dfol_pair_features_bwd_f32, and the train step's weight gradient over the store's rows: dfol_linear_wgrad_rows_supported,
  * dfol_linear_wgrad_bias_rows_f32 and dfol_linear_wgrad_bias_rows_bf16, and the bf16 form of the store: dfol_store_round_bf16,
  * dfol_gather_object_rows_bf16_f32, dfol_linear_rows_bf16t_supported, dfol_linear_act_rows_bf16t_f32, dfol_linear_wgrad_rows_bf16t_supported,
- * dfol_linear_wgrad_bias_rows_bf16t and dfol_set_feature_rows_bf16, and the logic cell with the trainable gate: dfol_filter_gate_fwd_f32,
+ * and dfol_linear_wgrad_bias_rows_bf16t, and the logic cell with the trainable gate: dfol_filter_gate_fwd_f32,
  * dfol_relate_gate_fwd_f32, dfol_filter_gate_bwd_scratch, dfol_filter_gate_bwd_f32 and dfol_relate_gate_bwd_f32, and the gated model on the
- * executor: dfol_relate_one_gate_fwd_f32, dfol_set_program_gates and DFOL_OP_FILTER_GATE / DFOL_OP_RELATE_ONE_GATE / DFOL_OP_RELATE_GATE (no
- * struct grows: the gate table travels beside the call, as dfol_set_feature_rows' arrays do), and the one-posterior gated Relate of the train
+ * executor: dfol_relate_one_gate_fwd_f32 and DFOL_OP_FILTER_GATE / DFOL_OP_RELATE_ONE_GATE / DFOL_OP_RELATE_GATE, and the one-posterior gated Relate of the train
  * step: dfol_relate_keep_gate_fwd_f32 and dfol_relate_keep_gate_bwd_f32, and the one-posterior gated Relate on bf16 tiles:
  * dfol_relate_one_gate_fwd_bf16 and DFOL_TILE_BF16 as DFOL_OP_RELATE_ONE_GATE's tile dtype (an older library refuses that operand), and the
  * one-posterior Relate of the ungated train step: dfol_relate_keep_fwd_f32 and dfol_relate_keep_bwd_f32, and the default arithmetic over a bf16
- * table in place: dfol_linear_wide_rows_bf16t_supported, dfol_linear_wide_rows_bf16t_h2_f32 and dfol_set_feature_rows_bf16_h2, with
- * dfol_store_bf16_is_f16, dfol_linear_wide_rows_bf16t_f16_h2_f32 and dfol_set_feature_rows_bf16_h2_f16 for a table of fp16 values, and the
+ * table in place: dfol_linear_wide_rows_bf16t_supported and dfol_linear_wide_rows_bf16t_h2_f32, with
+ * dfol_store_bf16_is_f16 and dfol_linear_wide_rows_bf16t_f16_h2_f32 for a table of fp16 values, and the
  * default arithmetic's weight gradient over it: dfol_linear_wgrad_rows_bf16t_x3_supported and dfol_linear_wgrad_bias_rows_bf16t_x3, and the listed pairs' rows of the scene-graph supervision:
  * dfol_scene_pair_rows_f32 and dfol_scene_pair_rows_bwd_f32;
  * a caller that needs them checks for the symbol, and a table that names an opcode an older library lacks is refused by it ("unknown opcode"). */
-#define DFOL_ABI_VERSION 3
+#define DFOL_ABI_VERSION 4
 
 /* ---- library ---------------------------------------------------------------------------------- */
 int dfol_abi_version(void);
@@ -1062,7 +1064,33 @@ typedef struct {            /* the neural modules of build_neural_modules, gqa_i
     int64_t ld_att_out;
     const float* att_out_b;     /* [att_out_n] or NULL */
     int32_t att_out_n;          /* 4 (dfol_modulate_f32's modulations) */
+    /* the gate table of a model with trainable gates (NULL, 0 without): [n_gates][18] device floats, one row per gate in the layout the gated
+     * kernels read (W [6, 2] row-major, then c [6]), what DFOL_OP_FILTER_GATE / DFOL_OP_RELATE_ONE_GATE / DFOL_OP_RELATE_GATE index with their slot */
+    const float* gates;
+    int32_t n_gates;
 } DfolProgramModel;
+
+/* DfolProgramScene.feature_form: where the featurizer's input (or output) comes from.  Every form but the matrix takes src_row [O] and box6 [O, 6]
+ * as dfol_store_rows_f32 writes them, and DFOL_OP_BOX_POSITIONS reads box6; the matrix form takes neither.  Plans are lowered as ever. */
+#define DFOL_FEATURES_MATRIX 0           /* features is the plain [O, ld_features] fp32 matrix */
+#define DFOL_FEATURES_ROWS_F32 1         /* index form: features / ld_features describe the feature store's [S * max_obj, K] table (raw_cols is ignored).
+                                          * The source-0 DFOL_OP_DENSE runs dfol_linear_wide_rows_h2_f32 - it must be a DFOL_DENSE_F16X2 layer of a shape
+                                          * dfol_linear_wide_supported(O, N, K) takes: the caller asks that first and hands over the gathered matrix
+                                          * otherwise; any other source-0 product is refused */
+#define DFOL_FEATURES_ROWS_BF16 2        /* the same for a bf16 table (feature_dtype="bf16"): features points at rows of bfloat16 and ld_features counts
+                                          * elements.  The source-0 DFOL_OP_DENSE runs dfol_linear_act_rows_bf16t_f32 - it must be a DFOL_DENSE_BF16 layer
+                                          * that dfol_linear_rows_bf16t_supported takes; any other layer kind is refused */
+#define DFOL_FEATURES_ROWS_BF16_H2 3     /* a bf16 table in front of the DEFAULT arithmetic: the source-0 DFOL_OP_DENSE runs
+                                          * dfol_linear_wide_rows_bf16t_h2_f32 (in place of the gathered fp32 matrix and dfol_linear_wide_h2_f32 over it - the
+                                          * same bits) - it must be a DFOL_DENSE_F16X2 layer of a shape dfol_linear_wide_rows_bf16t_supported(O, N, K,
+                                          * ld_features) takes; any other layer is refused with the reason */
+#define DFOL_FEATURES_ROWS_BF16_H2_F16 4 /* the same for a table that dfol_store_bf16_is_f16 certified: the product is
+                                          * dfol_linear_wide_rows_bf16t_f16_h2_f32 with its flag set (two products, the same bits).  Conditions and refusals as
+                                          * DFOL_FEATURES_ROWS_BF16_H2 */
+#define DFOL_FEATURES_CACHED 5           /* the featurizer's output is CACHED (a frozen featurizer; dfol_store_objects_f32): no featurizer product runs -
+                                          * every DFOL_OP_DENSE of set 0 is skipped, features is not read and may be NULL - and DFOL_OP_BOX_POSITIONS writes
+                                          * the whole object matrix: rows src_row [O] of cache [rows, ld_cache] (cache_cols = the instruction's pos_col
+                                          * columns, else refused) and the positions of box6 */
 
 typedef struct {            /* the scenes of one ProgramBatch (data_pipeline.py:149) */
     const float* features;  /* [O, ld_features]: raw object features, the last 6 of raw_cols columns are (W, H, x, y, w, h) */
@@ -1072,6 +1100,12 @@ typedef struct {            /* the scenes of one ProgramBatch (data_pipeline.py:
     int64_t n_obj;          /* byte offsets into `blob`: objects per QUESTION [Q] ... */
     int64_t img_n_obj;      /* ... per SCENE [scenes] (the same array unless questions share scenes) ... */
     int64_t obj_off;        /* ... and the first object row of every scene [scenes + 1] (int32) */
+    int32_t feature_form;   /* DFOL_FEATURES_*; a zero-initialised tail is the matrix form */
+    const int32_t* src_row; /* every form but the matrix; NULL there */
+    const float* box6;
+    const float* cache;     /* DFOL_FEATURES_CACHED alone; NULL / 0 otherwise */
+    int64_t ld_cache;
+    int32_t cache_cols;
 } DfolProgramScene;
 
 /* opcodes (operand lists in csrc/dfol_program.hip, written by dfol_vqa_amd/native_plan.py) */
@@ -1109,8 +1143,8 @@ typedef struct {            /* the scenes of one ProgramBatch (data_pipeline.py:
 #define DFOL_OP_ATTR_HEAD 24        /* pre1, ld_pre1, pred_img (blob), cols (blob), P, ll, scenes: dfol_attr_head_h2_f32 over the attribute network's last layer
                                      * (a two-layer network whose last layer is DFOL_DENSE_HEAD_F16X2) - replaces that layer's DFOL_OP_DENSE and DFOL_OP_ATTR_LL */
 /* The logic instructions of a model with trainable gates (trainable_gate: True).  The reference builds its FilterBatch / RelateBatch - and so
- * its gate parameters - per operator class (batch_gqa_ops.py), so every instruction names its cell: `slot` is a row of the table handed over with
- * dfol_set_program_gates, and a cell of arity 2 owns rows slot (axis 0, the subject's) and slot + 1 (axis 1).  Without a table, or with a slot
+ * its gate parameters - per operator class (batch_gqa_ops.py), so every instruction names its cell: `slot` is a row of the model's
+ * gate table (DfolProgramModel.gates), and a cell of arity 2 owns rows slot (axis 0, the subject's) and slot + 1 (axis 1).  Without a table, or with a slot
  * beyond it, the program is refused before the instruction launches anything. */
 #define DFOL_OP_FILTER_GATE 25      /* DFOL_OP_FILTER's operands, slot: dfol_filter_gate_fwd_f32 */
 #define DFOL_OP_RELATE_ONE_GATE 26  /* DFOL_OP_RELATE_ONE's operands, x_is_subject (blob, uint8 [P]), slot: dfol_relate_one_gate_fwd_f32, or
@@ -1124,33 +1158,9 @@ typedef struct {            /* the scenes of one ProgramBatch (data_pipeline.py:
 #define DFOL_WALK_ATT_MODULATIONS 4 /* forward state h, backward state h, out [rows, att_out_n] */
 
 int dfol_calib_walk_supported(int32_t KX, int32_t H); /* 1 / 0: DFOL_OP_CALIB_WALK takes a calibrator of input width KX and state width H */
-/* The NEXT dfol_run_program of the calling thread reads its scene in index form (a thread-local setting like dfol_set_range_status, cleared by that
- * call whether it succeeds or not; NULL, NULL clears it): scene->features / ld_features describe the feature store's [S * max_obj, K] table
- * (raw_cols is ignored), src_row [O] and box6 [O, 6] are dfol_store_rows_f32's.  The source-0 DFOL_OP_DENSE runs dfol_linear_wide_rows_h2_f32 - it
- * must be a DFOL_DENSE_F16X2 layer of a shape dfol_linear_wide_supported(O, N, K) takes: the caller asks that first and hands over the gathered
- * matrix otherwise; any other source-0 product is refused - and DFOL_OP_BOX_POSITIONS reads box6.  Plans are lowered as ever. */
-int dfol_set_feature_rows(const int32_t* src_row, const float* box6);
-/* The same for a bf16 table (feature_dtype="bf16"): scene->features points at rows of bfloat16 and ld_features counts elements.  The source-0
- * DFOL_OP_DENSE runs dfol_linear_act_rows_bf16t_f32 - it must be a DFOL_DENSE_BF16 layer that dfol_linear_rows_bf16t_supported takes; any other
- * layer kind is refused - and DFOL_OP_BOX_POSITIONS reads box6.  Either setting replaces the other. */
-int dfol_set_feature_rows_bf16(const int32_t* src_row, const float* box6);
-/* A bf16 table in front of the DEFAULT arithmetic: the source-0 DFOL_OP_DENSE runs dfol_linear_wide_rows_bf16t_h2_f32 (in place of the gathered
- * fp32 matrix and dfol_linear_wide_h2_f32 over it - the same bits) - it must be a DFOL_DENSE_F16X2 layer of a shape
- * dfol_linear_wide_rows_bf16t_supported(O, N, K, ld_features) takes; any other layer is refused with the reason - and DFOL_OP_BOX_POSITIONS
- * reads box6.  Each of the three settings replaces the others. */
-int dfol_set_feature_rows_bf16_h2(const int32_t* src_row, const float* box6);
-/* The same for a table that dfol_store_bf16_is_f16 certified: the product is dfol_linear_wide_rows_bf16t_f16_h2_f32 with its flag set (two
- * products, the same bits).  Conditions and refusals as dfol_set_feature_rows_bf16_h2. */
-int dfol_set_feature_rows_bf16_h2_f16(const int32_t* src_row, const float* box6);
-/* The same for a scene whose featurizer output is CACHED (a frozen featurizer; dfol_store_objects_f32): the NEXT dfol_run_program of the calling
- * thread runs no featurizer product - every DFOL_OP_DENSE of set 0 is skipped, scene->features is not read and may be NULL - and its
- * DFOL_OP_BOX_POSITIONS writes the whole object matrix: cache rows src_row [O] of cache [rows, ld_cache] (W = the instruction's pos_col columns,
- * else refused) and the positions of box6 [O, 6].  Cleared by that call; all NULL / 0 clears it.  It takes precedence over dfol_set_feature_rows. */
-int dfol_set_feature_cache(const float* cache, int64_t ld_cache, int32_t W, const int32_t* src_row, const float* box6);
-/* The gate table of the NEXT dfol_run_program of the calling thread (thread-local, consumed and cleared by that call whether it succeeds or not;
- * NULL, 0 clears it): table [n_gates][18] device floats, one row per gate in the layout the gated kernels read (W [6, 2] row-major, then c [6]),
- * what DFOL_OP_FILTER_GATE / DFOL_OP_RELATE_ONE_GATE / DFOL_OP_RELATE_GATE index with their slot. */
-int dfol_set_program_gates(const float* table, int32_t n_gates);
+/* Everything a run reads is in its arguments: the feature source in `scene` (DFOL_FEATURES_*), the gate table in `model`.  Inconsistent fields - a form
+ * out of range, src_row / box6 / cache missing or stray for the form, bad cache sizes, n_gates < 0 or a table without a count - are refused before
+ * anything is launched, with the field named in dfol_last_error(). */
 int dfol_run_program(const DfolProgramModel* model, const DfolProgramScene* scene, const int64_t* instr_host, int32_t n_instr,
                      const void* blob, void* workspace, void* stream);
 

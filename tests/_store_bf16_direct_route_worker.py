@@ -119,7 +119,7 @@ def train_step(world):
 
 
 def setter_refusal(world):
-    """dfol_set_feature_rows_bf16_h2 in front of a first layer that is not DFOL_DENSE_F16X2 (the bf16 mode's): refused with the reason."""
+    """DFOL_FEATURES_ROWS_BF16_H2 in front of a first layer that is not DFOL_DENSE_F16X2 (the bf16 mode's): refused with the reason."""
     switch(True)
     os.environ["DFOL_NATIVE"] = "1"
     world.mode("bf16", train=False)
@@ -127,9 +127,10 @@ def setter_refusal(world):
     real = _lib.call
 
     def call(name, *args):
-        if name == "dfol_run_program":
-            rows = pbs_dev[0]._object_features
-            real("dfol_set_feature_rows_bf16_h2", rows.src_row.data_ptr(), rows.box6.data_ptr())
+        if name == "dfol_run_program":                                   # (the bf16 mode's own run: its scene struct names DFOL_FEATURES_ROWS_BF16)
+            scene = args[1]._obj
+            assert scene.feature_form == native_exec.FEATURES_ROWS_BF16 and scene.src_row and scene.box6
+            scene.feature_form = native_exec.FEATURES_ROWS_BF16_H2
         return real(name, *args)
     _lib.call = call
     try:
@@ -137,7 +138,7 @@ def setter_refusal(world):
             world.model(pbs_dev[:1], False)
         raise AssertionError("not refused")
     except _lib.DfolError as e:
-        assert "DFOL_DENSE_F16X2" in str(e) and "dfol_set_feature_rows_bf16_h2" in str(e), str(e)
+        assert "DFOL_DENSE_F16X2" in str(e) and "(DFOL_FEATURES_ROWS_BF16_H2)" in str(e), str(e)
     finally:
         _lib.call = real
         world.mode(None, train=False)

@@ -109,7 +109,7 @@ def test_entry_point_is_exported_declared_and_bound(handle):
     m = re.search(r"\bint\s+%s\s*\((.*?)\)\s*;" % NAME, text, flags=re.S)
     assert m and "const uint16_t* tile" in m.group(1)
     assert len(_lib.SIGNATURES[NAME]) == len(_lib.SIGNATURES["dfol_relate_one_gate_fwd_f32"]) == len(m.group(1).split(","))
-    assert handle.dfol_abi_version() == 3                         # a pure addition
+    assert handle.dfol_abi_version() == 4 == _lib.ABI_VERSION      # (the entry point itself was a pure addition under 3)
 
 
 def test_entry_point_refuses_bad_sizes_without_a_device(handle):

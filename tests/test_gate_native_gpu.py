@@ -387,8 +387,7 @@ def test_refusals(monkeypatch):
         row[{NP.OP_FILTER_GATE: 8, NP.OP_RELATE_ONE_GATE: 13, NP.OP_RELATE_GATE: 15}[row[0]]] = slot
         instr = np.zeros((1, NP.INSTR_WIDTH), np.int64)
         instr[0, :len(row)] = row
-        if gates is not None:
-            _lib.call("dfol_set_program_gates", gates.data_ptr(), gates.shape[0])
+        model.gates, model.n_gates = (None, 0) if gates is None else (gates.data_ptr(), gates.shape[0])
         _lib.call("dfol_run_program", ctypes.byref(model), ctypes.byref(scene), instr.ctypes.data, 1, blob.data_ptr(), ws.data_ptr(), _lib._stream())
 
     for opcode, row in rows.items():
@@ -397,6 +396,6 @@ def test_refusals(monkeypatch):
         with pytest.raises(_lib.DfolError, match="gate slot"):
             run(row, table, slot=2 if opcode == NP.OP_FILTER_GATE else 1)       # beyond the table (an arity-2 cell needs slot + 1 as well)
         with pytest.raises(_lib.DfolError, match="gate slot"):
-            run(row)                                              # the table of the call before was consumed by it
+            run(row)                                              # after a refused run WITH a table, a model struct that carries none: nothing lingers
     torch.cuda.synchronize()                                      # nothing was launched, nothing faulted
     assert not ws.any().item()

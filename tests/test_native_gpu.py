@@ -670,3 +670,61 @@ def test_executor_batches_on_two_streams_keep_their_results_and_flags(full, monk
             assert r is None
             continue
         assert torch.equal(r["log_probability"], w[0]) and r["answer"] == w[1] and r["answer_log_probability"] == w[2], kinds[k]
+
+
+def test_a_host_error_before_the_call_leaves_nothing_to_the_next_batch(full, tmp_path, monkeypatch):
+    """What a run reads travels in its own structs: a direct-store batch whose host side raises AFTER it has built its scene struct (the
+    index form, src_row and box6 of the store) and BEFORE dfol_run_program hands the library nothing, so the plain-matrix batch that follows on
+    the same thread returns the bits it returns in a fresh state.  (The size predicate is answered for the host only, to choose the in-place
+    route for a store of five rows: the error fires before any call, so no kernel sees that shape.)"""
+    from dfol_vqa_amd import data
+    from dfol_vqa_amd.feature_store import StoreRows
+    from test_feature_store import write_chunks
+    model, ont, oont, names, categories = full
+    monkeypatch.setenv("DFOL_NATIVE", "1")
+    qs = syn.full_size_questions("exist", 3, 10, 20, names, categories, 410)
+    for q in qs:
+        q["scene"] = syn.feature_scene(q["question_id"], 1, 2048)
+
+    def plain_matrix_batch():
+        pbs = TableCollater(1, ont, "X").collate([dict(q) for q in qs])
+        for pb in pbs:
+            pb.create_sparse_tensors()
+        _lib.PATH_COUNTS.clear()
+        with torch.no_grad():
+            r = model([pb.to_cuda(DEV) for pb in pbs], False)
+        assert _lib.PATH_COUNTS.get("native_program", 0) == len(pbs) == 1
+        return r
+    want = plain_matrix_batch()
+
+    chunks, info = write_chunks(tmp_path, feature_dim=2048, max_obj=4, counts=[3, 2], per_chunk=2, seed=23)
+    store = data.DeviceFeatureStore(str(tmp_path), "objs", chunks, info, DEV, direct=True)
+    sq = syn.full_size_questions("exist", 2, 10, 20, names, categories, 31, with_scene=False)
+    for q, im in zip(sq, [1, 0]):
+        q["image_id"] = "img%03d" % im
+    pbs = data.BatchGQABoxFeaturesCollator(str(tmp_path), "objs", chunks, info, ont, 1, device_store=store.index).collate(sq)
+    for pb in pbs:
+        pb.create_sparse_tensors()
+    pbs = [pb.to_cuda(DEV) for pb in pbs]
+    assert isinstance(pbs[0]._object_features, StoreRows)
+    handed = []
+
+    def failing_refresh(self):
+        raise RuntimeError("a host step between the scene struct and the call")
+
+    def recording_call(name, *args, real=_lib.call):
+        handed.append(name)
+        return real(name, *args)
+    with monkeypatch.context() as m:
+        m.setattr(_lib, "linear_wide_supported", lambda M, N, K: True)
+        m.setattr(native_exec.NativeModel, "refresh_gates", failing_refresh)
+        m.setattr(_lib, "call", recording_call)
+        _lib.PATH_COUNTS.clear()
+        with pytest.raises(RuntimeError, match="a host step"), torch.no_grad():
+            model(pbs, False)
+    assert _lib.PATH_COUNTS.get("feature_store_direct", 0) == 1 and "native_program" not in _lib.PATH_COUNTS       # the in-place route, not run
+    assert handed == [], handed                                   # nothing was handed to the library: there is nothing to linger
+
+    got = plain_matrix_batch()
+    same_results(got, want, "after a failed direct-store batch")
+    assert np.array_equal(got["log_probability"].cpu().numpy().view(np.uint32), want["log_probability"].cpu().numpy().view(np.uint32))

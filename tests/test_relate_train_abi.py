@@ -37,8 +37,8 @@ def test_entry_points_in_header_and_table(lib):
         assert hasattr(handle, name)
         comment = raw[:raw.index("int " + name)].rsplit("/*", 1)[1]  # the header cites the reference lines each replaces
         assert "batch_gqa_ops.py:364-371" in comment and "batch_base_ops.py" in comment, name
-    assert handle.dfol_abi_version() == 3 == lib.ABI_VERSION
-    assert re.search(r"#define\s+DFOL_ABI_VERSION\s+3\b", raw)
+    assert handle.dfol_abi_version() == 4 == lib.ABI_VERSION
+    assert re.search(r"#define\s+DFOL_ABI_VERSION\s+4\b", raw)
     version_note = raw[:raw.index("#define DFOL_ABI_VERSION")].rsplit("/*", 1)[1]
     assert all(name in version_note for name in ENTRY_POINTS)
 

@@ -10,13 +10,13 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _program_inputs as PI  # noqa: E402
 from dfol_vqa_amd import _lib  # noqa: E402
 from dfol_vqa_amd.interpreter import store_layers_of  # noqa: E402
 from dfol_vqa_amd.visual_oracle import RegularMLP  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("dfol_linear_wide_rows_bf16t_h2_f32", "dfol_linear_wide_rows_bf16t_supported", "dfol_set_feature_rows_bf16_h2", "dfol_store_bf16_is_f16",
-       "dfol_linear_wide_rows_bf16t_f16_h2_f32", "dfol_set_feature_rows_bf16_h2_f16")
+NEW = ("dfol_linear_wide_rows_bf16t_h2_f32", "dfol_linear_wide_rows_bf16t_supported", "dfol_store_bf16_is_f16", "dfol_linear_wide_rows_bf16t_f16_h2_f32")
 CTYPE = {"int32_t": "_i32", "int64_t": "_i64", "float": "_f"}
 
 
@@ -32,11 +32,12 @@ def test_binding_table_names_the_new_entry_points_with_the_headers_signatures():
             arg = " ".join(arg.split())
             want.append("_p" if "*" in arg else CTYPE[arg.replace("const ", "").split(" ")[0]])
         assert name in _lib.SIGNATURES and [kinds[id(t)] for t in _lib.SIGNATURES[name]] == want, name
-    # the product's arguments are dfol_linear_wide_rows_h2_f32's (the table's element type aside); the setter's are its two siblings'
+    # the product's arguments are dfol_linear_wide_rows_h2_f32's (the table's element type aside); the route's two forms stand beside their siblings
     assert len(_lib.SIGNATURES["dfol_linear_wide_rows_bf16t_h2_f32"]) == len(_lib.SIGNATURES["dfol_linear_wide_rows_h2_f32"]) == 12
-    assert _lib.SIGNATURES["dfol_set_feature_rows_bf16_h2"] == _lib.SIGNATURES["dfol_set_feature_rows_bf16"] == _lib.SIGNATURES["dfol_set_feature_rows"]
-    assert "dfol_linear_wide_rows_bf16t_h2_f32 and dfol_set_feature_rows_bf16_h2" in header       # the "added under 3" list: a pure addition
-    assert _lib.ABI_VERSION == 3 and "#define DFOL_ABI_VERSION 3" in header
+    PI.assert_forms_and_layout()                                  # DFOL_FEATURES_ROWS_BF16_H2 and DFOL_FEATURES_ROWS_BF16_H2_F16, in the scene struct
+    assert "dfol_linear_wide_rows_bf16t_supported and dfol_linear_wide_rows_bf16t_h2_f32" in header       # the "added under 3" list
+    assert "dfol_store_bf16_is_f16 and dfol_linear_wide_rows_bf16t_f16_h2_f32" in header
+    assert _lib.ABI_VERSION == 4 and "#define DFOL_ABI_VERSION 4" in header
 
 
 def test_the_size_predicate_is_reachable_without_a_device():
@@ -58,8 +59,13 @@ def test_the_size_predicate_is_reachable_without_a_device():
     assert h.dfol_linear_wide_rows_bf16t_h2_f32(8, 2050, 8, 16, None, 8, 512, 4, 512, 2048, 0, None) != 0 and b"multiple of 4" in h.dfol_last_error()
     assert h.dfol_linear_wide_rows_bf16t_h2_f32(8, 2044, 8, 16, None, 8, 512, 4, 512, 2048, 0, None) != 0 and b"bad sizes" in h.dfol_last_error()
     assert h.dfol_linear_wide_rows_bf16t_h2_f32(12, 2048, 8, 16, None, 8, 512, 4, 512, 2048, 0, None) != 0 and b"8-byte" in h.dfol_last_error()
-    assert h.dfol_set_feature_rows_bf16_h2(8, None) != 0 and b"set_feature_rows_bf16_h2" in h.dfol_last_error()
-    assert h.dfol_set_feature_rows_bf16_h2(8, 8) == 0 and h.dfol_set_feature_rows_bf16_h2(None, None) == 0
+    for name in ("ROWS_BF16_H2", "ROWS_BF16_H2_F16", "ROWS_BF16"):
+        form = getattr(PI.native_exec, "FEATURES_" + name)
+        rc, err = PI.run_empty(feature_form=form, src_row=8)       # (an empty program: nothing is launched)
+        assert rc != 0 and b"src_row" in err and b"box6" in err and ("(DFOL_FEATURES_%s," % name).encode() in err, (form, err)
+        rc, err = PI.run_empty(feature_form=form)
+        assert rc != 0 and b"src_row" in err, (form, err)
+        assert PI.run_empty(feature_form=form, src_row=8, box6=8)[0] == 0 and PI.run_empty()[0] == 0
 
 
 def test_the_shared_predicate_follows_the_switch(monkeypatch):

@@ -484,16 +484,16 @@ def test_active_dropout_trains_over_the_materialised_matrix(world):
 
 
 def test_bf16_rows_in_front_of_another_first_layer_are_refused(world):
-    """dfol_set_feature_rows_bf16 with a model whose first featurizer layer is not DFOL_DENSE_BF16: the executor says why and runs nothing."""
+    """DFOL_FEATURES_ROWS_BF16 with a model whose first featurizer layer is not DFOL_DENSE_BF16: the executor says why and runs nothing."""
     from dfol_vqa_amd import native_exec
     world.mode(None, train=False)                                         # f16x2: the executor's first layer is DFOL_DENSE_F16X2
     pbs = world.host_batches("plain", "bf16", IMAGES, kind="exist")
     real = _lib.call
 
-    def call(name, *args):                                                # hand the executor the bf16 setting in front of its own run
+    def call(name, *args):                                                # hand the executor the bf16 index form in its own run's scene struct
         if name == "dfol_run_program":
-            rows = pbs_dev[0]._object_features
-            real("dfol_set_feature_rows_bf16", rows.src_row.data_ptr(), rows.box6.data_ptr())
+            rows, scene = pbs_dev[0]._object_features, args[1]._obj
+            scene.feature_form, scene.src_row, scene.box6 = native_exec.FEATURES_ROWS_BF16, rows.src_row.data_ptr(), rows.box6.data_ptr()
         return real(name, *args)
     pbs_dev = [pb.to_cuda(DEV) for pb in pbs]
     os.environ["DFOL_NATIVE"] = "1"

@@ -34,7 +34,7 @@ def test_binding_table_names_the_new_entry_points_with_the_headers_signatures():
     assert _lib.SIGNATURES["dfol_linear_wgrad_bias_rows_bf16t_x3"] == _lib.SIGNATURES["dfol_linear_wgrad_bias_rows_bf16t"]
     assert _lib.SIGNATURES["dfol_linear_wgrad_rows_bf16t_x3_supported"] == _lib.SIGNATURES["dfol_linear_wgrad_rows_bf16t_supported"]
     assert "dfol_linear_wgrad_rows_bf16t_x3_supported and dfol_linear_wgrad_bias_rows_bf16t_x3" in header      # the "added under 3" list
-    assert _lib.ABI_VERSION == 3 and "#define DFOL_ABI_VERSION 3" in header
+    assert _lib.ABI_VERSION == 4 and "#define DFOL_ABI_VERSION 4" in header
 
 
 def test_the_size_predicate(monkeypatch):

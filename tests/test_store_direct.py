@@ -9,11 +9,12 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _program_inputs as PI  # noqa: E402
 from dfol_vqa_amd import _lib, feature_store  # noqa: E402
 from dfol_vqa_amd.feature_store import ObjectFeatureRef  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("dfol_store_rows_f32", "dfol_linear_wide_rows_h2_f32", "dfol_set_feature_rows")
+NEW = ("dfol_store_rows_f32", "dfol_linear_wide_rows_h2_f32")
 CTYPE = {"int32_t": "_i32", "int64_t": "_i64", "float": "_f"}
 
 
@@ -29,8 +30,9 @@ def test_binding_table_names_the_new_entry_points_with_the_headers_signatures():
             arg = " ".join(arg.split())
             want.append("_p" if "*" in arg else CTYPE[arg.replace("const ", "").split(" ")[0]])
         assert [kinds[id(t)] for t in _lib.SIGNATURES[name]] == want, name
-    assert "dfol_store_rows_f32, dfol_linear_wide_rows_h2_f32 and dfol_set_feature_rows" in header       # the "added under 3" list
-    assert _lib.ABI_VERSION == 3 and "#define DFOL_ABI_VERSION 3" in header
+    assert "dfol_store_rows_f32 and dfol_linear_wide_rows_h2_f32" in header                              # the "added under 3" list
+    PI.assert_forms_and_layout()                                  # the index form travels in the scene struct: DFOL_FEATURES_ROWS_F32
+    assert _lib.ABI_VERSION == 4 and "#define DFOL_ABI_VERSION 4" in header
 
 
 MAX_OBJ = 40
@@ -79,5 +81,19 @@ def test_entry_points_validate_their_sizes_without_a_device():
         assert b"store_rows" in h.dfol_last_error()
     assert h.dfol_linear_wide_rows_h2_f32(None, 128, None, None, None, None, 512, 1, 512, 128, 0, None) != 0
     assert b"linear_wide_rows_h2" in h.dfol_last_error()
-    assert h.dfol_set_feature_rows(None, None) == 0
-    assert h.dfol_set_feature_rows(8, None) != 0 and b"set_feature_rows" in h.dfol_last_error()
+    # the scene's index form, on an empty program (nothing is launched): the fields are checked before anything else happens
+    F = PI.native_exec.FEATURES_ROWS_F32
+    assert PI.run_empty()[0] == 0                                                                          # a zeroed tail: the matrix form
+    assert PI.run_empty(feature_form=F, src_row=8, box6=8)[0] == 0
+    for fields in (dict(feature_form=F, src_row=8), dict(feature_form=F, box6=8), dict(feature_form=F), dict(src_row=8, box6=8), dict(src_row=8)):
+        rc, err = PI.run_empty(**fields)                                                                   # one without the other; a rows form
+        assert rc != 0 and b"src_row" in err and b"box6" in err, (fields, err)                             # without them; the matrix form with a stray one
+    assert b"DFOL_FEATURES_ROWS_F32" in PI.run_empty(feature_form=F, src_row=8)[1] and b"DFOL_FEATURES_MATRIX" in PI.run_empty(src_row=8)[1]
+    for bad in (-1, 6, 2 ** 31 - 1):
+        rc, err = PI.run_empty(feature_form=bad, src_row=8, box6=8)
+        assert rc != 0 and b"feature_form" in err and str(bad).encode() in err, (bad, err)
+    # the model's gate table likewise (n_gates is the struct's LAST field: its refusals show that the ctypes layout and the C layout agree)
+    assert PI.run_empty(model=dict(gates=8, n_gates=3))[0] == 0
+    for fields in (dict(n_gates=-1), dict(gates=8, n_gates=-1), dict(gates=8, n_gates=0), dict(n_gates=2)):
+        rc, err = PI.run_empty(model=fields)
+        assert rc != 0 and b"n_gates" in err and ("%d gates" % fields["n_gates"]).encode() in err, (fields, err)

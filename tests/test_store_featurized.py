@@ -10,12 +10,13 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _program_inputs as PI  # noqa: E402
 from dfol_vqa_amd import _lib, feature_store  # noqa: E402
 from dfol_vqa_amd.interpreter import BatchGQABoxFeaturizer, featurizer_trains, store_layers_of  # noqa: E402
 from dfol_vqa_amd.visual_oracle import RegularMLP  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("dfol_store_objects_f32", "dfol_set_feature_cache")
+NEW = ("dfol_store_objects_f32",)
 CTYPE = {"int32_t": "_i32", "int64_t": "_i64", "float": "_f"}
 
 
@@ -31,8 +32,9 @@ def test_binding_table_names_the_new_entry_points_with_the_headers_signatures():
             arg = " ".join(arg.split())
             want.append("_p" if "*" in arg else CTYPE[arg.replace("const ", "").split(" ")[0]])
         assert [kinds[id(t)] for t in _lib.SIGNATURES[name]] == want, name
-    assert "dfol_store_objects_f32 and dfol_set_feature_cache" in header            # the "added under 3" list: a pure addition keeps the version
-    assert _lib.ABI_VERSION == 3 and "#define DFOL_ABI_VERSION 3" in header
+    assert "its cached form: dfol_store_objects_f32" in header                      # the "added under 3" list
+    PI.assert_forms_and_layout()                                                    # the cached form travels in the scene struct: DFOL_FEATURES_CACHED
+    assert _lib.ABI_VERSION == 4 and "#define DFOL_ABI_VERSION 4" in header         # (the structs grew: a layout change moves the version)
 
 
 def test_entry_points_validate_their_sizes_without_a_device():
@@ -44,10 +46,21 @@ def test_entry_points_validate_their_sizes_without_a_device():
         assert h.dfol_store_objects_f32(None, ld_cache, None, None, O, W, None, ld_out, None) != 0, (O, W, ld_cache, ld_out)
         assert b"store_objects" in h.dfol_last_error()                                            # (the last: null pointers with O > 0)
     assert h.dfol_store_objects_f32(None, 512, None, None, 0, 512, None, 515, None) != 0 and b"ld_out" in h.dfol_last_error()
-    assert h.dfol_set_feature_cache(None, 0, 0, None, None) == 0
-    assert h.dfol_set_feature_cache(8, 512, 512, None, None) != 0 and b"set_feature_cache" in h.dfol_last_error()
-    assert h.dfol_set_feature_cache(8, 511, 512, 8, 8) != 0 and b"set_feature_cache" in h.dfol_last_error()
-    assert h.dfol_set_feature_cache(8, 512, 512, 8, 8) == 0 and h.dfol_set_feature_cache(None, 0, 0, None, None) == 0
+    # the scene's cached form, on an empty program (nothing is launched)
+    C = PI.native_exec.FEATURES_CACHED
+    assert PI.run_empty()[0] == 0
+    rc, err = PI.run_empty(feature_form=C, cache=8, ld_cache=512, cache_cols=512)                  # a cache without src_row and box6
+    assert rc != 0 and b"src_row" in err and b"DFOL_FEATURES_CACHED" in err, err
+    rc, err = PI.run_empty(feature_form=C, src_row=8, box6=8, ld_cache=512, cache_cols=512)        # src_row and box6 without a cache
+    assert rc != 0 and b"scene->cache" in err, err
+    rc, err = PI.run_empty(cache=8, ld_cache=512, cache_cols=512)                                  # a stray cache in the matrix form
+    assert rc != 0 and b"scene->cache" in err and b"DFOL_FEATURES_MATRIX" in err, err
+    rc, err = PI.run_empty(feature_form=C, cache=8, src_row=8, box6=8, ld_cache=511, cache_cols=512)
+    assert rc != 0 and b"cache_cols=512" in err and b"ld_cache=511" in err, err
+    rc, err = PI.run_empty(feature_form=C, cache=8, src_row=8, box6=8, ld_cache=512, cache_cols=0)  # (cache_cols is the struct's LAST field: the
+    assert rc != 0 and b"cache_cols=0" in err, err                                                 # ctypes layout and the C layout agree)
+    assert PI.run_empty(feature_form=C, cache=8, src_row=8, box6=8, ld_cache=512, cache_cols=512)[0] == 0
+    assert PI.run_empty(feature_form=C, cache=8, src_row=8, box6=8, ld_cache=516, cache_cols=512)[0] == 0 and PI.run_empty()[0] == 0
 
 
 def test_cache_key_follows_weight_versions_and_the_arithmetic():
